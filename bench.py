@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the embed-and-retrieve hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: either under python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ..., or
      plainly as above — then this file starts the N ranks itself as fresh child processes and relays rank 0's line)
 
@@ -67,7 +67,13 @@ def parse_args():
     ap.add_argument("--no-kernel-events", action="store_true", help="skip the instrumented replay (no roofline object)")
     ap.add_argument("--query-stream", choices=("own", "same"), default="same",
                     help="own: the query stage of step i on a second HIP stream beside the encode of step i+1; same: one stream")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's embeddings, top-k labels, "
+                         "distances, counts) as DIR/<name>.npy in float32 / float64")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args) -> int:
@@ -289,6 +295,11 @@ def main():
     last_out = drain()
     fence()
     elapsed = time.perf_counter() - t0
+    # --dump-outputs: what the last timed step handed its caller, copied out before any later leg reuses the embedding buffer
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"embeddings": cur_emb[0], "topk_labels": last_out[0],
+                                                  "topk_distances": last_out[1], "topk_counts": last_out[2]})
     # outside the timed region: the last pipelined result against the synchronous query of the same embeddings
     gs_timed = index.guard_stats()
     pipelined_equals_sync = None
@@ -893,9 +904,39 @@ def main():
                                                            "at N = 1 only (it needs the host cores the other ranks' launch threads use)"},
             "distributed": distributed,
         }
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: array with one row per query} -> out_dir/<name>.npy: floating arrays as float32, integer ones (labels, counts)
+    as float64, exact below 2^53. Above DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows of every array is
+    written, and its row numbers as rows.npy. Returns the JSON line's record of what was written."""
+    import numpy as np
+    import torch
+
+    host = {}
+    for name, a in arrays.items():
+        a = torch.as_tensor(a).detach().cpu().numpy()
+        host[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    n = next(iter(host.values())).shape[0]
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096) * n // (total + 8 * n)   # (+ 8 bytes per row of rows.npy, 4 KB for the headers)
+        rows = np.sort(np.random.Generator(np.random.Philox(0)).choice(n, size=keep, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": {name: [str(a.dtype), list(a.shape)] for name, a in host.items()},
+            "rows_sampled": "rows" in host}
 
 
 def bench_retrieval(args, torch, dist, np, dev, rank, world, local_rank, FlatIndex, merge_topk, _lib, all_gather,

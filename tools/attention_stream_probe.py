@@ -1,7 +1,7 @@
 """attention_stream_kernel (round 5) against attention_long_kernel on the ViT-L/14 shape: equality of the 16 full tiles,
 the last query within tolerance, bf16 and MXFP8 outputs, and isolated timings (us per launch)."""
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import mmiss_amd  # noqa
 from mmiss_amd import _lib

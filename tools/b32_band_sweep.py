@@ -1,6 +1,6 @@
 """ViT-B/32 bs-256 encode (the headline's encode half) against the band height of the persistent GEMMs' tile order (option gemm_p256_band)."""
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import mmiss_amd  # noqa
 from mmiss_amd import _lib

@@ -1,7 +1,7 @@
 """Per-kernel table (instrumented replay: HIP events around every launch) of one ViT-L/14 bs-128 fp8 encode, for an option set:
 python tools/l14_kernel_table.py [precision=bf16] [key=value ...]"""
-import sys
-sys.path.insert(0, "/root/repo")
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import mmiss_amd  # noqa
 from mmiss_amd import _lib
