@@ -276,9 +276,45 @@ int mmiss_index_guard_stats(mmiss_index* idx, int64_t out[4]);
  */
 int mmiss_index_guard_stats_ex(mmiss_index* idx, int64_t out[8]);
 
-/* persistence of rows + labels (replaces chroma_data/, backend/app/utils.py:21,113) */
+/*
+ * persistence of rows + labels (replaces chroma_data/, backend/app/utils.py:21,113). The file format (version 1) holds no
+ * tags: save does not write them and load resets every row's tag to 0 (a caller that filters re-derives them from its own
+ * metadata and sets them again, as the Python collection does).
+ */
 int mmiss_index_save(mmiss_index* idx, const char* path);
 int mmiss_index_load(mmiss_index* idx, const char* path);
+
+/* ---------------------------------------------------------------- filtered queries ------------- */
+/*
+ * Every row carries a 64-bit TAG word (0 when added; update keeps it; stable removal keeps the survivors'; clear and load
+ * reset it). A filtered query gives each query q two masks and admits row r iff
+ *     (tags[r] & require[q]) == require[q]  &&  (tags[r] & exclude[q]) == 0
+ * and returns the exact top-k AMONG ADMITTED ROWS: ids and distances bit-identical to an unfiltered query of an index that
+ * holds only the rows q admits, (distance, label) order, out_count[q] = min(k, admitted rows of q that have a direction),
+ * unused slots label -1 / distance +inf. Every pass of a filtered query (first pass, widen pass, exhaustive pass) is the
+ * streaming scan, which does not read rows that no query of its block admits; the score GEMM of unfiltered batches is not used.
+ * replaces the reference's POST-filter: collection.query(n_results=limit) and then dropping the hits whose
+ * filter_results_json answers are not all "yes" (backend/app/main.py:202-222, 258-278, 320-340), which returns fewer than
+ * `limit` results whenever the filter rejects some of the nearest rows.
+ */
+/* labels: int64 [n], tags: uint64 [n] (host or device). A label not in the index -> MMISS_ERR_ARG and nothing is changed. */
+int mmiss_index_set_tags(mmiss_index* idx, const int64_t* labels, const uint64_t* tags, int64_t n);
+/* out: uint64 [n] (host or device), the tags of `labels`; a label not in the index -> MMISS_ERR_ARG */
+int mmiss_index_get_tags(mmiss_index* idx, const int64_t* labels, int64_t n, uint64_t* out);
+/*
+ * As mmiss_index_query, with require / exclude: uint64 [Q] each, host or device memory, null = 0 for every query. Both
+ * null: exactly mmiss_index_query (same path, same results). The exactness guard works on the admitted rows (its bound is
+ * the k'-th approximate score among them; the widen pass collects admitted rows only; the exhaustive pass selects among
+ * them) and counts in the guard statistics like any query.
+ */
+int mmiss_index_query_filtered(mmiss_index* idx, const float* queries, int32_t Q, int32_t k,
+                               const uint64_t* require, const uint64_t* exclude,
+                               int64_t* out_labels, float* out_dist, int32_t* out_count);
+/* first half of mmiss_index_query_filtered; ended by mmiss_index_query_end or dropped by mmiss_index_query_abort. The
+ * masks are read before it returns. */
+int mmiss_index_query_filtered_begin(mmiss_index* idx, const float* queries, int32_t Q, int32_t k,
+                                     const uint64_t* require, const uint64_t* exclude,
+                                     int64_t* out_labels, float* out_dist, int32_t* out_count);
 
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*

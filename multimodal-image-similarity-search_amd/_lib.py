@@ -89,6 +89,10 @@ SIGNATURES = {
     "mmiss_index_guard_stats_ex": (_I, [_P, C.POINTER(_I64)]),
     "mmiss_index_save": (_I, [_P, C.c_char_p]),
     "mmiss_index_load": (_I, [_P, C.c_char_p]),
+    "mmiss_index_set_tags": (_I, [_P, _P, _P, _I64]),
+    "mmiss_index_get_tags": (_I, [_P, _P, _I64, _P]),
+    "mmiss_index_query_filtered": (_I, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "mmiss_index_query_filtered_begin": (_I, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "mmiss_blend": (_I, [_I, _P, _P, _P, C.c_double, _I32, _I32, _P]),
     "mmiss_merge_topk": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_prof_enable": (_I, [_I]),

@@ -8,6 +8,10 @@
 Same form-field names, same response shapes (`{"success": True, "metadata": ...}`, 409 with the duplicate's
 metadata, `{"results": [...]}` with `similarity_score`, 500 `{"success": False, "error": ...}` on any exception), same
 post-query yes/no filter on `filter_results_json` (main.py:202-222), `limit <= 0` meaning "All" (main.py:757).
+The post-filter returns however many of the `limit` nearest images pass the filters (often none for a selective one). The
+three search routes therefore take one optional field the reference does not have, `prefilter` ("1" / "true"): with it
+the filters go into the search itself and `limit` filtered results come back (the exact nearest among the images that pass;
+mmiss_amd.search's `filters=`). Without it the routes keep the reference's post-filter, byte for byte.
 This is SURVEY.md §8(f) N1: the caller of the hot path, kept thin; everything numeric goes through
 mmiss_amd.utils / mmiss_amd.search. The other ten routes (metadata editing, Moondream filters, reset, static
 files) are out of scope.
@@ -63,6 +67,11 @@ def _first(fields, name, default=None):
 
 def _as_bool(s) -> bool:
     return str(s).strip().lower() in ("1", "true", "yes", "on")
+
+
+def _prefilter(fields) -> bool:
+    """The optional `prefilter` field ("1" / "true"): filters applied inside the search instead of after it."""
+    return str(_first(fields, "prefilter", "")).strip().lower() in ("1", "true")
 
 
 def apply_filters(results: List[dict], filters: Optional[List[str]]) -> List[dict]:
@@ -162,6 +171,9 @@ def create_app():
             limit = int(_first(fields, "limit", 10))
             model, processor = utils.load_clip_model()
             embedding_result = utils.generate_clip_embedding(image=image, model=model, processor=processor)
+            if _prefilter(fields):
+                return {"results": search.search_similar(embedding=embedding_result["image"][0], limit=limit,
+                                                         filters=fields.get("filters"))}
             results = search.search_similar(embedding=embedding_result["image"][0], limit=limit)
             return {"results": apply_filters(results, fields.get("filters"))}
         except Exception as e:
@@ -182,6 +194,8 @@ def create_app():
                 got = search._collection().get(include=["metadatas"])
                 n = 1000 if limit <= 0 else limit
                 results = [dict(m or {}) for m in got["metadatas"]][:n]
+            elif _prefilter(fields):
+                return {"results": search.search_by_text(query_text=query, limit=limit, filters=filters)}
             else:
                 results = search.search_by_text(query_text=query, limit=limit)
             return {"results": apply_filters(results, filters)}
@@ -198,6 +212,9 @@ def create_app():
                 return JSONResponse(status_code=422, content={"detail": "field 'query' is required"})
             weight_image = float(_first(fields, "weight_image", 0.5))  # not clamped, as in the backend route
             limit = int(_first(fields, "limit", 10))
+            if _prefilter(fields):
+                return {"results": search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,
+                                                            limit=limit, filters=fields.get("filters"))}
             results = search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,
                                                limit=limit)
             return {"results": apply_filters(results, fields.get("filters"))}

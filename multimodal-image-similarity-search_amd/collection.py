@@ -9,6 +9,12 @@ Call sites mirrored (paths relative to the reference root):
   collection.delete(ids)                                                 backend/app/main.py:1065-1069
   collection.count()                                                     init_db.py:58
 
+Filtered search (query(..., filters=[names])) is exact PRE-filtering: the top-k among the rows whose filter_results_json
+answers "yes" to every named filter, where the reference post-filters the k nearest rows (backend/app/main.py:202-222) and
+so returns fewer. Each filter name gets one bit of the index rows' 64-bit tag words (FlatIndex.set_tags), in order of first
+appearance in label order; the bits are derived from the metadata, never persisted, and pushed to the index lazily — at
+the first filtered query after the metadata changed.
+
 Only the embedding arithmetic runs on the GPU (FlatIndex); ids, metadatas and documents are host-side
 bookkeeping exactly as they are bookkeeping inside chromadb's sqlite. String ids map to int64 labels
 handed out in insertion order; labels are the deterministic tie-break of equal distances.
@@ -27,6 +33,23 @@ from .index import FlatIndex
 
 logger = logging.getLogger("image-match")
 MAX_N_RESULTS = 2040  # mmiss_index_query's per-call limit on k
+MAX_FILTER_BITS = 64  # bits of a row's tag word (mmiss_index_set_tags)
+
+
+def filter_answers(metadata) -> dict:
+    """The yes/no answers of one row: its metadata's `filter_results_json` parsed (unparseable or not an object: none)."""
+    if not metadata or "filter_results_json" not in metadata:
+        return {}
+    try:
+        answers = json.loads(metadata["filter_results_json"])
+    except (json.JSONDecodeError, TypeError):
+        return {}
+    return answers if isinstance(answers, dict) else {}
+
+
+def answers_yes(value) -> bool:
+    """The normalisation of api.apply_filters (backend/app/main.py:216-218)."""
+    return str(value).lower().strip() == "yes"
 
 
 class DuplicateIDError(ValueError):
@@ -59,6 +82,10 @@ class FlatCollection:
         self._meta: Dict[int, Optional[dict]] = {}
         self._docs: Dict[int, Optional[str]] = {}
         self._next_label = 0
+        # filtered search: filter name -> tag bit, names answered past the 64th bit, labels whose tags the index does not have yet
+        self._filter_bits: Dict[str, int] = {}
+        self._filter_overflow: set = set()
+        self._tag_dirty: set = set()
         self._lock = threading.RLock()         # 1 writer + readers (the reference has a background updater, main.py:410)
         self._persist_dir = persist_dir
         self._autosave = autosave
@@ -216,6 +243,8 @@ class FlatCollection:
         self._meta = dict(zip(self._labels, blob["metadatas"]))
         self._docs = dict(zip(self._labels, blob["documents"]))
         self._index_gen = int(blob.get("index_gen", 0))
+        # the index file holds no tags (they load as 0): every row's tag is pushed again at the first filtered query
+        self._filter_bits, self._filter_overflow, self._tag_dirty = {}, set(), set(self._labels)
         if self._dim is not None and self._labels:
             self._ensure_index(self._dim)
             self._index.load(self._index_path(self._index_gen))
@@ -283,10 +312,66 @@ class FlatCollection:
             for lab, m, d in zip(labels.tolist(), metadatas, documents):
                 self._meta[lab] = dict(m) if m is not None else None
                 self._docs[lab] = d
+            self._tag_dirty.update(labels.tolist())
             self._saved({"op": "add", "ids": ids, "metadatas": metadatas, "documents": documents}, emb)
 
+    # ------------------------------------------------------------------ filtered search
+    def _push_tags(self) -> None:
+        """Give the index the tag words of every dirty label (under the lock, at a filtered query). Labels are visited in label
+        order, so a name's bit is the order of its first appearance."""
+        if not self._tag_dirty:
+            return
+        labs = sorted(self._tag_dirty)
+        tags = []
+        for lab in labs:
+            t = 0
+            for name, value in filter_answers(self._meta.get(lab)).items():
+                bit = self._filter_bits.get(name)
+                if bit is None and name not in self._filter_overflow:
+                    if len(self._filter_bits) < MAX_FILTER_BITS:
+                        bit = self._filter_bits[name] = len(self._filter_bits)
+                    else:
+                        self._filter_overflow.add(name)
+                if bit is not None and answers_yes(value):
+                    t |= 1 << bit
+            tags.append(t)
+        self._index.set_tags(np.asarray(labs, dtype=np.int64), np.asarray(tags, dtype=np.uint64))
+        self._tag_dirty.clear()
+
+    def _filtered_query(self, q: np.ndarray, k: int, filters: List[str]):
+        """Exact top-k among the rows answering "yes" to every filter -> (labels [Q,k], distances [Q,k], counts [Q])."""
+        self._push_tags()
+        Q = q.shape[0]
+        if any(f not in self._filter_bits and f not in self._filter_overflow for f in filters):
+            # a name no row has ever answered admits nothing
+            return (np.full((Q, k), -1, np.int64), np.full((Q, k), np.inf, np.float32), np.zeros((Q,), np.int32))
+        req = 0
+        for f in filters:
+            if f in self._filter_bits:
+                req |= 1 << self._filter_bits[f]
+        over = [f for f in filters if f in self._filter_overflow]
+        if not over:
+            return self._index.query(q, k, require=np.uint64(req))
+        # a name past the 64th bit: the mapped bits narrow the query, the rest is checked on the host. Exact as long as the rows
+        # passing the mapped bits fit one call (MAX_N_RESULTS); beyond that it is the best MAX_N_RESULTS of them, post-filtered.
+        ok = {lab for lab in self._labels if all(answers_yes(filter_answers(self._meta.get(lab)).get(f, "")) for f in filters)}
+        wide = min(len(self._labels), MAX_N_RESULTS)
+        labs_w, dist_w, cnt_w = self._index.query(q, wide, require=np.uint64(req))
+        labs = np.full((Q, k), -1, np.int64)
+        dist = np.full((Q, k), np.inf, np.float32)
+        cnt = np.zeros((Q,), np.int32)
+        for qi in range(Q):
+            keep = [j for j in range(int(cnt_w[qi])) if int(labs_w[qi, j]) in ok][:k]
+            labs[qi, :len(keep)] = labs_w[qi, keep]
+            dist[qi, :len(keep)] = dist_w[qi, keep]
+            cnt[qi] = len(keep)
+        return labs, dist, cnt
+
     def query(self, query_embeddings=None, n_results: int = 10, include: Sequence[str] = ("metadatas", "documents", "distances"),
-              **_unused) -> dict:
+              filters: Optional[Sequence[str]] = None, **_unused) -> dict:
+        """collection.query. filters: names of yes/no filters; when given, the result is the exact n_results nearest among the
+        rows whose filter_results_json answers "yes" to every one of them (pre-filtering; see the module docstring)."""
+        filters = list(dict.fromkeys(_as_list(filters))) if filters else []
         if query_embeddings is None:
             raise ValueError("FlatCollection.query needs query_embeddings (text embedding functions are out of scope)")
         q = self._embeddings_array(query_embeddings)
@@ -305,7 +390,10 @@ class FlatCollection:
                 if k > MAX_N_RESULTS:  # one mmiss_index_query call ranks at most 2040 rows per query: clamp, do not fail
                     logger.warning(f"n_results={n_results} clamped to {MAX_N_RESULTS}")
                     k = MAX_N_RESULTS
-                labs, dist, cnt = self._index.query(q, k)
+                if filters:
+                    labs, dist, cnt = self._filtered_query(q, k, filters)
+                else:
+                    labs, dist, cnt = self._index.query(q, k)
             label_to_id = dict(zip(self._labels, self._ids))
             out = {"ids": [], "distances": None, "metadatas": None, "documents": None, "embeddings": None,
                    "uris": None, "data": None, "included": include}
@@ -360,6 +448,7 @@ class FlatCollection:
                         merged = {} if _replace_metadata else dict(self._meta.get(lab) or {})
                         merged.update(m)  # chroma merges keys on update
                         self._meta[lab] = merged
+                        self._tag_dirty.add(lab)
             if documents is not None:
                 for lab, d in zip(labs, _as_list(documents)):
                     self._docs[lab] = d
@@ -389,6 +478,7 @@ class FlatCollection:
                 del self._by_id[i]
                 self._meta.pop(l, None)
                 self._docs.pop(l, None)
+                self._tag_dirty.discard(l)
             self._saved({"op": "delete", "ids": ids})
 
     def peek(self, limit: int = 10) -> dict:

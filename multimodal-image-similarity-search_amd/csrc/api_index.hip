@@ -21,6 +21,15 @@ struct mmiss_index {
     DevBuf rows, labels_d;
     DevBuf inv;   // MMISS_F8 only: [capacity] f32, inverse norm of every row's values (f8_row_inv_kernel); zero behind count
     std::vector<int64_t> labels_h;
+    // per-row 64-bit tag words of filtered queries (mmiss_index_set_tags): [capacity] u64 on the device, zero behind count, and
+    // their host mirror beside labels_h (the exhaustive pass selects on the host)
+    DevBuf tags;
+    std::vector<uint64_t> tags_h;
+    // the open query's predicate (mmiss_index_query_filtered*): masks per query on the host and the device; q_filt = false for
+    // an unfiltered query. fmask2 holds the masks of the flagged queries in the widen pass's compacted order.
+    bool q_filt = false;
+    std::vector<uint64_t> q_req, q_exc;
+    DevBuf fmask, fmask2, tag_stage;
     // scratch
     DevBuf stage, qn, qs, qstage, lists_s, lists_r, lists2_s, lists2_r, cand, cur_s, cur_r, out_c, map, gmax;
     // exactness guard + widen pass (see "exactness contract" above mmiss_index_query)
@@ -83,9 +92,11 @@ int index_reserve(mmiss_index* ix, int64_t need, hipStream_t st) {
     if (need <= ix->capacity) return MMISS_OK;
     int64_t cap = ix->capacity > 0 ? ix->capacity : 1024;
     while (cap < need) cap *= 2;
-    DevBuf nr, nl, ni;
+    DevBuf nr, nl, ni, nt;
     MM_TRY(nr.alloc((size_t)cap * ix->dim * ix->elt));
     MM_TRY(nl.alloc((size_t)cap * 8));
+    MM_TRY(nt.alloc((size_t)cap * 8));
+    MM_HIP(hipMemsetAsync(nt.p, 0, (size_t)cap * 8, st));   // (tags are zero behind the rows: the scan reads whole 16-row tiles)
     if (ix->dtype == MMISS_F8) {
         // zero behind the rows: the score GEMM reads the inverse norms of a whole 256-row tile, the scan of a 16-row one
         MM_TRY(ni.alloc((size_t)cap * 4));
@@ -95,11 +106,13 @@ int index_reserve(mmiss_index* ix, int64_t need, hipStream_t st) {
         MM_HIP(hipMemcpyAsync(nr.p, ix->rows.p, (size_t)ix->count * ix->dim * ix->elt, hipMemcpyDeviceToDevice, st));
         MM_HIP(hipMemcpyAsync(nl.p, ix->labels_d.p, (size_t)ix->count * 8, hipMemcpyDeviceToDevice, st));
         if (ni.p) MM_HIP(hipMemcpyAsync(ni.p, ix->inv.p, (size_t)ix->count * 4, hipMemcpyDeviceToDevice, st));
+        MM_HIP(hipMemcpyAsync(nt.p, ix->tags.p, (size_t)ix->count * 8, hipMemcpyDeviceToDevice, st));
     }
     MM_HIP(hipStreamSynchronize(st));
     std::swap(ix->rows.p, nr.p); std::swap(ix->rows.bytes, nr.bytes);
     std::swap(ix->labels_d.p, nl.p); std::swap(ix->labels_d.bytes, nl.bytes);
     std::swap(ix->inv.p, ni.p); std::swap(ix->inv.bytes, ni.bytes);
+    std::swap(ix->tags.p, nt.p); std::swap(ix->tags.bytes, nt.bytes);
     ix->capacity = cap;
     return MMISS_OK;
 }
@@ -141,24 +154,39 @@ int fetch_i64(const int64_t* p, int64_t n, std::vector<int64_t>& out) {
     return MMISS_OK;
 }
 
+// host copy of a (host or device) uint64 array; device memory is read on the index's stream
+int fetch_u64(const uint64_t* p, int64_t n, std::vector<uint64_t>& out, hipStream_t st) {
+    out.resize((size_t)n);
+    if (n == 0) return MMISS_OK;
+    if (mmiss_is_device_ptr(p)) {
+        MM_HIP(hipMemcpyAsync(out.data(), p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        MM_HIP(hipStreamSynchronize(st));
+    } else {
+        memcpy(out.data(), p, (size_t)n * 8);
+    }
+    return MMISS_OK;
+}
+
+inline bool tag_admits_h(uint64_t tag, uint64_t req, uint64_t exc) { return (tag & req) == req && (tag & exc) == 0; }
+
 int64_t find_row(const mmiss_index* ix, int64_t label) {
     auto it = std::lower_bound(ix->labels_h.begin(), ix->labels_h.end(), label);
     if (it == ix->labels_h.end() || *it != label) return -1;
     return it - ix->labels_h.begin();
 }
 
-template <typename T, int NQT, int CAP, int GS = 8>
+template <typename T, int NQT, int CAP, int GS = 8, bool FILT = false>
 int launch_scan_t(hipStream_t st, const ScanArgs& a, int slabs, int qtiles, int lds) {
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&scan_topk_kernel<T, NQT, CAP, GS>), lds));
-    hipLaunchKernelGGL((scan_topk_kernel<T, NQT, CAP, GS>), dim3(slabs, qtiles), dim3(256), lds, st, a);
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&scan_topk_kernel<T, NQT, CAP, GS, false, FILT>), lds));
+    hipLaunchKernelGGL((scan_topk_kernel<T, NQT, CAP, GS, false, FILT>), dim3(slabs, qtiles), dim3(256), lds, st, a);
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }
 
-template <typename T, int NQT>
+template <typename T, int NQT, bool FILT = false>
 int launch_scan_thr_t(hipStream_t st, const ScanArgs& a, int slabs, int qtiles, int lds) {
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&scan_topk_kernel<T, NQT, 32, 8, true>), lds));
-    hipLaunchKernelGGL((scan_topk_kernel<T, NQT, 32, 8, true>), dim3(slabs, qtiles), dim3(256), lds, st, a);
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&scan_topk_kernel<T, NQT, 32, 8, true, FILT>), lds));
+    hipLaunchKernelGGL((scan_topk_kernel<T, NQT, 32, 8, true, FILT>), dim3(slabs, qtiles), dim3(256), lds, st, a);
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }
@@ -208,6 +236,21 @@ int launch_scan(mmiss_index* ix, hipStream_t st, const ScanArgs& a, const ScanPl
     const double flops = 2.0 * a.Q * (double)a.N * a.D;
     const double bytes = (double)a.N * a.D * ix->elt;
     MM_PROF(ix->dtype == MMISS_F16 ? "scan_topk_f16" : ix->dtype == MMISS_F8 ? "scan_topk_f8" : "scan_topk_f32", st, flops, bytes);
+    if (a.tags) {   // filtered query (mmiss_index_query_filtered): the same plans, FILT instantiations
+        if (ix->dtype == MMISS_F8) {
+            if (p.nqt == 1) return launch_scan_t<F8, 1, 64, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+            if (p.nqt == 2) return launch_scan_t<F8, 2, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+            return launch_scan_t<F8, 4, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+        }
+        if (ix->dtype == MMISS_F16) {
+            if (p.nqt == 1) return launch_scan_t<_Float16, 1, 64, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+            if (p.nqt == 2) return launch_scan_t<_Float16, 2, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+            return launch_scan_t<_Float16, 4, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+        }
+        if (p.nqt == 1) return launch_scan_t<float, 1, 64, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+        if (p.nqt == 2) return launch_scan_t<float, 2, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+        return launch_scan_t<float, 4, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
+    }
     if (ix->dtype == MMISS_F8) {
         if (p.nqt == 1) return launch_scan_t<F8, 1, 64>(st, a, p.slabs, p.qtiles, p.lds);
         if (p.nqt == 2) return launch_scan_t<F8, 2, 32>(st, a, p.slabs, p.qtiles, p.lds);
@@ -333,13 +376,15 @@ extern "C" int mmiss_index_clear(mmiss_index* ix) {
     if (!ix) MM_FAIL(MMISS_ERR_ARG, "null index");
     std::lock_guard<std::mutex> lk(ix->mu);
     MM_NO_PENDING(ix, "mmiss_index_clear");
-    if (ix->dtype == MMISS_F8 && ix->capacity > 0) {   // (inverse norms are zero behind the rows)
+    if (ix->capacity > 0) {   // (inverse norms and tags are zero behind the rows)
         MM_TRY(mmiss_use_device(ix->device));
-        MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, ix->stream()));
+        if (ix->dtype == MMISS_F8) MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, ix->stream()));
+        MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, ix->stream()));
         MM_HIP(hipStreamSynchronize(ix->stream()));
     }
     ix->count = 0;
     ix->labels_h.clear();
+    ix->tags_h.clear();
     return MMISS_OK;
 }
 
@@ -381,6 +426,7 @@ extern "C" int mmiss_index_add(mmiss_index* ix, const float* vecs, const int64_t
     MM_HIP(hipMemcpyAsync(ix->labels_d.as<int64_t>() + ix->count, lab.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
     MM_HIP(hipStreamSynchronize(st));
     ix->labels_h.insert(ix->labels_h.end(), lab.begin(), lab.end());
+    ix->tags_h.resize((size_t)(ix->count + n), 0);   // new rows: tag 0 (the device tags behind count are zero)
     ix->count += n;
     return MMISS_OK;
 }
@@ -432,11 +478,15 @@ extern "C" int mmiss_index_remove(mmiss_index* ix, const int64_t* labels, int64_
     if (ndrop == 0) return MMISS_OK;
     const int64_t keep = ix->count - ndrop;
     std::vector<int64_t> map((size_t)keep), nl((size_t)keep);
+    std::vector<uint64_t> ntag((size_t)keep);
     for (int64_t r = 0, o = 0; r < ix->count; ++r)
-        if (!drop[r]) { map[o] = r; nl[o] = ix->labels_h[r]; ++o; }
+        if (!drop[r]) { map[o] = r; nl[o] = ix->labels_h[r]; ntag[o] = ix->tags_h[r]; ++o; }
     if (keep > 0) {
         // stable compaction into fresh buffers (row order == label order is the tie-break contract)
-        DevBuf nr, nlab, ninv;
+        DevBuf nr, nlab, ninv, ntg;
+        MM_TRY(ntg.alloc((size_t)ix->capacity * 8));
+        MM_HIP(hipMemsetAsync(ntg.p, 0, (size_t)ix->capacity * 8, st));
+        MM_HIP(hipMemcpyAsync(ntg.p, ntag.data(), (size_t)keep * 8, hipMemcpyHostToDevice, st));   // (the host mirror, compacted)
         MM_TRY(nr.alloc((size_t)ix->capacity * ix->dim * ix->elt));
         MM_TRY(nlab.alloc((size_t)ix->capacity * 8));
         if (ix->dtype == MMISS_F8) {
@@ -463,12 +513,15 @@ extern "C" int mmiss_index_remove(mmiss_index* ix, const int64_t* labels, int64_
         std::swap(ix->rows.p, nr.p); std::swap(ix->rows.bytes, nr.bytes);
         std::swap(ix->labels_d.p, nlab.p); std::swap(ix->labels_d.bytes, nlab.bytes);
         std::swap(ix->inv.p, ninv.p); std::swap(ix->inv.bytes, ninv.bytes);
+        std::swap(ix->tags.p, ntg.p); std::swap(ix->tags.bytes, ntg.bytes);
     }
-    else if (ix->dtype == MMISS_F8 && ix->capacity > 0) {   // every row removed: the inverse norms stay zero behind `count` (mmiss_index_clear's invariant)
-        MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st));
+    else if (ix->capacity > 0) {   // every row removed: inverse norms and tags stay zero behind `count` (mmiss_index_clear's invariant)
+        if (ix->dtype == MMISS_F8) MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st));
+        MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st));
         MM_HIP(hipStreamSynchronize(st));
     }
     ix->labels_h.swap(nl);
+    ix->tags_h.swap(ntag);
     ix->count = keep;
     return MMISS_OK;
 }
@@ -513,6 +566,64 @@ extern "C" int mmiss_index_labels(mmiss_index* ix, int64_t* out, int64_t cap) {
     std::lock_guard<std::mutex> lk(ix->mu);
     const int64_t n = std::min<int64_t>(cap, ix->count);
     if (n > 0) memcpy(out, ix->labels_h.data(), (size_t)n * 8);
+    return MMISS_OK;
+}
+
+// ================================================================================================ tags (filtered queries)
+extern "C" int mmiss_index_set_tags(mmiss_index* ix, const int64_t* labels, const uint64_t* tags, int64_t n) {
+    if (!ix || (n > 0 && (!labels || !tags))) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_set_tags: null argument");
+    if (n < 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_set_tags: n = %lld", (long long)n);
+    if (n == 0) return MMISS_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, "mmiss_index_set_tags");
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    std::vector<int64_t> lab;
+    std::vector<uint64_t> val;
+    MM_TRY(fetch_i64(labels, n, lab));
+    MM_TRY(fetch_u64(tags, n, val, st));
+    std::vector<int64_t> rows((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {   // every label first: a missing one changes nothing
+        rows[i] = find_row(ix, lab[i]);
+        if (rows[i] < 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_set_tags: label %lld not in the index", (long long)lab[i]);
+    }
+    // the host mirror in call order (a label given twice keeps its last tag), then its values for the distinct rows to the device
+    std::vector<uint64_t>& mirror = ix->tags_h;
+    for (int64_t i = 0; i < n; ++i) mirror[(size_t)rows[i]] = val[i];
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    const int64_t m = (int64_t)rows.size();
+    std::vector<uint64_t> pack((size_t)m * 2);
+    for (int64_t i = 0; i < m; ++i) { pack[i] = (uint64_t)rows[i]; pack[m + i] = mirror[(size_t)rows[i]]; }
+    MM_TRY(ix->tag_stage.ensure((size_t)m * 16));
+    MM_HIP(hipMemcpyAsync(ix->tag_stage.p, pack.data(), (size_t)m * 16, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(scatter_u64_kernel, dim3((int)std::min<int64_t>(4096, (m + 255) / 256)), dim3(256), 0, st,
+                       ix->tags.as<uint64_t>(), ix->tag_stage.as<int64_t>(), ix->tag_stage.as<uint64_t>() + m, m);
+    MM_HIP(hipGetLastError());
+    MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_get_tags(mmiss_index* ix, const int64_t* labels, int64_t n, uint64_t* out) {
+    if (!ix || (n > 0 && (!labels || !out))) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_get_tags: null argument");
+    if (n <= 0) return n == 0 ? MMISS_OK : MMISS_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, "mmiss_index_get_tags");
+    std::vector<int64_t> lab;
+    MM_TRY(fetch_i64(labels, n, lab));
+    std::vector<uint64_t> val((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t r = find_row(ix, lab[i]);
+        if (r < 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_get_tags: label %lld not in the index", (long long)lab[i]);
+        val[i] = ix->tags_h[(size_t)r];
+    }
+    if (mmiss_is_device_ptr(out)) {
+        MM_TRY(mmiss_use_device(ix->device));
+        MM_HIP(hipMemcpyAsync(out, val.data(), (size_t)n * 8, hipMemcpyHostToDevice, ix->stream()));
+        MM_HIP(hipStreamSynchronize(ix->stream()));
+    } else {
+        memcpy(out, val.data(), (size_t)n * 8);
+    }
     return MMISS_OK;
 }
 
@@ -614,9 +725,12 @@ int exhaustive_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_
         MM_HIP(hipMemcpyAsync(ix->dist_pin, ix->dist_all.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
         MM_HIP(hipStreamSynchronize(st));
         std::priority_queue<Ent> heap;  // max-heap: top = the worst of the best kk so far, by (distance, row)
+        const bool filt = ix->q_filt;   // filtered query: rows it does not admit never enter (host mirror of the tags)
+        const uint64_t rq = filt ? ix->q_req[(size_t)q] : 0, rx = filt ? ix->q_exc[(size_t)q] : 0;
         for (int64_t r = 0; r < N; ++r) {
             const float d = dist[(size_t)r];
             if (d != d) continue;
+            if (filt && !tag_admits_h(ix->tags_h[(size_t)r], rq, rx)) continue;
             if ((int)heap.size() < kk) heap.push(Ent(d, (int32_t)r));
             else if (Ent(d, (int32_t)r) < heap.top()) { heap.pop(); heap.push(Ent(d, (int32_t)r)); }
         }
@@ -676,8 +790,9 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
     // the score GEMM for an f16 index once the flagged queries fill a quarter of a 256-query tile (it costs about what 1.2
     // streaming scans cost, and a scan serves 64 queries), the scan otherwise
     const bool gemm8 = ix->dtype == MMISS_F8 && mmiss_option("score_f8_gemm", 1) != 0;
-    const bool gemm = (ix->dtype == MMISS_F16 || gemm8) && (D % 128) == 0 && D >= 256 && Qf > mmiss_option("sweep_gemm_min_q", 64) &&
-                      mmiss_option("score_strip_v3", 1) != 0;
+    // (filtered queries: always the scan, whose FILT form collects admitted rows only; the score GEMM has no filtered epilogue)
+    const bool gemm = !ix->q_filt && (ix->dtype == MMISS_F16 || gemm8) && (D % 128) == 0 && D >= 256 &&
+                      Qf > mmiss_option("sweep_gemm_min_q", 64) && mmiss_option("score_strip_v3", 1) != 0;
     const int Qfp = (int)round_up(Qf, 256);
     MM_TRY(ix->swp_cnt.ensure((size_t)Qfp * 4));
     MM_TRY(ix->swp_list.ensure((size_t)Qf * SWEEP_CAP * 4));
@@ -688,6 +803,15 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
     const void* qs_sw = ix->qs.p;          // [>= Qfp rows][D] scan operand (rows >= Qf are zero or masked by thr = +inf)
     const float* thr_sw = ix->thr.as<float>();
     const int32_t* qmap_sw = nullptr;
+    const uint64_t* fm_sw = ix->fmask.as<uint64_t>();   // filtered: [Qf] required, then [Qf] excluded masks, in the sweep's order
+    std::vector<uint64_t> fm2;
+    if (!all && ix->q_filt) {
+        fm2.resize((size_t)Qf * 2);
+        for (int i = 0; i < Qf; ++i) { fm2[i] = ix->q_req[(size_t)which[i]]; fm2[Qf + i] = ix->q_exc[(size_t)which[i]]; }
+        MM_TRY(ix->fmask2.ensure((size_t)Qf * 16));
+        MM_HIP(hipMemcpyAsync(ix->fmask2.p, fm2.data(), (size_t)Qf * 16, hipMemcpyHostToDevice, st));
+        fm_sw = ix->fmask2.as<uint64_t>();
+    }
     if (!all) {
         std::vector<int64_t> map64(which.begin(), which.end());
         MM_TRY(ix->qmap.ensure((size_t)Qf * 4));
@@ -728,6 +852,7 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
         ScanArgs a{};
         a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>(); a.qs = qs_sw; a.Q = Qf;
         a.thr = thr_sw; a.gcnt = ix->swp_cnt.as<int32_t>(); a.glist = ix->swp_list.as<int32_t>(); a.gcap = SWEEP_CAP;
+        if (ix->q_filt) { a.tags = ix->tags.as<uint64_t>(); a.req = fm_sw; a.exc = fm_sw + Qf; }
         // the widest query tile the flagged queries fill AND whose staged query block fits the CU's LDS (f32 rows at the
         // reference's D = 768: 64 queries x 3088 B = 193 KB do not, 32 do). nqt = 1 always fits: mmiss_index_create
         // admits only dims whose 16-query block does.
@@ -746,7 +871,21 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
         const int slabs = (int)((ntiles + tpb - 1) / tpb);
         MM_PROF(ix->dtype == MMISS_F16 ? "sweep_scan_f16" : ix->dtype == MMISS_F8 ? "sweep_scan_f8" : "sweep_scan_f32", st,
                 2.0 * Qf * (double)N * D, (double)qtiles * N * D * ix->elt);
-        if (ix->dtype == MMISS_F16) {
+        if (ix->q_filt) {
+            if (ix->dtype == MMISS_F16) {
+                if (nqt == 4) MM_TRY((launch_scan_thr_t<_Float16, 4, true>(st, a, slabs, qtiles, lds)));
+                else if (nqt == 2) MM_TRY((launch_scan_thr_t<_Float16, 2, true>(st, a, slabs, qtiles, lds)));
+                else MM_TRY((launch_scan_thr_t<_Float16, 1, true>(st, a, slabs, qtiles, lds)));
+            } else if (ix->dtype == MMISS_F8) {
+                if (nqt == 4) MM_TRY((launch_scan_thr_t<F8, 4, true>(st, a, slabs, qtiles, lds)));
+                else if (nqt == 2) MM_TRY((launch_scan_thr_t<F8, 2, true>(st, a, slabs, qtiles, lds)));
+                else MM_TRY((launch_scan_thr_t<F8, 1, true>(st, a, slabs, qtiles, lds)));
+            } else {
+                if (nqt == 4) MM_TRY((launch_scan_thr_t<float, 4, true>(st, a, slabs, qtiles, lds)));
+                else if (nqt == 2) MM_TRY((launch_scan_thr_t<float, 2, true>(st, a, slabs, qtiles, lds)));
+                else MM_TRY((launch_scan_thr_t<float, 1, true>(st, a, slabs, qtiles, lds)));
+            }
+        } else if (ix->dtype == MMISS_F16) {
             if (nqt == 4) MM_TRY((launch_scan_thr_t<_Float16, 4>(st, a, slabs, qtiles, lds)));
             else if (nqt == 2) MM_TRY((launch_scan_thr_t<_Float16, 2>(st, a, slabs, qtiles, lds)));
             else MM_TRY((launch_scan_thr_t<_Float16, 1>(st, a, slabs, qtiles, lds)));
@@ -817,8 +956,9 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
 namespace {
 
 // first pass of a query: everything up to and including the rerank is QUEUED on the stream; ix->pend describes it
+// filt: a filtered query (mmiss_index_query_filtered*), req / exc = its [Q] masks (host or device, null = 0)
 int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int64_t* out_labels, float* out_dist,
-                       int32_t* out_count) {
+                       int32_t* out_count, bool filt = false, const uint64_t* req = nullptr, const uint64_t* exc = nullptr) {
     MM_TRY(mmiss_use_device(ix->device));
     hipStream_t st = ix->stream();
     const int D = ix->dim;
@@ -826,6 +966,17 @@ int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t
     const bool out_dev = mmiss_is_device_ptr(out_labels);
     if (out_dev != mmiss_is_device_ptr(out_dist) || (out_count && out_dev != mmiss_is_device_ptr(out_count)))
         MM_FAIL(MMISS_ERR_ARG, "mmiss_index_query: output pointers must be all host or all device");
+    ix->q_filt = false;
+    if (filt) {
+        // the masks on the host (the exhaustive pass and the widen pass's compaction read them) and on the device: [Q] required,
+        // then [Q] excluded
+        if (req) MM_TRY(fetch_u64(req, Q, ix->q_req, st)); else ix->q_req.assign((size_t)Q, 0);
+        if (exc) MM_TRY(fetch_u64(exc, Q, ix->q_exc, st)); else ix->q_exc.assign((size_t)Q, 0);
+        MM_TRY(ix->fmask.ensure((size_t)Q * 16));
+        MM_HIP(hipMemcpyAsync(ix->fmask.p, ix->q_req.data(), (size_t)Q * 8, hipMemcpyHostToDevice, st));
+        MM_HIP(hipMemcpyAsync(ix->fmask.as<uint64_t>() + Q, ix->q_exc.data(), (size_t)Q * 8, hipMemcpyHostToDevice, st));
+        ix->q_filt = true;
+    }
 
     // outputs: the caller's device buffers, or the pinned host block (copied to the caller's host buffers at the end)
     int64_t* d_lab = out_labels; float* d_dist = out_dist; int32_t* d_cnt = out_count;
@@ -881,9 +1032,10 @@ int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t
     // batched path: f16 rows, more than one MFMA tile of queries, single page
     // ... and fp8 rows from two 128-query tiles on (round 4: the strip kernel widens the codes to f16 in its operand load —
     // gemm256s_kernel<_Float16, .., W8>; below that the streaming scan, which reads half the bytes per row, is the faster)
-    const bool dense8 = (N > 0) && ix->dtype == MMISS_F8 && pages == 1 && Q >= mmiss_option("score_big_min_q", 129) &&
+    // (filtered queries never take it: every pass of theirs is the streaming scan's FILT form)
+    const bool dense8 = !filt && (N > 0) && ix->dtype == MMISS_F8 && pages == 1 && Q >= mmiss_option("score_big_min_q", 129) &&
                         (D % 128) == 0 && D >= 256 && mmiss_option("score_strip_v3", 1) != 0 && mmiss_option("score_f8_gemm", 1) != 0;
-    const bool dense = ((N > 0) && ix->dtype == MMISS_F16 && Q > 16 && pages == 1) || dense8;
+    const bool dense = (!filt && (N > 0) && ix->dtype == MMISS_F16 && Q > 16 && pages == 1) || dense8;
     MM_TRY(ix->cand.ensure((size_t)Q * ncand * 4));
     // (score, row) of the last candidate stage 1 kept per query, -inf when it kept every row: the paging cursor, and the
     // guard's bound on what was left out
@@ -1006,6 +1158,7 @@ int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t
             a.cur_r = paging ? ix->cur_r.as<int32_t>() : nullptr;
             a.kp = kp; a.tiles_per_block = p.tiles_per_block;
             a.out_s = ix->lists_s.as<float>(); a.out_r = ix->lists_r.as<int32_t>();
+            if (filt) { a.tags = ix->tags.as<uint64_t>(); a.req = ix->fmask.as<uint64_t>(); a.exc = ix->fmask.as<uint64_t>() + Q; }
             MM_TRY(launch_scan(ix, st, a, p));
             MergeArgs m{};
             m.in_s = ix->lists_s.as<float>(); m.in_r = ix->lists_r.as<int32_t>();
@@ -1094,6 +1247,26 @@ extern "C" int mmiss_index_query_begin(mmiss_index* ix, const float* queries, in
     std::lock_guard<std::mutex> lk(ix->mu);
     MM_NO_PENDING(ix, "mmiss_index_query_begin");
     return query_begin_locked(ix, queries, Q, k, out_labels, out_dist, out_count);
+}
+
+extern "C" int mmiss_index_query_filtered(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const uint64_t* require,
+                                          const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count) {
+    MM_TRY(query_check_args(ix, queries, Q, k, out_labels, out_dist, "mmiss_index_query_filtered"));
+    if (Q == 0) return MMISS_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, "mmiss_index_query_filtered");
+    // both masks null: mmiss_index_query itself (same path, same results)
+    MM_TRY(query_begin_locked(ix, queries, Q, k, out_labels, out_dist, out_count, require || exclude, require, exclude));
+    return query_end_locked(ix);
+}
+
+extern "C" int mmiss_index_query_filtered_begin(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const uint64_t* require,
+                                                const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count) {
+    MM_TRY(query_check_args(ix, queries, Q, k, out_labels, out_dist, "mmiss_index_query_filtered_begin"));
+    if (Q == 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_query_filtered_begin: Q = 0");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, "mmiss_index_query_filtered_begin");
+    return query_begin_locked(ix, queries, Q, k, out_labels, out_dist, out_count, require || exclude, require, exclude);
 }
 
 extern "C" int mmiss_index_query_end(mmiss_index* ix) {
@@ -1217,8 +1390,10 @@ extern "C" int mmiss_index_load(mmiss_index* ix, const char* path) {
         // a read or copy error with part of the rows already overwritten: old labels / inverse norms no longer describe what the
         // buffer holds, so the index is left EMPTY rather than inconsistent
         if (ix->dtype == MMISS_F8 && ix->capacity > 0) { (void)hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st); (void)hipStreamSynchronize(st); }
+        if (ix->capacity > 0) { (void)hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st); (void)hipStreamSynchronize(st); }
         ix->count = 0;
         ix->labels_h.clear();
+        ix->tags_h.clear();
         MM_FAIL(MMISS_ERR_IO, "%s could not be read to its end; the index was cleared", path);
     }
     if (h.count) MM_HIP(hipMemcpy(ix->labels_d.p, lab.data(), (size_t)h.count * 8, hipMemcpyHostToDevice));
@@ -1228,6 +1403,12 @@ extern "C" int mmiss_index_load(mmiss_index* ix, const char* path) {
         MM_TRY(launch_f8_inv(ix, 0, h.count, st));
         MM_HIP(hipStreamSynchronize(st));
     }
+    // the file holds no tags (format version 1): every row's tag is 0 after a load
+    if (ix->capacity > 0) {
+        MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st));
+        MM_HIP(hipStreamSynchronize(st));
+    }
+    ix->tags_h.assign((size_t)h.count, 0);
     ix->labels_h.swap(lab);
     ix->count = h.count;
     return MMISS_OK;

@@ -223,7 +223,21 @@ struct ScanArgs {
     int32_t* glist;       // [Q][gcap]
     int gcap;
     const float* inv;     // fp8 rows: [>= N rounded up to 16] inverse norm of every row's values (f8_row_inv_kernel); scores are x inv
+    // filtered queries (scan_topk_kernel<.., FILT = true>): row r is ADMITTED for query q iff (tags[r] & req[q]) == req[q] and
+    // (tags[r] & exc[q]) == 0; a row no query admits is neither scored nor appended (appended at the end: the unfiltered
+    // instantiations read the same kernel-argument offsets as before)
+    const uint64_t* tags; // [>= N rounded up to 16] per-row tag words, zero behind the index's count
+    const uint64_t* req;  // [Q] required bits per query
+    const uint64_t* exc;  // [Q] excluded bits per query
 };
+
+__device__ __forceinline__ bool tag_admits(uint64_t tag, uint64_t req, uint64_t exc) {
+    return (tag & req) == req && (tag & exc) == 0;
+}
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
+    return ((uint64_t)hi << 32) | lo;
+}
 
 template <int NQT, int CAP>
 struct ScanLds {
@@ -252,7 +266,12 @@ __device__ __forceinline__ u32x4 scan_row_load(const u32x4* p) {
 #endif
 }
 
-template <typename T, int NQT, int CAP, int GS = 8, bool THR = false>
+// FILT (filtered queries): per 16-row tile the wave reads the 16 tag words (fetched four tiles at a time, one word per lane, one
+// batch ahead, so that a sparse filter is not a chain of dependent tag loads), skips the tile when no query of the block admits
+// any of its rows, masks the row loads of the rows no query admits (their MFMA operand is zero), and drops every (row, query)
+// pair the query does not admit from the lists / the threshold appends. The queries' masks live in registers: a lane owns one
+// query per query tile (qt * 16 + fr). No LDS beyond the unfiltered kernel's.
+template <typename T, int NQT, int CAP, int GS = 8, bool THR = false, bool FILT = false>
 __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ELT = ScanTraits<T>::ELT, QELT = ScanTraits<T>::QELT;
@@ -293,6 +312,15 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
         cur_r[qt] = (a.cur_r && q < a.Q) ? a.cur_r[q] : -1;
         if constexpr (THR) tau_r[qt] = q < a.Q ? a.thr[q] : INFINITY;
     }
+    uint64_t freq[NQT], fexc[NQT];   // FILT: this lane's queries' masks (a padding query admits nothing)
+    if constexpr (FILT) {
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+            const int q = qbase + qt * 16 + fr;
+            freq[qt] = q < a.Q ? a.req[q] : ~0ull;
+            fexc[qt] = q < a.Q ? a.exc[q] : ~0ull;
+        }
+    }
 
     // compaction of every list of this wave that is longer than kp (wave-uniform control flow)
     auto compact_all = [&]() {
@@ -318,8 +346,42 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
     int64_t tile_end = tile0 + a.tiles_per_block;
     if (tile_end > ntiles_total) tile_end = ntiles_total;
 
+    // FILT: tag words of four consecutive tiles of this wave, lane l holding row (l & 15) of the tile 4 * (l >> 4) after `first`
+    // (rows of the last tile behind N read the zeros behind the index's count: in bounds, dropped by row < N)
+    auto tag_batch = [&](int64_t first) -> uint64_t {
+        const int64_t t = first + 4 * (lane >> 4);
+        return t < tile_end ? a.tags[(t << 4) + (lane & 15)] : 0ull;
+    };
+    uint64_t tb_cur = 0, tb_next = 0;
+    int fit = 0;
+    if constexpr (FILT) tb_next = tag_batch(tile0 + wave);
+
     for (int64_t tile = tile0 + wave; tile < tile_end; tile += 4) {
         const int64_t row0 = tile << 4;
+        // FILT: tg[reg] = tag of row row0 + 4 fg + reg (the rows whose scores this lane holds); `live`: some query of the block
+        // admits this lane's LOAD row row0 + fr
+        uint64_t tg[4];
+        bool live = true;
+        if constexpr (FILT) {
+            const int j = fit & 3;
+            ++fit;
+            if (j == 0) { tb_cur = tb_next; tb_next = tag_batch(tile + 16); }   // the next batch flies while this one is used
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) tg[reg] = shfl_u64(tb_cur, 16 * j + 4 * fg + reg);
+            uint32_t rowmask = 0;   // bit r: some query of the block admits row row0 + r (wave-uniform)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                bool any = false;
+#pragma unroll
+                for (int qt = 0; qt < NQT; ++qt) any |= tag_admits(tg[reg], freq[qt], fexc[qt]);
+                const uint64_t b = __ballot(any);   // lane 16 g + fr: query fr (any qt) admits row 4 g + reg
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    if ((b >> (16 * g)) & 0xffffull) rowmask |= 1u << (4 * g + reg);
+            }
+            if (rowmask == 0) continue;   // no admitted row in the tile: nothing is loaded
+            live = (rowmask >> fr) & 1u;
+        }
         int64_t rload = row0 + fr;
         if (rload >= a.N) rload = a.N - 1;  // clamp: loads stay in bounds, the result is masked below
         const char* rp = reinterpret_cast<const char*>(a.rows) + (size_t)rload * D * ELT + fg * 16;
@@ -336,8 +398,17 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
         auto steps = [&](auto nsteps_tag, int byte0) {
             constexpr int NS = decltype(nsteps_tag)::value;
             u32x4 araw[NS];
+            if constexpr (FILT) {   // a row no query admits is not read: zeros into the MFMA
 #pragma unroll
-            for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp + byte0 + s * 64));
+                for (int s = 0; s < NS; ++s) araw[s] = u32x4{0u, 0u, 0u, 0u};
+                if (live) {
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp + byte0 + s * 64));
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp + byte0 + s * 64));
+            }
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
 #pragma unroll
@@ -367,8 +438,17 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
             const char* rp8 = reinterpret_cast<const char*>(a.rows) + (size_t)rload * D + fg * 16;
             const char* qp8 = sQ + fr * L.qstride + fg * 32;
             u32x4 araw[NS];
+            if constexpr (FILT) {
 #pragma unroll
-            for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp8 + (span0 + s) * 64));
+                for (int s = 0; s < NS; ++s) araw[s] = u32x4{0u, 0u, 0u, 0u};
+                if (live) {
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp8 + (span0 + s) * 64));
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp8 + (span0 + s) * 64));
+            }
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
 #pragma unroll
@@ -412,9 +492,16 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
                 for (int reg = 0; reg < 4; ++reg) {
                     const int64_t row = row0 + 4 * fg + reg;
                     const float s = acc[qt][reg] * rinv[reg];
+                    if constexpr (FILT) {   // only admitted rows are collected (and counted)
+                        if (q < a.Q && row < a.N && s >= tau_r[qt] && tag_admits(tg[reg], freq[qt], fexc[qt])) {
+                            const int pos = atomicAdd(a.gcnt + q, 1);
+                            if (pos < a.gcap) a.glist[(size_t)q * a.gcap + pos] = (int)row;
+                        }
+                    } else {
                     if (q < a.Q && row < a.N && s >= tau_r[qt]) {
                         const int pos = atomicAdd(a.gcnt + q, 1);
                         if (pos < a.gcap) a.glist[(size_t)q * a.gcap + pos] = (int)row;
+                    }
                     }
                 }
             }
@@ -432,10 +519,18 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
                 const float s = acc[qt][reg] * rinv[reg];   // (f16 / f32 rows: x 1; fp8 rows: x inv[row] / 128, one rounding)
                 const int ri = (int)row;
                 const bool after = (s < cur_s[qt]) || (s == cur_s[qt] && ri > cur_r[qt]);
+                if constexpr (FILT) {   // (row, query) pairs the query does not admit are dropped like rows >= N
+                    if (qok && row < a.N && s > tau_r[qt] && after && tag_admits(tg[reg], freq[qt], fexc[qt])) {
+                        const int pos = atomicAdd(&cnt[ql], 1);
+                        cs[ql * CAP + pos] = s;
+                        cr[ql * CAP + pos] = ri;
+                    }
+                } else {
                 if (qok && row < a.N && s > tau_r[qt] && after) {
                     const int pos = atomicAdd(&cnt[ql], 1);
                     cs[ql * CAP + pos] = s;
                     cr[ql * CAP + pos] = ri;
+                }
                 }
             }
         }
@@ -1103,6 +1198,11 @@ __global__ __launch_bounds__(256) void gather_rows_f8_f32_kernel(const F8* __res
         const int d = (int)(i - r * D);
         dst[i] = (float)src[map[r] * D + d] * inv[map[r]];
     }
+}
+// tags[rows[i]] = vals[i] (mmiss_index_set_tags; distinct rows)
+__global__ void scatter_u64_kernel(uint64_t* __restrict__ dst, const int64_t* __restrict__ rows, const uint64_t* __restrict__ vals, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dst[rows[i]] = vals[i];
 }
 __global__ void gather_i64_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ map,
                                   int64_t* __restrict__ dst, int64_t n) {

@@ -107,31 +107,107 @@ class FlatIndex:
             _lib.check(self._lib.mmiss_index_get(self._h, lab.ctypes.data, int(lab.shape[0]), out.ctypes.data))
         return out
 
-    def query(self, queries, k: int) -> Tuple["np.ndarray", "np.ndarray", "np.ndarray"]:
-        """-> (labels int64 [Q,k], distances float32 [Q,k], counts int32 [Q]); numpy in -> numpy out,
-        CUDA tensor in -> CUDA tensors out (no host round trip)."""
-        return self._query(queries, k, split=False)
+    # ------------------------------------------------------------------ tags (filtered queries)
+    def set_tags(self, labels, tags) -> None:
+        """Per-row 64-bit tag words (mmiss_index_set_tags): labels [n], tags [n] (uint64, or int64 bit patterns). A label not in
+        the index raises and changes nothing. Rows are added with tag 0; update keeps a row's tag; load resets every tag to 0."""
+        lab = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        t = np.asarray(tags)
+        if t.dtype.kind not in "ui" and not (t.dtype == object and t.size == 0):
+            raise TypeError(f"tags must be integers, got {t.dtype}")
+        t = np.ascontiguousarray(t.astype(np.int64, copy=False).view(np.uint64) if t.dtype.kind == "i" else t.astype(np.uint64)).reshape(-1)
+        if t.shape[0] != lab.shape[0]:
+            raise ValueError(f"{lab.shape[0]} labels but {t.shape[0]} tags")
+        with self._call_lock:
+            _lib.check(self._lib.mmiss_index_set_tags(self._h, lab.ctypes.data, t.ctypes.data, int(lab.shape[0])))
 
-    def query_begin(self, queries, k: int) -> "PendingQuery":
+    def get_tags(self, labels) -> np.ndarray:
+        """-> uint64 [n], the tag words of `labels` (a label not in the index raises)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        out = np.zeros(lab.shape[0], dtype=np.uint64)
+        if lab.shape[0]:
+            with self._call_lock:
+                _lib.check(self._lib.mmiss_index_get_tags(self._h, lab.ctypes.data, int(lab.shape[0]), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _mask(m, Q: int, q, name: str):
+        """A query mask -> None, a uint64 numpy [Q], or a contiguous int64 CUDA tensor [Q] (bit patterns). A scalar is the same
+        mask for every query. CUDA masks go with CUDA queries (they are read on the query's stream)."""
+        if m is None:
+            return None
+        if _is_torch(m):
+            import torch
+
+            if m.dtype.is_floating_point or m.dtype == torch.bool or m.dtype.is_complex:
+                raise TypeError(f"{name}: integer mask expected, got {m.dtype}")
+            if m.dim() == 0:
+                m = m.reshape(1).expand(Q)
+            if m.dim() != 1 or int(m.shape[0]) != Q:
+                raise ValueError(f"{name}: expected a scalar or [{Q}] masks, got shape {tuple(m.shape)}")
+            if m.is_cuda:
+                if m.dtype != torch.int64 and str(m.dtype) != "torch.uint64":
+                    m = m.to(torch.int64)
+                return m.contiguous()
+            m = m.cpu().numpy()
+        if isinstance(m, (bool, np.bool_)) or isinstance(m, float) or isinstance(m, np.floating):
+            raise TypeError(f"{name}: integer mask expected, got {type(m).__name__}")
+        if isinstance(m, (int, np.integer)):
+            v = int(m)
+            if not -(1 << 63) <= v < (1 << 64):
+                raise ValueError(f"{name}: {v} does not fit 64 bits")
+            return np.full(Q, v & ((1 << 64) - 1), dtype=np.uint64)
+        a = np.asarray(m)
+        if a.dtype.kind not in "ui":
+            raise TypeError(f"{name}: integer mask expected, got {a.dtype}")
+        if a.ndim == 0:
+            a = np.full(Q, a, dtype=a.dtype)
+        if a.ndim != 1 or a.shape[0] != Q:
+            raise ValueError(f"{name}: expected a scalar or [{Q}] masks, got shape {a.shape}")
+        a = a.astype(np.int64, copy=False).view(np.uint64) if a.dtype.kind == "i" else a.astype(np.uint64, copy=False)
+        return np.ascontiguousarray(a)
+
+    def query(self, queries, k: int, require=None, exclude=None) -> Tuple["np.ndarray", "np.ndarray", "np.ndarray"]:
+        """-> (labels int64 [Q,k], distances float32 [Q,k], counts int32 [Q]); numpy in -> numpy out,
+        CUDA tensor in -> CUDA tensors out (no host round trip).
+        require / exclude (filtered query, mmiss_index_query_filtered): row r is admitted for query q iff
+        (tags[r] & require[q]) == require[q] and (tags[r] & exclude[q]) == 0, and the result is the exact top-k among admitted
+        rows. Each is a scalar (every query) or [Q] integers, numpy or a CUDA tensor; None = 0. Both None: mmiss_index_query."""
+        return self._query(queries, k, split=False, require=require, exclude=exclude)
+
+    def query_begin(self, queries, k: int, require=None, exclude=None) -> "PendingQuery":
         """Queue the query's first pass and return at once (mmiss_index_query_begin); `.result()` of the returned handle waits
         for it, widens what the exactness guard could not prove, and returns what query() returns. Between the two the caller
-        may queue other GPU work on the same stream (the next batch's encode) — but no other call on this index."""
-        return self._query(queries, k, split=True)
+        may queue other GPU work on the same stream (the next batch's encode) — but no other call on this index.
+        require / exclude as in query()."""
+        return self._query(queries, k, split=True, require=require, exclude=exclude)
 
-    def query_next(self, pending: "PendingQuery", queries, k: int):
+    def query_next(self, pending: "PendingQuery", queries, k: int, require=None, exclude=None):
         """`pending.result()` and `query_begin(queries, k)` back to back -> (results of `pending`, the new PendingQuery). Everything
         Python has to do for the NEW query (layout checks, output buffers) happens BEFORE the pending one is ended, so between the
         last operation of its widen pass and the first kernel of the new first pass lie two C calls and nothing else. In a serving
         loop that keeps one query batch open per step (bench.py) the GPU idled ~87 us per step there (rocprofv3 kernel trace of
         round 6: the gap between the widen pass's count readback and prep_queries_kernel)."""
         q, outs = self._prepare(queries, k)
+        masks = self._masks(q, require, exclude)
         prev = pending.result()
         with self._call_lock:
             self._sync_stream(q)
-            _lib.check(self._lib.mmiss_index_query_begin(self._h, _lib.ptr(q), int(q.shape[0]), int(k), _lib.ptr(outs[0]), _lib.ptr(outs[1]),
-                                                         _lib.ptr(outs[2])))
+            if masks is None:
+                _lib.check(self._lib.mmiss_index_query_begin(self._h, _lib.ptr(q), int(q.shape[0]), int(k), _lib.ptr(outs[0]), _lib.ptr(outs[1]),
+                                                             _lib.ptr(outs[2])))
+            else:
+                _lib.check(self._lib.mmiss_index_query_filtered_begin(self._h, _lib.ptr(q), int(q.shape[0]), int(k), _lib.ptr(masks[0]),
+                                                                      _lib.ptr(masks[1]), _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2])))
             self._query_gen += 1
-            return prev, PendingQuery(self, q, outs, self._query_gen)
+            return prev, PendingQuery(self, q, outs, self._query_gen, masks)
+
+    def _masks(self, q, require, exclude):
+        """(require, exclude) in the form the C call takes, or None when both are None (the unfiltered call)."""
+        if require is None and exclude is None:
+            return None
+        Q = int(q.shape[0])
+        return (self._mask(require, Q, q, "require"), self._mask(exclude, Q, q, "exclude"))
 
     def _prepare(self, queries, k: int):
         q = self._vecs(queries)
@@ -150,16 +226,22 @@ class FlatIndex:
             cnt = np.empty((Q,), dtype=np.int32)
         return q, (lab, dist, cnt)
 
-    def _query(self, queries, k: int, split: bool):
+    def _query(self, queries, k: int, split: bool, require=None, exclude=None):
         q, (lab, dist, cnt) = self._prepare(queries, k)
         Q = int(q.shape[0])
+        masks = self._masks(q, require, exclude)
         with self._call_lock:  # stream hand-over + call are one unit per handle (threads: pipeline.BatchLanes)
             self._sync_stream(q)
-            fn = self._lib.mmiss_index_query_begin if split else self._lib.mmiss_index_query
-            _lib.check(fn(self._h, _lib.ptr(q), Q, int(k), _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt)))
+            if masks is None:
+                fn = self._lib.mmiss_index_query_begin if split else self._lib.mmiss_index_query
+                _lib.check(fn(self._h, _lib.ptr(q), Q, int(k), _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt)))
+            else:
+                fn = self._lib.mmiss_index_query_filtered_begin if split else self._lib.mmiss_index_query_filtered
+                _lib.check(fn(self._h, _lib.ptr(q), Q, int(k), _lib.ptr(masks[0]), _lib.ptr(masks[1]), _lib.ptr(lab), _lib.ptr(dist),
+                              _lib.ptr(cnt)))
             if split:
                 self._query_gen += 1
-                return PendingQuery(self, q, (lab, dist, cnt), self._query_gen)
+                return PendingQuery(self, q, (lab, dist, cnt), self._query_gen, masks)
         return (lab, dist, cnt)
 
     def guard_stats(self) -> dict:
@@ -203,8 +285,9 @@ class PendingQuery:
     """A query between FlatIndex.query_begin and its result(): holds the query rows and the output buffers alive. It owns the
     index's open-query slot only while its generation is the index's current one (FlatIndex._query_gen)."""
 
-    def __init__(self, index: "FlatIndex", q, outs, gen: int):
+    def __init__(self, index: "FlatIndex", q, outs, gen: int, masks=None):
         self._index, self._q, self._outs, self._gen, self._done = index, q, outs, gen, False
+        self._masks = masks   # (read by the begin call already; kept with the query for symmetry with `q`)
 
     def _current(self) -> bool:
         idx = self._index

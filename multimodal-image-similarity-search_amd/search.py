@@ -8,6 +8,8 @@ backend/app/main.py (same names, argument meaning, return layout and error behav
 
 plus batched forms (the reference is batch-1 everywhere; BASELINE configs 2-4 are batched).
 Like the reference, the wrappers catch every exception, log it and return [].
+Every search takes a keyword-only `filters` (names of yes/no filters): the exact `limit` nearest among the images that answer
+"yes" to all of them (FlatCollection.query(filters=...)); the default None searches everything, as the reference does.
 """
 from __future__ import annotations
 
@@ -60,12 +62,16 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
     return similar_images
 
 
-def search_similar(embedding: np.ndarray, limit: int = 10) -> List[Dict]:
+def _filter_kw(filters) -> dict:
+    return {"filters": list(filters)} if filters else {}
+
+
+def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None) -> List[Dict]:
     """Search for similar images using an embedding (main.py:748-805)."""
     try:
         actual_limit = 1000 if limit <= 0 else limit  # "All" option (limit of 0), main.py:757
         results = _collection().query(query_embeddings=[np.asarray(embedding, dtype=np.float32).tolist()],
-                                      n_results=actual_limit, include=["metadatas", "distances"])
+                                      n_results=actual_limit, include=["metadatas", "distances"], **_filter_kw(filters))
         out = _results_from_query(results, 0)
         logger.info(f"Found {len(out)} similar images")
         return out
@@ -74,31 +80,33 @@ def search_similar(embedding: np.ndarray, limit: int = 10) -> List[Dict]:
         return []
 
 
-def search_similar_batch(embeddings: np.ndarray, limit: int = 10) -> List[List[Dict]]:
+def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None) -> List[List[Dict]]:
     """[Q, D] embeddings -> one result list per query, one index pass for the whole batch."""
     try:
         actual_limit = 1000 if limit <= 0 else limit
         q = np.asarray(embeddings, dtype=np.float32)
-        results = _collection().query(query_embeddings=q, n_results=actual_limit, include=["metadatas", "distances"])
+        results = _collection().query(query_embeddings=q, n_results=actual_limit, include=["metadatas", "distances"],
+                                      **_filter_kw(filters))
         return [_results_from_query(results, qi) for qi in range(q.shape[0])]
     except Exception as e:
         logger.error(f"Error searching for similar images: {e}")
         return []
 
 
-def search_by_text(query_text: str, limit: int = 10) -> List[Dict]:
+def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequence[str]] = None) -> List[Dict]:
     """Search for images using a text query (main.py:807-827)."""
     try:
         model, processor = utils.load_clip_model()
         embedding_result = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)
         text_embedding = embedding_result["text"][0]
-        return search_similar(embedding=text_embedding, limit=limit)
+        return search_similar(embedding=text_embedding, limit=limit, filters=filters)
     except Exception as e:
         logger.error(f"Error in text search: {e}")
         return []
 
 
-def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: int = 10) -> List[Dict]:
+def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: int = 10, *,
+                      filters: Optional[Sequence[str]] = None) -> List[Dict]:
     """Search using both image and text with a weighted combination (main.py:829-867); weight_image is not
     clamped, as in the backend route."""
     try:
@@ -107,17 +115,17 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
         text_embedding = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)["text"][0]
         # normalise both, weighted sum, normalise again (main.py:852-860) — one GPU kernel
         combined_embedding = blend(image_embedding[None], text_embedding[None], weight_image)[0]
-        return search_similar(embedding=combined_embedding, limit=limit)
+        return search_similar(embedding=combined_embedding, limit=limit, filters=filters)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
 
 
 def search_multimodal_batch(image_embeddings: np.ndarray, text_embeddings: np.ndarray, weight_image: float = 0.5,
-                            limit: int = 10) -> List[List[Dict]]:
+                            limit: int = 10, *, filters: Optional[Sequence[str]] = None) -> List[List[Dict]]:
     """BASELINE config 4: a batch of (image, text) embedding pairs, blended and searched in one pass."""
     try:
-        return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit)
+        return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit, filters=filters)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []

@@ -105,15 +105,22 @@ class ShardedIndex:
         return torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(self.group) == "nccl" else torch.device("cpu")
 
     # ------------------------------------------------------------------ query
-    def query(self, queries, k: int, src: Optional[int] = 0):
+    def query(self, queries, k: int, src: Optional[int] = 0, require=None, exclude=None):
         """queries: [Q,D] (numpy or torch). src = rank whose queries are used (broadcast); src=None means every
         rank passes its own [Qr,D] block and the blocks are all-gathered (equal Qr on all ranks).
+        require / exclude: the filtered query's masks (FlatIndex.query), handed to every shard as given — they must describe
+        the query batch every shard runs (scalars, or [Q] for the broadcast / gathered batch); the merge by label is unchanged.
         -> (labels [Q,k], distances [Q,k], counts [Q]) identical on every rank."""
         import torch
         import torch.distributed as dist
 
+        kw = {}
+        if require is not None:
+            kw["require"] = require
+        if exclude is not None:
+            kw["exclude"] = exclude
         if self.world == 1:
-            return self.local.query(queries, k)
+            return self.local.query(queries, k, **kw)
         dev = self._device()
         q = torch.as_tensor(np.asarray(queries) if not hasattr(queries, "device") else queries).to(dev, torch.float32).contiguous()
         if src is None:
@@ -122,7 +129,7 @@ class ShardedIndex:
             q = gathered
         else:
             dist.broadcast(q, src=src, group=self.group)
-        lab, dst, _ = self.local.query(q if dev.type == "cuda" else q.numpy(), k)
+        lab, dst, _ = self.local.query(q if dev.type == "cuda" else q.numpy(), k, **kw)
         lab_all, dst_all = exchange_topk(torch.as_tensor(lab).to(dev), torch.as_tensor(dst).to(dev), self.world, self.group)
         if dev.type == "cuda":
             from .index import merge_topk
