@@ -25,10 +25,8 @@ struct mmiss_index {
     // their host mirror beside labels_h (the exhaustive pass selects on the host)
     DevBuf tags;
     std::vector<uint64_t> tags_h;
-    // the open query's predicate (mmiss_index_query_filtered*): masks per query on the host and the device; q_filt = false for
-    // an unfiltered query. fmask2 holds the masks of the flagged queries in the widen pass's compacted order.
-    bool q_filt = false;
-    std::vector<uint64_t> q_req, q_exc;
+    // a filtered query's masks on the device (Pending::d_mask points here); fmask2 holds the masks of the flagged queries in the
+    // widen pass's compacted order
     DevBuf fmask, fmask2, tag_stage;
     // scratch
     DevBuf stage, qn, qs, qstage, lists_s, lists_r, lists2_s, lists2_r, cand, cur_s, cur_r, out_c, map, gmax;
@@ -39,27 +37,8 @@ struct mmiss_index {
     // Pinned, device-visible host block a query's LAST kernel (the rerank) writes straight into: the guard's per-query flags
     // always, and labels / distances / counts when the caller's outputs are host buffers. The call then ends with ONE stream
     // synchronisation and no copy-engine operation (round 3: four small device-to-host copies used to sit there, ~25 us).
-    char* pin = nullptr;
-    size_t pin_bytes = 0;
-    int32_t* swp_pin = nullptr;   // pinned: the widen pass's list lengths, written by the re-rank kernel itself (RerankArgs::cnt_host)
-    size_t swp_pin_n = 0;
-    int ensure_swp_pin(size_t n) {
-        if (n <= swp_pin_n) return MMISS_OK;
-        if (swp_pin) { MM_HIP(hipStreamSynchronize(stream())); MM_HIP(hipHostFree(swp_pin)); swp_pin = nullptr; swp_pin_n = 0; }
-        const size_t cap = n < 1024 ? 1024 : n * 2;
-        MM_HIP(hipHostMalloc(reinterpret_cast<void**>(&swp_pin), cap * 4, hipHostMallocDefault));
-        swp_pin_n = cap;
-        return MMISS_OK;
-    }
-    int ensure_pin(size_t need) {
-        if (need <= pin_bytes) return MMISS_OK;
-        size_t cap = pin_bytes ? pin_bytes : 4096;
-        while (cap < need) cap *= 2;
-        if (pin) { MM_HIP(hipStreamSynchronize(stream())); MM_HIP(hipHostFree(pin)); pin = nullptr; pin_bytes = 0; }
-        MM_HIP(hipHostMalloc(reinterpret_cast<void**>(&pin), cap, hipHostMallocDefault));
-        pin_bytes = cap;
-        return MMISS_OK;
-    }
+    PinBuf pin;
+    PinBuf swp_pin;   // the widen pass's list lengths, written by the re-rank kernel itself (RerankArgs::cnt_host)
     int64_t stat_queries = 0, stat_flagged = 0, stat_rounds = 0, stat_pages = 0, stat_exhaustive = 0, stat_swept_rows = 0;
     // a query between mmiss_index_query_begin and mmiss_index_query_end: its first pass is queued, `done_ev` marks its end
     struct Pending {
@@ -67,10 +46,14 @@ struct mmiss_index {
         int Q = 0, k = 0;
         int64_t* d_lab = nullptr; float* d_dist = nullptr; int32_t* d_cnt = nullptr; int32_t* h_flags = nullptr;
         int64_t* out_labels = nullptr; float* out_dist = nullptr; int32_t* out_count = nullptr;
+        // the predicate of a filtered query (mmiss_index_query_filtered*; filt = false for an unfiltered one): [Q] required and
+        // [Q] excluded masks on the host (the widen pass's compaction and the exhaustive pass read them) and on the device
+        bool filt = false;
+        std::vector<uint64_t> req, exc;
+        const uint64_t* d_mask = nullptr;   // [Q] required, then [Q] excluded
     } pend;
     DevBuf dist_all;  // exhaustive fallback: one canonical distance per row
-    float* dist_pin = nullptr;   // ... and the pinned host block they come back through
-    int64_t dist_pin_rows = 0;
+    PinBuf dist_pin;  // ... and the pinned host block they come back through
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -88,31 +71,63 @@ int mmiss_index_build_flags(void) {
 
 namespace {
 
+// The element types of an index's storage dtype: T the rows as the kernels read them, Q the first pass's query operand (f16
+// for f16 and fp8 rows), Bits the type a row element is moved as. with_storage() is the one place a dtype becomes types; it
+// returns f(Storage<..>{}) for `dtype`.
+template <typename T_, typename Q_, typename Bits_> struct Storage { using T = T_; using Q = Q_; using Bits = Bits_; };
+template <typename F> auto with_storage(int dtype, F&& f) {
+    if (dtype == MMISS_F16) return f(Storage<_Float16, _Float16, _Float16>{});
+    if (dtype == MMISS_F8) return f(Storage<F8, _Float16, uint8_t>{});
+    return f(Storage<float, float, float>{});
+}
+template <typename S> constexpr bool is_f8 = std::is_same<typename S::T, F8>::value;
+
+// A set of the four per-row buffers for `cap` rows. Inverse norms (fp8 rows only) and tags are zero behind the rows: the score
+// GEMM reads the inverse norms of a whole 256-row tile, the scan the tags and inverse norms of a 16-row one.
+struct RowStore {
+    DevBuf rows, labels, inv, tags;
+    int alloc(const mmiss_index* ix, int64_t cap, hipStream_t st) {
+        MM_TRY(rows.alloc((size_t)cap * ix->dim * ix->elt));
+        MM_TRY(labels.alloc((size_t)cap * 8));
+        MM_TRY(tags.alloc((size_t)cap * 8));
+        MM_HIP(hipMemsetAsync(tags.p, 0, (size_t)cap * 8, st));
+        if (ix->dtype == MMISS_F8) {
+            MM_TRY(inv.alloc((size_t)cap * 4));
+            MM_HIP(hipMemsetAsync(inv.p, 0, (size_t)cap * 4, st));
+        }
+        return MMISS_OK;
+    }
+};
+
+// the index's row buffers and `s` trade places (the old ones leave with `s`)
+void swap_rows(mmiss_index* ix, RowStore& s) { ix->rows.swap(s.rows); ix->labels_d.swap(s.labels); ix->inv.swap(s.inv); ix->tags.swap(s.tags); }
+
+// Empty the index: no rows, and inverse norms and tags zero up to capacity (the invariant behind `count`); returns drained.
+int reset_rows(mmiss_index* ix, hipStream_t st) {
+    ix->count = 0;
+    ix->labels_h.clear();
+    ix->tags_h.clear();
+    if (ix->capacity == 0) return MMISS_OK;
+    if (ix->dtype == MMISS_F8) MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st));
+    MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st));
+    MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
 int index_reserve(mmiss_index* ix, int64_t need, hipStream_t st) {
     if (need <= ix->capacity) return MMISS_OK;
     int64_t cap = ix->capacity > 0 ? ix->capacity : 1024;
     while (cap < need) cap *= 2;
-    DevBuf nr, nl, ni, nt;
-    MM_TRY(nr.alloc((size_t)cap * ix->dim * ix->elt));
-    MM_TRY(nl.alloc((size_t)cap * 8));
-    MM_TRY(nt.alloc((size_t)cap * 8));
-    MM_HIP(hipMemsetAsync(nt.p, 0, (size_t)cap * 8, st));   // (tags are zero behind the rows: the scan reads whole 16-row tiles)
-    if (ix->dtype == MMISS_F8) {
-        // zero behind the rows: the score GEMM reads the inverse norms of a whole 256-row tile, the scan of a 16-row one
-        MM_TRY(ni.alloc((size_t)cap * 4));
-        MM_HIP(hipMemsetAsync(ni.p, 0, (size_t)cap * 4, st));
-    }
+    RowStore fresh;
+    MM_TRY(fresh.alloc(ix, cap, st));
     if (ix->count > 0) {
-        MM_HIP(hipMemcpyAsync(nr.p, ix->rows.p, (size_t)ix->count * ix->dim * ix->elt, hipMemcpyDeviceToDevice, st));
-        MM_HIP(hipMemcpyAsync(nl.p, ix->labels_d.p, (size_t)ix->count * 8, hipMemcpyDeviceToDevice, st));
-        if (ni.p) MM_HIP(hipMemcpyAsync(ni.p, ix->inv.p, (size_t)ix->count * 4, hipMemcpyDeviceToDevice, st));
-        MM_HIP(hipMemcpyAsync(nt.p, ix->tags.p, (size_t)ix->count * 8, hipMemcpyDeviceToDevice, st));
+        MM_HIP(hipMemcpyAsync(fresh.rows.p, ix->rows.p, (size_t)ix->count * ix->dim * ix->elt, hipMemcpyDeviceToDevice, st));
+        MM_HIP(hipMemcpyAsync(fresh.labels.p, ix->labels_d.p, (size_t)ix->count * 8, hipMemcpyDeviceToDevice, st));
+        if (fresh.inv.p) MM_HIP(hipMemcpyAsync(fresh.inv.p, ix->inv.p, (size_t)ix->count * 4, hipMemcpyDeviceToDevice, st));
+        MM_HIP(hipMemcpyAsync(fresh.tags.p, ix->tags.p, (size_t)ix->count * 8, hipMemcpyDeviceToDevice, st));
     }
     MM_HIP(hipStreamSynchronize(st));
-    std::swap(ix->rows.p, nr.p); std::swap(ix->rows.bytes, nr.bytes);
-    std::swap(ix->labels_d.p, nl.p); std::swap(ix->labels_d.bytes, nl.bytes);
-    std::swap(ix->inv.p, ni.p); std::swap(ix->inv.bytes, ni.bytes);
-    std::swap(ix->tags.p, nt.p); std::swap(ix->tags.bytes, nt.bytes);
+    swap_rows(ix, fresh);
     ix->capacity = cap;
     return MMISS_OK;
 }
@@ -130,17 +145,12 @@ int launch_f8_inv(mmiss_index* ix, int64_t row0, int64_t n, hipStream_t st) {
 int launch_normalize(mmiss_index* ix, const float* src_dev, void* dst, int64_t n, hipStream_t st, int64_t row0) {
     if (n <= 0) return MMISS_OK;
     MM_PROF("normalize_rows", st, 4.0 * n * ix->dim, (double)n * ix->dim * (4 + ix->elt));
-    const int grid = (int)((n + 3) / 4);
-    if (ix->dtype == MMISS_F16)
-        hipLaunchKernelGGL(normalize_rows_kernel<_Float16>, dim3(grid), dim3(256), 0, st, src_dev, (_Float16*)dst, n, ix->dim);
-    else if (ix->dtype == MMISS_F8) {
-        hipLaunchKernelGGL(normalize_rows_kernel<F8>, dim3(grid), dim3(256), 0, st, src_dev, (F8*)dst, n, ix->dim);
-        MM_HIP(hipGetLastError());
-        return launch_f8_inv(ix, row0, n, st);
-    } else
-        hipLaunchKernelGGL(normalize_rows_kernel<float>, dim3(grid), dim3(256), 0, st, src_dev, (float*)dst, n, ix->dim);
+    with_storage(ix->dtype, [&](auto s) {
+        using T = typename decltype(s)::T;
+        hipLaunchKernelGGL(normalize_rows_kernel<T>, dim3((int)((n + 3) / 4)), dim3(256), 0, st, src_dev, (T*)dst, n, ix->dim);
+    });
     MM_HIP(hipGetLastError());
-    return MMISS_OK;
+    return launch_f8_inv(ix, row0, n, st);   // (fp8 rows only)
 }
 
 // host copy of a (host or device) int64 array
@@ -175,24 +185,11 @@ int64_t find_row(const mmiss_index* ix, int64_t label) {
     return it - ix->labels_h.begin();
 }
 
-template <typename T, int NQT, int CAP, int GS = 8, bool FILT = false>
-int launch_scan_t(hipStream_t st, const ScanArgs& a, int slabs, int qtiles, int lds) {
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&scan_topk_kernel<T, NQT, CAP, GS, false, FILT>), lds));
-    hipLaunchKernelGGL((scan_topk_kernel<T, NQT, CAP, GS, false, FILT>), dim3(slabs, qtiles), dim3(256), lds, st, a);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-template <typename T, int NQT, bool FILT = false>
-int launch_scan_thr_t(hipStream_t st, const ScanArgs& a, int slabs, int qtiles, int lds) {
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&scan_topk_kernel<T, NQT, 32, 8, true, FILT>), lds));
-    hipLaunchKernelGGL((scan_topk_kernel<T, NQT, 32, 8, true, FILT>), dim3(slabs, qtiles), dim3(256), lds, st, a);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
+// a streaming scan launch: 16 * nqt queries per block in list mode (cap entries per query and wave) or, thr, in threshold mode
+// (the widen pass: every row reaching its query's threshold is appended to a.glist)
 struct ScanPlan {
     int nqt, cap, lds, slabs, qtiles, tiles_per_block;
+    bool thr;
 };
 
 constexpr int SCAN_LDS_LIMIT = 160 * 1024;
@@ -210,14 +207,11 @@ ScanPlan plan_scan(int D, int elt, int Q, int kp, int64_t N) {
     const int limit = SCAN_LDS_LIMIT;
     p.nqt = 1; p.cap = 64;
     if (kp <= 16 && Q > 16) {
-        for (int nqt : {4, 2}) {
-            const int NQ = 16 * nqt;
-            const int lds = (((NQ * (D * elt + 16)) + 15) & ~15) + 2 * 4 * NQ * 32 * 4 + 2 * 4 * NQ * 4;
-            if (lds <= limit && (Q > 16 * nqt / 2)) { p.nqt = nqt; p.cap = 32; break; }
-        }
+        for (int nqt : {4, 2})
+            if (scan_lds_bytes(D, elt, nqt, 32) <= limit && (Q > 16 * nqt / 2)) { p.nqt = nqt; p.cap = 32; break; }
     }
     const int NQ = 16 * p.nqt;
-    p.lds = (((NQ * (D * elt + 16)) + 15) & ~15) + 2 * 4 * NQ * p.cap * 4 + 2 * 4 * NQ * 4;
+    p.lds = scan_lds_bytes(D, elt, p.nqt, p.cap);
     p.qtiles = (Q + NQ - 1) / NQ;
     const int64_t ntiles = (N + 15) / 16;
     const int blocks_per_cu = std::max(1, std::min(8, limit / p.lds));
@@ -232,41 +226,55 @@ ScanPlan plan_scan(int D, int elt, int Q, int kp, int64_t N) {
     return p;
 }
 
+// The widen pass's scan of Qf queries: the widest query tile the flagged queries fill AND whose staged query block fits the
+// CU's LDS (f32 rows at the reference's D = 768: 64 queries x 3088 B = 193 KB do not, 32 do). nqt = 1 always fits:
+// mmiss_index_create admits only dims whose 16-query block does.
+ScanPlan plan_sweep(int D, int qelt, int Qf, int64_t N) {
+    ScanPlan p{};
+    p.thr = true;
+    p.cap = 32;
+    p.nqt = Qf > 32 ? 4 : Qf > 16 ? 2 : 1;
+    while (p.nqt > 1 && sweep_scan_lds(D, qelt, p.nqt) > SCAN_LDS_LIMIT) p.nqt >>= 1;
+    p.lds = sweep_scan_lds(D, qelt, p.nqt);
+    p.qtiles = (Qf + 16 * p.nqt - 1) / (16 * p.nqt);
+    const int64_t ntiles = (N + 15) / 16;
+    const int per_cu = std::max(1, std::min(8, SCAN_LDS_LIMIT / p.lds));
+    int64_t target = std::max<int64_t>(1, (int64_t)256 * per_cu / p.qtiles);
+    int64_t tpb = std::max<int64_t>(4, (((ntiles + target - 1) / target) + 3) / 4 * 4);
+    p.tiles_per_block = (int)tpb;
+    p.slabs = (int)((ntiles + tpb - 1) / tpb);
+    return p;
+}
+
+// The one map from a scan plan to its kernel: list mode keeps 64 entries per query and wave in a 16-query tile and 32 in the
+// wider ones (plan_scan's cap), threshold mode 32 in all; rows in groups of 8, or of 16 for unfiltered f16 lists of a 16-query
+// tile with scan_group = 16. FILT: a filtered query (mmiss_index_query_filtered), the same plans.
+typedef void (*ScanKernel)(ScanArgs);
+template <typename T, bool THR, bool FILT>
+ScanKernel scan_kernel(const ScanPlan& p) {
+    if (p.nqt == 4) return &scan_topk_kernel<T, 4, 32, 8, THR, FILT>;
+    if (p.nqt == 2) return &scan_topk_kernel<T, 2, 32, 8, THR, FILT>;
+    if constexpr (std::is_same<T, _Float16>::value && !THR && !FILT)
+        if (mmiss_option("scan_group", 8) == 16) return &scan_topk_kernel<T, 1, 64, 16, false, false>;
+    return &scan_topk_kernel<T, 1, THR ? 32 : 64, 8, THR, FILT>;
+}
+
 int launch_scan(mmiss_index* ix, hipStream_t st, const ScanArgs& a, const ScanPlan& p) {
+    // (threshold mode: every query tile reads the whole index)
     const double flops = 2.0 * a.Q * (double)a.N * a.D;
-    const double bytes = (double)a.N * a.D * ix->elt;
-    MM_PROF(ix->dtype == MMISS_F16 ? "scan_topk_f16" : ix->dtype == MMISS_F8 ? "scan_topk_f8" : "scan_topk_f32", st, flops, bytes);
-    if (a.tags) {   // filtered query (mmiss_index_query_filtered): the same plans, FILT instantiations
-        if (ix->dtype == MMISS_F8) {
-            if (p.nqt == 1) return launch_scan_t<F8, 1, 64, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-            if (p.nqt == 2) return launch_scan_t<F8, 2, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-            return launch_scan_t<F8, 4, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-        }
-        if (ix->dtype == MMISS_F16) {
-            if (p.nqt == 1) return launch_scan_t<_Float16, 1, 64, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-            if (p.nqt == 2) return launch_scan_t<_Float16, 2, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-            return launch_scan_t<_Float16, 4, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-        }
-        if (p.nqt == 1) return launch_scan_t<float, 1, 64, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-        if (p.nqt == 2) return launch_scan_t<float, 2, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-        return launch_scan_t<float, 4, 32, 8, true>(st, a, p.slabs, p.qtiles, p.lds);
-    }
-    if (ix->dtype == MMISS_F8) {
-        if (p.nqt == 1) return launch_scan_t<F8, 1, 64>(st, a, p.slabs, p.qtiles, p.lds);
-        if (p.nqt == 2) return launch_scan_t<F8, 2, 32>(st, a, p.slabs, p.qtiles, p.lds);
-        return launch_scan_t<F8, 4, 32>(st, a, p.slabs, p.qtiles, p.lds);
-    }
-    if (ix->dtype == MMISS_F16) {
-        if (p.nqt == 1) {
-            if (mmiss_option("scan_group", 8) == 16) return launch_scan_t<_Float16, 1, 64, 16>(st, a, p.slabs, p.qtiles, p.lds);
-            return launch_scan_t<_Float16, 1, 64>(st, a, p.slabs, p.qtiles, p.lds);
-        }
-        if (p.nqt == 2) return launch_scan_t<_Float16, 2, 32>(st, a, p.slabs, p.qtiles, p.lds);
-        return launch_scan_t<_Float16, 4, 32>(st, a, p.slabs, p.qtiles, p.lds);
-    }
-    if (p.nqt == 1) return launch_scan_t<float, 1, 64>(st, a, p.slabs, p.qtiles, p.lds);
-    if (p.nqt == 2) return launch_scan_t<float, 2, 32>(st, a, p.slabs, p.qtiles, p.lds);
-    return launch_scan_t<float, 4, 32>(st, a, p.slabs, p.qtiles, p.lds);
+    const double bytes = (p.thr ? (double)p.qtiles : 1.0) * a.N * a.D * ix->elt;
+    const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
+    MM_PROF(p.thr ? (f16 ? "sweep_scan_f16" : f8 ? "sweep_scan_f8" : "sweep_scan_f32")
+                  : (f16 ? "scan_topk_f16" : f8 ? "scan_topk_f8" : "scan_topk_f32"), st, flops, bytes);
+    const ScanKernel kern = with_storage(ix->dtype, [&](auto s) {
+        using T = typename decltype(s)::T;
+        if (p.thr) return a.tags ? scan_kernel<T, true, true>(p) : scan_kernel<T, true, false>(p);
+        return a.tags ? scan_kernel<T, false, true>(p) : scan_kernel<T, false, false>(p);
+    });
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), p.lds));
+    hipLaunchKernelGGL(kern, dim3(p.slabs, p.qtiles), dim3(256), p.lds, st, a);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
 }
 
 // merge L per-slab lists of every query into its candidate page; above 64 lists in two levels so that a single
@@ -339,9 +347,6 @@ extern "C" int mmiss_index_destroy(mmiss_index* ix) {
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
     if (ix->own_stream) (void)hipStreamDestroy(ix->own_stream);
-    if (ix->pin) (void)hipHostFree(ix->pin);
-    if (ix->swp_pin) (void)hipHostFree(ix->swp_pin);
-    if (ix->dist_pin) (void)hipHostFree(ix->dist_pin);
     if (ix->done_ev) (void)hipEventDestroy(ix->done_ev);
     delete ix;
     return MMISS_OK;
@@ -376,16 +381,8 @@ extern "C" int mmiss_index_clear(mmiss_index* ix) {
     if (!ix) MM_FAIL(MMISS_ERR_ARG, "null index");
     std::lock_guard<std::mutex> lk(ix->mu);
     MM_NO_PENDING(ix, "mmiss_index_clear");
-    if (ix->capacity > 0) {   // (inverse norms and tags are zero behind the rows)
-        MM_TRY(mmiss_use_device(ix->device));
-        if (ix->dtype == MMISS_F8) MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, ix->stream()));
-        MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, ix->stream()));
-        MM_HIP(hipStreamSynchronize(ix->stream()));
-    }
-    ix->count = 0;
-    ix->labels_h.clear();
-    ix->tags_h.clear();
-    return MMISS_OK;
+    if (ix->capacity > 0) MM_TRY(mmiss_use_device(ix->device));
+    return reset_rows(ix, ix->stream());
 }
 
 // ================================================================================================ mutation
@@ -477,49 +474,29 @@ extern "C" int mmiss_index_remove(mmiss_index* ix, const int64_t* labels, int64_
     if (removed) *removed = ndrop;
     if (ndrop == 0) return MMISS_OK;
     const int64_t keep = ix->count - ndrop;
+    if (keep == 0) return reset_rows(ix, st);   // every row removed
     std::vector<int64_t> map((size_t)keep), nl((size_t)keep);
     std::vector<uint64_t> ntag((size_t)keep);
     for (int64_t r = 0, o = 0; r < ix->count; ++r)
         if (!drop[r]) { map[o] = r; nl[o] = ix->labels_h[r]; ntag[o] = ix->tags_h[r]; ++o; }
-    if (keep > 0) {
-        // stable compaction into fresh buffers (row order == label order is the tie-break contract)
-        DevBuf nr, nlab, ninv, ntg;
-        MM_TRY(ntg.alloc((size_t)ix->capacity * 8));
-        MM_HIP(hipMemsetAsync(ntg.p, 0, (size_t)ix->capacity * 8, st));
-        MM_HIP(hipMemcpyAsync(ntg.p, ntag.data(), (size_t)keep * 8, hipMemcpyHostToDevice, st));   // (the host mirror, compacted)
-        MM_TRY(nr.alloc((size_t)ix->capacity * ix->dim * ix->elt));
-        MM_TRY(nlab.alloc((size_t)ix->capacity * 8));
-        if (ix->dtype == MMISS_F8) {
-            MM_TRY(ninv.alloc((size_t)ix->capacity * 4));
-            MM_HIP(hipMemsetAsync(ninv.p, 0, (size_t)ix->capacity * 4, st));
-        }
-        MM_TRY(ix->map.ensure((size_t)keep * 8));
-        MM_HIP(hipMemcpyAsync(ix->map.p, map.data(), (size_t)keep * 8, hipMemcpyHostToDevice, st));
-        const int grid = (int)std::min<int64_t>(4096, (keep * ix->dim + 255) / 256);
-        if (ix->dtype == MMISS_F16)
-            hipLaunchKernelGGL(gather_rows_kernel<_Float16>, dim3(grid), dim3(256), 0, st, ix->rows.as<_Float16>(),
-                               ix->map.as<int64_t>(), nr.as<_Float16>(), keep, ix->dim);
-        else if (ix->dtype == MMISS_F8) {
-            hipLaunchKernelGGL(gather_rows_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, ix->rows.as<uint8_t>(),
-                               ix->map.as<int64_t>(), nr.as<uint8_t>(), keep, ix->dim);
+    // stable compaction into fresh buffers (row order == label order is the tie-break contract)
+    RowStore fresh;
+    MM_TRY(fresh.alloc(ix, ix->capacity, st));
+    MM_HIP(hipMemcpyAsync(fresh.tags.p, ntag.data(), (size_t)keep * 8, hipMemcpyHostToDevice, st));   // (the host mirror, compacted)
+    MM_TRY(ix->map.ensure((size_t)keep * 8));
+    MM_HIP(hipMemcpyAsync(ix->map.p, map.data(), (size_t)keep * 8, hipMemcpyHostToDevice, st));
+    with_storage(ix->dtype, [&](auto s) {
+        using B = typename decltype(s)::Bits;
+        hipLaunchKernelGGL(gather_rows_kernel<B>, dim3((int)std::min<int64_t>(4096, (keep * ix->dim + 255) / 256)), dim3(256), 0, st,
+                           ix->rows.as<B>(), ix->map.as<int64_t>(), fresh.rows.as<B>(), keep, ix->dim);
+        if constexpr (is_f8<decltype(s)>)
             hipLaunchKernelGGL(gather_rows_kernel<float>, dim3((int)std::min<int64_t>(4096, (keep + 255) / 256)), dim3(256), 0, st,
-                               ix->inv.as<float>(), ix->map.as<int64_t>(), ninv.as<float>(), keep, 1);
-        } else
-            hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(grid), dim3(256), 0, st, ix->rows.as<float>(),
-                               ix->map.as<int64_t>(), nr.as<float>(), keep, ix->dim);
-        MM_HIP(hipGetLastError());
-        MM_HIP(hipMemcpyAsync(nlab.p, nl.data(), (size_t)keep * 8, hipMemcpyHostToDevice, st));
-        MM_HIP(hipStreamSynchronize(st));
-        std::swap(ix->rows.p, nr.p); std::swap(ix->rows.bytes, nr.bytes);
-        std::swap(ix->labels_d.p, nlab.p); std::swap(ix->labels_d.bytes, nlab.bytes);
-        std::swap(ix->inv.p, ninv.p); std::swap(ix->inv.bytes, ninv.bytes);
-        std::swap(ix->tags.p, ntg.p); std::swap(ix->tags.bytes, ntg.bytes);
-    }
-    else if (ix->capacity > 0) {   // every row removed: inverse norms and tags stay zero behind `count` (mmiss_index_clear's invariant)
-        if (ix->dtype == MMISS_F8) MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st));
-        MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st));
-        MM_HIP(hipStreamSynchronize(st));
-    }
+                               ix->inv.as<float>(), ix->map.as<int64_t>(), fresh.inv.as<float>(), keep, 1);
+    });
+    MM_HIP(hipGetLastError());
+    MM_HIP(hipMemcpyAsync(fresh.labels.p, nl.data(), (size_t)keep * 8, hipMemcpyHostToDevice, st));
+    MM_HIP(hipStreamSynchronize(st));
+    swap_rows(ix, fresh);
     ix->labels_h.swap(nl);
     ix->tags_h.swap(ntag);
     ix->count = keep;
@@ -546,15 +523,15 @@ extern "C" int mmiss_index_get(mmiss_index* ix, const int64_t* labels, int64_t n
     float* dst = out;
     if (!out_dev) { MM_TRY(ix->stage.ensure((size_t)n * ix->dim * 4)); dst = ix->stage.as<float>(); }
     const int grid = (int)std::min<int64_t>(4096, (n * ix->dim + 255) / 256);
-    if (ix->dtype == MMISS_F16)
-        hipLaunchKernelGGL(gather_rows_f32_kernel<_Float16>, dim3(grid), dim3(256), 0, st, ix->rows.as<_Float16>(),
-                           ix->map.as<int64_t>(), dst, n, ix->dim);
-    else if (ix->dtype == MMISS_F8)   // the vectors the rows represent: values x inverse norm
-        hipLaunchKernelGGL(gather_rows_f8_f32_kernel, dim3(grid), dim3(256), 0, st, ix->rows.as<F8>(), ix->inv.as<float>(),
-                           ix->map.as<int64_t>(), dst, n, ix->dim);
-    else
-        hipLaunchKernelGGL(gather_rows_f32_kernel<float>, dim3(grid), dim3(256), 0, st, ix->rows.as<float>(),
-                           ix->map.as<int64_t>(), dst, n, ix->dim);
+    with_storage(ix->dtype, [&](auto s) {
+        using T = typename decltype(s)::T;
+        if constexpr (is_f8<decltype(s)>)   // the vectors the rows represent: values x inverse norm
+            hipLaunchKernelGGL(gather_rows_f8_f32_kernel, dim3(grid), dim3(256), 0, st, ix->rows.as<F8>(), ix->inv.as<float>(),
+                               ix->map.as<int64_t>(), dst, n, ix->dim);
+        else
+            hipLaunchKernelGGL(gather_rows_f32_kernel<T>, dim3(grid), dim3(256), 0, st, ix->rows.as<T>(), ix->map.as<int64_t>(), dst,
+                               n, ix->dim);
+    });
     MM_HIP(hipGetLastError());
     if (!out_dev) MM_HIP(hipMemcpyAsync(out, dst, (size_t)n * ix->dim * 4, hipMemcpyDeviceToHost, st));
     MM_HIP(hipStreamSynchronize(st));
@@ -671,39 +648,27 @@ int launch_rerank(mmiss_index* ix, hipStream_t st, const RerankArgs& r, int bloc
     const int lds = npow * 8 + 16;
     MM_PROF("rerank", st, 2.0 * blocks * r.ncand * r.D, (double)blocks * r.ncand * r.D * ix->elt);
     const int threads = r.ncand >= 16 ? 1024 : 256;  // one wave per candidate row: more waves hide the gather latency
-    if (ix->dtype == MMISS_F16) {
-        if (lds > 32768) MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&rerank_kernel<_Float16>), lds));
-        hipLaunchKernelGGL(rerank_kernel<_Float16>, dim3(blocks), dim3(threads), lds, st, r);
-    } else if (ix->dtype == MMISS_F8) {
-        if (lds > 32768) MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&rerank_kernel<F8>), lds));
-        hipLaunchKernelGGL(rerank_kernel<F8>, dim3(blocks), dim3(threads), lds, st, r);
-    } else {
-        if (lds > 32768) MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&rerank_kernel<float>), lds));
-        hipLaunchKernelGGL(rerank_kernel<float>, dim3(blocks), dim3(threads), lds, st, r);
-    }
+    void (*kern)(RerankArgs) = with_storage(ix->dtype, [](auto s) { return &rerank_kernel<typename decltype(s)::T>; });
+    if (lds > 32768) MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, st, r);
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }
 
-// Exhaustive canonical pass for the queries listed in `which`: canonical distance of every row (canonical_scan_kernel), the
-// k best by (distance, row) picked on the host (a bounded heap: O(N log k)), final ordering / labels / counts by the ordinary
-// rerank kernel with "nothing was left out" (tau = -inf).
-int exhaustive_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& which, int k, int64_t* d_lab, float* d_dist,
-                       int32_t* d_cnt) {
+// Exhaustive canonical pass for the queries of `pd` listed in `which`: canonical distance of every row (canonical_scan_kernel),
+// the k best by (distance, row) picked on the host (a bounded heap: O(N log k)), final ordering / labels / counts by the
+// ordinary rerank kernel with "nothing was left out" (tau = -inf).
+int exhaustive_queries(mmiss_index* ix, hipStream_t st, const mmiss_index::Pending& pd, const std::vector<int32_t>& which) {
     const int64_t N = ix->count;
     const int D = ix->dim, KP = 32;
-    const int kk = (int)std::min<int64_t>(k, N);
+    const int kk = (int)std::min<int64_t>(pd.k, N);
     const int kkpad = (int)round_up(std::max(kk, 1), KP);
     const int nq = (int)which.size();
     if (nq == 0 || N <= 0) return MMISS_OK;
     MM_TRY(ix->dist_all.ensure((size_t)N * 4));
     // the distances come back through a PINNED block (a pageable destination makes the copy synchronous and slow: ADVICE r3)
-    if (ix->dist_pin_rows < N) {
-        if (ix->dist_pin) { MM_HIP(hipHostFree(ix->dist_pin)); ix->dist_pin = nullptr; ix->dist_pin_rows = 0; }
-        MM_HIP(hipHostMalloc(reinterpret_cast<void**>(&ix->dist_pin), (size_t)N * 4, hipHostMallocDefault));
-        ix->dist_pin_rows = N;
-    }
-    const float* dist = ix->dist_pin;
+    MM_TRY(ix->dist_pin.ensure((size_t)N * 4, st));
+    const float* dist = ix->dist_pin.as<float>();
     std::vector<int32_t> cand((size_t)nq * kkpad, -1);
     typedef std::pair<float, int32_t> Ent;  // (distance, row); NaN distances never enter
     for (int i = 0; i < nq; ++i) {
@@ -711,26 +676,21 @@ int exhaustive_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_
         {
             MM_PROF("canonical_scan", st, 2.0 * N * D, (double)N * D * ix->elt);
             const int grid = (int)std::min<int64_t>(8192, (N + 15) / 16);
-            if (ix->dtype == MMISS_F16)
-                hipLaunchKernelGGL(canonical_scan_kernel<_Float16>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
-                                   ix->qn.as<float>() + (size_t)q * D, ix->dist_all.as<float>(), (const float*)nullptr);
-            else if (ix->dtype == MMISS_F8)
-                hipLaunchKernelGGL(canonical_scan_kernel<F8>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
+            with_storage(ix->dtype, [&](auto s) {   // (inv: the inverse norms of fp8 rows, null for the others)
+                hipLaunchKernelGGL(canonical_scan_kernel<typename decltype(s)::T>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
                                    ix->qn.as<float>() + (size_t)q * D, ix->dist_all.as<float>(), (const float*)ix->inv.as<float>());
-            else
-                hipLaunchKernelGGL(canonical_scan_kernel<float>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
-                                   ix->qn.as<float>() + (size_t)q * D, ix->dist_all.as<float>(), (const float*)nullptr);
+            });
             MM_HIP(hipGetLastError());
         }
-        MM_HIP(hipMemcpyAsync(ix->dist_pin, ix->dist_all.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+        MM_HIP(hipMemcpyAsync(ix->dist_pin.p, ix->dist_all.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
         MM_HIP(hipStreamSynchronize(st));
         std::priority_queue<Ent> heap;  // max-heap: top = the worst of the best kk so far, by (distance, row)
-        const bool filt = ix->q_filt;   // filtered query: rows it does not admit never enter (host mirror of the tags)
-        const uint64_t rq = filt ? ix->q_req[(size_t)q] : 0, rx = filt ? ix->q_exc[(size_t)q] : 0;
+        // filtered query: rows it does not admit never enter (host mirror of the tags)
+        const uint64_t rq = pd.filt ? pd.req[(size_t)q] : 0, rx = pd.filt ? pd.exc[(size_t)q] : 0;
         for (int64_t r = 0; r < N; ++r) {
             const float d = dist[(size_t)r];
             if (d != d) continue;
-            if (filt && !tag_admits_h(ix->tags_h[(size_t)r], rq, rx)) continue;
+            if (pd.filt && !tag_admits_h(ix->tags_h[(size_t)r], rq, rx)) continue;
             if ((int)heap.size() < kk) heap.push(Ent(d, (int32_t)r));
             else if (Ent(d, (int32_t)r) < heap.top()) { heap.pop(); heap.push(Ent(d, (int32_t)r)); }
         }
@@ -746,8 +706,8 @@ int exhaustive_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_
     RerankArgs r{};
     r.rows = ix->rows.p; r.D = D; r.inv = ix->inv.as<float>(); r.qn = ix->qn.as<float>(); r.cand = ix->cand2.as<int32_t>();
     r.cand_stride = kkpad; r.ncand = kkpad; r.group_mode = 0; r.nrows = N;
-    r.labels = ix->labels_d.as<int64_t>(); r.k = k;
-    r.out_labels = d_lab; r.out_dist = d_dist; r.out_count = d_cnt;
+    r.labels = ix->labels_d.as<int64_t>(); r.k = pd.k;
+    r.out_labels = pd.d_lab; r.out_dist = pd.d_dist; r.out_count = pd.d_cnt;
     r.qmap = ix->qmap.as<int32_t>();
     MM_TRY(launch_rerank(ix, st, r, nq));
     MM_HIP(hipStreamSynchronize(st));  // (`cand` and `which` leave scope with the caller)
@@ -778,36 +738,51 @@ int strip_length(int Mq, int64_t nbn, int64_t ncol) {
     return strip;
 }
 
-// The widen pass for the queries listed in `which` (original indices): ONE threshold pass over the index for all of them
-// (thr_q = c_k - eps_q, left in ix->thr by the first pass's re-rank), the canonical re-rank of the rows it collected, and the
-// exhaustive pass for the lists that overflowed. Results overwrite the queries' rows of d_lab / d_dist / d_cnt. Returns with
-// the stream drained.
-int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& which, int Q_all, int k, int64_t* d_lab,
-                  float* d_dist, int32_t* d_cnt) {
+// the strip score GEMM on the staggered loop of the persistent encoder GEMM (gemm_bf16_p256.h; round 3): D % 128 == 0
+bool strip_v3(const mmiss_index* ix) { return mmiss_option("score_strip_v3", 1) != 0 && (ix->dim % 128) == 0 && ix->dim >= 256; }
+
+// the rows the strip score GEMM serves: f16, and fp8 unless score_f8_gemm = 0 (round 4: gemm256s_kernel<_Float16, .., W8>
+// widens the codes to f16 in its operand load)
+bool strip_gemm_rows(const mmiss_index* ix) {
+    return ix->dtype == MMISS_F16 || (ix->dtype == MMISS_F8 && mmiss_option("score_f8_gemm", 1) != 0);
+}
+
+// the strip score GEMM of M queries `qs` against the index's first N rows: fp8 rows in the W8 form, f16 rows on the staggered
+// loop or, v3 = false, on the strip kernel of gemm_bf16_256.h
+int launch_strip_gemm(mmiss_index* ix, hipStream_t st, bool v3, const void* qs, const GemmEpi& ep, int M, int N, int strip,
+                      const StripFilter* flt) {
+    if (ix->dtype == MMISS_F8) return launch_gemm256s<_Float16, true>(st, qs, ix->rows.p, ep, M, N, ix->dim, strip, flt);
+    if (v3) return launch_gemm256s<_Float16>(st, qs, ix->rows.p, ep, M, N, ix->dim, strip, flt);
+    return launch_gemm256_strip<_Float16>(st, qs, ix->rows.p, ep, M, N, ix->dim, strip, flt);
+}
+
+// The widen pass for the queries of `pd` listed in `which` (original indices): ONE threshold pass over the index for all of
+// them (thr_q = c_k - eps_q, left in ix->thr by the first pass's re-rank), the canonical re-rank of the rows it collected, and
+// the exhaustive pass for the lists that overflowed. Results overwrite the queries' rows of pd's outputs. Returns with the
+// stream drained.
+int sweep_queries(mmiss_index* ix, hipStream_t st, const mmiss_index::Pending& pd, const std::vector<int32_t>& which) {
     const int Qf = (int)which.size(), D = ix->dim;
     const int64_t N = ix->count;
     if (Qf == 0 || N <= 0) return MMISS_OK;
     // the score GEMM for an f16 index once the flagged queries fill a quarter of a 256-query tile (it costs about what 1.2
     // streaming scans cost, and a scan serves 64 queries), the scan otherwise
-    const bool gemm8 = ix->dtype == MMISS_F8 && mmiss_option("score_f8_gemm", 1) != 0;
     // (filtered queries: always the scan, whose FILT form collects admitted rows only; the score GEMM has no filtered epilogue)
-    const bool gemm = !ix->q_filt && (ix->dtype == MMISS_F16 || gemm8) && (D % 128) == 0 && D >= 256 &&
-                      Qf > mmiss_option("sweep_gemm_min_q", 64) && mmiss_option("score_strip_v3", 1) != 0;
+    const bool gemm = !pd.filt && strip_gemm_rows(ix) && strip_v3(ix) && Qf > mmiss_option("sweep_gemm_min_q", 64);
     const int Qfp = (int)round_up(Qf, 256);
     MM_TRY(ix->swp_cnt.ensure((size_t)Qfp * 4));
     MM_TRY(ix->swp_list.ensure((size_t)Qf * SWEEP_CAP * 4));
     MM_HIP(hipMemsetAsync(ix->swp_cnt.p, 0, (size_t)Qfp * 4, st));
     // Every query of the call flagged (the encoder's own embeddings as the index: all of them, every call): the first pass's
     // operands are the sweep's operands — no gather, no map, nothing crosses PCIe. Otherwise the flagged queries are compacted.
-    const bool all = Qf == Q_all;
+    const bool all = Qf == pd.Q;
     const void* qs_sw = ix->qs.p;          // [>= Qfp rows][D] scan operand (rows >= Qf are zero or masked by thr = +inf)
     const float* thr_sw = ix->thr.as<float>();
     const int32_t* qmap_sw = nullptr;
-    const uint64_t* fm_sw = ix->fmask.as<uint64_t>();   // filtered: [Qf] required, then [Qf] excluded masks, in the sweep's order
+    const uint64_t* fm_sw = pd.d_mask;     // filtered: [Qf] required, then [Qf] excluded masks, in the sweep's order
     std::vector<uint64_t> fm2;
-    if (!all && ix->q_filt) {
+    if (!all && pd.filt) {
         fm2.resize((size_t)Qf * 2);
-        for (int i = 0; i < Qf; ++i) { fm2[i] = ix->q_req[(size_t)which[i]]; fm2[Qf + i] = ix->q_exc[(size_t)which[i]]; }
+        for (int i = 0; i < Qf; ++i) { fm2[i] = pd.req[(size_t)which[i]]; fm2[Qf + i] = pd.exc[(size_t)which[i]]; }
         MM_TRY(ix->fmask2.ensure((size_t)Qf * 16));
         MM_HIP(hipMemcpyAsync(ix->fmask2.p, fm2.data(), (size_t)Qf * 16, hipMemcpyHostToDevice, st));
         fm_sw = ix->fmask2.as<uint64_t>();
@@ -822,13 +797,11 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
         MM_HIP(hipMemcpyAsync(ix->qmap64.p, map64.data(), (size_t)Qf * 8, hipMemcpyHostToDevice, st));
         MM_HIP(hipStreamSynchronize(st));   // (pageable sources: `map64` goes out of scope)
         if (Qfp > Qf) MM_HIP(hipMemsetAsync(ix->qs2.as<char>() + (size_t)Qf * D * ix->qelt(), 0, (size_t)(Qfp - Qf) * D * ix->qelt(), st));
-        const int grid = (int)std::min<int64_t>(4096, ((int64_t)Qf * D + 255) / 256);
-        if (ix->dtype != MMISS_F32)   // (f16 query operand for f16 and fp8 rows)
-            hipLaunchKernelGGL(gather_rows_kernel<_Float16>, dim3(grid), dim3(256), 0, st, ix->qs.as<_Float16>(),
-                               ix->qmap64.as<int64_t>(), ix->qs2.as<_Float16>(), (int64_t)Qf, D);
-        else
-            hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(grid), dim3(256), 0, st, ix->qs.as<float>(),
-                               ix->qmap64.as<int64_t>(), ix->qs2.as<float>(), (int64_t)Qf, D);
+        with_storage(ix->dtype, [&](auto s) {   // (f16 query operand for f16 and fp8 rows)
+            using QT = typename decltype(s)::Q;
+            hipLaunchKernelGGL(gather_rows_kernel<QT>, dim3((int)std::min<int64_t>(4096, ((int64_t)Qf * D + 255) / 256)), dim3(256), 0, st,
+                               ix->qs.as<QT>(), ix->qmap64.as<int64_t>(), ix->qs2.as<QT>(), (int64_t)Qf, D);
+        });
         MM_HIP(hipGetLastError());
         hipLaunchKernelGGL(gather_rows_kernel<float>, dim3((Qf + 255) / 256), dim3(256), 0, st, ix->thr.as<float>(),
                            ix->qmap64.as<int64_t>(), ix->thr2.as<float>(), (int64_t)Qf, 1);
@@ -844,61 +817,20 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
         flt.tau = thr_sw; flt.tau_stride = 1; flt.cnt = ix->swp_cnt.as<int32_t>();
         flt.buf_s = nullptr; flt.buf_g = ix->swp_list.as<int32_t>(); flt.cap = SWEEP_CAP; flt.bn_begin = 0;
         const int strip = strip_length(Qfp, nbn, nbn);
-        MM_PROF(gemm8 ? "sweep_gemm_f8" : "sweep_gemm_f16", st, 2.0 * Qf * (double)N * D, (double)N * D * ix->elt);
-        if (gemm8) MM_TRY((launch_gemm256s<_Float16, true>(st, qs_sw, ix->rows.p, ep, Qfp, (int)Npad, D, strip, &flt)));
-        else MM_TRY((launch_gemm256s<_Float16>(st, qs_sw, ix->rows.p, ep, Qfp, (int)Npad, D, strip, &flt)));
+        MM_PROF(ix->dtype == MMISS_F8 ? "sweep_gemm_f8" : "sweep_gemm_f16", st, 2.0 * Qf * (double)N * D, (double)N * D * ix->elt);
+        MM_TRY(launch_strip_gemm(ix, st, true, qs_sw, ep, Qfp, (int)Npad, strip, &flt));
         ix->stat_pages += 1;
     } else {
+        const ScanPlan p = plan_sweep(D, ix->qelt(), Qf, N);
+        if (p.lds > SCAN_LDS_LIMIT)
+            MM_FAIL(MMISS_ERR_UNSUPPORTED, "widen pass: a 16-query block of dim %d does not fit the LDS (%d bytes)", D, p.lds);
         ScanArgs a{};
         a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>(); a.qs = qs_sw; a.Q = Qf;
         a.thr = thr_sw; a.gcnt = ix->swp_cnt.as<int32_t>(); a.glist = ix->swp_list.as<int32_t>(); a.gcap = SWEEP_CAP;
-        if (ix->q_filt) { a.tags = ix->tags.as<uint64_t>(); a.req = fm_sw; a.exc = fm_sw + Qf; }
-        // the widest query tile the flagged queries fill AND whose staged query block fits the CU's LDS (f32 rows at the
-        // reference's D = 768: 64 queries x 3088 B = 193 KB do not, 32 do). nqt = 1 always fits: mmiss_index_create
-        // admits only dims whose 16-query block does.
-        int nqt = Qf > 32 ? 4 : Qf > 16 ? 2 : 1;
-        while (nqt > 1 && sweep_scan_lds(D, ix->qelt(), nqt) > SCAN_LDS_LIMIT) nqt >>= 1;
-        const int NQ = 16 * nqt;
-        const int lds = sweep_scan_lds(D, ix->qelt(), nqt);
-        if (lds > SCAN_LDS_LIMIT)
-            MM_FAIL(MMISS_ERR_UNSUPPORTED, "widen pass: a 16-query block of dim %d does not fit the LDS (%d bytes)", D, lds);
-        const int qtiles = (Qf + NQ - 1) / NQ;
-        const int64_t ntiles = (N + 15) / 16;
-        const int per_cu = std::max(1, std::min(8, SCAN_LDS_LIMIT / lds));
-        int64_t target = std::max<int64_t>(1, (int64_t)256 * per_cu / qtiles);
-        int64_t tpb = std::max<int64_t>(4, (((ntiles + target - 1) / target) + 3) / 4 * 4);
-        a.tiles_per_block = (int)tpb;
-        const int slabs = (int)((ntiles + tpb - 1) / tpb);
-        MM_PROF(ix->dtype == MMISS_F16 ? "sweep_scan_f16" : ix->dtype == MMISS_F8 ? "sweep_scan_f8" : "sweep_scan_f32", st,
-                2.0 * Qf * (double)N * D, (double)qtiles * N * D * ix->elt);
-        if (ix->q_filt) {
-            if (ix->dtype == MMISS_F16) {
-                if (nqt == 4) MM_TRY((launch_scan_thr_t<_Float16, 4, true>(st, a, slabs, qtiles, lds)));
-                else if (nqt == 2) MM_TRY((launch_scan_thr_t<_Float16, 2, true>(st, a, slabs, qtiles, lds)));
-                else MM_TRY((launch_scan_thr_t<_Float16, 1, true>(st, a, slabs, qtiles, lds)));
-            } else if (ix->dtype == MMISS_F8) {
-                if (nqt == 4) MM_TRY((launch_scan_thr_t<F8, 4, true>(st, a, slabs, qtiles, lds)));
-                else if (nqt == 2) MM_TRY((launch_scan_thr_t<F8, 2, true>(st, a, slabs, qtiles, lds)));
-                else MM_TRY((launch_scan_thr_t<F8, 1, true>(st, a, slabs, qtiles, lds)));
-            } else {
-                if (nqt == 4) MM_TRY((launch_scan_thr_t<float, 4, true>(st, a, slabs, qtiles, lds)));
-                else if (nqt == 2) MM_TRY((launch_scan_thr_t<float, 2, true>(st, a, slabs, qtiles, lds)));
-                else MM_TRY((launch_scan_thr_t<float, 1, true>(st, a, slabs, qtiles, lds)));
-            }
-        } else if (ix->dtype == MMISS_F16) {
-            if (nqt == 4) MM_TRY((launch_scan_thr_t<_Float16, 4>(st, a, slabs, qtiles, lds)));
-            else if (nqt == 2) MM_TRY((launch_scan_thr_t<_Float16, 2>(st, a, slabs, qtiles, lds)));
-            else MM_TRY((launch_scan_thr_t<_Float16, 1>(st, a, slabs, qtiles, lds)));
-        } else if (ix->dtype == MMISS_F8) {
-            if (nqt == 4) MM_TRY((launch_scan_thr_t<F8, 4>(st, a, slabs, qtiles, lds)));
-            else if (nqt == 2) MM_TRY((launch_scan_thr_t<F8, 2>(st, a, slabs, qtiles, lds)));
-            else MM_TRY((launch_scan_thr_t<F8, 1>(st, a, slabs, qtiles, lds)));
-        } else {
-            if (nqt == 4) MM_TRY((launch_scan_thr_t<float, 4>(st, a, slabs, qtiles, lds)));
-            else if (nqt == 2) MM_TRY((launch_scan_thr_t<float, 2>(st, a, slabs, qtiles, lds)));
-            else MM_TRY((launch_scan_thr_t<float, 1>(st, a, slabs, qtiles, lds)));
-        }
-        ix->stat_pages += qtiles;
+        if (pd.filt) { a.tags = ix->tags.as<uint64_t>(); a.req = fm_sw; a.exc = fm_sw + Qf; }
+        a.tiles_per_block = p.tiles_per_block;
+        MM_TRY(launch_scan(ix, st, a, p));
+        ix->stat_pages += p.qtiles;
     }
     // Re-rank what was collected. The typical list is short (tens to hundreds of rows), so the first launch sorts at most
     // SWEEP_FAST rows per query WITHOUT waiting to learn the counts; the counts come back with it (one small copy behind the
@@ -909,18 +841,18 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
     r.rows = ix->rows.p; r.D = D; r.inv = ix->inv.as<float>(); r.qn = ix->qn.as<float>(); r.cand = ix->swp_list.as<int32_t>();
     r.cand_stride = SWEEP_CAP; r.ncand = SWEEP_FAST; r.cand_cnt = ix->swp_cnt.as<int32_t>();
     r.group_mode = 0; r.nrows = N;
-    r.labels = ix->labels_d.as<int64_t>(); r.k = k;
-    r.out_labels = d_lab; r.out_dist = d_dist; r.out_count = d_cnt;
+    r.labels = ix->labels_d.as<int64_t>(); r.k = pd.k;
+    r.out_labels = pd.d_lab; r.out_dist = pd.d_dist; r.out_count = pd.d_cnt;
     r.qmap = qmap_sw;
     // the list lengths come back with the re-rank itself: every block stores its list's raw length into a pinned block (a copy
     // into pageable memory behind the kernel was a second operation and a staged host copy in front of the next query's first
     // launch: part of the ~87 us the GPU idled per pipelined step, round 6)
-    MM_TRY(ix->ensure_swp_pin((size_t)Qf));
-    r.cnt_host = ix->swp_pin;
+    MM_TRY(ix->swp_pin.ensure((size_t)Qf * 4, st, (size_t)(Qf < 1024 ? 1024 : 2 * Qf) * 4));
+    r.cnt_host = ix->swp_pin.as<int32_t>();
     MM_TRY(launch_rerank(ix, st, r, Qf));
     r.cnt_host = nullptr;
     MM_HIP(hipStreamSynchronize(st));
-    const int32_t* cnt = ix->swp_pin;
+    const int32_t* cnt = ix->swp_pin.as<int32_t>();
     ix->stat_rounds += 1;
     std::vector<int32_t> big_b, rest;   // blocks that need the large re-rank / original indices for the exhaustive pass
     int maxc = 1;
@@ -945,7 +877,7 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
         r.qmap = ix->cand2.as<int32_t>() + nb;
         MM_TRY(launch_rerank(ix, st, r, nb));
     }
-    MM_TRY(exhaustive_queries(ix, st, rest, k, d_lab, d_dist, d_cnt));
+    MM_TRY(exhaustive_queries(ix, st, pd, rest));
     MM_HIP(hipStreamSynchronize(st));
     return MMISS_OK;
 }
@@ -955,55 +887,106 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& w
 // ================================================================================================ query
 namespace {
 
-// first pass of a query: everything up to and including the rerank is QUEUED on the stream; ix->pend describes it
-// filt: a filtered query (mmiss_index_query_filtered*), req / exc = its [Q] masks (host or device, null = 0)
-int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int64_t* out_labels, float* out_dist,
-                       int32_t* out_count, bool filt = false, const uint64_t* req = nullptr, const uint64_t* exc = nullptr) {
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
-    const int D = ix->dim;
-    const int64_t N = ix->count;
-    const bool out_dev = mmiss_is_device_ptr(out_labels);
-    if (out_dev != mmiss_is_device_ptr(out_dist) || (out_count && out_dev != mmiss_is_device_ptr(out_count)))
-        MM_FAIL(MMISS_ERR_ARG, "mmiss_index_query: output pointers must be all host or all device");
-    ix->q_filt = false;
-    if (filt) {
-        // the masks on the host (the exhaustive pass and the widen pass's compaction read them) and on the device: [Q] required,
-        // then [Q] excluded
-        if (req) MM_TRY(fetch_u64(req, Q, ix->q_req, st)); else ix->q_req.assign((size_t)Q, 0);
-        if (exc) MM_TRY(fetch_u64(exc, Q, ix->q_exc, st)); else ix->q_exc.assign((size_t)Q, 0);
-        MM_TRY(ix->fmask.ensure((size_t)Q * 16));
-        MM_HIP(hipMemcpyAsync(ix->fmask.p, ix->q_req.data(), (size_t)Q * 8, hipMemcpyHostToDevice, st));
-        MM_HIP(hipMemcpyAsync(ix->fmask.as<uint64_t>() + Q, ix->q_exc.data(), (size_t)Q * 8, hipMemcpyHostToDevice, st));
-        ix->q_filt = true;
-    }
+// The path of one query call, decided once from its shape and the options (plan_query).
+struct QueryPlan {
+    int kp = 0, pages = 0, ncand = 0;   // candidates per page (k'; groups of 16 rows on the dense path), pages of them
+    bool dense = false;      // first pass: the score GEMM to group maxima, select, merge; the paged streaming scan otherwise
+    bool dense8 = false;     // ... on fp8 rows
+    bool big = false;        // ... in 256x256 tiles (Q >= score_big_min_q), else the 128-query tile
+    bool strip_v3 = false;   // ... on the staggered loop (strip_v3())
+    bool sample = false;     // ... in the threshold-filtered sample form
+    int Mq = 0, strip = 1, filter_cap = 0;
+    int64_t Npad = 0, nbn = 0, ns_tiles = 0, Ndense = 0;
+};
 
-    // outputs: the caller's device buffers, or the pinned host block (copied to the caller's host buffers at the end)
-    int64_t* d_lab = out_labels; float* d_dist = out_dist; int32_t* d_cnt = out_count;
-    const size_t pin_lab = 0, pin_dist = (size_t)Q * k * 8, pin_cnt = pin_dist + (size_t)Q * k * 4, pin_flags = pin_cnt + (size_t)Q * 4;
-    MM_TRY(ix->ensure_pin(pin_flags + (size_t)Q * 4));
-    if (!out_dev) {
-        d_lab = reinterpret_cast<int64_t*>(ix->pin + pin_lab); d_dist = reinterpret_cast<float*>(ix->pin + pin_dist);
-        d_cnt = reinterpret_cast<int32_t*>(ix->pin + pin_cnt);
+int plan_query(const mmiss_index* ix, int Q, int k, bool filt, QueryPlan& p) {
+    const int64_t N = ix->count;
+    // effective k: never more than the rows there are
+    const int64_t want = std::min<int64_t>(k, N);
+    if (want <= 10) { p.kp = 16; p.pages = 1; }
+    else if (want <= 24) { p.kp = 32; p.pages = 1; }
+    else {
+        p.kp = 32;
+        p.pages = (int)((std::min<int64_t>(want + 8, N) + 31) / 32);
+    }
+    p.ncand = p.kp * p.pages;
+    if (p.ncand > 2048) MM_FAIL(MMISS_ERR_UNSUPPORTED, "mmiss_index_query: k = %d too large (max 2040)", k);
+
+    // batched path: f16 rows, more than one MFMA tile of queries, single page
+    // ... and fp8 rows from two 128-query tiles on (round 4: below that the streaming scan, which reads half the bytes per
+    // row, is the faster)
+    // (filtered queries never take it: every pass of theirs is the streaming scan's FILT form)
+    const bool single = !filt && N > 0 && p.pages == 1;
+    p.big = Q >= mmiss_option("score_big_min_q", 129);
+    p.strip_v3 = strip_v3(ix);
+    p.dense8 = single && ix->dtype == MMISS_F8 && p.big && p.strip_v3 && strip_gemm_rows(ix);
+    p.dense = (single && ix->dtype == MMISS_F16 && Q > 16) || p.dense8;
+    if (!p.dense) return MMISS_OK;
+    // 256x256 phase-pipelined tile once there are two 128-query tiles to share a row panel
+    p.Npad = round_up(N, p.big ? 256 : 128);
+    p.Mq = (int)round_up(Q, p.big ? 256 : 128);
+    // Threshold-filtered selection (Q > 128, index of at least 128 tiles): the first 1/32 of the rows (the SAMPLE) goes
+    // through the dense path — group maxima to HBM, select, merge — which yields each query's k' best sample groups and
+    // their k'-th score tau_q. tau_q is a lower bound of the final k'-th best group maximum, so over the other 31/32 of
+    // the rows the strip kernel only APPENDS the groups reaching tau_q (~31 k' per query) to a per-query candidate
+    // list; one merge over {sample list} + {appended} gives exactly the k' groups the dense path selects. The Q x N/16
+    // group-maximum matrix (2.56 GB at Q = 1024, N = 10M) is neither written nor read back. A query whose list overflows
+    // (a tau_q far below the final one: sorted or clustered data) is handed to the widen pass by the guard.
+    // It costs four extra small launches (~35 us), so it is taken when the matrix it avoids is worth more: from
+    // Q x N = 10^9 scores (256 MB of group maxima written and read back). Option score_filter: 0 never, 2 whenever possible.
+    p.nbn = p.Npad / 256;
+    p.ns_tiles = std::max<int64_t>(16, p.nbn / std::max(1, mmiss_option("score_sample_div", 32)));
+    const int filter_opt = mmiss_option("score_filter", 1);
+    p.sample = p.big && p.nbn >= 128 && filter_opt != 0 && (filter_opt == 2 || (double)p.Mq * (double)p.Npad >= 1e9);
+    p.Ndense = p.sample ? p.ns_tiles * 256 : p.Npad;   // rows whose group maxima are materialised
+    if (p.big) p.strip = strip_length(p.Mq, p.nbn, p.sample ? p.nbn - p.ns_tiles : p.nbn);
+    if (p.sample) p.filter_cap = mmiss_option("score_filter_cap", 2048);
+    return MMISS_OK;
+}
+
+// the query's predicate into ix->pend: its masks on the host and on the device (both null: an unfiltered query)
+int stage_filter(mmiss_index* ix, hipStream_t st, int Q, const uint64_t* req, const uint64_t* exc) {
+    mmiss_index::Pending& pd = ix->pend;
+    pd.filt = req || exc;
+    pd.d_mask = nullptr;
+    if (!pd.filt) return MMISS_OK;
+    if (req) MM_TRY(fetch_u64(req, Q, pd.req, st)); else pd.req.assign((size_t)Q, 0);
+    if (exc) MM_TRY(fetch_u64(exc, Q, pd.exc, st)); else pd.exc.assign((size_t)Q, 0);
+    MM_TRY(ix->fmask.ensure((size_t)Q * 16));
+    MM_HIP(hipMemcpyAsync(ix->fmask.p, pd.req.data(), (size_t)Q * 8, hipMemcpyHostToDevice, st));
+    MM_HIP(hipMemcpyAsync(ix->fmask.as<uint64_t>() + Q, pd.exc.data(), (size_t)Q * 8, hipMemcpyHostToDevice, st));
+    pd.d_mask = ix->fmask.as<uint64_t>();
+    return MMISS_OK;
+}
+
+// outputs: the caller's device buffers, or the pinned host block (copied to the caller's host buffers at the end); the guard's
+// per-query flags always go to the pinned block
+int stage_outputs(mmiss_index* ix, hipStream_t st, int Q, int k, int64_t* out_labels, float* out_dist, int32_t* out_count) {
+    mmiss_index::Pending& pd = ix->pend;
+    pd.Q = Q; pd.k = k;
+    const size_t pin_dist = (size_t)Q * k * 8, pin_cnt = pin_dist + (size_t)Q * k * 4, pin_flags = pin_cnt + (size_t)Q * 4;
+    const size_t need = pin_flags + (size_t)Q * 4;
+    size_t grow = 4096;
+    while (grow < need) grow *= 2;
+    MM_TRY(ix->pin.ensure(need, st, grow));
+    char* const pin = ix->pin.as<char>();
+    pd.d_lab = out_labels; pd.d_dist = out_dist; pd.d_cnt = out_count;
+    if (!pd.out_dev) {
+        pd.d_lab = reinterpret_cast<int64_t*>(pin); pd.d_dist = reinterpret_cast<float*>(pin + pin_dist);
+        pd.d_cnt = reinterpret_cast<int32_t*>(pin + pin_cnt);
     } else if (!out_count) {
         MM_TRY(ix->out_c.ensure((size_t)Q * 4));
-        d_cnt = ix->out_c.as<int32_t>();
+        pd.d_cnt = ix->out_c.as<int32_t>();
     }
-    int32_t* const h_flags = reinterpret_cast<int32_t*>(ix->pin + pin_flags);
+    pd.h_flags = reinterpret_cast<int32_t*>(pin + pin_flags);
+    pd.out_labels = out_labels; pd.out_dist = out_dist; pd.out_count = out_count;
+    return MMISS_OK;
+}
 
-    // effective k: never more than the rows there are
-    int kp, pages;
-    const int64_t want = std::min<int64_t>(k, N);
-    if (want <= 10) { kp = 16; pages = 1; }
-    else if (want <= 24) { kp = 32; pages = 1; }
-    else {
-        kp = 32;
-        pages = (int)((std::min<int64_t>(want + 8, N) + 31) / 32);
-    }
-    const int ncand = kp * pages;
-    if (ncand > 2048) MM_FAIL(MMISS_ERR_UNSUPPORTED, "mmiss_index_query: k = %d too large (max 2040)", k);
-
-    // queries -> device, canonical normalisation
+// queries -> device, canonical normalisation: qn (f32, the re-rank's operand), qs (the first pass's operand) and eps_q (the
+// guard's bound per query)
+int upload_queries(mmiss_index* ix, hipStream_t st, const float* queries, int Q) {
+    const int D = ix->dim;
     const int Qpad = (int)round_up(Q, 256);
     const float* qsrc = queries;
     if (!mmiss_is_device_ptr(queries)) {
@@ -1015,187 +998,177 @@ int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t
     MM_TRY(ix->qs.ensure((size_t)Qpad * D * ix->qelt()));
     MM_TRY(ix->eps_q.ensure((size_t)Qpad * 4));
     MM_TRY(ix->thr.ensure((size_t)Qpad * 4));
+    MM_PROF("prep_queries", st, 4.0 * Q * D, (double)Q * D * (8 + ix->elt));
+    double eps_fixed, cnorm;
+    guard_terms(ix, &eps_fixed, &cnorm);
+    with_storage(ix->dtype, [&](auto s) {   // (f16 query operand for f16 and fp8 rows)
+        using QT = typename decltype(s)::Q;
+        hipLaunchKernelGGL(prep_queries_kernel<QT>, dim3((Qpad + 3) / 4), dim3(256), 0, st, qsrc, ix->qn.as<float>(), ix->qs.as<QT>(),
+                           Q, Qpad, D, ix->eps_q.as<float>(), eps_fixed, cnorm);
+    });
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+// The dense first pass: the score GEMM writes the maximum of every group of 16 rows per query, select_topk / merge_lists keep
+// the k' best groups per query as its candidates (threshold-filtered sample form: see plan_query).
+int dense_pass(mmiss_index* ix, hipStream_t st, const QueryPlan& p, int Q) {
+    const int D = ix->dim, kp = p.kp;
+    const int64_t N = ix->count;
+    // the pad rows up to the tile multiple are readable (capacity is a multiple of 1024) and masked in the epilogue
+    const int ng = (int)(p.Ndense / 16);
+    MM_TRY(ix->gmax.ensure((size_t)p.Mq * ng * 4));
+    GemmEpi ep{};
+    ep.out = ix->gmax.p; ep.ldo = ng; ep.m_valid = Q; ep.p0 = (int)N; ep.m_fast = 1;
+    ep.aux = ix->inv.as<float>();   // (fp8 rows: inverse norms; null otherwise)
     {
-        MM_PROF("prep_queries", st, 4.0 * Q * D, (double)Q * D * (8 + ix->elt));
-        const int grid = (Qpad + 3) / 4;
-        double eps_fixed, cnorm;
-        guard_terms(ix, &eps_fixed, &cnorm);
-        if (ix->dtype != MMISS_F32)   // (f16 query operand for f16 and fp8 rows)
-            hipLaunchKernelGGL(prep_queries_kernel<_Float16>, dim3(grid), dim3(256), 0, st, qsrc, ix->qn.as<float>(),
-                               ix->qs.as<_Float16>(), Q, Qpad, D, ix->eps_q.as<float>(), eps_fixed, cnorm);
-        else
-            hipLaunchKernelGGL(prep_queries_kernel<float>, dim3(grid), dim3(256), 0, st, qsrc, ix->qn.as<float>(),
-                               ix->qs.as<float>(), Q, Qpad, D, ix->eps_q.as<float>(), eps_fixed, cnorm);
+        MM_PROF(p.dense8 ? (p.sample ? "score_gemm_f8_sample" : "score_gemm_f8") : (p.sample ? "score_gemm_f16_sample" : "score_gemm_f16"), st,
+                2.0 * Q * (double)std::min<int64_t>(N, p.Ndense) * D, (double)std::min<int64_t>(N, p.Ndense) * D * ix->elt);
+        if (p.big) MM_TRY(launch_strip_gemm(ix, st, p.strip_v3, ix->qs.p, ep, p.Mq, (int)p.Ndense, p.strip, nullptr));
+        else MM_TRY((launch_gemm_inst<_Float16, 128, MMISS_EPI_GROUPMAX_F32>(st, ix->qs.p, ix->rows.p, ep, p.Mq, (int)p.Npad, D)));
+    }
+    const int units = (ng + 1023) / 1024;
+    int splits = (1024 + Q - 1) / Q;
+    if (splits > units) splits = units;
+    if (splits > 32) splits = 32;
+    if (splits < 1) splits = 1;
+    MM_TRY(ix->lists_s.ensure((size_t)splits * Q * kp * 4));
+    MM_TRY(ix->lists_r.ensure((size_t)splits * Q * kp * 4));
+    SelectArgs sa{};
+    sa.G = ix->gmax.as<float>(); sa.ldg = ng; sa.ng = ng; sa.kp = kp; sa.Q = Q;
+    sa.out_s = ix->lists_s.as<float>(); sa.out_r = ix->lists_r.as<int32_t>();
+    {
+        MM_PROF("select_topk", st, 0.0, (double)Q * ng * 4);
+        hipLaunchKernelGGL(select_topk_kernel, dim3(Q, splits), dim3(256), 0, st, sa);
         MM_HIP(hipGetLastError());
     }
+    MergeArgs m{};
+    m.in_s = ix->lists_s.as<float>(); m.in_r = ix->lists_r.as<int32_t>();
+    m.L = splits; m.Q = Q; m.kp = kp;
+    if (p.sample) {
+        const int cap = p.filter_cap;
+        MM_TRY(ix->seed_s.ensure((size_t)p.Mq * kp * 4));
+        MM_TRY(ix->seed_r.ensure((size_t)p.Mq * kp * 4));
+        MM_TRY(ix->fcnt.ensure((size_t)p.Mq * 4));
+        MM_TRY(ix->fbuf_s.ensure((size_t)p.Mq * cap * 4));
+        MM_TRY(ix->fbuf_g.ensure((size_t)p.Mq * cap * 4));
+        {   // the sample's k' best groups per query WITH their scores: seed of the final merge, source of tau_q
+            MergeArgs m1 = m;
+            m1.lists_per_block = splits; m1.out_s = ix->seed_s.as<float>(); m1.out_r = ix->seed_r.as<int32_t>();
+            MM_PROF("merge_lists", st, 0.0, (double)splits * Q * kp * 8);
+            hipLaunchKernelGGL(merge_lists_kernel, dim3(Q, 1), dim3(256), 0, st, m1);
+            MM_HIP(hipGetLastError());
+        }
+        MM_HIP(hipMemsetAsync(ix->fcnt.p, 0, (size_t)p.Mq * 4, st));
+        StripFilter flt{};
+        flt.tau = ix->seed_s.as<float>() + (kp - 1); flt.tau_stride = kp;
+        flt.cnt = ix->fcnt.as<int32_t>(); flt.buf_s = ix->fbuf_s.as<float>(); flt.buf_g = ix->fbuf_g.as<int32_t>();
+        flt.cap = cap; flt.bn_begin = (int)p.ns_tiles;
+        {
+            MM_PROF(p.dense8 ? "score_gemm_f8" : "score_gemm_f16", st, 2.0 * Q * (double)(N - p.Ndense) * D, (double)(N - p.Ndense) * D * ix->elt);
+            MM_TRY(launch_strip_gemm(ix, st, p.strip_v3, ix->qs.p, ep, p.Mq, (int)p.Npad, p.strip, &flt));
+        }
+        m.in_s = ix->seed_s.as<float>(); m.in_r = ix->seed_r.as<int32_t>(); m.L = 1;
+        m.flat_s = ix->fbuf_s.as<float>(); m.flat_r = ix->fbuf_g.as<int32_t>(); m.flat_cnt = ix->fcnt.as<int32_t>();
+        m.flat_cap = cap;
+    }
+    m.cand = ix->cand.as<int32_t>(); m.cand_stride = p.ncand; m.page_off = 0;
+    m.cur_s = ix->cur_s.as<float>(); m.cur_r = ix->cur_r.as<int32_t>();  // k'-th group maximum
+    return launch_merge(ix, st, m);
+}
 
-    // batched path: f16 rows, more than one MFMA tile of queries, single page
-    // ... and fp8 rows from two 128-query tiles on (round 4: the strip kernel widens the codes to f16 in its operand load —
-    // gemm256s_kernel<_Float16, .., W8>; below that the streaming scan, which reads half the bytes per row, is the faster)
-    // (filtered queries never take it: every pass of theirs is the streaming scan's FILT form)
-    const bool dense8 = !filt && (N > 0) && ix->dtype == MMISS_F8 && pages == 1 && Q >= mmiss_option("score_big_min_q", 129) &&
-                        (D % 128) == 0 && D >= 256 && mmiss_option("score_strip_v3", 1) != 0 && mmiss_option("score_f8_gemm", 1) != 0;
-    const bool dense = (!filt && (N > 0) && ix->dtype == MMISS_F16 && Q > 16 && pages == 1) || dense8;
-    MM_TRY(ix->cand.ensure((size_t)Q * ncand * 4));
+// The paged streaming-scan first pass (filtered queries: its FILT form): per page, every slab's k' best rows per query, merged
+// into the query's candidate page; a later page continues behind the last candidate of the one before (cur_s / cur_r).
+int scan_pass(mmiss_index* ix, hipStream_t st, const QueryPlan& qp, int Q) {
+    const mmiss_index::Pending& pd = ix->pend;
+    const int kp = qp.kp;
+    const ScanPlan p = plan_scan(ix->dim, ix->qelt(), Q, kp, ix->count);
+    MM_TRY(ix->lists_s.ensure((size_t)p.slabs * Q * kp * 4));
+    MM_TRY(ix->lists_r.ensure((size_t)p.slabs * Q * kp * 4));
+    const bool paging = qp.pages > 1;
+    if (paging) {
+        std::vector<float> inf((size_t)Q, INFINITY);
+        std::vector<int32_t> neg((size_t)Q, -1);
+        MM_HIP(hipMemcpyAsync(ix->cur_s.p, inf.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
+        MM_HIP(hipMemcpyAsync(ix->cur_r.p, neg.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
+        MM_HIP(hipStreamSynchronize(st));  // the host vectors go out of scope
+    }
+    for (int page = 0; page < qp.pages; ++page) {
+        ScanArgs a{};
+        a.rows = ix->rows.p; a.N = ix->count; a.D = ix->dim; a.inv = ix->inv.as<float>(); a.qs = ix->qs.p; a.Q = Q;
+        a.cur_s = paging ? ix->cur_s.as<float>() : nullptr;
+        a.cur_r = paging ? ix->cur_r.as<int32_t>() : nullptr;
+        a.kp = kp; a.tiles_per_block = p.tiles_per_block;
+        a.out_s = ix->lists_s.as<float>(); a.out_r = ix->lists_r.as<int32_t>();
+        if (pd.filt) { a.tags = ix->tags.as<uint64_t>(); a.req = pd.d_mask; a.exc = pd.d_mask + Q; }
+        MM_TRY(launch_scan(ix, st, a, p));
+        MergeArgs m{};
+        m.in_s = ix->lists_s.as<float>(); m.in_r = ix->lists_r.as<int32_t>();
+        m.L = p.slabs; m.Q = Q; m.kp = kp;
+        m.cand = ix->cand.as<int32_t>(); m.cand_stride = qp.ncand; m.page_off = page * kp;
+        m.cur_s = ix->cur_s.as<float>(); m.cur_r = ix->cur_r.as<int32_t>();  // the scan reads them only when paging
+        MM_TRY(launch_merge(ix, st, m));
+    }
+    return MMISS_OK;
+}
+
+// The first pass's canonical re-rank of the candidates: labels, distances and counts of ix->pend. With the guard on (see
+// "exactness contract") it also writes a flag per query it cannot prove — one plain store per query into the pinned block,
+// counted on the host — and the threshold the widen pass starts from.
+int rerank_first(mmiss_index* ix, hipStream_t st, const QueryPlan& p) {
+    const mmiss_index::Pending& pd = ix->pend;
+    RerankArgs r{};
+    r.rows = ix->rows.p; r.D = ix->dim; r.inv = ix->inv.as<float>(); r.qn = ix->qn.as<float>(); r.cand = ix->cand.as<int32_t>();
+    r.cand_stride = p.ncand; r.ncand = p.dense ? p.ncand * 16 : p.ncand; r.group_mode = p.dense ? 1 : 0; r.nrows = ix->count;
+    r.labels = ix->labels_d.as<int64_t>(); r.k = pd.k;
+    r.out_labels = pd.d_lab; r.out_dist = pd.d_dist; r.out_count = pd.d_cnt;
+    if (pd.guard) {
+        r.tau = ix->cur_s.as<float>(); r.eps_q = ix->eps_q.as<float>();
+        r.thr_out = ix->thr.as<float>();
+        r.flags = pd.h_flags; r.nflag = nullptr;
+        r.force_flag = mmiss_option("guard_force", 0);
+        // threshold-filtered selection: per-query append counts and their capacity
+        if (p.sample) { r.ovf_cnt = ix->fcnt.as<int32_t>(); r.ovf_cap = p.filter_cap; }
+    }
+    return launch_rerank(ix, st, r, pd.Q);
+}
+
+// first pass of a query: everything up to and including the rerank is QUEUED on the stream; ix->pend describes it
+// req / exc: a filtered query's [Q] masks (host or device, null = 0; both null: unfiltered)
+int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const uint64_t* req, const uint64_t* exc,
+                       int64_t* out_labels, float* out_dist, int32_t* out_count) {
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    const int64_t N = ix->count;
+    mmiss_index::Pending& pd = ix->pend;
+    pd.out_dev = mmiss_is_device_ptr(out_labels);
+    if (pd.out_dev != mmiss_is_device_ptr(out_dist) || (out_count && pd.out_dev != mmiss_is_device_ptr(out_count)))
+        MM_FAIL(MMISS_ERR_ARG, "mmiss_index_query: output pointers must be all host or all device");
+    MM_TRY(stage_filter(ix, st, Q, req, exc));
+    MM_TRY(stage_outputs(ix, st, Q, k, out_labels, out_dist, out_count));
+    QueryPlan p;
+    MM_TRY(plan_query(ix, Q, k, pd.filt, p));
+    MM_TRY(upload_queries(ix, st, queries, Q));
+    MM_TRY(ix->cand.ensure((size_t)Q * p.ncand * 4));
     // (score, row) of the last candidate stage 1 kept per query, -inf when it kept every row: the paging cursor, and the
     // guard's bound on what was left out
     MM_TRY(ix->cur_s.ensure((size_t)Q * 4));
     MM_TRY(ix->cur_r.ensure((size_t)Q * 4));
-    const bool guard = N > 0 && mmiss_option("exact_guard", 1) != 0;
-    const int32_t* ovf_cnt = nullptr;  // threshold-filtered selection: per-query append counts and their capacity
-    int ovf_cap = 0;
-    if (N == 0) {
-        MM_HIP(hipMemsetAsync(ix->cand.p, 0xff, (size_t)Q * ncand * 4, st));  // all -1
-    } else if (dense) {
-        // the pad rows up to the tile multiple are readable (capacity is a multiple of 1024) and masked in the epilogue
-        // 256x256 phase-pipelined tile once there are two 128-query tiles to share a row panel
-        const bool big = Q >= mmiss_option("score_big_min_q", 129);
-        const int64_t Npad = round_up(N, big ? 256 : 128);
-        const int Mq = (int)round_up(Q, big ? 256 : 128);
-        // Threshold-filtered selection (Q > 128, index of at least 128 tiles): the first 1/32 of the rows (the SAMPLE) goes
-        // through the dense path — group maxima to HBM, select, merge — which yields each query's k' best sample groups and
-        // their k'-th score tau_q. tau_q is a lower bound of the final k'-th best group maximum, so over the other 31/32 of
-        // the rows the strip kernel only APPENDS the groups reaching tau_q (~31 k' per query) to a per-query candidate
-        // list; one merge over {sample list} + {appended} gives exactly the k' groups the dense path selects. The Q x N/16
-        // group-maximum matrix (2.56 GB at Q = 1024, N = 10M) is neither written nor read back. A query whose list overflows
-        // (a tau_q far below the final one: sorted or clustered data) is handed to the widen pass by the guard.
-        // It costs four extra small launches (~35 us), so it is taken when the matrix it avoids is worth more: from
-        // Q x N = 10^9 scores (256 MB of group maxima written and read back). Option score_filter: 0 never, 2 whenever possible.
-        const int64_t nbn = Npad / 256;
-        const int64_t ns_tiles = std::max<int64_t>(16, nbn / std::max(1, mmiss_option("score_sample_div", 32)));
-        const int filter_opt = mmiss_option("score_filter", 1);
-        const bool filtered = big && nbn >= 128 && filter_opt != 0 && (filter_opt == 2 || (double)Mq * (double)Npad >= 1e9);
-        const int64_t Ndense = filtered ? ns_tiles * 256 : Npad;   // rows whose group maxima are materialised
-        const int ng = (int)(Ndense / 16);
-        MM_TRY(ix->gmax.ensure((size_t)Mq * ng * 4));
-        GemmEpi ep{};
-        ep.out = ix->gmax.p; ep.ldo = ng; ep.m_valid = Q; ep.p0 = (int)N; ep.m_fast = 1;
-        ep.aux = ix->inv.as<float>();   // (fp8 rows: inverse norms; null otherwise)
-        int strip = 1;
-        // the strip kernel on the staggered loop of the persistent encoder GEMM (gemm_bf16_p256.h; round 3): D % 128 == 0
-        const bool strip_v3 = mmiss_option("score_strip_v3", 1) != 0 && (D % 128) == 0 && D >= 256;
-        if (big) strip = strip_length(Mq, nbn, filtered ? nbn - ns_tiles : nbn);
-        {
-            MM_PROF(dense8 ? (filtered ? "score_gemm_f8_sample" : "score_gemm_f8") : (filtered ? "score_gemm_f16_sample" : "score_gemm_f16"), st,
-                    2.0 * Q * (double)std::min<int64_t>(N, Ndense) * D, (double)std::min<int64_t>(N, Ndense) * D * ix->elt);
-            if (dense8)
-                MM_TRY((launch_gemm256s<_Float16, true>(st, ix->qs.p, ix->rows.p, ep, Mq, (int)Ndense, D, strip)));
-            else if (big && strip_v3)
-                MM_TRY((launch_gemm256s<_Float16>(st, ix->qs.p, ix->rows.p, ep, Mq, (int)Ndense, D, strip)));
-            else if (big)
-                MM_TRY((launch_gemm256_strip<_Float16>(st, ix->qs.p, ix->rows.p, ep, Mq, (int)Ndense, D, strip)));
-            else
-                MM_TRY((launch_gemm_inst<_Float16, 128, MMISS_EPI_GROUPMAX_F32>(st, ix->qs.p, ix->rows.p, ep, Mq, (int)Npad, D)));
-        }
-        const int units = (ng + 1023) / 1024;
-        int splits = (1024 + Q - 1) / Q;
-        if (splits > units) splits = units;
-        if (splits > 32) splits = 32;
-        if (splits < 1) splits = 1;
-        MM_TRY(ix->lists_s.ensure((size_t)splits * Q * kp * 4));
-        MM_TRY(ix->lists_r.ensure((size_t)splits * Q * kp * 4));
-        SelectArgs sa{};
-        sa.G = ix->gmax.as<float>(); sa.ldg = ng; sa.ng = ng; sa.kp = kp; sa.Q = Q;
-        sa.out_s = ix->lists_s.as<float>(); sa.out_r = ix->lists_r.as<int32_t>();
-        {
-            MM_PROF("select_topk", st, 0.0, (double)Q * ng * 4);
-            hipLaunchKernelGGL(select_topk_kernel, dim3(Q, splits), dim3(256), 0, st, sa);
-            MM_HIP(hipGetLastError());
-        }
-        MergeArgs m{};
-        m.in_s = ix->lists_s.as<float>(); m.in_r = ix->lists_r.as<int32_t>();
-        m.L = splits; m.Q = Q; m.kp = kp;
-        if (filtered) {
-            const int cap = mmiss_option("score_filter_cap", 2048);
-            MM_TRY(ix->seed_s.ensure((size_t)Mq * kp * 4));
-            MM_TRY(ix->seed_r.ensure((size_t)Mq * kp * 4));
-            MM_TRY(ix->fcnt.ensure((size_t)Mq * 4));
-            MM_TRY(ix->fbuf_s.ensure((size_t)Mq * cap * 4));
-            MM_TRY(ix->fbuf_g.ensure((size_t)Mq * cap * 4));
-            {   // the sample's k' best groups per query WITH their scores: seed of the final merge, source of tau_q
-                MergeArgs m1 = m;
-                m1.lists_per_block = splits; m1.out_s = ix->seed_s.as<float>(); m1.out_r = ix->seed_r.as<int32_t>();
-                MM_PROF("merge_lists", st, 0.0, (double)splits * Q * kp * 8);
-                hipLaunchKernelGGL(merge_lists_kernel, dim3(Q, 1), dim3(256), 0, st, m1);
-                MM_HIP(hipGetLastError());
-            }
-            MM_HIP(hipMemsetAsync(ix->fcnt.p, 0, (size_t)Mq * 4, st));
-            StripFilter flt{};
-            flt.tau = ix->seed_s.as<float>() + (kp - 1); flt.tau_stride = kp;
-            flt.cnt = ix->fcnt.as<int32_t>(); flt.buf_s = ix->fbuf_s.as<float>(); flt.buf_g = ix->fbuf_g.as<int32_t>();
-            flt.cap = cap; flt.bn_begin = (int)ns_tiles;
-            {
-                MM_PROF(dense8 ? "score_gemm_f8" : "score_gemm_f16", st, 2.0 * Q * (double)(N - Ndense) * D, (double)(N - Ndense) * D * ix->elt);
-                if (dense8) MM_TRY((launch_gemm256s<_Float16, true>(st, ix->qs.p, ix->rows.p, ep, Mq, (int)Npad, D, strip, &flt)));
-                else if (strip_v3) MM_TRY((launch_gemm256s<_Float16>(st, ix->qs.p, ix->rows.p, ep, Mq, (int)Npad, D, strip, &flt)));
-                else MM_TRY((launch_gemm256_strip<_Float16>(st, ix->qs.p, ix->rows.p, ep, Mq, (int)Npad, D, strip, &flt)));
-            }
-            m.in_s = ix->seed_s.as<float>(); m.in_r = ix->seed_r.as<int32_t>(); m.L = 1;
-            m.flat_s = ix->fbuf_s.as<float>(); m.flat_r = ix->fbuf_g.as<int32_t>(); m.flat_cnt = ix->fcnt.as<int32_t>();
-            m.flat_cap = cap;
-            ovf_cnt = ix->fcnt.as<int32_t>();
-            ovf_cap = cap;
-        }
-        m.cand = ix->cand.as<int32_t>(); m.cand_stride = ncand; m.page_off = 0;
-        m.cur_s = ix->cur_s.as<float>(); m.cur_r = ix->cur_r.as<int32_t>();  // k'-th group maximum
-        MM_TRY(launch_merge(ix, st, m));
-    } else {
-        const ScanPlan p = plan_scan(D, ix->qelt(), Q, kp, N);
-        MM_TRY(ix->lists_s.ensure((size_t)p.slabs * Q * kp * 4));
-        MM_TRY(ix->lists_r.ensure((size_t)p.slabs * Q * kp * 4));
-        const bool paging = pages > 1;
-        if (paging) {
-            std::vector<float> inf((size_t)Q, INFINITY);
-            std::vector<int32_t> neg((size_t)Q, -1);
-            MM_HIP(hipMemcpyAsync(ix->cur_s.p, inf.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
-            MM_HIP(hipMemcpyAsync(ix->cur_r.p, neg.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
-            MM_HIP(hipStreamSynchronize(st));  // the host vectors go out of scope
-        }
-        for (int page = 0; page < pages; ++page) {
-            ScanArgs a{};
-            a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>(); a.qs = ix->qs.p; a.Q = Q;
-            a.cur_s = paging ? ix->cur_s.as<float>() : nullptr;
-            a.cur_r = paging ? ix->cur_r.as<int32_t>() : nullptr;
-            a.kp = kp; a.tiles_per_block = p.tiles_per_block;
-            a.out_s = ix->lists_s.as<float>(); a.out_r = ix->lists_r.as<int32_t>();
-            if (filt) { a.tags = ix->tags.as<uint64_t>(); a.req = ix->fmask.as<uint64_t>(); a.exc = ix->fmask.as<uint64_t>() + Q; }
-            MM_TRY(launch_scan(ix, st, a, p));
-            MergeArgs m{};
-            m.in_s = ix->lists_s.as<float>(); m.in_r = ix->lists_r.as<int32_t>();
-            m.L = p.slabs; m.Q = Q; m.kp = kp;
-            m.cand = ix->cand.as<int32_t>(); m.cand_stride = ncand; m.page_off = page * kp;
-            m.cur_s = ix->cur_s.as<float>(); m.cur_r = ix->cur_r.as<int32_t>();  // the scan reads them only when paging
-            MM_TRY(launch_merge(ix, st, m));
-        }
-    }
-    {
-        RerankArgs r{};
-        r.rows = ix->rows.p; r.D = D; r.inv = ix->inv.as<float>(); r.qn = ix->qn.as<float>(); r.cand = ix->cand.as<int32_t>();
-        r.cand_stride = ncand; r.ncand = dense ? ncand * 16 : ncand; r.group_mode = dense ? 1 : 0; r.nrows = N;
-        r.labels = ix->labels_d.as<int64_t>(); r.k = k;
-        r.out_labels = d_lab; r.out_dist = d_dist; r.out_count = d_cnt;
-        if (guard) {
-            r.tau = ix->cur_s.as<float>(); r.eps_q = ix->eps_q.as<float>();
-            r.thr_out = ix->thr.as<float>();   // what the widen pass starts from
-            r.flags = h_flags; r.nflag = nullptr;  // one plain store per query into the pinned block; counted on the host
-            r.force_flag = mmiss_option("guard_force", 0);
-            r.ovf_cnt = ovf_cnt; r.ovf_cap = ovf_cap;
-        }
-        MM_TRY(launch_rerank(ix, st, r, Q));
-    }
+    if (N == 0) MM_HIP(hipMemsetAsync(ix->cand.p, 0xff, (size_t)Q * p.ncand * 4, st));  // all -1
+    else if (p.dense) MM_TRY(dense_pass(ix, st, p, Q));
+    else MM_TRY(scan_pass(ix, st, p, Q));
+    pd.guard = N > 0 && mmiss_option("exact_guard", 1) != 0;
+    MM_TRY(rerank_first(ix, st, p));
     ix->stat_queries += Q;
     MM_HIP(hipEventRecord(ix->done_ev, st));
-    mmiss_index::Pending& pd = ix->pend;
-    pd.active = true; pd.out_dev = out_dev; pd.guard = guard; pd.Q = Q; pd.k = k;
-    pd.d_lab = d_lab; pd.d_dist = d_dist; pd.d_cnt = d_cnt; pd.h_flags = h_flags;
-    pd.out_labels = out_labels; pd.out_dist = out_dist; pd.out_count = out_count;
+    pd.active = true;
     return MMISS_OK;
 }
 
 // second half: wait for the first pass (its event, NOT the stream: the caller may have queued the next batch's encode behind
 // it), widen what the guard could not prove, hand host outputs over
 int query_end_locked(mmiss_index* ix) {
-    mmiss_index::Pending pd = ix->pend;
+    const mmiss_index::Pending& pd = ix->pend;   // (unchanged until the next query begins)
     ix->pend.active = false;
     MM_TRY(mmiss_use_device(ix->device));
     hipStream_t st = ix->stream();
@@ -1210,7 +1183,7 @@ int query_end_locked(mmiss_index* ix) {
             if (pd.h_flags[q]) which.push_back(q);
         if (!which.empty()) {
             ix->stat_flagged += (int64_t)which.size();
-            MM_TRY(sweep_queries(ix, st, which, pd.Q, pd.k, pd.d_lab, pd.d_dist, pd.d_cnt));  // returns with the stream drained
+            MM_TRY(sweep_queries(ix, st, pd, which));  // returns with the stream drained
         }
     }
     if (!pd.out_dev) {
@@ -1221,52 +1194,42 @@ int query_end_locked(mmiss_index* ix) {
     return MMISS_OK;
 }
 
-int query_check_args(const mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const int64_t* out_labels,
-                     const float* out_dist, const char* who) {
+// the four query entry points: req / exc the masks of a filtered query (both null: mmiss_index_query itself, same path, same
+// results); begin_only leaves the query open for mmiss_index_query_end; `who` names the entry point in errors
+int query_entry(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const uint64_t* req, const uint64_t* exc,
+                int64_t* out_labels, float* out_dist, int32_t* out_count, bool begin_only, const char* who) {
     if (!ix || !queries || !out_labels || !out_dist) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
     if (Q < 0 || k <= 0) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d", who, Q, k);
-    return MMISS_OK;
+    if (Q == 0) {
+        if (begin_only) MM_FAIL(MMISS_ERR_ARG, "%s: Q = 0", who);
+        return MMISS_OK;
+    }
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    MM_TRY(query_begin_locked(ix, queries, Q, k, req, exc, out_labels, out_dist, out_count));
+    return begin_only ? MMISS_OK : query_end_locked(ix);
 }
 
 }  // namespace
 
 extern "C" int mmiss_index_query(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int64_t* out_labels,
                                  float* out_dist, int32_t* out_count) {
-    MM_TRY(query_check_args(ix, queries, Q, k, out_labels, out_dist, "mmiss_index_query"));
-    if (Q == 0) return MMISS_OK;
-    std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_query");
-    MM_TRY(query_begin_locked(ix, queries, Q, k, out_labels, out_dist, out_count));
-    return query_end_locked(ix);
+    return query_entry(ix, queries, Q, k, nullptr, nullptr, out_labels, out_dist, out_count, false, "mmiss_index_query");
 }
 
 extern "C" int mmiss_index_query_begin(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int64_t* out_labels,
                                        float* out_dist, int32_t* out_count) {
-    MM_TRY(query_check_args(ix, queries, Q, k, out_labels, out_dist, "mmiss_index_query_begin"));
-    if (Q == 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_query_begin: Q = 0");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_query_begin");
-    return query_begin_locked(ix, queries, Q, k, out_labels, out_dist, out_count);
+    return query_entry(ix, queries, Q, k, nullptr, nullptr, out_labels, out_dist, out_count, true, "mmiss_index_query_begin");
 }
 
 extern "C" int mmiss_index_query_filtered(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const uint64_t* require,
                                           const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count) {
-    MM_TRY(query_check_args(ix, queries, Q, k, out_labels, out_dist, "mmiss_index_query_filtered"));
-    if (Q == 0) return MMISS_OK;
-    std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_query_filtered");
-    // both masks null: mmiss_index_query itself (same path, same results)
-    MM_TRY(query_begin_locked(ix, queries, Q, k, out_labels, out_dist, out_count, require || exclude, require, exclude));
-    return query_end_locked(ix);
+    return query_entry(ix, queries, Q, k, require, exclude, out_labels, out_dist, out_count, false, "mmiss_index_query_filtered");
 }
 
 extern "C" int mmiss_index_query_filtered_begin(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const uint64_t* require,
                                                 const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count) {
-    MM_TRY(query_check_args(ix, queries, Q, k, out_labels, out_dist, "mmiss_index_query_filtered_begin"));
-    if (Q == 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_query_filtered_begin: Q = 0");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_query_filtered_begin");
-    return query_begin_locked(ix, queries, Q, k, out_labels, out_dist, out_count, require || exclude, require, exclude);
+    return query_entry(ix, queries, Q, k, require, exclude, out_labels, out_dist, out_count, true, "mmiss_index_query_filtered_begin");
 }
 
 extern "C" int mmiss_index_query_end(mmiss_index* ix) {
@@ -1312,6 +1275,33 @@ struct IdxHeader {
     int32_t version, dim, dtype, reserved;
     int64_t count;
 };
+
+// the `n` rows of an index file, read behind its header and labels `lab`, over the index's own buffers (capacity >= n), with
+// their labels, inverse norms and tags; any failure leaves rows that no longer match the index's other state
+int load_rows(mmiss_index* ix, FILE* f, const char* path, int64_t n, const std::vector<int64_t>& lab, hipStream_t st) {
+    const size_t row_bytes = (size_t)ix->dim * ix->elt;
+    const int64_t chunk = std::max<int64_t>(1, (64 << 20) / (int64_t)row_bytes);
+    std::vector<char> buf((size_t)std::min<int64_t>(chunk, std::max<int64_t>(n, 1)) * row_bytes);
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t nr = std::min(chunk, n - r0);
+        if (fread(buf.data(), row_bytes, (size_t)nr, f) != (size_t)nr ||
+            hipMemcpy(ix->rows.as<char>() + (size_t)r0 * row_bytes, buf.data(), (size_t)nr * row_bytes, hipMemcpyHostToDevice) != hipSuccess)
+            MM_FAIL(MMISS_ERR_IO, "%s could not be read to its end", path);
+    }
+    if (n) MM_HIP(hipMemcpy(ix->labels_d.p, lab.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    // fp8 rows: the file holds the codes only; their inverse norms are a function of the codes (files of round 4 load as they are)
+    if (ix->dtype == MMISS_F8 && ix->capacity > 0) {
+        MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st));
+        MM_TRY(launch_f8_inv(ix, 0, n, st));
+        MM_HIP(hipStreamSynchronize(st));
+    }
+    // the file holds no tags (format version 1): every row's tag is 0 after a load
+    if (ix->capacity > 0) {
+        MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st));
+        MM_HIP(hipStreamSynchronize(st));
+    }
+    return MMISS_OK;
+}
 }  // namespace
 
 extern "C" int mmiss_index_save(mmiss_index* ix, const char* path) {
@@ -1377,36 +1367,14 @@ extern "C" int mmiss_index_load(mmiss_index* ix, const char* path) {
     if (!ok) { fclose(f); MM_FAIL(MMISS_ERR_IO, "%s: labels unreadable or not strictly increasing; the index is unchanged", path); }
     int rc = index_reserve(ix, h.count, st);
     if (rc != MMISS_OK) { fclose(f); return rc; }
-    const int64_t chunk = std::max<int64_t>(1, (64 << 20) / (int64_t)row_bytes);
-    std::vector<char> buf((size_t)std::min<int64_t>(chunk, std::max<int64_t>(h.count, 1)) * row_bytes);
-    for (int64_t r0 = 0; ok && rc == MMISS_OK && r0 < h.count; r0 += chunk) {
-        const int64_t nr = std::min(chunk, h.count - r0);
-        ok = fread(buf.data(), row_bytes, (size_t)nr, f) == (size_t)nr;
-        if (ok && hipMemcpy(ix->rows.as<char>() + (size_t)r0 * row_bytes, buf.data(), (size_t)nr * row_bytes,
-                            hipMemcpyHostToDevice) != hipSuccess) ok = false;
-    }
+    rc = load_rows(ix, f, path, h.count, lab, st);
     fclose(f);
-    if (!ok) {
-        // a read or copy error with part of the rows already overwritten: old labels / inverse norms no longer describe what the
-        // buffer holds, so the index is left EMPTY rather than inconsistent
-        if (ix->dtype == MMISS_F8 && ix->capacity > 0) { (void)hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st); (void)hipStreamSynchronize(st); }
-        if (ix->capacity > 0) { (void)hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st); (void)hipStreamSynchronize(st); }
-        ix->count = 0;
-        ix->labels_h.clear();
-        ix->tags_h.clear();
-        MM_FAIL(MMISS_ERR_IO, "%s could not be read to its end; the index was cleared", path);
-    }
-    if (h.count) MM_HIP(hipMemcpy(ix->labels_d.p, lab.data(), (size_t)h.count * 8, hipMemcpyHostToDevice));
-    // fp8 rows: the file holds the codes only; their inverse norms are a function of the codes (files of round 4 load as they are)
-    if (ix->dtype == MMISS_F8 && ix->capacity > 0) {
-        MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st));
-        MM_TRY(launch_f8_inv(ix, 0, h.count, st));
-        MM_HIP(hipStreamSynchronize(st));
-    }
-    // the file holds no tags (format version 1): every row's tag is 0 after a load
-    if (ix->capacity > 0) {
-        MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st));
-        MM_HIP(hipStreamSynchronize(st));
+    if (rc != MMISS_OK) {
+        // part of the rows already overwritten: old labels / inverse norms no longer describe what the buffer holds, so the
+        // index is left EMPTY rather than inconsistent
+        const std::string why = mmiss_last_error();
+        (void)reset_rows(ix, st);
+        MM_FAIL(rc, "%s; the index was cleared", why.c_str());
     }
     ix->tags_h.assign((size_t)h.count, 0);
     ix->labels_h.swap(lab);

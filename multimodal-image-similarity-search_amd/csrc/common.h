@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include <string>
+#include <utility>
 #include <vector>
 #include <mutex>
 #include "../../include/mmiss.h"
@@ -95,10 +96,34 @@ struct DevBuf {
     }
     ~DevBuf() { release(); }
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
     DevBuf() = default;
     DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+};
+
+// pinned, device-visible host block that kernels write straight into; when it grows, the old block is freed only after `st`
+// has drained (a queued kernel may still write it)
+struct PinBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    // room for `need` bytes; a block that has to grow becomes `alloc` bytes (at least `need`)
+    int ensure(size_t need, hipStream_t st, size_t alloc = 0) {
+        if (need <= bytes) return MMISS_OK;
+        if (p) { MM_HIP(hipStreamSynchronize(st)); MM_HIP(hipHostFree(p)); p = nullptr; bytes = 0; }
+        if (alloc < need) alloc = need;
+        void* q = nullptr;
+        MM_HIP(hipHostMalloc(&q, alloc, hipHostMallocDefault));
+        p = q;
+        bytes = alloc;
+        return MMISS_OK;
+    }
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
 };
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
