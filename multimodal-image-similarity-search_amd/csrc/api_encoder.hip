@@ -68,8 +68,6 @@ struct Tower {
     int ws_batch = 0;
     DevBuf x, h, qkv, ctx, u, pooled, proj_out, pool_row, out_stage, taps;
     int pool_B = -1, pool_T = -1;   // vision: pool_row currently holds b * pool_T for b < pool_B (written once per shape)
-    bool embed_stats = false;       // this call's embedding stage already left xb + row statistics (layernorm_stats_kernel)
-    bool embed_stats16 = false;     // ... xb + the 16-column statistics of the one-request mode (prelayernorm_skinny_kernel)
     DevBuf xc, hc, ctxc, uc;  // compact [Bp, *] buffers of the pooled rows (last-layer pruning)
     DevBuf stats;             // [Mp][hidden/64][2] partial row (sum, sumsq) for the LayerNorm-fused GEMMs
     DevBuf stats_final;       // [Mp][2] finished (mean, rstd): hidden > 768 on the persistent GEMM (ln_finalize_kernel)
@@ -107,8 +105,8 @@ struct mmiss_encoder {
     bool record_taps = false;
     // How LayerNorm1/2 reach the QKV / FC1 GEMMs:
     //   0 separate LayerNorm kernels (x f32 -> h bf16);
-    //   1 normalised while the f32 rows are staged as the A operand (correct, but SLOWER at B=256: every one of the
-    //     18-24 column blocks re-normalises its rows through registers, 342-371 TF);
+    //   (1, normalised while the f32 rows were staged as the A operand, was removed in round 4: every one of the 18-24
+    //     column blocks re-normalised its rows through registers, 342-371 TF; set_fuse_ln and option ln_mode refuse it)
     //   2 folded algebraically: A = bf16(x) written by the residual epilogues, gamma folded into the weights, the
     //     (mean, rstd) correction applied in the GEMM epilogue — no LayerNorm pass at all. Same precision
     //     (1-cos 5e-6 either way). With the f32 residual rows stored non-temporally (they would push the bf16 copy the
@@ -117,7 +115,7 @@ struct mmiss_encoder {
     //     weight-streaming and split-K paths it cannot feed are worth more.
     //     Hidden size 1024 (ViT-L/14) loses 4 % with it (16 partial statistics per row in the epilogues, and FC1 gives up
     //     its 256 x 256 tile): 4.54 vs 4.74 k images/s.
-    // -1 (default) = automatic: 2 from `ln_fold_min_rows` (6000) rows per call when hidden <= 768, else 0.
+    // -1 (default) = automatic: 2 from `ln_fold_min_rows` (6000) rows per call when hidden <= 1024 (option ln_fold_1024), else 0.
     int ln_mode = -1;
     // MMISS_PREC_FP8: the QKV / FC1 / FC2 GEMMs of calls with at least `fp8_min_rows` rows run on the block-scaled fp8
     // MFMA (gemm_fp8.h); out-proj, the pruned last layer, the embeddings and the head stay bf16
@@ -258,49 +256,68 @@ int ensure_tower_ws(mmiss_encoder* e, Tower& tw, int max_batch, int proj_dim) {
     return MMISS_OK;
 }
 
-// One request at a time: all four GEMMs of a layer on the weight-streaming skinny kernel with the LayerNorm folded in (run_layers)
-static bool skinny_fold_ok(const Tower& tw, int M) {
-    const int d = tw.hidden;
-    if (M > 128 || (d % 128) != 0 || mmiss_option("skinny_fold", 1) == 0) return false;
-    GemmEpi probe{};
-    probe.stats16 = 1;
-    return gemm_skinny_ok(MMISS_EPI_LNFOLD_BF16, M, 3 * d, d, probe) && gemm_skinny_ok(MMISS_EPI_LNFOLD_QGELU_BF16, M, tw.mlp, d, probe) &&
-           gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, M, d, d, probe) && gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, M, d, tw.mlp, probe);
-}
+// Which kernel runs one GEMM role of the layer loop (plan_layers picks it, run_wide / run_resid launch it): the BM x 128 tile
+// (launch_gemm, _fold, _resid16), the 256 x 256 tile (gemm_bf16_256.h), the persistent 256 x 256 (gemm_bf16_p256.h), the 160 x 256
+// residual GEMM (gemm_bf16_p160.h), the skinny GEMM with the LayerNorm folded in (gemm_skinny.h), the BM x 128 fp8 tile
+// (gemm_fp8.h), the persistent fp8 256 x 256 (gemm_fp8_p256.h) and its folded-LayerNorm form (fold8: xt 1 for QKV / FC1, 2 after)
+enum class GemmKind { Tile, Tile256, P256, P160, Skinny, Fp8Tile, P256Fp8, P256Fp8Xt };
+struct GemmPick { GemmKind kind; int bm; };   // bm: tile height of Tile / Fp8Tile, M is padded to it
+static bool is_fp8(GemmKind k) { return k == GemmKind::Fp8Tile || k == GemmKind::P256Fp8 || k == GemmKind::P256Fp8Xt; }
 
-// the transformer stack shared by both towers; x holds the embeddings on entry
-// LayerNorm placement for a call of M token rows: 0 separate kernels, 1 staged (experiments), 2 folded into the GEMMs
-static int pick_ln_mode(const mmiss_encoder* e, const Tower& tw, int M, bool& fp8) {
+// What the vision embedding stage leaves for the first layer besides x: nothing (in-place pre-LayerNorm; the text tower),
+// xb + 64-column row statistics (layernorm_stats_kernel), xb + the 16-column statistics of one request (prelayernorm_skinny_kernel)
+enum class EmbedOut { Nothing, Stats64, Stats16 };
+
+// How one call's layers run, decided once per chunk from its shape and the options. Never cached: options change between calls.
+struct LayerPlan {
+    int B = 0, M = 0;       // items, token rows
+    bool causal = false;    // the text tower
+    bool fold = false, fold_final = false;  // LayerNorm folded into QKV / FC1 (mode 2; else kernels), on FINISHED (mean, rstd) (d > 768)
+    bool fp8 = false;       // QKV / FC1 / FC2 on the block-scaled fp8 GEMMs
+    bool fold8 = false;     // fp8 with the LayerNorm folded into QKV / FC1 (hidden 1024)
+    bool out8 = false;      // the attention output leaves as MXFP8 and the out-projection runs on fp8 (not the pruned last layer)
+    bool resid16 = false;   // the residual stream is the bf16 rows xb (no f32 stream)
+    bool sfold = false;     // one request: skinny GEMMs with the LayerNorm folded in (16-column statistics)
+    bool prune = false;     // the last layer runs on the pooled rows only
+    EmbedOut embed = EmbedOut::Nothing;
+    GemmPick qkv{}, out{}, fc1{}, fc2{};
+};
+
+static const char* const kLnMode1Removed = "LayerNorm mode 1 (normalised during operand staging) was removed in round 4: measured 342-371 TF, profiles/gemm_variants_r01.md";
+
+int plan_layers(const mmiss_encoder* e, const Tower& tw, int B, bool causal, LayerPlan& P) {
+    const int d = tw.hidden, M = B * tw.T;
+    P = LayerPlan{};
+    P.B = B; P.M = M; P.causal = causal;
+    const int fold_min_rows = mmiss_option("ln_fold_min_rows", 6000);
+    // LayerNorm placement: set_fuse_ln, else option ln_mode, else automatic: folded (2) from `ln_fold_min_rows` rows while the
+    // hidden size allows it (ViT-L/14's 1024 folds since round 4: finished row statistics in front of the persistent GEMM;
+    // option ln_fold_1024 = 0 gives the separate LayerNorm kernels back), separate kernels (0) below
     int mode = e->ln_mode;
     if (mode < 0) {
         const int forced = mmiss_option("ln_mode", -1);
-        // (hidden 1024 — ViT-L/14 — folds since round 4: finished row statistics in front of the persistent GEMM; option
-        // ln_fold_1024 = 0 gives the separate LayerNorm kernels back)
+        if (forced == 1) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s", kLnMode1Removed);
         const int max_hidden = mmiss_option("ln_fold_1024", 1) != 0 ? 1024 : 768;
-        mode = forced >= 0 ? forced : ((M >= mmiss_option("ln_fold_min_rows", 6000) && tw.hidden <= max_hidden) ? 2 : 0);
+        mode = forced >= 0 ? forced : ((M >= fold_min_rows && d <= max_hidden) ? 2 : 0);
     }
-    fp8 = e->fp8_tower[&tw == &e->txt ? 1 : 0] && tw.fp8_ready && tw.h8.p && M >= mmiss_option("fp8_min_rows", 1024);
-    if (fp8) mode = 0;  // the fp8 GEMMs take their A operand from the MXFP8 LayerNorm kernel
-    return mode;
-}
-
-int run_layers(mmiss_encoder* e, Tower& tw, int B, bool causal, hipStream_t st) {
-    const int d = tw.hidden, M = B * tw.T;
-    const float eps = e->cfg.ln_eps;
-    // per-GEMM tile height (fills the 256 CUs x 2 blocks evenly) and the row count padded to it
-    // the LayerNorm-fused / folded GEMMs (ln_mode 1, 2) exist for the 128-column tiles only
-    bool fp8 = false;
-    const int mode = pick_ln_mode(e, tw, M, fp8);
+    P.fp8 = e->fp8_tower[&tw == &e->txt ? 1 : 0] && tw.fp8_ready && tw.h8.p && M >= mmiss_option("fp8_min_rows", 1024);
+    if (P.fp8) mode = 0;  // the fp8 GEMMs take their A operand from the MXFP8 LayerNorm kernel
     const bool plain = mode == 0;
-    int bm_qkv = plain ? gemm_pick_variant(M, 3 * d) : gemm_pick_bm(M, 3 * d);
-    int bm_d = plain ? gemm_pick_variant(M, d) : gemm_pick_bm(M, d);
-    int bm_mlp = plain ? gemm_pick_variant(M, tw.mlp) : gemm_pick_bm(M, tw.mlp);
-    // experiment knobs (tools/option_ab.py): force a tile variant per GEMM family
-    if (const int f = mmiss_option("gemm_bm_qkv", 0)) bm_qkv = f;
-    if (const int f = mmiss_option("gemm_bm_d", 0)) bm_d = f;
-    if (const int f = mmiss_option("gemm_bm_mlp", 0)) bm_mlp = f;
-    auto padded = [&](int bm) { return (int)round_up(M, bm % 1000); };
-    const int bm8_qkv = gemm_pick_bm(M, 3 * d), bm8_d = gemm_pick_bm(M, d), bm8_mlp = gemm_pick_bm(M, tw.mlp);
+    P.fold = mode == 2;
+    P.fold_final = d > 768;
+
+    // per-GEMM tile height (fills the 256 CUs x 2 blocks evenly); experiment knobs (tools/option_ab.py) force one per GEMM family
+    auto tile_height = [&](const char* key, int N, int& bm) -> int {
+        bm = mmiss_option(key, 0);
+        if (bm == 0) bm = gemm_pick_bm(M, N);
+        else if (bm != 128 && bm != 160 && bm != 192) MM_FAIL(MMISS_ERR_ARG, "option %s = %d: tile height must be 128, 160 or 192", key, bm);
+        return MMISS_OK;
+    };
+    int bm_qkv, bm_d, bm_mlp;
+    MM_TRY(tile_height("gemm_bm_qkv", 3 * d, bm_qkv));
+    MM_TRY(tile_height("gemm_bm_d", d, bm_d));
+    MM_TRY(tile_height("gemm_bm_mlp", tw.mlp, bm_mlp));
+
     // fp8 GEMMs on the persistent 256 x 256 kernel (gemm_fp8_p256.h, round 5) once there is a tile per CU; K % 256 == 0 (round 6:
     // every GEMM of ViT-L/14 AND of ViT-B/32, whose K = 768 is three K-tile pairs). Option gemm_p256_fp8 = 0 turns it off,
     // n > 1 = minimum tile count. The N = 768 GEMMs of ViT-B/32 at 12 800 rows (FC2, out-projection) are 150 tiles of 256 x 256
@@ -316,10 +333,8 @@ int run_layers(mmiss_encoder* e, Tower& tw, int B, bool causal, hipStream_t st) 
         if (p8_min == 1 && p8_narrow > 0 && tiles < 256 && tiles >= p8_narrow && M >= 6000) return true;   // (measured at 12 800 rows only)
         return tiles >= (p8_min > 1 ? p8_min : 256);
     };
-    auto gemm8_any = [&](int epi, int bm, Gemm8Args g8, int xt = 0) -> int {   // g8.M unset: padded here to the kernel's tile height
-        if (xt != 0 || p8(epi, g8.N, g8.K)) { g8.M = (int)round_up(M, 256); return launch_gemm256p8(st, epi, g8, xt); }
-        g8.M = (int)round_up(M, bm % 1000);
-        return launch_gemm8(st, epi, bm, g8);
+    auto pick8 = [&](int epi, int N, int K) -> GemmPick {
+        return p8(epi, N, K) ? GemmPick{GemmKind::P256Fp8, 256} : GemmPick{GemmKind::Fp8Tile, gemm_pick_bm(M, N)};
     };
     // 256 x 256 phase-pipelined tile for the widest GEMMs. Round 1 used it from N = 4096 (the ViT-L/14 FC1: 336 -> 320 us);
     // with the banded tile order the 128-column kernel now does that GEMM in 292 us (312 us on the 256 x 256 tile, whose
@@ -333,27 +348,25 @@ int run_layers(mmiss_encoder* e, Tower& tw, int B, bool causal, hipStream_t st) 
     // -1 = this rule, 0 = never, n > 0 = from N = n whatever the fill.
     const int min_n256f = mmiss_option("gemm_256_fold", -1);
     auto fold256 = [&](int N) {
-        if (mode != 2 || min_n256f == 0 || (N % 256) != 0 || (d % 64) != 0 || M <= 512) return false;
+        if (!P.fold || min_n256f == 0 || (N % 256) != 0 || (d % 64) != 0 || M <= 512) return false;
         if (min_n256f > 0) return N >= min_n256f;
         const int64_t tiles = (int64_t)((M + 255) / 256) * (N / 256), rounds = (tiles + 255) / 256;
         return tiles * 100 >= rounds * 256 * 85;
     };  // (workspace rows are padded to round_up(M, 128) + 192 >= round_up(M, 256))
+    const bool fold256_mlp = mmiss_option("gemm_256_fold_mlp", 0) != 0;   // (A/B knob: 78 -> 84 us at 12 800 rows, off)
     // Persistent form of that tile (gemm_bf16_p256.h, round 3): one workgroup per CU walks its tiles as one K stream with the
     // epilogue in registers. Taken for the wide GEMMs (QKV, FC1) of calls with at least 256 tiles (one per CU); option
     // gemm_p256 = 0 turns it off, n > 1 = minimum tile count.
     const int p256_min = mmiss_option("gemm_p256", 1);
-    const bool fold_final = d > 768;   // the folded persistent GEMM takes FINISHED (mean, rstd) per row (tw.stats_final)
     auto p256 = [&](int epi, int N) {
         const bool is_fold = epi == MMISS_EPI_LNFOLD_BF16 || epi == MMISS_EPI_LNFOLD_QGELU_BF16;
-        if (p256_min == 0 || !gemm256p_ok(epi, padded(256), N, d, is_fold && fold_final && tw.stats_final.p)) return false;
-        return (int64_t)(padded(256) / 256) * (N / 256) >= (p256_min > 1 ? p256_min : 256);
+        if (p256_min == 0 || !gemm256p_ok(epi, (int)round_up(M, 256), N, d, is_fold && P.fold_final && tw.stats_final.p)) return false;
+        return (int64_t)(round_up(M, 256) / 256) * (N / 256) >= (p256_min > 1 ? p256_min : 256);
     };
-    auto finalize_stats = [&]() -> int {   // partial (sum, sumsq) per 64 columns -> (mean, rstd) per row
-        MM_PROF("ln_finalize", st, 4.0 * M * (d / 64), (double)M * ((d / 64) * 8 + 8));
-        hipLaunchKernelGGL(ln_finalize_kernel, dim3((M * 8 + 255) / 256), dim3(256), 0, st, tw.stats.as<float>(),
-                           tw.stats_final.as<float>(), M, d / 64, d, eps);
-        MM_HIP(hipGetLastError());
-        return MMISS_OK;
+    auto wide = [&](int epi, int epi_fold, int N, int bm, bool fold256_ok) -> GemmPick {
+        if (P.fold ? p256(epi_fold, N) : p256(epi, N)) return {GemmKind::P256, 256};
+        if (P.fold ? fold256(N) && fold256_ok : use256(N)) return {GemmKind::Tile256, 256};
+        return {GemmKind::Tile, bm};
     };
     // The residual GEMMs on the bf16 stream (out-projection, FC2) on the 160 x 256 tile of the two-phase staggered loop
     // (gemm_bf16_p160.h, round 3) when that grid is about one round of the chip, or K is long: isolated, ViT-B/32 bs 256
@@ -361,10 +374,197 @@ int run_layers(mmiss_encoder* e, Tower& tw, int B, bool causal, hipStream_t st) 
     // 828 tiles of K = 1024, is faster on the 128-column tile: 93 vs 98 us). Option gemm_p160 = 0 turns it off.
     const int p160_opt = mmiss_option("gemm_p160", 1);
     auto p160 = [&](int N, int K) {
-        if (p160_opt == 0 || !gemm160p_ok(padded(160), N, K)) return false;
-        const int64_t tiles = (int64_t)(padded(160) / 160) * (N / 256);
+        if (p160_opt == 0 || !gemm160p_ok((int)round_up(M, 160), N, K)) return false;
+        const int64_t tiles = (int64_t)(round_up(M, 160) / 160) * (N / 256);
         return tiles >= 200 && (tiles <= 256 || K >= 2048);
     };
+    auto resid = [&](int K) -> GemmPick {
+        return P.resid16 && p160(d, K) ? GemmPick{GemmKind::P160, 160} : GemmPick{GemmKind::Tile, bm_d};
+    };
+
+    // Only the pooled row of every item (token 0 / first EOS) leaves the last layer (HF:modeling_clip.py:650-651,
+    // 561-581), and rows do not mix after the attention: out-proj, LN2 and the MLP of the LAST layer run on those B
+    // rows only (compacted). Kept off while taps are recorded so the tests can compare every row of every layer.
+    P.prune = !e->record_taps;
+    // bf16 residual stream for the large calls (needs the pruned last layer, i.e. no taps): the residual GEMMs
+    // read-modify-write the bf16 rows; in the folded mode these rows are the A operand of the next GEMM as well, in the
+    // separate-LayerNorm mode (hidden > 768: ViT-L/14) the LayerNorm kernel reads them. Default under MMISS_PREC_BF16 from
+    // `ln_fold_min_rows` rows; MMISS_PREC_BF16_F32RESID or option resid16 = 0 keep the f32 stream (small calls always do).
+    // ViT-B/32, 256 images: residual GEMMs 33.8 -> 28.5 us (K = 768), 71.4 -> 66.6 us (K = 3072), encode 3.05 -> 2.91 ms;
+    // 1 - cos vs the fp32 oracle 5e-6 -> 5e-5 (tolerance 1e-3).
+    const int r16opt = mmiss_option("resid16", -1);
+    const bool r16mode = P.fold || (plain && M >= fold_min_rows);  // (fp8 GEMMs included)
+    P.resid16 = r16mode && P.prune && tw.layers >= 1 && (r16opt >= 0 ? r16opt != 0 : e->precision != MMISS_PREC_BF16_F32RESID);
+    // One request at a time (all four GEMMs of a layer on the weight-streaming skinny kernel, M <= 128): LayerNorm folded
+    // into the QKV / FC1 weights there as well — the skinny residual GEMMs leave a bf16 copy of the new rows and their
+    // partial statistics per 16 columns, the skinny QKV / FC1 GEMMs apply (mean, rstd) in their epilogue. 24 of the ~99
+    // launches of a ViT-B/32 request disappear. Option skinny_fold = 0 keeps the LayerNorm kernels.
+    // (round 6, VERDICT r5 next #8, tried and removed: every skinny launch touching the weight lines of the NEXT skinny launch — one
+    // dword per 128-byte line, workgroup L taking blocks L, L + grid, ... so that they land in the L2 of the XCD that reads them
+    // next — made the request 3 % SLOWER, 0.4603 against 0.4466 ms per encode, same bits: profiles/single_request_r06.txt)
+    if (plain && !P.fp8 && M <= 128 && (d % 128) == 0 && mmiss_option("skinny_fold", 1) != 0) {
+        GemmEpi probe{};
+        probe.stats16 = 1;
+        P.sfold = gemm_skinny_ok(MMISS_EPI_LNFOLD_BF16, M, 3 * d, d, probe) && gemm_skinny_ok(MMISS_EPI_LNFOLD_QGELU_BF16, M, tw.mlp, d, probe) &&
+                  gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, M, d, d, probe) && gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, M, d, tw.mlp, probe);
+    }
+    // fp8 tower: the attention output leaves the kernel as MXFP8 and the out-projection runs on the fp8 GEMM too (round 4:
+    // the long-sequence kernels, ViT-L/14; round 6: the one-pass kernels as well, ViT-B/32's 50 keys; option fp8_outproj = 0:
+    // bf16 ctx + bf16 out-projection as in round 3). Not in the pruned last layer (its out-projection is a 128-row bf16
+    // GEMM on gathered rows).
+    const bool fp8_outproj = mmiss_option("fp8_outproj", 1) != 0;
+    P.out8 = P.fp8 && !causal && P.resid16 && tw.L[0].wo8.p && tw.ctx8.p && attention_mx_ok(tw.T, tw.heads) && fp8_outproj;
+    // fp8 tower with the LayerNorm FOLDED into the QKV / FC1 GEMMs (round 5; hidden 1024 on the persistent fp8 kernel): the residual
+    // GEMMs' epilogue leaves the new bf16 rows as MXFP8 — raw — with their 256-column statistics, the QKV / FC1 epilogue applies
+    // (mean, rstd): 46 of the 47 LayerNorm launches of a ViT-L/14 encode disappear (tools/fp8_fold_sim.py: the same 1 - cos as
+    // LayerNorm-then-quantise). OFF by default (option fp8_ln_fold = 1 turns it on): measured inside the bs-128 encode the 1.03 ms
+    // of LayerNorm kernels (HBM-bound, 4.5 TB/s) come back as 1.3 ms of epilogue time in the GEMMs — +12 us per residual GEMM
+    // (half again as many bytes stored in the epilogue burst of 256 workgroups in step), +12 / +20 us per QKV / FC1 (two more packed
+    // operations per value and a workgroup barrier per tile), with the matrix pipes idle meanwhile: 9.19 k against 9.40 k images/s
+    // (tools/l14_fp8_ab.py, tools/l14_kernel_table.py; DESIGN.md 3b).
+    if (P.fp8 && P.resid16 && !causal && d == 1024 && tw.layers >= 1 && tw.L[0].wqkv8f.p && tw.ctx8.p && attention_mx_ok(tw.T, tw.heads) &&
+        fp8_outproj && mmiss_option("fp8_ln_fold", 0) != 0 && p8(MMISS_EPI8_BIAS_BF16, 3 * d, d) &&
+        p8(MMISS_EPI8_QGELU_MXFP8, tw.mlp, d) && p8(MMISS_EPI8_BIAS_RESID_BF16, d, d) && p8(MMISS_EPI8_BIAS_RESID_BF16, d, tw.mlp)) {
+        Gemm8Args t{};   // (the residual form must not end in a round of half tiles)
+        t.M = (int)round_up(M, 256); t.N = d; t.K = d; t.m_valid = M;
+        t.ragged = (t.M >= 512 && M > t.M - 256 && M <= t.M - 128 && mmiss_option("gemm_p256_ragged", 1) != 0) ? M - (t.M - 256) : 0;
+        t.q_out = tw.h8.as<uint8_t>(); t.q_scale = tw.hs.as<uint8_t>(); t.stats_out = tw.stats.as<float>(); t.ld_qs = mx_scale_row_bytes(d);
+        P.fold8 = gemm256p8_xt_ok(MMISS_EPI8_BIAS_RESID_BF16, 2, t);
+    }
+
+    const GemmPick xt{GemmKind::P256Fp8Xt, 256}, skinny{GemmKind::Skinny, 0};
+    P.qkv = P.fold8 ? xt : P.fp8 ? pick8(MMISS_EPI8_BIAS_BF16, 3 * d, d)
+          : P.sfold ? skinny : wide(MMISS_EPI_BIAS_BF16, MMISS_EPI_LNFOLD_BF16, 3 * d, bm_qkv, true);
+    P.fc1 = P.fold8 ? xt : P.fp8 ? pick8(MMISS_EPI8_QGELU_MXFP8, tw.mlp, d)
+          : P.sfold ? skinny : wide(MMISS_EPI_BIAS_QGELU_BF16, MMISS_EPI_LNFOLD_QGELU_BF16, tw.mlp, bm_mlp, fold256_mlp);
+    P.out = P.out8 ? (P.fold8 ? xt : pick8(MMISS_EPI8_BIAS_RESID_BF16, d, d)) : resid(d);
+    P.fc2 = P.fp8 ? (P.fold8 ? xt : pick8(P.resid16 ? MMISS_EPI8_BIAS_RESID_BF16 : MMISS_EPI8_BIAS_RESID_F32, d, tw.mlp)) : resid(tw.mlp);
+
+    // the vision embedding stage's pre-LayerNorm: one request at a time (the layers run in the skinny folded mode) CLS rows,
+    // pre_layrnorm and the mode's entry statistics are ONE launch behind the patch GEMM (option embed_fused = 0: off); when
+    // the layers want the bf16 copy and the row statistics (folded LayerNorm, bf16 residual stream) the LayerNorm writes them
+    if (&tw == &e->vis && !e->record_taps) {
+        if (P.sfold && d <= 1024 && (d % 16) == 0 && mmiss_option("embed_fused", 1) != 0)
+            P.embed = EmbedOut::Stats16;
+        else if (d % 128 == 0 && r16mode && mmiss_option("prelayernorm_stats", 1) != 0)
+            P.embed = EmbedOut::Stats64;
+    }
+    return MMISS_OK;
+}
+
+// an fp8 GEMM on the planned kernel, M rows padded to its tile height (xt: the folded-LayerNorm form of P256Fp8Xt)
+static int launch_gemm8_pick(hipStream_t st, GemmPick k, int epi, Gemm8Args g, int M, int xt) {
+    if (k.kind == GemmKind::Fp8Tile) { g.M = (int)round_up(M, k.bm); return launch_gemm8(st, epi, k.bm, g); }
+    g.M = (int)round_up(M, 256);
+    return launch_gemm256p8(st, epi, g, k.kind == GemmKind::P256Fp8Xt ? xt : 0);
+}
+
+// QKV / FC1: LayerNorm(x; g, beta) W^T + bias (+ QuickGELU for FC1), with the LayerNorm as the plan places it
+struct WideRole {
+    int N;
+    bool gelu;                        // FC1
+    const DevBuf *g, *beta;           // LayerNorm
+    const DevBuf *W, *b;              // bf16 weights [N, d], bias
+    const DevBuf *Wf, *bf, *c;        // the LayerNorm folded in: gamma-folded weights, bias b', row sums c (fold, sfold)
+    const DevBuf *W8, *s8;            // fp8 weights, per-channel scales
+    const DevBuf *W8f, *s8f, *c16;    // fp8 of the folded weights, scales, f16 row sums (fold8)
+    void *out, *out8;                 // bf16 [M, N]; on the fp8 path bf16 (QKV) or e4m3 + MXFP8 scales (FC1)
+    uint8_t* out8_scale;
+};
+
+int run_wide(hipStream_t st, Tower& tw, const LayerPlan& P, GemmPick k, const WideRole& r, float eps) {
+    const int d = tw.hidden, M = P.M, N = r.N;
+    if (is_fp8(k.kind)) {
+        Gemm8Args g{};
+        if (k.kind == GemmKind::P256Fp8Xt) {   // A = the raw rows as MXFP8 + statistics, the bf16 rows for a ragged block
+            g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
+            g.ln_stats = tw.stats.as<float>(); g.x16 = tw.xb.as<uint16_t>(); g.ln_eps = eps;
+            g.W = r.W8f->as<uint8_t>(); g.wscale = r.s8f->as<float>(); g.bias = r.bf->as<float>(); g.c16 = r.c16->as<uint16_t>();
+        } else {
+            MM_TRY(launch_layernorm_mxfp8(st, P.resid16 ? tw.xb.p : tw.x.p, P.resid16, r.g->as<float>(), r.beta->as<float>(),
+                                          tw.h8.as<uint8_t>(), tw.hs.as<uint8_t>(), M, d, eps));
+            g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
+            g.W = r.W8->as<uint8_t>(); g.wscale = r.s8->as<float>(); g.bias = r.b->as<float>();
+        }
+        g.out = r.out8;
+        if (r.out8_scale) { g.out_scale = r.out8_scale; g.ld_os = mx_scale_row_bytes(N); }
+        g.ldo = N; g.N = N; g.K = d; g.m_valid = M;
+        return launch_gemm8_pick(st, k, r.gelu ? MMISS_EPI8_QGELU_MXFP8 : MMISS_EPI8_BIAS_BF16, g, M, 1);
+    }
+    GemmEpi ep{};
+    ep.out = r.out; ep.bias = r.b->as<float>(); ep.ldo = N; ep.m_valid = M;
+    int epi = r.gelu ? MMISS_EPI_BIAS_QGELU_BF16 : MMISS_EPI_BIAS_BF16;
+    const void* A = tw.h.p;
+    const void* W = r.W->p;
+    if (k.kind == GemmKind::Skinny || P.fold) {   // A = the bf16 rows, (mean, rstd) applied in the epilogue
+        epi = r.gelu ? MMISS_EPI_LNFOLD_QGELU_BF16 : MMISS_EPI_LNFOLD_BF16;
+        A = tw.xb.p; W = r.Wf->p;
+        ep.bias = r.bf->as<float>(); ep.aux = r.c->as<float>(); ep.ln_stats = tw.stats.as<float>(); ep.ln_eps = eps;
+        if (k.kind == GemmKind::Skinny) {
+            ep.ln_parts = d / 16; ep.stats16 = 1;
+            return launch_gemm_skinny_fold(st, epi, A, W, ep, M, N, d);
+        }
+        ep.ln_parts = d / 64;
+        if (k.kind == GemmKind::P256 && P.fold_final) {   // partial (sum, sumsq) per 64 columns -> (mean, rstd) per row
+            MM_PROF("ln_finalize", st, 4.0 * M * (d / 64), (double)M * ((d / 64) * 8 + 8));
+            hipLaunchKernelGGL(ln_finalize_kernel, dim3((M * 8 + 255) / 256), dim3(256), 0, st, tw.stats.as<float>(),
+                               tw.stats_final.as<float>(), M, d / 64, d, eps);
+            MM_HIP(hipGetLastError());
+            ep.ln_final = tw.stats_final.as<float>();
+        }
+    } else if (P.resid16) {
+        MM_TRY(launch_layernorm16(st, tw.xb.as<uint16_t>(), r.g->as<float>(), r.beta->as<float>(), tw.h.p, M, d, eps));
+    } else {
+        MM_TRY(launch_layernorm(st, tw.x.as<float>(), r.g->as<float>(), r.beta->as<float>(), tw.h.p, true, nullptr, M, d, eps));
+    }
+    switch (k.kind) {
+        case GemmKind::P256: return launch_gemm256p(st, epi, A, W, ep, (int)round_up(M, 256), N, d);
+        case GemmKind::Tile256: return launch_gemm256(st, epi, A, W, ep, (int)round_up(M, 256), N, d);
+        case GemmKind::Tile:
+            if (P.fold) return launch_gemm_fold(st, epi, k.bm, A, W, ep, (int)round_up(M, k.bm), N, d);
+            return launch_gemm(st, epi, k.bm, A, W, ep, (int)round_up(M, k.bm), N, d);
+        default: MM_FAIL(MMISS_ERR_UNSUPPORTED, "run_wide: kernel %d planned for a QKV / FC1 GEMM", (int)k.kind);
+    }
+}
+
+// out-projection / FC2: the residual stream (f32 x, or the bf16 rows xb) += A W^T + bias
+struct ResidRole {
+    int K;
+    const void* A;                  // bf16 [M, K]
+    const uint8_t *A8, *As;         // the same as MXFP8 (fp8 kernels)
+    const DevBuf *W, *b;            // bf16 weights [d, K], bias
+    const DevBuf *W8, *s8;          // fp8 weights, per-channel scales
+    bool splitk;                    // FC2: the split-K scratch of the middle batch sizes
+};
+
+int run_resid(hipStream_t st, Tower& tw, const LayerPlan& P, GemmPick k, const ResidRole& r) {
+    const int d = tw.hidden, M = P.M;
+    if (is_fp8(k.kind)) {
+        Gemm8Args g{};
+        g.A = r.A8; g.As = r.As; g.ld_as = mx_scale_row_bytes(r.K);
+        g.W = r.W8->as<uint8_t>(); g.wscale = r.s8->as<float>(); g.bias = r.b->as<float>();
+        g.out = P.resid16 ? tw.xb.p : tw.x.p; g.ldo = d; g.N = d; g.K = r.K; g.m_valid = M;
+        if (k.kind == GemmKind::P256Fp8Xt) {   // fold8: the new rows also leave as MXFP8 + statistics for the next QKV / FC1
+            g.q_out = tw.h8.as<uint8_t>(); g.q_scale = tw.hs.as<uint8_t>(); g.ld_qs = mx_scale_row_bytes(d); g.stats_out = tw.stats.as<float>();
+        }
+        return launch_gemm8_pick(st, k, P.resid16 ? MMISS_EPI8_BIAS_RESID_BF16 : MMISS_EPI8_BIAS_RESID_F32, g, M, 2);
+    }
+    GemmEpi ep{};
+    ep.out = tw.x.p; ep.bias = r.b->as<float>(); ep.ldo = d; ep.m_valid = M;
+    ep.stats_out = (P.fold || P.sfold) ? tw.stats.as<float>() : nullptr;  // row statistics of the new residual for the next LayerNorm
+    ep.xb_out = (P.fold || P.sfold) ? tw.xb.p : nullptr;
+    ep.stats16 = P.sfold ? 1 : 0;
+    if (r.splitk) { ep.splitk_ws = tw.splitk.as<float>(); ep.splitk_ws_bytes = tw.splitk.bytes; }
+    if (!P.resid16) return launch_gemm(st, MMISS_EPI_BIAS_RESID_F32, k.bm, r.A, r.W->p, ep, (int)round_up(M, k.bm), d, r.K);
+    ep.out = tw.xb.p; ep.xb_out = nullptr;  // the bf16 rows ARE the residual stream: read-modify-write in place, no f32 stream
+    if (k.kind == GemmKind::P160) return launch_gemm160p(st, r.A, r.W->p, ep, (int)round_up(M, 160), d, r.K);
+    return launch_gemm_resid16(st, k.bm, r.A, r.W->p, ep, (int)round_up(M, k.bm), d, r.K);
+}
+
+// the transformer stack shared by both towers, as planned; x (and what P.embed names) holds the embeddings on entry
+int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) {
+    const int d = tw.hidden, M = P.M, B = P.B;
+    const float eps = e->cfg.ln_eps;
     // split-K scratch for the narrow long-K GEMM (FC2) while its grid is far below the CU count
     if (gemm_splitk_candidate((int64_t)((M + 127) / 128) * (d / GEMM_BN), tw.mlp))
         MM_TRY(tw.splitk.ensure((size_t)8 * (round_up(M, 128) + 192) * d * 4));  // any tile height's row padding
@@ -375,139 +575,46 @@ int run_layers(mmiss_encoder* e, Tower& tw, int B, bool causal, hipStream_t st) 
         return MMISS_OK;
     };
     MM_TRY(tap(0));
-    // Only the pooled row of every item (token 0 / first EOS) leaves the last layer (HF:modeling_clip.py:650-651,
-    // 561-581), and rows do not mix after the attention: out-proj, LN2 and the MLP of the LAST layer run on those B
-    // rows only (compacted). Kept off while taps are recorded so the tests can compare every row of every layer.
-    const bool prune = !e->record_taps;
     tw.pooled_compact = false;
-    const bool fuse = mode == 1, fold = mode == 2;
-    // bf16 residual stream for the large calls (needs the pruned last layer, i.e. no taps): the residual GEMMs
-    // read-modify-write the bf16 rows; in the folded mode these rows are the A operand of the next GEMM as well, in the
-    // separate-LayerNorm mode (hidden > 768: ViT-L/14) the LayerNorm kernel reads them. Default under MMISS_PREC_BF16 from
-    // `ln_fold_min_rows` rows; MMISS_PREC_BF16_F32RESID or option resid16 = 0 keep the f32 stream (small calls always do).
-    // ViT-B/32, 256 images: residual GEMMs 33.8 -> 28.5 us (K = 768), 71.4 -> 66.6 us (K = 3072), encode 3.05 -> 2.91 ms;
-    // 1 - cos vs the fp32 oracle 5e-6 -> 5e-5 (tolerance 1e-3).
-    const int r16opt = mmiss_option("resid16", -1);
-    const bool r16mode = fold || (plain && M >= mmiss_option("ln_fold_min_rows", 6000) && bm_d < 1000);  // (fp8 GEMMs included)
-    const bool resid16 = r16mode && prune && tw.layers >= 1 &&
-                         (r16opt >= 0 ? r16opt != 0 : e->precision != MMISS_PREC_BF16_F32RESID);
-    // One request at a time (all four GEMMs of a layer on the weight-streaming skinny kernel, M <= 128): LayerNorm folded
-    // into the QKV / FC1 weights there as well — the skinny residual GEMMs leave a bf16 copy of the new rows and their
-    // partial statistics per 16 columns, the skinny QKV / FC1 GEMMs apply (mean, rstd) in their epilogue. 24 of the ~99
-    // launches of a ViT-B/32 request disappear. Option skinny_fold = 0 keeps the LayerNorm kernels.
-    const bool sfold = plain && !fp8 && skinny_fold_ok(tw, M);
-    // (round 6, VERDICT r5 next #8, tried and removed: every skinny launch touching the weight lines of the NEXT skinny launch — one
-    // dword per 128-byte line, workgroup L taking blocks L, L + grid, ... so that they land in the L2 of the XCD that reads them
-    // next — made the request 3 % SLOWER, 0.4603 against 0.4466 ms per encode, same bits: profiles/single_request_r06.txt)
-    const int parts = d / 64;
-    const bool have_embed_stats16 = tw.embed_stats16;   // (the one-request embedding stage already wrote xb + the 16-column statistics)
-    tw.embed_stats16 = false;
-    if (sfold && !have_embed_stats16) {
+    // entry statistics of the first layer's LayerNorm, unless the embedding stage already left them
+    if (P.sfold && P.embed != EmbedOut::Stats16) {
         MM_PROF("row_stats", st, 3.0 * M * d, 6.0 * M * d);
         hipLaunchKernelGGL(skinny_row_stats16_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), tw.stats.as<float>(),
                            tw.xb.as<uint16_t>(), M, d);
         MM_HIP(hipGetLastError());
     }
-    const bool have_embed_stats = tw.embed_stats;  // (the vision embedding stage's pre-LN already wrote xb + statistics)
-    tw.embed_stats = false;
-    if ((fuse || fold || resid16) && !have_embed_stats) {  // (separate-LayerNorm mode with a bf16 stream: only the bf16 copy is used)
-        MM_PROF("row_stats", st, 3.0 * M * d, (fold ? 6.0 : 4.0) * M * d);
+    if ((P.fold || P.resid16) && P.embed != EmbedOut::Stats64) {  // (separate-LayerNorm mode with a bf16 stream: only the bf16 copy is used)
+        MM_PROF("row_stats", st, 3.0 * M * d, (P.fold ? 6.0 : 4.0) * M * d);
         hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), tw.stats.as<float>(),
-                           (fold || resid16) ? tw.xb.as<uint16_t>() : nullptr, M, d, parts);
+                           tw.xb.as<uint16_t>(), M, d, d / 64);
         MM_HIP(hipGetLastError());
     }
-    // fp8 tower with the LayerNorm FOLDED into the QKV / FC1 GEMMs (round 5; hidden 1024 on the persistent fp8 kernel): the residual
-    // GEMMs' epilogue leaves the new bf16 rows as MXFP8 — raw — with their 256-column statistics, the QKV / FC1 epilogue applies
-    // (mean, rstd): 46 of the 47 LayerNorm launches of a ViT-L/14 encode disappear (tools/fp8_fold_sim.py: the same 1 - cos as
-    // LayerNorm-then-quantise). OFF by default (option fp8_ln_fold = 1 turns it on): measured inside the bs-128 encode the 1.03 ms
-    // of LayerNorm kernels (HBM-bound, 4.5 TB/s) come back as 1.3 ms of epilogue time in the GEMMs — +12 us per residual GEMM
-    // (half again as many bytes stored in the epilogue burst of 256 workgroups in step), +12 / +20 us per QKV / FC1 (two more packed
-    // operations per value and a workgroup barrier per tile), with the matrix pipes idle meanwhile: 9.19 k against 9.40 k images/s
-    // (tools/l14_fp8_ab.py, tools/l14_kernel_table.py; DESIGN.md 3b).
-    bool fold8 = false;
-    if (fp8 && resid16 && !causal && d == 1024 && tw.layers >= 1 && tw.L[0].wqkv8f.p && tw.ctx8.p && attention_mx_ok(tw.T, tw.heads) &&
-        mmiss_option("fp8_outproj", 1) != 0 && mmiss_option("fp8_ln_fold", 0) != 0 && p8(MMISS_EPI8_BIAS_BF16, 3 * d, d) &&
-        p8(MMISS_EPI8_QGELU_MXFP8, tw.mlp, d) && p8(MMISS_EPI8_BIAS_RESID_BF16, d, d) && p8(MMISS_EPI8_BIAS_RESID_BF16, d, tw.mlp)) {
-        Gemm8Args t{};   // (the residual form must not end in a round of half tiles)
-        t.M = (int)round_up(M, 256); t.N = d; t.K = d; t.m_valid = M;
-        t.ragged = (t.M >= 512 && M > t.M - 256 && M <= t.M - 128 && mmiss_option("gemm_p256_ragged", 1) != 0) ? M - (t.M - 256) : 0;
-        t.q_out = tw.h8.as<uint8_t>(); t.q_scale = tw.hs.as<uint8_t>(); t.stats_out = tw.stats.as<float>(); t.ld_qs = mx_scale_row_bytes(d);
-        fold8 = gemm256p8_xt_ok(MMISS_EPI8_BIAS_RESID_BF16, 2, t);
-    }
-    if (fold8) {
+    if (P.fold8) {
         MM_PROF("quant16_mxfp8_stats", st, 3.0 * M * d, 3.0 * M * d);
         hipLaunchKernelGGL(quant16_mxfp8_stats_1024_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.xb.as<uint16_t>(), tw.h8.as<uint8_t>(),
                            tw.hs.as<uint8_t>(), tw.stats.as<float>(), M, mx_scale_row_bytes(d));
         MM_HIP(hipGetLastError());
     }
-    auto fold8_args = [&](Gemm8Args& g) {   // the consumer side: A = the raw rows as MXFP8, statistics, the bf16 rows for a ragged block
-        g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
-        g.ln_stats = tw.stats.as<float>(); g.x16 = tw.xb.as<uint16_t>(); g.ln_eps = eps;
-    };
-    auto mxq_args = [&](Gemm8Args& g) {     // the producer side
-        g.q_out = tw.h8.as<uint8_t>(); g.q_scale = tw.hs.as<uint8_t>(); g.ld_qs = mx_scale_row_bytes(d); g.stats_out = tw.stats.as<float>();
-    };
     for (int l = 0; l < tw.layers; ++l) {
         LayerW& L = tw.L[l];
-        GemmEpi ep{};
-        ep.out = tw.qkv.p; ep.bias = L.bqkv.as<float>(); ep.ldo = 3 * d; ep.m_valid = M;
-        if (fold8) {
-            Gemm8Args g{};
-            fold8_args(g);
-            g.W = L.wqkv8f.as<uint8_t>(); g.wscale = L.sqkvf.as<float>(); g.bias = L.bqkv_f.as<float>(); g.c16 = L.cqkv16.as<uint16_t>();
-            g.out = tw.qkv.p; g.ldo = 3 * d; g.N = 3 * d; g.K = d; g.m_valid = M;
-            MM_TRY(gemm8_any(MMISS_EPI8_BIAS_BF16, bm8_qkv, g, 1));
-        } else if (fold) {
-            ep.bias = L.bqkv_f.as<float>(); ep.aux = L.cqkv.as<float>();
-            ep.ln_stats = tw.stats.as<float>(); ep.ln_parts = parts; ep.ln_eps = eps;
-            if (p256(MMISS_EPI_LNFOLD_BF16, 3 * d)) {
-                if (fold_final) { MM_TRY(finalize_stats()); ep.ln_final = tw.stats_final.as<float>(); }
-                MM_TRY(launch_gemm256p(st, MMISS_EPI_LNFOLD_BF16, tw.xb.p, L.wqkv_f.p, ep, padded(256), 3 * d, d));
-            } else if (fold256(3 * d)) {
-                MM_TRY(launch_gemm256(st, MMISS_EPI_LNFOLD_BF16, tw.xb.p, L.wqkv_f.p, ep, padded(256), 3 * d, d));
-            } else {
-                MM_TRY(launch_gemm_fold(st, MMISS_EPI_LNFOLD_BF16, bm_qkv, tw.xb.p, L.wqkv_f.p, ep, padded(bm_qkv), 3 * d, d));
-            }
-        } else if (fp8) {
-            MM_TRY(launch_layernorm_mxfp8(st, resid16 ? tw.xb.p : tw.x.p, resid16, L.ln1g.as<float>(), L.ln1b.as<float>(), tw.h8.as<uint8_t>(),
-                                          tw.hs.as<uint8_t>(), M, d, eps));
-            Gemm8Args g{};
-            g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
-            g.W = L.wqkv8.as<uint8_t>(); g.wscale = L.sqkv.as<float>(); g.bias = L.bqkv.as<float>();
-            g.out = tw.qkv.p; g.ldo = 3 * d; g.N = 3 * d; g.K = d; g.m_valid = M;
-            MM_TRY(gemm8_any(MMISS_EPI8_BIAS_BF16, bm8_qkv, g));
-        } else if (sfold) {
-            ep.bias = L.bqkv_f.as<float>(); ep.aux = L.cqkv.as<float>();
-            ep.ln_stats = tw.stats.as<float>(); ep.ln_parts = d / 16; ep.ln_eps = eps; ep.stats16 = 1;
-            MM_TRY(launch_gemm_skinny_fold(st, MMISS_EPI_LNFOLD_BF16, tw.xb.p, L.wqkv_f.p, ep, M, 3 * d, d));
-        } else {
-            if (resid16) MM_TRY(launch_layernorm16(st, tw.xb.as<uint16_t>(), L.ln1g.as<float>(), L.ln1b.as<float>(), tw.h.p, M, d, eps));
-            else
-            MM_TRY(launch_layernorm(st, tw.x.as<float>(), L.ln1g.as<float>(), L.ln1b.as<float>(), tw.h.p, true, nullptr, M,
-                                    d, eps));
-            if (p256(MMISS_EPI_BIAS_BF16, 3 * d)) MM_TRY(launch_gemm256p(st, MMISS_EPI_BIAS_BF16, tw.h.p, L.wqkv.p, ep, padded(256), 3 * d, d));
-            else if (use256(3 * d)) MM_TRY(launch_gemm256(st, MMISS_EPI_BIAS_BF16, tw.h.p, L.wqkv.p, ep, padded(256), 3 * d, d));
-            else MM_TRY(launch_gemm(st, MMISS_EPI_BIAS_BF16, bm_qkv, tw.h.p, L.wqkv.p, ep, padded(bm_qkv), 3 * d, d));
-        }
-        // fp8 tower: the attention output leaves the kernel as MXFP8 and the out-projection runs on the fp8 GEMM too (round 4:
-        // the long-sequence kernels, ViT-L/14; round 6: the one-pass kernels as well, ViT-B/32's 50 keys; option fp8_outproj = 0:
-        // bf16 ctx + bf16 out-projection as in round 3). Not in the pruned last layer (its out-projection is a 128-row bf16
-        // GEMM on gathered rows).
-        const bool last_pruned = prune && l == tw.layers - 1;
-        const bool out8 = fp8 && !causal && !last_pruned && resid16 && L.wo8.p && tw.ctx8.p && attention_mx_ok(tw.T, tw.heads) &&
-                          mmiss_option("fp8_outproj", 1) != 0;
-        if (out8) MM_TRY(launch_attention_mx(st, tw.qkv.p, tw.ctx8.as<uint8_t>(), tw.ctxs.as<uint8_t>(), mx_scale_row_bytes(d), B, tw.T, tw.heads));
+        WideRole qkv{};
+        qkv.N = 3 * d; qkv.g = &L.ln1g; qkv.beta = &L.ln1b; qkv.W = &L.wqkv; qkv.b = &L.bqkv; qkv.Wf = &L.wqkv_f; qkv.bf = &L.bqkv_f;
+        qkv.c = &L.cqkv; qkv.W8 = &L.wqkv8; qkv.s8 = &L.sqkv; qkv.W8f = &L.wqkv8f; qkv.s8f = &L.sqkvf; qkv.c16 = &L.cqkv16; qkv.out = qkv.out8 = tw.qkv.p;
+        MM_TRY(run_wide(st, tw, P, P.qkv, qkv, eps));
+        const bool last_pruned = P.prune && l == tw.layers - 1;
+        if (P.out8 && !last_pruned)
+            MM_TRY(launch_attention_mx(st, tw.qkv.p, tw.ctx8.as<uint8_t>(), tw.ctxs.as<uint8_t>(), mx_scale_row_bytes(d), B, tw.T, tw.heads));
         else
-        MM_TRY(launch_attention(st, tw.qkv.p, tw.ctx.p, B, tw.T, tw.heads, causal));
-        if (prune && l == tw.layers - 1) {
+            MM_TRY(launch_attention(st, tw.qkv.p, tw.ctx.p, B, tw.T, tw.heads, P.causal));
+        if (last_pruned) {
             const int Bp = (int)round_up(B, 128);
             const int grid = (B * d / 4 + 255) / 256;
             // pooled rows of the attention output (bf16) and of the residual stream (f32, or widened bf16) in ONE launch
             hipLaunchKernelGGL(gather_pooled_kernel, dim3(grid), dim3(256), 0, st, tw.ctx.as<uint16_t>(), tw.ctxc.as<uint16_t>(),
-                               resid16 ? nullptr : tw.x.as<float>(), resid16 ? tw.xb.as<uint16_t>() : nullptr,
+                               P.resid16 ? nullptr : tw.x.as<float>(), P.resid16 ? tw.xb.as<uint16_t>() : nullptr,
                                tw.xc.as<float>(), tw.pool_row.as<int32_t>(), B, d);
             MM_HIP(hipGetLastError());
-            ep = GemmEpi{};
+            GemmEpi ep{};
             ep.out = tw.xc.p; ep.bias = L.bo.as<float>(); ep.ldo = d; ep.m_valid = B;
             MM_TRY(launch_gemm(st, MMISS_EPI_BIAS_RESID_F32, 128, tw.ctxc.p, L.wo.p, ep, Bp, d, d));
             MM_TRY(launch_layernorm(st, tw.xc.as<float>(), L.ln2g.as<float>(), L.ln2b.as<float>(), tw.hc.p, true, nullptr,
@@ -521,87 +628,19 @@ int run_layers(mmiss_encoder* e, Tower& tw, int B, bool causal, hipStream_t st) 
             tw.pooled_compact = true;
             break;
         }
-        ep = GemmEpi{};
-        ep.out = tw.x.p; ep.bias = L.bo.as<float>(); ep.ldo = d; ep.m_valid = M;
-        ep.stats_out = (fuse || fold || sfold) ? tw.stats.as<float>() : nullptr;  // row statistics of the new residual for LN2
-        ep.xb_out = (fold || sfold) ? tw.xb.p : nullptr;
-        ep.stats16 = sfold ? 1 : 0;
-        if (out8) {
-            Gemm8Args g{};
-            g.A = tw.ctx8.as<uint8_t>(); g.As = tw.ctxs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
-            g.W = L.wo8.as<uint8_t>(); g.wscale = L.so.as<float>(); g.bias = L.bo.as<float>();
-            g.out = tw.xb.p; g.ldo = d; g.N = d; g.K = d; g.m_valid = M;
-            if (fold8) mxq_args(g);
-            MM_TRY(gemm8_any(MMISS_EPI8_BIAS_RESID_BF16, bm8_d, g, fold8 ? 2 : 0));
-        } else if (resid16) {  // the bf16 rows ARE the residual stream: read-modify-write in place, no f32 stream
-            ep.out = tw.xb.p; ep.xb_out = nullptr;
-            if (p160(d, d)) MM_TRY(launch_gemm160p(st, tw.ctx.p, L.wo.p, ep, padded(160), d, d));
-            else MM_TRY(launch_gemm_resid16(st, bm_d, tw.ctx.p, L.wo.p, ep, padded(bm_d), d, d));
-        } else {
-            MM_TRY(launch_gemm(st, MMISS_EPI_BIAS_RESID_F32, bm_d, tw.ctx.p, L.wo.p, ep, padded(bm_d), d, d));
-        }
-        ep = GemmEpi{};
-        ep.out = tw.u.p; ep.bias = L.b1.as<float>(); ep.ldo = tw.mlp; ep.m_valid = M;
-        if (fold) {
-            ep.bias = L.b1_f.as<float>(); ep.aux = L.c1.as<float>();
-            ep.ln_stats = tw.stats.as<float>(); ep.ln_parts = parts; ep.ln_eps = eps;
-            if (p256(MMISS_EPI_LNFOLD_QGELU_BF16, tw.mlp)) {
-                if (fold_final) { MM_TRY(finalize_stats()); ep.ln_final = tw.stats_final.as<float>(); }
-                MM_TRY(launch_gemm256p(st, MMISS_EPI_LNFOLD_QGELU_BF16, tw.xb.p, L.w1_f.p, ep, padded(256), tw.mlp, d));
-            } else if (fold256(tw.mlp) && mmiss_option("gemm_256_fold_mlp", 0)) {  // (A/B knob: 78 -> 84 us at 12 800 rows, off)
-                MM_TRY(launch_gemm256(st, MMISS_EPI_LNFOLD_QGELU_BF16, tw.xb.p, L.w1_f.p, ep, padded(256), tw.mlp, d));
-            } else {
-                MM_TRY(launch_gemm_fold(st, MMISS_EPI_LNFOLD_QGELU_BF16, bm_mlp, tw.xb.p, L.w1_f.p, ep, padded(bm_mlp), tw.mlp, d));
-            }
-        } else if (fp8) {
-            // LN2 -> MXFP8 (fold8: folded into FC1), FC1 + QuickGELU -> MXFP8 (per row and 64 columns), FC2 + residual: `u` crosses HBM as 1 byte
-            Gemm8Args g{};
-            if (fold8) {
-                fold8_args(g);
-                g.W = L.w1_8f.as<uint8_t>(); g.wscale = L.s1f.as<float>(); g.bias = L.b1_f.as<float>(); g.c16 = L.c1_16.as<uint16_t>();
-            } else {
-                MM_TRY(launch_layernorm_mxfp8(st, resid16 ? tw.xb.p : tw.x.p, resid16, L.ln2g.as<float>(), L.ln2b.as<float>(), tw.h8.as<uint8_t>(),
-                                              tw.hs.as<uint8_t>(), M, d, eps));
-                g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
-                g.W = L.w1_8.as<uint8_t>(); g.wscale = L.s1.as<float>(); g.bias = L.b1.as<float>();
-            }
-            g.out = tw.u8.p; g.out_scale = tw.us.as<uint8_t>(); g.ld_os = mx_scale_row_bytes(tw.mlp);
-            g.ldo = tw.mlp; g.N = tw.mlp; g.K = d; g.m_valid = M;
-            MM_TRY(gemm8_any(MMISS_EPI8_QGELU_MXFP8, bm8_mlp, g, fold8 ? 1 : 0));
-            g = Gemm8Args{};
-            g.A = tw.u8.as<uint8_t>(); g.As = tw.us.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(tw.mlp);
-            g.W = L.w2_8.as<uint8_t>(); g.wscale = L.s2.as<float>(); g.bias = L.b2.as<float>();
-            g.out = resid16 ? tw.xb.p : tw.x.p; g.ldo = d; g.N = d; g.K = tw.mlp; g.m_valid = M;
-            if (fold8) mxq_args(g);
-            MM_TRY(gemm8_any(resid16 ? MMISS_EPI8_BIAS_RESID_BF16 : MMISS_EPI8_BIAS_RESID_F32, bm8_d, g, fold8 ? 2 : 0));
-            MM_TRY(tap(l + 1));
-            continue;
-        } else if (sfold) {
-            ep.bias = L.b1_f.as<float>(); ep.aux = L.c1.as<float>();
-            ep.ln_stats = tw.stats.as<float>(); ep.ln_parts = d / 16; ep.ln_eps = eps; ep.stats16 = 1;
-            MM_TRY(launch_gemm_skinny_fold(st, MMISS_EPI_LNFOLD_QGELU_BF16, tw.xb.p, L.w1_f.p, ep, M, tw.mlp, d));
-        } else {
-            if (resid16) MM_TRY(launch_layernorm16(st, tw.xb.as<uint16_t>(), L.ln2g.as<float>(), L.ln2b.as<float>(), tw.h.p, M, d, eps));
-            else
-            MM_TRY(launch_layernorm(st, tw.x.as<float>(), L.ln2g.as<float>(), L.ln2b.as<float>(), tw.h.p, true, nullptr, M,
-                                    d, eps));
-            if (p256(MMISS_EPI_BIAS_QGELU_BF16, tw.mlp)) MM_TRY(launch_gemm256p(st, MMISS_EPI_BIAS_QGELU_BF16, tw.h.p, L.w1.p, ep, padded(256), tw.mlp, d));
-            else if (use256(tw.mlp)) MM_TRY(launch_gemm256(st, MMISS_EPI_BIAS_QGELU_BF16, tw.h.p, L.w1.p, ep, padded(256), tw.mlp, d));
-            else MM_TRY(launch_gemm(st, MMISS_EPI_BIAS_QGELU_BF16, bm_mlp, tw.h.p, L.w1.p, ep, padded(bm_mlp), tw.mlp, d));
-        }
-        ep = GemmEpi{};
-        ep.out = tw.x.p; ep.bias = L.b2.as<float>(); ep.ldo = d; ep.m_valid = M;
-        ep.stats_out = (fuse || fold || sfold) ? tw.stats.as<float>() : nullptr;  // ... and for the next layer's LN1
-        ep.xb_out = (fold || sfold) ? tw.xb.p : nullptr;
-        ep.stats16 = sfold ? 1 : 0;
-        ep.splitk_ws = tw.splitk.as<float>(); ep.splitk_ws_bytes = tw.splitk.bytes;
-        if (resid16) {
-            ep.out = tw.xb.p; ep.xb_out = nullptr;
-            if (p160(d, tw.mlp)) MM_TRY(launch_gemm160p(st, tw.u.p, L.w2.p, ep, padded(160), d, tw.mlp));
-            else MM_TRY(launch_gemm_resid16(st, bm_d, tw.u.p, L.w2.p, ep, padded(bm_d), d, tw.mlp));
-        } else {
-            MM_TRY(launch_gemm(st, MMISS_EPI_BIAS_RESID_F32, bm_d, tw.u.p, L.w2.p, ep, padded(bm_d), d, tw.mlp));
-        }
+        ResidRole out{};
+        out.K = d; out.A = tw.ctx.p; out.A8 = tw.ctx8.as<uint8_t>(); out.As = tw.ctxs.as<uint8_t>();
+        out.W = &L.wo; out.b = &L.bo; out.W8 = &L.wo8; out.s8 = &L.so;
+        MM_TRY(run_resid(st, tw, P, P.out, out));
+        WideRole fc1{};
+        fc1.N = tw.mlp; fc1.gelu = true; fc1.g = &L.ln2g; fc1.beta = &L.ln2b; fc1.W = &L.w1; fc1.b = &L.b1; fc1.Wf = &L.w1_f; fc1.bf = &L.b1_f;
+        fc1.c = &L.c1; fc1.W8 = &L.w1_8; fc1.s8 = &L.s1; fc1.W8f = &L.w1_8f; fc1.s8f = &L.s1f; fc1.c16 = &L.c1_16;
+        fc1.out = tw.u.p; fc1.out8 = tw.u8.p; fc1.out8_scale = tw.us.as<uint8_t>();
+        MM_TRY(run_wide(st, tw, P, P.fc1, fc1, eps));
+        ResidRole fc2{};
+        fc2.K = tw.mlp; fc2.A = tw.u.p; fc2.A8 = tw.u8.as<uint8_t>(); fc2.As = tw.us.as<uint8_t>();
+        fc2.W = &L.w2; fc2.b = &L.b2; fc2.W8 = &L.w2_8; fc2.s8 = &L.s2; fc2.splitk = true;
+        MM_TRY(run_resid(st, tw, P, P.fc2, fc2));
         MM_TRY(tap(l + 1));
     }
     return MMISS_OK;
@@ -631,25 +670,20 @@ int run_head(mmiss_encoder* e, Tower& tw, int B, float* out_dev, hipStream_t st)
 
 int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B, float* out_dev, hipStream_t st) {
     Tower& tw = e->vis;
-    // "the embedding stage already left xb + row statistics" is said by THIS call's embedding stage only: a call that failed between
-    // setting and consuming the flags must not make the next one fold stale statistics
-    tw.embed_stats = tw.embed_stats16 = false;
+    LayerPlan plan;
+    MM_TRY(plan_layers(e, tw, B, false, plan));
     const int d = tw.hidden, S = e->cfg.v_image, P = e->cfg.v_patch;
     const int Mpatch = B * e->G * e->G;
-    const int bm_p = gemm_pick_variant(Mpatch, d);
-    const int Mpp = (int)round_up(Mpatch, bm_p % 1000);
+    const int bm_p = gemm_pick_bm(Mpatch, d);
+    const int Mpp = (int)round_up(Mpatch, bm_p);
     MM_TRY(launch_im2col(st, pix_dev, src_u8, e->patches.p, B, S, P, e->Kp));
-    // One request at a time (the layers will run in the skinny folded mode): CLS rows, pre_layrnorm and the mode's entry
-    // statistics are ONE launch behind the patch GEMM (prelayernorm_skinny_kernel) instead of three. Option embed_fused = 0: off.
-    bool fp8_l = false;
-    const bool fused_embed = !e->record_taps && d <= 1024 && (d % 16) == 0 && pick_ln_mode(e, tw, B * tw.T, fp8_l) == 0 && !fp8_l &&
-                             skinny_fold_ok(tw, B * tw.T) && mmiss_option("embed_fused", 1) != 0;
-    if (!fused_embed)
+    // (Stats16: the CLS rows come with the pre-LayerNorm below, prelayernorm_skinny_kernel)
+    if (plan.embed != EmbedOut::Stats16)
         hipLaunchKernelGGL(cls_rows_kernel, dim3((B * d + 255) / 256), dim3(256), 0, st, tw.x.as<float>(),
                            e->cls.as<float>(), tw.pos.as<float>(), B, tw.T, d);
     GemmEpi ep{};
     ep.out = tw.x.p; ep.aux = tw.pos.as<float>(); ep.ldo = d; ep.m_valid = Mpatch; ep.p0 = e->G * e->G; ep.p1 = tw.T;
-    if (gemm_splitk_candidate((int64_t)(Mpp / (bm_p % 1000)) * (d / GEMM_BN), e->Kp)) {
+    if (gemm_splitk_candidate((int64_t)(Mpp / bm_p) * (d / GEMM_BN), e->Kp)) {
         MM_TRY(tw.splitk.ensure((size_t)8 * Mpp * d * 4));
         ep.splitk_ws = tw.splitk.as<float>(); ep.splitk_ws_bytes = tw.splitk.bytes;
     }
@@ -661,32 +695,22 @@ int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B
         else
             MM_TRY(launch_gemm(st, MMISS_EPI_PATCH_F32, bm_p, e->patches.p, e->patch_w.p, ep, Mpp, d, e->Kp));
     }
-    // pre_layrnorm, in place on the fp32 residual stream (HF:modeling_clip.py:640); when the layers will want the bf16 copy
-    // and the row statistics of the result (folded LayerNorm, bf16 residual stream) the same pass writes them
-    {
-        const int M = B * tw.T;
-        bool fp8 = false;
-        const int mode = pick_ln_mode(e, tw, M, fp8);
-        const bool want = !e->record_taps && d % 128 == 0 &&
-                          (mode == 2 || (mode == 0 && M >= mmiss_option("ln_fold_min_rows", 6000))) &&
-                          mmiss_option("prelayernorm_stats", 1) != 0;
-        if (fused_embed) {
-            MM_PROF("layernorm", st, 12.0 * M * d, (double)M * d * 10);
-            hipLaunchKernelGGL(prelayernorm_skinny_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->cls.as<float>(),
-                               tw.pos.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(),
-                               M, tw.T, d, e->cfg.ln_eps);
-            MM_HIP(hipGetLastError());
-            tw.embed_stats16 = true;
-        } else if (want) {
-            MM_PROF("layernorm", st, 10.0 * M * d, (double)M * d * 10);
-            hipLaunchKernelGGL(layernorm_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->pre_g.as<float>(),
-                               e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(), M, d, d / 64, e->cfg.ln_eps);
-            MM_HIP(hipGetLastError());
-            tw.embed_stats = true;
-        } else {
-            MM_TRY(launch_layernorm(st, tw.x.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.x.p, false, nullptr, M, d,
-                                    e->cfg.ln_eps));
-        }
+    // pre_layrnorm, in place on the fp32 residual stream (HF:modeling_clip.py:640), with what the plan's first layer wants
+    const int M = plan.M;
+    if (plan.embed == EmbedOut::Stats16) {   // + CLS rows, xb and the 16-column statistics, in one launch
+        MM_PROF("layernorm", st, 12.0 * M * d, (double)M * d * 10);
+        hipLaunchKernelGGL(prelayernorm_skinny_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->cls.as<float>(),
+                           tw.pos.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(),
+                           M, tw.T, d, e->cfg.ln_eps);
+        MM_HIP(hipGetLastError());
+    } else if (plan.embed == EmbedOut::Stats64) {   // + xb and the 64-column statistics
+        MM_PROF("layernorm", st, 10.0 * M * d, (double)M * d * 10);
+        hipLaunchKernelGGL(layernorm_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->pre_g.as<float>(),
+                           e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(), M, d, d / 64, e->cfg.ln_eps);
+        MM_HIP(hipGetLastError());
+    } else {
+        MM_TRY(launch_layernorm(st, tw.x.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.x.p, false, nullptr, M, d,
+                                e->cfg.ln_eps));
     }
     if (tw.pool_B < B || tw.pool_T != tw.T) {  // token 0 of every image: the same table until the shape changes
         const int nb = tw.ws_batch > B ? tw.ws_batch : B;
@@ -694,7 +718,7 @@ int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B
         tw.pool_B = nb;
         tw.pool_T = tw.T;
     }
-    MM_TRY(run_layers(e, tw, B, false, st));
+    MM_TRY(run_layers(e, tw, plan, st));
     MM_TRY(run_head(e, tw, B, out_dev, st));
     tw.last_B = B;
     tw.last_T = tw.T;
@@ -706,9 +730,13 @@ int encode_text_chunk(mmiss_encoder* e, const int32_t* ids_dev, int B, int T, fl
     const int d = tw.hidden;
     const int savedT = tw.T;
     tw.T = T;  // shorter-than-ctx sequences run at their own length (positions 0..T-1)
-    hipLaunchKernelGGL(text_embed_kernel, dim3(B), dim3(256), 0, st, ids_dev, e->tok.as<float>(), tw.pos.as<float>(),
-                       tw.x.as<float>(), tw.pool_row.as<int32_t>(), T, d, e->cfg.t_vocab, e->cfg.eos_token_id);
-    int rc = run_layers(e, tw, B, true, st);
+    LayerPlan plan;
+    int rc = plan_layers(e, tw, B, true, plan);
+    if (rc == MMISS_OK) {
+        hipLaunchKernelGGL(text_embed_kernel, dim3(B), dim3(256), 0, st, ids_dev, e->tok.as<float>(), tw.pos.as<float>(),
+                           tw.x.as<float>(), tw.pool_row.as<int32_t>(), T, d, e->cfg.t_vocab, e->cfg.eos_token_id);
+        rc = run_layers(e, tw, plan, st);
+    }
     if (rc == MMISS_OK) rc = run_head(e, tw, B, out_dev, st);
     tw.T = savedT;
     tw.last_B = B;
@@ -1291,7 +1319,7 @@ extern "C" int mmiss_encode_text(mmiss_encoder* enc, const int32_t* ids, int32_t
 extern "C" int mmiss_dbg_encoder_set_fuse_ln(mmiss_encoder* enc, int on) {
     if (!enc) MM_FAIL(MMISS_ERR_ARG, "null encoder");
     std::lock_guard<std::mutex> lk(enc->mu);
-    if (on == 1) MM_FAIL(MMISS_ERR_UNSUPPORTED, "LayerNorm mode 1 (normalised during operand staging) was removed in round 4: measured 342-371 TF, profiles/gemm_variants_r01.md");
+    if (on == 1) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s", kLnMode1Removed);
     enc->ln_mode = on < 0 ? -1 : (on > 2 ? 2 : on);  // -1 automatic, 0 separate kernels, 2 folded
     return MMISS_OK;
 }
@@ -1354,6 +1382,26 @@ extern "C" int mmiss_encoder_tap(mmiss_encoder* enc, int tower, int what, float*
 }
 
 // ================================================================================================ debug ABI
+// ms per launch of run() on st over `iters` launches, after three warm-up launches; the events are destroyed on every path
+template <typename Run>
+static int time_launches(hipStream_t st, int iters, Run&& run, float* ms_per_launch) {
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    MM_HIP(hipEventCreate(&ev.e0));
+    MM_HIP(hipEventCreate(&ev.e1));
+    for (int i = 0; i < 3; ++i) MM_TRY(run());
+    MM_HIP(hipEventRecord(ev.e0, st));
+    for (int i = 0; i < iters; ++i) MM_TRY(run());
+    MM_HIP(hipEventRecord(ev.e1, st));
+    MM_HIP(hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    MM_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *ms_per_launch = ms / iters;
+    return MMISS_OK;
+}
+
 extern "C" int mmiss_dbg_gemm(int device, void* hip_stream, int epi, int variant, const void* A, const void* W,
                               void* out, const float* bias, const float* aux, int32_t M, int32_t N, int32_t K,
                               int32_t p0, int32_t p1) {
@@ -1382,21 +1430,9 @@ extern "C" int mmiss_dbg_gemm_p256(int device, void* hip_stream, int epi, const 
     ep.out = out; ep.bias = bias; ep.aux = aux; ep.ldo = N; ep.m_valid = m_valid;
     ep.ln_stats = ln_stats; ep.ln_parts = K / 64; ep.ln_eps = ln_eps;
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    if (iters <= 0 || !ms_per_launch) return launch_gemm256p(st, epi, A, W, ep, M, N, K);
-    hipEvent_t e0, e1;
-    MM_HIP(hipEventCreate(&e0));
-    MM_HIP(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) MM_TRY(launch_gemm256p(st, epi, A, W, ep, M, N, K));
-    MM_HIP(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) MM_TRY(launch_gemm256p(st, epi, A, W, ep, M, N, K));
-    MM_HIP(hipEventRecord(e1, st));
-    MM_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_launch = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return MMISS_OK;
+    auto run = [&]() -> int { return launch_gemm256p(st, epi, A, W, ep, M, N, K); };
+    if (iters <= 0 || !ms_per_launch) return run();
+    return time_launches(st, iters, run, ms_per_launch);
 }
 
 // the residual GEMM on a bf16 stream (out = bf16(f32(out) + A W^T + bias), in place; stats_out [M][N/64][2] optional) in
@@ -1414,20 +1450,7 @@ extern "C" int mmiss_dbg_gemm_resid16(int device, void* hip_stream, int variant,
         return variant == 0 ? launch_gemm160p(st, A, W, ep, M, N, K) : launch_gemm_resid16(st, variant, A, W, ep, M, N, K);
     };
     if (iters <= 0 || !ms_per_launch) return run();
-    hipEvent_t e0, e1;
-    MM_HIP(hipEventCreate(&e0));
-    MM_HIP(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) MM_TRY(run());
-    MM_HIP(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) MM_TRY(run());
-    MM_HIP(hipEventRecord(e1, st));
-    MM_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_launch = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return MMISS_OK;
+    return time_launches(st, iters, run, ms_per_launch);
 }
 
 extern "C" int mmiss_dbg_gemm_time(int device, int epi, int variant, const void* A, const void* W, void* out,
@@ -1437,25 +1460,12 @@ extern "C" int mmiss_dbg_gemm_time(int device, int epi, int variant, const void*
     MM_TRY(mmiss_use_device(device));
     GemmEpi ep{};
     ep.out = out; ep.bias = bias; ep.aux = aux; ep.ldo = N; ep.m_valid = M; ep.p0 = p0; ep.p1 = p1;
-    hipEvent_t e0, e1;
-    MM_HIP(hipEventCreate(&e0));
-    MM_HIP(hipEventCreate(&e1));
     auto run = [&]() -> int {
         if (variant == 256) return launch_gemm256(nullptr, epi, A, W, ep, M, N, K);
         if (variant > 1000) MM_FAIL(MMISS_ERR_UNSUPPORTED, "GEMM variant %d was removed in round 4", variant);
         return launch_gemm(nullptr, epi, variant, A, W, ep, M, N, K);
     };
-    for (int i = 0; i < 3; ++i) MM_TRY(run());
-    MM_HIP(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i) MM_TRY(run());
-    MM_HIP(hipEventRecord(e1, nullptr));
-    MM_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *ms_per_launch = ms / iters;
-    return MMISS_OK;
+    return time_launches(nullptr, iters, run, ms_per_launch);
 }
 
 extern "C" int mmiss_dbg_layernorm(int device, void* hip_stream, const float* x, const float* gamma, const float* beta,
@@ -1624,19 +1634,7 @@ extern "C" int mmiss_dbg_gemm8_time(int device, int epi, int bm, const void* A8,
                                     const float* wscale, const float* bias, void* out, void* out_scale, int32_t M, int32_t N,
                                     int32_t K, int32_t iters, float* ms_per_launch) {
     if (!ms_per_launch || iters <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm8_time: bad argument");
-    hipEvent_t e0, e1;
     MM_TRY(mmiss_use_device(device));
-    MM_HIP(hipEventCreate(&e0));
-    MM_HIP(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) MM_TRY(mmiss_dbg_gemm8(device, nullptr, epi, bm, A8, As, W8, wscale, bias, out, out_scale, M, N, K));
-    MM_HIP(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i) MM_TRY(mmiss_dbg_gemm8(device, nullptr, epi, bm, A8, As, W8, wscale, bias, out, out_scale, M, N, K));
-    MM_HIP(hipEventRecord(e1, nullptr));
-    MM_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *ms_per_launch = ms / iters;
-    return MMISS_OK;
+    auto run = [&]() -> int { return mmiss_dbg_gemm8(device, nullptr, epi, bm, A8, As, W8, wscale, bias, out, out_scale, M, N, K); };
+    return time_launches(nullptr, iters, run, ms_per_launch);
 }

@@ -659,11 +659,6 @@ static inline int gemm_pick_bm(int64_t M_rows, int N) {
     return best;
 }
 
-// Tile variant for launch_gemm = the tile height (128 / 160 / 192: BM x 128 tile, 4 waves, 2 workgroups per CU). (The BM x 256
-// tiles with 8 waves, variants 2000 + BM of rounds 1-3 — 3-11 % faster as isolated launches, 8 % slower inside the encode —
-// were removed in round 4; profiles/gemm_variants_r01.md.)
-static inline int gemm_pick_variant(int64_t M_rows, int N) { return gemm_pick_bm(M_rows, N); }
-
 template <typename IN, int BM, int EPI, bool ALN = false, int NWN = 2, bool S3 = false, int NWM = 2>
 static int launch_gemm_inst(hipStream_t st, const void* A, const void* W, const GemmEpi& ep, int M, int N, int K,
                             int splits = 1) {
@@ -860,7 +855,7 @@ static int launch_gemm(hipStream_t st, int epi, int bm, const void* A, const voi
         }
     }
     if (bm == 0) bm = 128;
-    if (M <= 0 || N <= 0 || K <= 0 || (M % (bm % 1000)) || (N % GEMM_BN) || (K % GEMM_BK))
+    if (M <= 0 || N <= 0 || K <= 0 || (M % bm) || (N % GEMM_BN) || (K % GEMM_BK))
         MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm: M=%d N=%d K=%d must be multiples of %d/%d/%d", M, N, K, bm, GEMM_BN,
                 GEMM_BK);
     static const char* names[] = {"gemm_bf16_f32", "gemm_bf16_bias", "gemm_bf16_bias_qgelu",
@@ -870,19 +865,17 @@ static int launch_gemm(hipStream_t st, int epi, int bm, const void* A, const voi
     const int mv = ep.m_valid < M ? ep.m_valid : M;
     const double bytes = 2.0 * ((double)mv * K + (double)N * K) +
                          (double)out_elt * mv * N * (epi == MMISS_EPI_BIAS_RESID_F32 ? 2 : 1);
-    if (bm < 1000) {
-        const int splits = gemm_splitk_splits((M / bm) * (N / GEMM_BN), K, M, N, ep);
-        if (splits > 1) {
-            static const char* knames[] = {"gemm_splitk_f32", "gemm_splitk_bias", "gemm_splitk_bias_qgelu",
-                                           "gemm_splitk_bias_resid", "gemm_splitk_patch"};
-            MM_PROF(knames[epi], st, gemm_flops(mv, N, K), bytes + 8.0 * splits * (double)M * N);
-            switch (epi) {
-                case MMISS_EPI_F32: return launch_gemm_splitk<MMISS_EPI_F32>(st, bm, splits, A, W, ep, M, N, K);
-                case MMISS_EPI_BIAS_BF16: return launch_gemm_splitk<MMISS_EPI_BIAS_BF16>(st, bm, splits, A, W, ep, M, N, K);
-                case MMISS_EPI_BIAS_QGELU_BF16: return launch_gemm_splitk<MMISS_EPI_BIAS_QGELU_BF16>(st, bm, splits, A, W, ep, M, N, K);
-                case MMISS_EPI_BIAS_RESID_F32: return launch_gemm_splitk<MMISS_EPI_BIAS_RESID_F32>(st, bm, splits, A, W, ep, M, N, K);
-                default: return launch_gemm_splitk<MMISS_EPI_PATCH_F32>(st, bm, splits, A, W, ep, M, N, K);
-            }
+    const int splits = gemm_splitk_splits((M / bm) * (N / GEMM_BN), K, M, N, ep);
+    if (splits > 1) {
+        static const char* knames[] = {"gemm_splitk_f32", "gemm_splitk_bias", "gemm_splitk_bias_qgelu",
+                                       "gemm_splitk_bias_resid", "gemm_splitk_patch"};
+        MM_PROF(knames[epi], st, gemm_flops(mv, N, K), bytes + 8.0 * splits * (double)M * N);
+        switch (epi) {
+            case MMISS_EPI_F32: return launch_gemm_splitk<MMISS_EPI_F32>(st, bm, splits, A, W, ep, M, N, K);
+            case MMISS_EPI_BIAS_BF16: return launch_gemm_splitk<MMISS_EPI_BIAS_BF16>(st, bm, splits, A, W, ep, M, N, K);
+            case MMISS_EPI_BIAS_QGELU_BF16: return launch_gemm_splitk<MMISS_EPI_BIAS_QGELU_BF16>(st, bm, splits, A, W, ep, M, N, K);
+            case MMISS_EPI_BIAS_RESID_F32: return launch_gemm_splitk<MMISS_EPI_BIAS_RESID_F32>(st, bm, splits, A, W, ep, M, N, K);
+            default: return launch_gemm_splitk<MMISS_EPI_PATCH_F32>(st, bm, splits, A, W, ep, M, N, K);
         }
     }
     // the residual epilogue serves two shapes of very different arithmetic intensity (out-proj K = hidden, FC2 K = mlp):

@@ -353,7 +353,7 @@ class ClipEncoder:
 
     def set_fuse_ln(self, mode=-1):
         """-1 = automatic (folded from ~6000 rows per call, separate below; the default), 0 = separate LayerNorm kernels,
-        1 = normalise during operand staging, 2 = folded into the GEMMs."""
+        2 = folded into the GEMMs. Mode 1 (normalised during operand staging) was removed and is refused."""
         _lib.check(self._lib.mmiss_dbg_encoder_set_fuse_ln(self._h, int(mode)))
 
     def tap(self, tower: int, what: int, n: int) -> np.ndarray:

@@ -220,6 +220,7 @@ def test_device_tensor_io(tiny):
 
 
 def test_errors_are_loud(tiny):
+    from mmiss_amd import _lib
     from mmiss_amd.encoder import ClipEncoder, ClipShape
 
     enc, W, co = tiny
@@ -227,6 +228,16 @@ def test_errors_are_loud(tiny):
         enc.encode_image(np.zeros((1, 3, 32, 32), np.float32))
     with pytest.raises(RuntimeError):
         enc.encode_text(np.zeros((1, co.TINY.t_ctx + 1), np.int32))
+    _lib.set_option("ln_mode", 1)  # LayerNorm mode 1 was removed: the option is refused like set_fuse_ln(1)
+    try:
+        with pytest.raises(RuntimeError, match="LayerNorm mode 1"):
+            enc.encode_image(np.zeros((1, 3, co.TINY.v_image, co.TINY.v_image), np.float32))
+        with pytest.raises(RuntimeError, match="LayerNorm mode 1"):
+            enc.encode_text(np.zeros((1, co.TINY.t_ctx), np.int32))
+    finally:
+        _lib.set_option("ln_mode", -1)
+    with pytest.raises(RuntimeError, match="LayerNorm mode 1"):
+        enc.set_fuse_ln(1)
     fresh = ClipEncoder(ClipShape.from_any(co.TINY), max_batch_image=2, max_batch_text=2)
     with pytest.raises(RuntimeError):  # weights missing -> finalize fails
         fresh.load_state_dict({k: v for k, v in list(W.items())[:10]})
