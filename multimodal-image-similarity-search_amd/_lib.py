@@ -111,7 +111,6 @@ SIGNATURES = {
     "mmiss_dbg_encoder_record_taps": (_I, [_P, _I]),
     "mmiss_dbg_encoder_set_fuse_ln": (_I, [_P, _I]),
     "mmiss_dbg_set_option": (_I, [C.c_char_p, _I]),
-    "mmiss_dbg_build_flags": (_I, []),
     "mmiss_dbg_quantize_weights_fp8": (_I, [_I, _P, _P, _P, _P, _I32, _I32]),
     "mmiss_dbg_layernorm_mxfp8": (_I, [_I, _P, _P, _P, _P, _P, _P, _I32, _I32, C.c_float]),
     "mmiss_dbg_layernorm16_mxfp8": (_I, [_I, _P, _P, _P, _P, _P, _P, _I32, _I32, C.c_float]),
@@ -147,11 +146,6 @@ def load() -> C.CDLL:
             fn.argtypes = args
         if lib.mmiss_abi_version() != 1:
             raise ImportError("libmmiss.so ABI version mismatch")
-        if (lib.mmiss_dbg_build_flags() & 2) and os.environ.get("MMISS_ALLOW_AB_BUILD") != "1":
-            raise ImportError(
-                f"{LIB_PATH} was built with a timing-experiment macro (tools/*_ab.sh: P256_NO_LATE_WAIT, P256_SPLIT_STAGE, P256_STAGE_FIRST, "
-                "MMISS_SCAN_NT) and is not a product build; rebuild it (`make -C .../csrc clean all`) or set "
-                "MMISS_ALLOW_AB_BUILD=1 for the A/B run itself")
         _lib = lib
         # experiment knobs from the environment: MMISS_OPTIONS="gemm_wide=1,scan_rounds=2" (see mmiss_dbg_set_option)
         for kv in filter(None, os.environ.get("MMISS_OPTIONS", "").split(",")):
@@ -194,11 +188,6 @@ def current_stream_ptr(device=None):
     import torch
 
     return int(torch.cuda.current_stream(device).cuda_stream)
-
-
-def has_experiments() -> bool:
-    """True when libmmiss.so was built with `make EXPERIMENTS=1` (measured-slower GEMM / LayerNorm alternatives)."""
-    return bool(load().mmiss_dbg_build_flags() & 1)
 
 
 def set_option(key: str, value: int) -> None:

@@ -1324,18 +1324,6 @@ extern "C" int mmiss_dbg_encoder_set_fuse_ln(mmiss_encoder* enc, int on) {
     return MMISS_OK;
 }
 
-int mmiss_index_build_flags(void);   // api_index.hip: the same question for that translation unit
-extern "C" int mmiss_dbg_build_flags(void) {
-    int f = mmiss_index_build_flags();
-#ifdef MMISS_EXPERIMENTS
-    f |= 1;
-#endif
-#if defined(P256_NO_LATE_WAIT) || defined(P256_SPLIT_STAGE) || defined(P256_STAGE_FIRST) || defined(P256_A_POLICY) || defined(P256_W_POLICY) || defined(P256_PRIO) || defined(MMISS_SCAN_NT) || defined(Q256_STAGE_MID)
-    f |= 2;   // built with a timing-experiment macro (tools/*_ab.sh): NOT a product build
-#endif
-    return f;
-}
-
 extern "C" int mmiss_dbg_encoder_record_taps(mmiss_encoder* enc, int on) {
     if (!enc) MM_FAIL(MMISS_ERR_ARG, "null encoder");
     std::lock_guard<std::mutex> lk(enc->mu);

@@ -61,14 +61,6 @@ struct mmiss_index {
 #define MM_NO_PENDING(ix, who) \
     do { if ((ix)->pend.active) MM_FAIL(MMISS_ERR_STATE, "%s: a query begun with mmiss_index_query_begin is still open", who); } while (0)
 
-int mmiss_index_build_flags(void) {
-#if defined(P256_NO_LATE_WAIT) || defined(P256_SPLIT_STAGE) || defined(P256_STAGE_FIRST) || defined(P256_A_POLICY) || defined(P256_W_POLICY) || defined(P256_PRIO) || defined(MMISS_SCAN_NT)
-    return 2;
-#else
-    return 0;
-#endif
-}
-
 namespace {
 
 // The element types of an index's storage dtype: T the rows as the kernels read them, Q the first pass's query operand (f16

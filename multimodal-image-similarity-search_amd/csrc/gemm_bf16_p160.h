@@ -10,7 +10,7 @@
 //   * 8 waves as 2 (m) x 4 (n): a wave owns 80 rows x 64 columns = 5 x 4 accumulator blocks of 16 x 16.
 //   * TWO phases per K-tile, one per K STEP of 32 columns — [5 A + 4 W fragment reads, staging] B [20 MFMAs] B, twice — with the
 //     two wave halves one barrier apart (one half's read part beside the other's MFMAs). Measured on FC2, us per K-tile net of
-//     the launch's ~12 us of fill, prefetch and epilogue (tools/gemm_p160_ablate.py; the 80 MFMAs alone take 0.58, the 52 KB
+//     the launch's ~12 us of fill, prefetch and epilogue (round 3, ablation builds since removed; the 80 MFMAs alone take 0.58, the 52 KB
 //     of LDS-DMA alone 0.62-0.67, the 36 fragment reads alone 0.29-0.35): the four quadrant phases of the 256 x 256 tile
 //     (12 / 12 / 8 / 8 MFMAs; 80 rows do not halve evenly) 1.3; two staggered phases split by n half (14 + 4 reads) 1.06; these
 //     two (9 + 9 reads) 0.96; an unstaggered form with two fragment sets in registers (a wave reads the next phase's fragments,
@@ -33,14 +33,12 @@
 #define G160_DUMP (3 * G160_BUF)            // 8 waves x 256 B: where the 4-byte filler pieces land
 #define G160_LDS (G160_DUMP + 2048)         // 161 792 B of the CU's 163 840
 
-// VARIANT (timing experiments, EXPERIMENTS builds, tools/gemm_p160_ablate.py; results are wrong by construction): a mask —
-// 1 = no MFMAs, 2 = no staging, 4 = no fragment reads. 0 = the kernel.
 // EPI: MMISS_EPI_BIAS_RESID_BF16 (the residual GEMMs) or MMISS_EPI_PATCH_F32 (the patch-embedding GEMM: f32 rows scattered to
 // item * tokens + 1 + patch with the position row added, gemm_bf16.h gemm_epilogue's contract; no bias, no residual).
 // KT: the K-tile count as a compile-time tag (0 = read K at run time). It exists so that the shapes of one encode are
-// DISTINCT SYMBOLS in rocprofv3's kernel trace and PMC passes — out-projection (K = 768: <9,0,12>) and FC2 (K = 3072: <9,0,48>)
+// DISTINCT SYMBOLS in rocprofv3's kernel trace and PMC passes — out-projection (K = 768: <9,12>) and FC2 (K = 3072: <9,48>)
 // were one symbol with a 24-75 us "class average" in round 3 — and gives the K loop a constant trip count.
-template <int EPI, int VARIANT, int KT = 0>
+template <int EPI, int KT = 0>
 __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ W, int M,
                                                           int N, int K, GemmEpi ep) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -77,7 +75,7 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(dump), 4, lane_vo, so, 0, 0)
 // the A slot of buffer b2 <- K-tile at byte offset ko: THREE operations per wave
 #define G160_STAGE_A(b2, ko)                                                                                 \
-    if constexpr (!((VARIANT & 2) != 0)) {                                                                  \
+    {                                                                                                       \
         char* sl_ = smem + (b2) * G160_BUF + a_dst;                                                         \
         G160_BLDS(srdA, a_so + (ko), sl_);                                                                  \
         G160_BLDS(srdA, a_so + 8 * row8 + (ko), sl_ + 8 * 1024);                                            \
@@ -86,7 +84,7 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     }
 // the W slot of n half nq: TWO operations per wave
 #define G160_STAGE_W(b2, nq, ko)                                                                             \
-    if constexpr (!((VARIANT & 2) != 0)) {                                                                  \
+    {                                                                                                       \
         char* sl_ = smem + (b2) * G160_BUF + G160_A_BYTES + (nq) * G160_W_BYTES + w_dst;                    \
         const int so_ = w_so + (nq) * 4 * row8 + (ko);                                                      \
         G160_BLDS(srdW, so_, sl_);                                                                          \
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
 
 // the fragments of k step s (32 of the K-tile's 64 columns): five A row blocks, four W column blocks (n0: 0, 1; n1: 2, 3)
 #define G160_READ(b, s)                                                                                      \
-    if constexpr (!((VARIANT & 4) != 0)) {                                                                  \
+    {                                                                                                       \
         _Pragma("unroll") for (int mf = 0; mf < 5; ++mf)                                                    \
             am[mf] = *reinterpret_cast<const frag*>(smem + ab[s] + (b) * G160_BUF + mf * 2048);             \
         _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                       \
@@ -119,12 +117,7 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     }
 // the 20 MFMAs of one phase: all five row blocks against all four column blocks, one k step
 #define G160_MMA()                                                                                           \
-    if constexpr ((VARIANT & 1) != 0) {                                                                     \
-        _Pragma("unroll") for (int mf = 0; mf < 5; ++mf) asm volatile("" ::"v"(am[mf]));                    \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(wq[i]));                        \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                       \
-            _Pragma("unroll") for (int mf = 0; mf < 5; ++mf) asm volatile("" : "+v"(acc[i][mf]));           \
-    } else {                                                                                                \
+    {                                                                                                       \
         __builtin_amdgcn_s_setprio(1);                                                                      \
         _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                       \
             _Pragma("unroll") for (int mf = 0; mf < 5; ++mf)                                                \
@@ -337,23 +330,10 @@ static int launch_gemm160p(hipStream_t st, const void* A, const void* W, const G
     char pname[48];
     snprintf(pname, sizeof(pname), "gemm_bf16_bias_resid16_p160_k%d", K);
     MM_PROF(pname, st, 2.0 * mv * N * K, bytes);
-#ifdef MMISS_EXPERIMENTS
-    const int dbg = mmiss_option("gemm_p160_dbg", 0);
-#define G160_DBG_CASE(D)                                                                                                        \
-    if (dbg == D) {                                                                                                             \
-        MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16, D>), G160_LDS));                             \
-        hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16, D>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, st,                            \
-                           reinterpret_cast<const __bf16*>(A), reinterpret_cast<const __bf16*>(W), M, N, K, ep);                \
-        MM_HIP(hipGetLastError());                                                                                              \
-        return MMISS_OK;                                                                                                        \
-    }
-    G160_DBG_CASE(1) G160_DBG_CASE(2) G160_DBG_CASE(3) G160_DBG_CASE(4) G160_DBG_CASE(5) G160_DBG_CASE(6) G160_DBG_CASE(7)
-#undef G160_DBG_CASE
-#endif
 #define G160_KT_CASE(KT_)                                                                                                        \
     if (K == (KT_) * GEMM_BK) {                                                                                                  \
-        MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16, 0, KT_>), G160_LDS)); \
-        hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16, 0, KT_>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, \
+        MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16, KT_>), G160_LDS)); \
+        hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16, KT_>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, \
                            st, reinterpret_cast<const __bf16*>(A), reinterpret_cast<const __bf16*>(W), M, N, K, ep);            \
         MM_HIP(hipGetLastError());                                                                                              \
         return MMISS_OK;                                                                                                        \
@@ -361,8 +341,8 @@ static int launch_gemm160p(hipStream_t st, const void* A, const void* W, const G
     // the towers' shapes: ViT-B/32 out-projection / FC2 (768, 3072), its text tower (512, 2048), ViT-L/14 (1024, 4096)
     G160_KT_CASE(12) G160_KT_CASE(48) G160_KT_CASE(8) G160_KT_CASE(32) G160_KT_CASE(16) G160_KT_CASE(64)
 #undef G160_KT_CASE
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16, 0>), G160_LDS));
-    hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16, 0>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, st, reinterpret_cast<const __bf16*>(A),
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16>), G160_LDS));
+    hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_BIAS_RESID_BF16>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, st, reinterpret_cast<const __bf16*>(A),
                        reinterpret_cast<const __bf16*>(W), M, N, K, ep);
     MM_HIP(hipGetLastError());
     return MMISS_OK;
@@ -375,8 +355,8 @@ static int launch_gemm160p_patch(hipStream_t st, const void* A, const void* W, c
     if (!ep.out || !ep.aux || ep.p0 <= 0 || ep.p1 <= 0 || ep.ldo < N) MM_FAIL(MMISS_ERR_ARG, "gemm160p_patch: missing operand");
     const int mv = ep.m_valid < M ? ep.m_valid : M;
     MM_PROF("gemm_bf16_patch_p160", st, 2.0 * mv * N * K, 2.0 * ((double)mv * K + (double)N * K) + 4.0 * (double)mv * N);
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_PATCH_F32, 0>), G160_LDS));
-    hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_PATCH_F32, 0>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, st,
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_PATCH_F32>), G160_LDS));
+    hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_PATCH_F32>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, st,
                        reinterpret_cast<const __bf16*>(A), reinterpret_cast<const __bf16*>(W), M, N, K, ep);
     MM_HIP(hipGetLastError());
     return MMISS_OK;

@@ -16,7 +16,7 @@
 //   * the loop is unrolled over the two staging buffers: every LDS address is base register + immediate, every LDS-DMA
 //     source a scalar base + a per-lane 32-bit offset computed once, staging is unconditional (past the end of the stream
 //     it re-reads the last tile into free slots) and the waits are plain immediates — the first version of this loop spent
-//     0.3 us per K-tile on scalar bookkeeping alone (tools/gemm_p256_ablate.py);
+//     0.3 us per K-tile on scalar bookkeeping alone (round 3, ablation builds since removed: profiles/gemm_p256_r03.txt);
 //   * everything the epilogue needs from memory arrives by LDS-DMA as well — the tile's 256 bias / c values (one 4-byte
 //     piece per wave) and, in the folded-LayerNorm mode, the raw (sum, sumsq) partials of its 256 rows (K/256 16-byte
 //     pieces per wave), finalised to (mean, rstd) by 256 threads in a wait-free phase of K-tile 2 — because an ordinary
@@ -52,18 +52,14 @@ __device__ __forceinline__ f16x8 p256_widen_f8(u32x2 w) {
     return r;
 }
 
-// DBG (timing experiments only, EXPERIMENTS builds, tools/gemm_p256_ablate.py; results are wrong by construction), a
-// compile-time mask: 1 = no MFMAs, 2 = no staging inside the loop, 4 = no fragment reads, 8 = every tile loads tile (0, 0)
-// (operands L2-hot), 16 = no epilogue, 32 = epilogue without its stores, 64 = no barriers, 128 = the loop on
-// v_mfma_f32_32x32x16_bf16 (8 instructions of 8 passes per phase instead of 16 of 4; the same fragment reads, the same LDS
-// layout; the epilogue reads the accumulators as if they had the 16 x 16 layout)
-// STYLE: how the epilogue gets from "a lane holds 4 consecutive columns of one row" to wide stores: 0 = a 16 x 64 transpose
-// per wave through a private 2 KB LDS patch, whole 128-byte rows per store instruction; 1 = two v_permlane16_swap per
-// 16 x 32 block, 8 consecutive columns per lane, 64-byte row segments (two adjacent instructions per line).
+// Tried and removed (rounds 3-4; numbers in profiles/gemm_p256_r03.txt, profiles/gemm_p256_r04.txt, DESIGN.md sections 3b, 6):
+// compile-time ablations of the loop (no MFMAs / staging / fragment reads / barriers / epilogue) — the parts add up instead
+// of overlapping; the loop on v_mfma_f32_32x32x16_bf16 — 5-6 % slower; an epilogue of two v_permlane16_swap per 16 x 32 block
+// with 64-byte row segments instead of the LDS transpose patch below — equal or slower.
 // XP = statistic pieces per wave and tile in the folded modes: K / 256 16-byte pieces of RAW partials (K = 512, 768: finalised
 // in the kernel), or 1 = ONE 4-byte piece of FINISHED (mean, rstd) pairs from ep.ln_final (any K; ln_finalize_kernel ran first);
 // 0 otherwise
-template <int EPI, int XP, int STYLE = 0, int DBG = 0>
+template <int EPI, int XP>
 __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ W, int M,
                                                           int N, int K, GemmEpi ep) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -137,60 +133,39 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restri
     constexpr bool W8 = false;   // (the retrieval kernel below also takes fp8 index rows as its W operand)
     const int stage_dst = wave * 2048;
 #define P256_SLOT(which, b) (((which) * 2 + (b)) * G256_SLOT)
-// cache policy of the operand loads (the builtin's aux: 1 sc0, 2 nt, 16 sc1), per operand; A/B knobs of
-// tools/p256_policy_ab.sh (-DP256_A_POLICY=.. -DP256_W_POLICY=..), 0 = default in product builds
-#ifdef P256_A_POLICY
-#define P256_AUX_srdA P256_A_POLICY
-#else
-#define P256_AUX_srdA 0
-#endif
-#ifdef P256_W_POLICY
-#define P256_AUX_srdW P256_W_POLICY
-#else
-#define P256_AUX_srdW 0
-#endif
+// (default cache policy, aux = 0: nt operand loads measured 5-12 % slower on either operand, sc0 / sc1 equal; round 4)
 #define P256_BLDS(srd, vo, so, dst) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(dst), 16, vo, so, 0, P256_AUX_##srd)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(dst), 16, vo, so, 0, 0)
 #define P256_BLDS4(srd, vo, so, dst) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(dst), 4, vo, so, 0, P256_AUX_##srd)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(dst), 4, vo, so, 0, 0)
+// One slot's staging: both pieces are issued in the read part of the phase, behind its fragment reads. The second piece issued
+// from the middle of the MFMA part instead measured 3-6 % SLOWER (round 3, 4096^3: 116-121 vs 111-113 us), the pieces issued
+// BEFORE the fragment reads equal or slower (round 4): the read part is not what bounds the loop.
 // LIVE = false: the slot is not read (the A m1 slot of a half tile): its two pieces shrink to 4 bytes per lane — the K
 // stream is bound by LDS-DMA bytes per CU (64 KB per K-tile at ~40 GB/s), the operation COUNT must stay what the waits assume
-// PCS: which of the slot's two 8-row pieces (bit 0 / bit 1)
-#define P256_STAGE_P(which, b, oA, oW, LIVE, PCS)                                                            \
-    if constexpr (!((DBG & 2) != 0)) {                                                                      \
+#define P256_STAGE(which, b, oA, oW, LIVE)                                                                   \
+    {                                                                                                       \
         char* dst_ = smem + P256_SLOT(which, b) + stage_dst;                                                \
         if constexpr ((which) < 2) {                                                                        \
             const int so_ = (oA);                                                                           \
             if (LIVE) {                                                                                     \
-                if constexpr (((PCS) & 1) != 0) P256_BLDS(srdA, a_vo, so_, dst_);                           \
-                if constexpr (((PCS) & 2) != 0) P256_BLDS(srdA, a_vo, so_ + row8, dst_ + 1024);             \
+                P256_BLDS(srdA, a_vo, so_, dst_);                                                           \
+                P256_BLDS(srdA, a_vo, so_ + row8, dst_ + 1024);                                             \
             } else {                                                                                        \
-                if constexpr (((PCS) & 1) != 0) P256_BLDS4(srdA, a_vo, so_, dst_);                          \
-                if constexpr (((PCS) & 2) != 0) P256_BLDS4(srdA, a_vo, so_ + row8, dst_ + 1024);            \
+                P256_BLDS4(srdA, a_vo, so_, dst_);                                                          \
+                P256_BLDS4(srdA, a_vo, so_ + row8, dst_ + 1024);                                            \
             }                                                                                               \
         } else if constexpr (W8) {                                                                          \
             /* fp8 index rows: a slot is 128 rows x 64 bytes = ONE 16-row piece per wave (the counted waits know: P256_WAIT) */ \
             const int so_ = (oW) + ((which) & 1) * 4 * w_row8;                                              \
             char* dst8_ = smem + P256_SLOT(which, b) + wave * 1024;                                         \
-            if constexpr (((PCS) & 1) != 0) P256_BLDS(srdW, w_vo, so_, dst8_);                              \
+            P256_BLDS(srdW, w_vo, so_, dst8_);                                                              \
         } else {                                                                                            \
             const int so_ = (oW) + ((which) & 1) * 4 * w_row8;                                              \
-            if constexpr (((PCS) & 1) != 0) P256_BLDS(srdW, w_vo, so_, dst_);                               \
-            if constexpr (((PCS) & 2) != 0) P256_BLDS(srdW, w_vo, so_ + w_row8, dst_ + 1024);               \
+            P256_BLDS(srdW, w_vo, so_, dst_);                                                               \
+            P256_BLDS(srdW, w_vo, so_ + w_row8, dst_ + 1024);                                               \
         }                                                                                                   \
     }
-// Both pieces of a slot are issued in the read part of the phase. P256_SPLIT_STAGE issues the second one from the middle of
-// the MFMA part instead (where a piece is said to cost ~60 cycles of issue against 100-185 beside fragment reads): measured
-// 3-6 % SLOWER (4096^3: 116-121 vs 111-113 us on one box, tools/p256_split_ab.sh) — the read part is not what bounds the loop.
-#ifndef P256_SPLIT_STAGE
-#define P256_STAGE(which, b, oA, oW, LIVE) P256_STAGE_P(which, b, oA, oW, LIVE, 3)
-#define P256_STAGE_MID(which, b, oA, oW, LIVE)
-#define P256_INFLIGHT 10
-#else
-#define P256_STAGE(which, b, oA, oW, LIVE) P256_STAGE_P(which, b, oA, oW, LIVE, 1)
-#define P256_STAGE_MID(which, b, oA, oW, LIVE) P256_STAGE_P(which, b, oA, oW, LIVE, 2)
-#define P256_INFLIGHT 9
-#endif
     // what the epilogue of tile (bm, bn) reads from memory, by LDS-DMA: 1 + XP pieces per wave
     auto stage_x = [&](int bm, int bn, int par) {
         const float* src = ((FOLD && wave >= 4) ? ep.aux : ep.bias) + bn * 256 + (wave & 3) * 64 + lane;
@@ -216,48 +191,18 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restri
         ab[s] = (wm * 64 + fr) * 128 + (((4 * s + fg) ^ (fr & 7)) << 4);
         wb[s] = P256_SLOT(2, 0) + (wn * 32 + fr) * 128 + (((4 * s + fg) ^ (fr & 7)) << 4);
     }
-    // (DBG & 128: lane l feeds row l & 31, k = 16 ks + 8 (l >> 5) .. + 7 of k step ks = 0 .. 3; one base per k step)
-    uint32_t ab32[4], wb32[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        ab32[s] = (wm * 64 + (lane & 31)) * 128 + (((2 * s + (lane >> 5)) ^ (lane & 7)) << 4);
-        wb32[s] = P256_SLOT(2, 0) + (wn * 32 + (lane & 31)) * 128 + (((2 * s + (lane >> 5)) ^ (lane & 7)) << 4);
-    }
     frag am[4][2];
     frag wq[2][2][2];
     f32x4 acc[4][8];
-    f32x16 acc32[2][4];   // (DBG & 128) [n quarter][m quarter x 2 + 32-row block]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc32[i][j][r] = 0.f;
-    auto acc_get = [&](int i, int j, int r) -> float {
-        if constexpr ((DBG & 128) != 0) return acc32[i >> 1][j >> 1][((i & 1) * 2 + (j & 1)) * 4 + r];
-        else return acc[i][j][r];
-    };
-    auto acc_zero = [&](int i, int j) {
-        if constexpr ((DBG & 128) != 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc32[i >> 1][j >> 1][((i & 1) * 2 + (j & 1)) * 4 + r] = 0.f;
-        } else acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    };
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
 #define P256_READ_A(b, mq)                                                                                   \
-    if constexpr ((DBG & 128) != 0) {                                                                       \
-        _Pragma("unroll") for (int mb = 0; mb < 2; ++mb)                                                    \
-            _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                \
-                am[mb * 2 + (ks >> 1)][ks & 1] = *reinterpret_cast<const frag*>(smem + ab32[ks] + P256_SLOT(mq, b) + mb * 4096); \
-    } else if constexpr (!((DBG & 4) != 0)) {                                                               \
-        _Pragma("unroll") for (int mf = 0; mf < 4; ++mf) {                                                  \
-            am[mf][0] = *reinterpret_cast<const frag*>(smem + ab[0] + P256_SLOT(mq, b) + mf * 2048);        \
-            am[mf][1] = *reinterpret_cast<const frag*>(smem + ab[1] + P256_SLOT(mq, b) + mf * 2048);        \
-        }                                                                                                   \
+    _Pragma("unroll") for (int mf = 0; mf < 4; ++mf) {                                                      \
+        am[mf][0] = *reinterpret_cast<const frag*>(smem + ab[0] + P256_SLOT(mq, b) + mf * 2048);            \
+        am[mf][1] = *reinterpret_cast<const frag*>(smem + ab[1] + P256_SLOT(mq, b) + mf * 2048);            \
     }
 #define P256_READ_W(b, nq)                                                                                   \
     if constexpr (W8) {                                                                                     \
@@ -265,121 +210,79 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restri
             wq[nq][nf][0] = __builtin_bit_cast(frag, p256_widen_f8(*reinterpret_cast<const u32x2*>(smem + wb[0] + P256_SLOT(nq, b) + nf * 1024))); \
             wq[nq][nf][1] = __builtin_bit_cast(frag, p256_widen_f8(*reinterpret_cast<const u32x2*>(smem + wb[1] + P256_SLOT(nq, b) + nf * 1024))); \
         }                                                                                                   \
-    } else if constexpr ((DBG & 128) != 0) {                                                                \
-        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                    \
-            wq[nq][ks >> 1][ks & 1] = *reinterpret_cast<const frag*>(smem + wb32[ks] + P256_SLOT(nq, b));   \
-    } else if constexpr (!((DBG & 4) != 0)) {                                                               \
+    } else {                                                                                                \
         _Pragma("unroll") for (int nf = 0; nf < 2; ++nf) {                                                  \
             wq[nq][nf][0] = *reinterpret_cast<const frag*>(smem + wb[0] + P256_SLOT(nq, b) + nf * 2048);    \
             wq[nq][nf][1] = *reinterpret_cast<const frag*>(smem + wb[1] + P256_SLOT(nq, b) + nf * 2048);    \
         }                                                                                                   \
     }
 #define P256_MMA_HALF(mq, nq, s)                                                                             \
-    if constexpr ((DBG & 128) != 0) {                                                                       \
-        if constexpr (std::is_same<IN_T, __bf16>::value) {                                                  \
-            _Pragma("unroll") for (int kq = 0; kq < 2; ++kq)                                                \
-                _Pragma("unroll") for (int mb = 0; mb < 2; ++mb)                                            \
-                    acc32[nq][(mq) * 2 + mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                     \
-                        wq[nq][s][kq], am[mb * 2 + (s)][kq], acc32[nq][(mq) * 2 + mb], 0, 0, 0);            \
-        }                                                                                                   \
-    } else {                                                                                                \
-        _Pragma("unroll") for (int nf = 0; nf < 2; ++nf)                                                    \
-            _Pragma("unroll") for (int mf = 0; mf < 4; ++mf)                                                \
-                acc[(nq) * 2 + nf][(mq) * 4 + mf] = MfmaIn<IN_T>::mma(                                      \
-                    wq[nq][nf][s], am[mf][s], acc[(nq) * 2 + nf][(mq) * 4 + mf]);                           \
-    }
-// wave priority inside / outside the MFMA part (A/B knob of tools/p256_prio_ab.sh: -DP256_PRIO=mma*4+rest; product 1 / 0)
-#ifdef P256_PRIO
-#define P256_PRIO_MMA ((P256_PRIO) / 4)
-#define P256_PRIO_REST ((P256_PRIO) % 4)
-#else
-#define P256_PRIO_MMA 1
-#define P256_PRIO_REST 0
-#endif
-// 16 MFMAs with MID (a slot's second LDS-DMA piece, or nothing) issued behind the first eight
-#define P256_MMA(mq, nq, MID)                                                                                \
-    if constexpr ((DBG & 1) != 0) {                                                                         \
-        _Pragma("unroll") for (int mf = 0; mf < 4; ++mf) asm volatile("" ::"v"(am[mf][0]), "v"(am[mf][1]));  \
-        _Pragma("unroll") for (int nf = 0; nf < 2; ++nf) asm volatile("" ::"v"(wq[nq][nf][0]), "v"(wq[nq][nf][1])); \
-        _Pragma("unroll") for (int nf = 0; nf < 2; ++nf)                                                    \
-            _Pragma("unroll") for (int mf = 0; mf < 4; ++mf) asm volatile("" : "+v"(acc[(nq) * 2 + nf][(mq) * 4 + mf])); \
-        MID;                                                                                                \
-    } else {                                                                                                \
-        __builtin_amdgcn_s_setprio(P256_PRIO_MMA);                                                          \
+    _Pragma("unroll") for (int nf = 0; nf < 2; ++nf)                                                        \
+        _Pragma("unroll") for (int mf = 0; mf < 4; ++mf)                                                    \
+            acc[(nq) * 2 + nf][(mq) * 4 + mf] = MfmaIn<IN_T>::mma(                                          \
+                wq[nq][nf][s], am[mf][s], acc[(nq) * 2 + nf][(mq) * 4 + mf]);
+// 16 MFMAs at wave priority 1, 0 outside (other priorities inside / outside the MFMA part: no effect, round 4). The two
+// sched_barriers between the halves are where the split-staging experiment issued its piece.
+#define P256_MMA(mq, nq)                                                                                     \
+    {                                                                                                       \
+        __builtin_amdgcn_s_setprio(1);                                                                      \
         P256_MMA_HALF(mq, nq, 0)                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
-        MID;                                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
         P256_MMA_HALF(mq, nq, 1)                                                                            \
-        __builtin_amdgcn_s_setprio(P256_PRIO_REST);                                                         \
+        __builtin_amdgcn_s_setprio(0);                                                                      \
     }
-// counted wait: P256_INFLIGHT = the pieces of the younger slot loads that stay in flight (four slots and a half: 9); POST = the stores and pieces of the
-// previous tile's epilogue are younger than the slot waited for
+// counted wait: P256_INFLIGHT = the pieces of the younger slot loads that stay in flight (five slots of two); POST = the stores
+// and pieces of the previous tile's epilogue are younger than the slot waited for
 // WHICH = which of the K-tile's three waits (0, 1: behind the A stagings of phases 0 / 1; 3: behind W n1's in phase 3). With two
 // operations per slot and wave they all leave 10 younger operations in flight (6 + 2w, 6 + 2w, 4 + 3w for w = 2 operations
 // per W slot); an fp8 W slot is ONE operation per wave (w = 1): 8, 8, 7.
+#define P256_INFLIGHT 10
 #define P256_WAIT(POST, WHICH)                                                                                 \
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((W8 ? ((WHICH) == 3 ? P256_INFLIGHT - 3 : P256_INFLIGHT - 2) : P256_INFLIGHT) + ((POST) ? EX : 0)) : "memory")
 #define P256_BARRIER()                                                \
     {                                                                 \
         __builtin_amdgcn_sched_barrier(0);                            \
-        if constexpr (!((DBG & 64) != 0)) __builtin_amdgcn_s_barrier(); \
+        __builtin_amdgcn_s_barrier();                                 \
         __builtin_amdgcn_sched_barrier(0);                            \
     }
 // The slots the LATE half (wm = 1) reads in a phase are restaged by the early half right after the next barrier: its reads
 // must have completed before that barrier (the early half's own reads complete a whole barrier earlier, with its MFMAs).
-#ifdef P256_NO_LATE_WAIT   // (A/B experiment only: without it the restage-after-read order holds by timing, not by construction)
-#define P256_LATE_READS_DONE()
-#else
+// (Free: 4096^3 101.8-104.1 us without it, 102.0-103.2 with it, round 3. Without it the order holds by timing only, not by construction.)
 #define P256_LATE_READS_DONE() \
     if (wm == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#endif
 // One K-tile out of buffer B: four phases [reads + one slot's staging + wait] B [16 MFMAs] B. The wait that retires a slot
 // sits in the read part of the phase BEFORE the one that reads it (both halves' waits and a barrier precede both halves'
 // reads); a slot is restaged in the phase AFTER its last read. P0 / P1 / P3 = post-epilogue form of the three waits; FIN =
 // this is K-tile 2 of a tile (the raw statistics landed behind the waits of K-tile 1).
-// P256_STAGE_FIRST (A/B experiment, tools/p256_stagefirst_ab.sh): a phase's two LDS-DMA pieces issued BEFORE its fragment
-// reads instead of behind them (they touch different slots: either order is correct)
-#ifdef P256_STAGE_FIRST
-#define P256_STAGE_A(...) P256_STAGE(__VA_ARGS__)
-#define P256_STAGE_B(...)
-#else
-#define P256_STAGE_A(...)
-#define P256_STAGE_B(...) P256_STAGE(__VA_ARGS__)
-#endif
 #define P256_KTILE(B, P0, P1, P3, FIN, HALF)                                                                       \
     {                                                                                                       \
-        P256_STAGE_A(1, (B) ^ 1, oA1 + mA1, oW1, mA1 != 0);                                                 \
         P256_READ_A(B, 0);                                                                                  \
         P256_READ_W(B, 0);                                                                                  \
-        P256_STAGE_B(1, (B) ^ 1, oA1 + mA1, oW1, mA1 != 0); /* A m1 of K-tile t+1 */                                          \
+        P256_STAGE(1, (B) ^ 1, oA1 + mA1, oW1, mA1 != 0); /* A m1 of K-tile t+1 */                                            \
         P256_LATE_READS_DONE();                                                                             \
         P256_WAIT(P0, 0);                 /* retires W n1 of this K-tile */                                 \
         P256_BARRIER();                                                                                     \
-        P256_MMA(0, 0, P256_STAGE_MID(1, (B) ^ 1, oA1 + mA1, oW1, mA1 != 0));                               \
+        P256_MMA(0, 0);                                                                                     \
         P256_BARRIER();                                                                                     \
-        P256_STAGE_A(0, B, oA2, oW2, true);                                                                 \
         P256_READ_W(B, 1);                                                                                  \
-        P256_STAGE_B(0, B, oA2, oW2, true);       /* A m0 of K-tile t+2 */                                          \
+        P256_STAGE(0, B, oA2, oW2, true);         /* A m0 of K-tile t+2 */                                          \
         P256_LATE_READS_DONE();                                                                             \
         P256_WAIT(P1, 1);                 /* retires A m1 of this K-tile */                                 \
         P256_BARRIER();                                                                                     \
-        P256_MMA(0, 1, P256_STAGE_MID(0, B, oA2, oW2, true));                                               \
+        P256_MMA(0, 1);                                                                                     \
         P256_BARRIER();                                                                                     \
-        P256_STAGE_A(2, B, oA2, oW2, true);                                                                 \
         if constexpr (!(HALF)) { P256_READ_A(B, 1); }                                                       \
-        P256_STAGE_B(2, B, oA2, oW2, true);       /* W n0 of K-tile t+2; nothing new is read in the next phase: no wait */ \
+        P256_STAGE(2, B, oA2, oW2, true);         /* W n0 of K-tile t+2; nothing new is read in the next phase: no wait */ \
         P256_LATE_READS_DONE();                                                                             \
         P256_BARRIER();                                                                                     \
-        if constexpr (!(HALF)) { P256_MMA(1, 1, P256_STAGE_MID(2, B, oA2, oW2, true)); }                    \
-        else { P256_STAGE_MID(2, B, oA2, oW2, true); }                                                      \
+        if constexpr (!(HALF)) { P256_MMA(1, 1); }                                                          \
         P256_BARRIER();                                                                                     \
         P256_STAGE(3, B, oA2, oW2, true);       /* W n1 of K-tile t+2 */                                          \
         P256_FIN_HOOK(FIN);                                                                                 \
         P256_WAIT(P3, 3);                 /* retires A m0 / W n0 of the next K-tile */                      \
         P256_BARRIER();                                                                                     \
-        if constexpr (!(HALF)) { P256_MMA(1, 0, P256_STAGE_MID(3, B, oA2, oW2, true)); }                    \
-        else { P256_STAGE_MID(3, B, oA2, oW2, true); }                                                      \
+        if constexpr (!(HALF)) { P256_MMA(1, 0); }                                                          \
         P256_BARRIER();                                                                                     \
         P256_ADVANCE();                                                                                     \
     }
@@ -399,7 +302,6 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restri
         oA2 = bm_ * 256 * K * 2 + (hf_ == 2 ? 8 * row8 : 0);                                                \
         oW2 = bn_ * 256 * K * 2;                                                                            \
         mA2 = hf_ ? 0 : 8 * row8;                                                                           \
-        if constexpr ((DBG & 8) != 0) { oA2 = 0; oW2 = 0; }                                                 \
     } else {                                                                                                \
         oA2 += GEMM_BK * 2; oW2 += GEMM_BK * 2;                                                             \
     }
@@ -421,7 +323,6 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restri
     int cbm, cbn, chalf;
     tile_of(0, cbm, cbn, chalf);
     int oA1 = cbm * 256 * K * 2 + (chalf == 2 ? 8 * row8 : 0), oW1 = cbn * 256 * K * 2;  // K-tile 0 of tile 0, then position t+1
-    if constexpr ((DBG & 8) != 0) { oA1 = 0; oW1 = 0; }
     int oA2 = oA1 + GEMM_BK * 2, oW2 = oW1 + GEMM_BK * 2;
     int mA1 = chalf ? 0 : 8 * row8, mA2 = mA1;   // where a position's A m1 slot comes from (a half tile has none: m0 again)
     int o2 = 0, k2 = 1;
@@ -451,7 +352,6 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restri
     // hrow = 0 / 64 for its m0 / m1 rows) 16-row sub-tiles per wave. Runs while the next tile's first K-tiles are in flight.
     auto epilogue = [&](auto jn_c, int hrow, int par) {
         constexpr int JN = decltype(jn_c)::value;
-        if constexpr (!((DBG & 16) != 0)) {
         int lane_e = lane;  // (opaque here: what the epilogue derives from the lane id is not kept live through the K loop)
         asm volatile("" : "+v"(lane_e));
         const int fr = lane_e & 15, fg = lane_e >> 4;
@@ -472,84 +372,47 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restri
                 mu[j] = tb[0]; rs[j] = tb[1];
             }
         }
-        uint16_t* outp = reinterpret_cast<uint16_t*>(ep.out);
         const __amdgpu_buffer_rsrc_t srdO = __builtin_amdgcn_make_buffer_rsrc(ep.out, 0, 0x7fffffff, 0x00020000);
         const int st_pol = ep.nt_out;  // cache policy of the output stores (launch_gemm256p_inst)
-        if constexpr (STYLE == 0) {
-            // Each wave transposes 16 rows x 64 columns at a time through a private 2 KB patch (its own share of the raw
-            // statistics area, dead since K-tile 2 and refilled by this wave only after these stores). 8-byte slot s of
-            // row r lies at slot s ^ 2 (r & 7).
-            char* patch = smem + P256_RAW + wave * (XP >= 2 ? XP * 1024 : 2048);  // = the bytes stage_x() of THIS wave refills
-            const int rrow = lane_e >> 3, rchunk = lane_e & 7;
-            const int wr_off = fr * 128, wr_sw = 2 * (fr & 7);
-            const int col = cbn * 256 + wn * 64 + rchunk * 8;
+        // Each wave transposes 16 rows x 64 columns at a time through a private 2 KB patch (its own share of the raw
+        // statistics area, dead since K-tile 2 and refilled by this wave only after these stores). 8-byte slot s of
+        // row r lies at slot s ^ 2 (r & 7).
+        char* patch = smem + P256_RAW + wave * (XP >= 2 ? XP * 1024 : 2048);  // = the bytes stage_x() of THIS wave refills
+        const int rrow = lane_e >> 3, rchunk = lane_e & 7;
+        const int wr_off = fr * 128, wr_sw = 2 * (fr & 7);
+        const int col = cbn * 256 + wn * 64 + rchunk * 8;
 #pragma unroll
-            for (int j = 0; j < JN; ++j) {
+        for (int j = 0; j < JN; ++j) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float y[4];
+            for (int i = 0; i < 4; ++i) {
+                float y[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if constexpr (FOLD) y[r] = rs[j] * (acc_get(i, j, r) - mu[j] * cvec[i][r]) + bias[i][r];
-                        else y[r] = acc_get(i, j, r) + bias[i][r];
-                        if constexpr (GELU) y[r] = quick_gelu(y[r]);
-                    }
-                    u32x2 pk;
-                    pk[0] = pack_bf16x2(y[0], y[1]);
-                    pk[1] = pack_bf16x2(y[2], y[3]);
-                    *reinterpret_cast<u32x2*>(patch + wr_off + (((i * 4 + fg) ^ wr_sw) << 3)) = pk;
-                    acc_zero(i, j);
+                for (int r = 0; r < 4; ++r) {
+                    if constexpr (FOLD) y[r] = rs[j] * (acc[i][j][r] - mu[j] * cvec[i][r]) + bias[i][r];
+                    else y[r] = acc[i][j][r] + bias[i][r];
+                    if constexpr (GELU) y[r] = quick_gelu(y[r]);
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-                for (int rh = 0; rh < 2; ++rh) {
-                    const int row = rh * 8 + rrow;
-                    const u32x4 v = *reinterpret_cast<const u32x4*>(patch + row * 128 + (((2 * rchunk) ^ (2 * (row & 7))) << 3));
-                    const int m = cbm * 256 + wm * 128 + hrow + j * 16 + row;
-                    const int vo = ((m < ep.m_valid ? m : dump_row) * ep.ldo + col) * 2;
-                    if constexpr ((DBG & 32) != 0) asm volatile("" ::"v"(v));
-                    else if (st_pol == 16) __builtin_amdgcn_raw_buffer_store_b128(v, srdO, vo, 0, 16);   // sc1: written through, dropped from L2
-                    else if (st_pol == 2) __builtin_amdgcn_raw_buffer_store_b128(v, srdO, vo, 0, 2);      // nt
-                    else __builtin_amdgcn_raw_buffer_store_b128(v, srdO, vo, 0, 0);
-                }
-                __builtin_amdgcn_wave_barrier();  // the patch is rewritten by the next j
+                u32x2 pk;
+                pk[0] = pack_bf16x2(y[0], y[1]);
+                pk[1] = pack_bf16x2(y[2], y[3]);
+                *reinterpret_cast<u32x2*>(patch + wr_off + (((i * 4 + fg) ^ wr_sw) << 3)) = pk;
+                acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-        } else {
-            const int colb = cbn * 256 + wn * 64 + (fg >> 1) * 8 + (fg & 1) * 16;  // + pair * 32
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-            for (int j = 0; j < JN; ++j) {
-                uint32_t pk[4][2];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float y[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if constexpr (FOLD) y[r] = rs[j] * (acc_get(i, j, r) - mu[j] * cvec[i][r]) + bias[i][r];
-                        else y[r] = acc_get(i, j, r) + bias[i][r];
-                        if constexpr (GELU) y[r] = quick_gelu(y[r]);
-                    }
-                    pk[i][0] = pack_bf16x2(y[0], y[1]);
-                    pk[i][1] = pack_bf16x2(y[2], y[3]);
-                    acc_zero(i, j);
-                }
-                const int m = cbm * 256 + wm * 128 + hrow + j * 16 + fr;
-                uint16_t* orow = outp + (size_t)(m < ep.m_valid ? m : dump_row) * ep.ldo + colb;
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) {
-                    // lanes of the odd 16-lane rows take the even rows' values of the second 16-column block and give
-                    // their values of the first: every lane ends up with 8 consecutive columns
-                    const auto s0 = __builtin_amdgcn_permlane16_swap(pk[2 * pr][0], pk[2 * pr + 1][0], false, false);
-                    const auto s1 = __builtin_amdgcn_permlane16_swap(pk[2 * pr][1], pk[2 * pr + 1][1], false, false);
-                    u32x4 v;
-                    v[0] = s0[0]; v[1] = s1[0]; v[2] = s0[1]; v[3] = s1[1];
-                    if constexpr ((DBG & 32) != 0) asm volatile("" ::"v"(v));
-                    else *reinterpret_cast<u32x4*>(orow + pr * 32) = v;
-                }
+            for (int rh = 0; rh < 2; ++rh) {
+                const int row = rh * 8 + rrow;
+                const u32x4 v = *reinterpret_cast<const u32x4*>(patch + row * 128 + (((2 * rchunk) ^ (2 * (row & 7))) << 3));
+                const int m = cbm * 256 + wm * 128 + hrow + j * 16 + row;
+                const int vo = ((m < ep.m_valid ? m : dump_row) * ep.ldo + col) * 2;
+                if (st_pol == 16) __builtin_amdgcn_raw_buffer_store_b128(v, srdO, vo, 0, 16);   // sc1: written through, dropped from L2
+                else if (st_pol == 2) __builtin_amdgcn_raw_buffer_store_b128(v, srdO, vo, 0, 2);      // nt
+                else __builtin_amdgcn_raw_buffer_store_b128(v, srdO, vo, 0, 0);
             }
+            __builtin_amdgcn_wave_barrier();  // the patch is rewritten by the next j
         }
-        }  // (DBG & 16)
     };
 
     const int npair = nt >> 1;
@@ -589,16 +452,6 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const __bf16* __restri
         }
         if (wm == 0) P256_BARRIER();
         epilogue(std::integral_constant<int, 4>{}, chalf == 2 ? 64 : 0, nfull & 1);
-    }
-    if constexpr ((DBG & 16) != 0) {  // (ablation without epilogue: keep the accumulators alive)
-        f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sum[r] += acc_get(i, j, r);
-        if (sum[0] + sum[1] + sum[2] + sum[3] == 12345.678f) reinterpret_cast<float*>(ep.out)[tid] = sum[0];
     }
     // the unconditional staging of the last K-tiles is still in flight: LDS must not be handed on with DMA writes pending
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -641,8 +494,6 @@ __global__ __launch_bounds__(512, 2) void gemm256s_kernel(const IN* __restrict__
     static_assert(!W8 || std::is_same<IN, _Float16>::value, "fp8 rows are widened to f16");
     constexpr int WELT = W8 ? 1 : (int)sizeof(IN);
     constexpr float WSCALE = W8 ? 1.0f / 128.0f : 1.0f;
-    constexpr int DBG = 0;
-    uint32_t ab32[4], wb32[4]; f32x16 acc32[2][4];   // (named by the loop macros' DBG & 128 branches only: never touched here)
     constexpr bool FOLD = false;
     // fp8 rows carry one inverse norm each (ep.aux, f8_row_inv_kernel): the 64 of a wave's column quarter arrive by a 4-byte
     // LDS-DMA piece per wave into the wave's private 256 bytes behind the staging slots. The piece is issued at the head of
@@ -885,16 +736,10 @@ __global__ __launch_bounds__(512, 2) void gemm256s_kernel(const IN* __restrict__
 }
 
 #undef P256_STAGE
-#undef P256_STAGE_A
-#undef P256_STAGE_B
-#undef P256_STAGE_P
-#undef P256_STAGE_MID
 #undef P256_INFLIGHT
 #undef P256_MMA_HALF
 #undef P256_SLOT
 #undef P256_BLDS
-#undef P256_AUX_srdA
-#undef P256_AUX_srdW
 #undef P256_BLDS4
 #undef P256_READ_A
 #undef P256_READ_W
@@ -906,18 +751,6 @@ __global__ __launch_bounds__(512, 2) void gemm256s_kernel(const IN* __restrict__
 #undef P256_ADVANCE
 #undef P256_LATE_READS_DONE
 
-template <int EPI, int XP, int STYLE, int DBG>
-static int launch_gemm256p_kern(hipStream_t st, const void* A, const void* W, const GemmEpi& ep, int M, int N, int K) {
-    const int lds = XP == 1 ? P256_FTAB + 4096 : P256_RAW + (XP >= 2 ? XP * 8192 : 16384);  // (the epilogue's transpose patches live in the raw-statistics area)
-    const int T = (M / 256) * (N / 256);
-    const int grid = T >= 256 ? 256 : T;
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm256p_kernel<EPI, XP, STYLE, DBG>), lds));
-    hipLaunchKernelGGL((gemm256p_kernel<EPI, XP, STYLE, DBG>), dim3(grid), dim3(512), lds, st, reinterpret_cast<const __bf16*>(A),
-                       reinterpret_cast<const __bf16*>(W), M, N, K, ep);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
 template <int EPI, int XP>
 static int launch_gemm256p_inst(hipStream_t st, const void* A, const void* W, const GemmEpi& ep_in, int M, int N, int K) {
     GemmEpi ep = ep_in;
@@ -926,19 +759,14 @@ static int launch_gemm256p_inst(hipStream_t st, const void* A, const void* W, co
     // time and in fabric reads (FETCH_SIZE x 2 = 119-126 MB per FC1 launch either way): one round of an XCD's 32 tiles streams
     // 4.6 MB of distinct operand bytes through its 4 MB L2, so nothing survives to the next round whatever the stores do.
     ep.nt_out = mmiss_option("gemm_p256_store", 0);
-#ifdef MMISS_EXPERIMENTS
-    if constexpr (EPI == MMISS_EPI_LNFOLD_QGELU_BF16 && XP == 3) {
-        const int dbg = mmiss_option("gemm_p256_dbg", 0);  // timing ablations (wrong results by construction)
-#define P256_DBG_CASE(D) if (dbg == D) return launch_gemm256p_kern<EPI, XP, 0, D>(st, A, W, ep, M, N, K);
-        P256_DBG_CASE(1) P256_DBG_CASE(2) P256_DBG_CASE(4) P256_DBG_CASE(8) P256_DBG_CASE(5) P256_DBG_CASE(6) P256_DBG_CASE(7)
-        P256_DBG_CASE(16) P256_DBG_CASE(32) P256_DBG_CASE(64) P256_DBG_CASE(23) P256_DBG_CASE(39) P256_DBG_CASE(87)
-        P256_DBG_CASE(128) P256_DBG_CASE(136) P256_DBG_CASE(144) P256_DBG_CASE(132)
-#undef P256_DBG_CASE
-        if (dbg) MM_FAIL(MMISS_ERR_ARG, "gemm_p256_dbg = %d is not compiled", dbg);
-    }
-    if (mmiss_option("gemm_p256_style", 0) == 1) return launch_gemm256p_kern<EPI, XP, 1, 0>(st, A, W, ep, M, N, K);
-#endif
-    return launch_gemm256p_kern<EPI, XP, 0, 0>(st, A, W, ep, M, N, K);
+    const int lds = XP == 1 ? P256_FTAB + 4096 : P256_RAW + (XP >= 2 ? XP * 8192 : 16384);  // (the epilogue's transpose patches live in the raw-statistics area)
+    const int T = (M / 256) * (N / 256);
+    const int grid = T >= 256 ? 256 : T;
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm256p_kernel<EPI, XP>), lds));
+    hipLaunchKernelGGL((gemm256p_kernel<EPI, XP>), dim3(grid), dim3(512), lds, st, reinterpret_cast<const __bf16*>(A),
+                       reinterpret_cast<const __bf16*>(W), M, N, K, ep);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
 }
 
 // can this GEMM run on the persistent kernel? (bf16 output epilogues; the folded forms need K = 512 or 768: the raw
@@ -988,26 +816,19 @@ static int launch_gemm256s(hipStream_t st, const void* A, const void* W, const G
     const int nbn = N / 256;
     if (W8 && !ep.aux) MM_FAIL(MMISS_ERR_ARG, "gemm256s: fp8 rows need their inverse norms (ep.aux)");
     const int lds = G256_LDS + (W8 ? 2048 : 0);   // + 8 waves x 64 inverse norms
-    if (flt) {
-        const bool rows_mode = flt->buf_s == nullptr;   // (the row threshold pass keeps no scores)
-        if (flt->bn_begin < 0 || flt->bn_begin >= nbn || !flt->tau || !flt->cnt || !flt->buf_g || flt->cap <= 0)
-            MM_FAIL(MMISS_ERR_ARG, "gemm256s: bad filter");
-        const int nwg = (M / 256) * ((nbn - flt->bn_begin + strip - 1) / strip);
-        if (rows_mode) {
-            MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm256s_kernel<IN, 2, W8>), lds));
-            hipLaunchKernelGGL((gemm256s_kernel<IN, 2, W8>), dim3(nwg), dim3(512), lds, st, reinterpret_cast<const IN*>(A),
-                               W, M, N, K, strip, ep, *flt);
-        } else {
-            MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm256s_kernel<IN, 1, W8>), lds));
-            hipLaunchKernelGGL((gemm256s_kernel<IN, 1, W8>), dim3(nwg), dim3(512), lds, st, reinterpret_cast<const IN*>(A),
-                               W, M, N, K, strip, ep, *flt);
-        }
-    } else {
-        MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm256s_kernel<IN, 0, W8>), lds));
-        const int nwg = (M / 256) * ((nbn + strip - 1) / strip);
-        hipLaunchKernelGGL((gemm256s_kernel<IN, 0, W8>), dim3(nwg), dim3(512), lds, st, reinterpret_cast<const IN*>(A),
-                           W, M, N, K, strip, ep, StripFilter{});
-    }
+    if (flt && (flt->bn_begin < 0 || flt->bn_begin >= nbn || !flt->tau || !flt->cnt || !flt->buf_g || flt->cap <= 0))
+        MM_FAIL(MMISS_ERR_ARG, "gemm256s: bad filter");
+    const int nwg = (M / 256) * ((nbn - (flt ? flt->bn_begin : 0) + strip - 1) / strip);
+    auto launch = [&](auto filter_c) -> int {
+        constexpr int FILTER = decltype(filter_c)::value;
+        MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm256s_kernel<IN, FILTER, W8>), lds));
+        hipLaunchKernelGGL((gemm256s_kernel<IN, FILTER, W8>), dim3(nwg), dim3(512), lds, st, reinterpret_cast<const IN*>(A),
+                           W, M, N, K, strip, ep, flt ? *flt : StripFilter{});
+        return MMISS_OK;
+    };
+    if (!flt) MM_TRY(launch(std::integral_constant<int, 0>{}));
+    else if (flt->buf_s) MM_TRY(launch(std::integral_constant<int, 1>{}));
+    else MM_TRY(launch(std::integral_constant<int, 2>{}));   // (the row threshold pass keeps no scores)
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }

@@ -118,11 +118,6 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
     const int npair = nt >> 1;      // ODD = npair & 1
     const int ngrp = (nt + 3) >> 2; // 512-k scale groups per tile (ODD: the last one is a half group of one pair)
     __builtin_assume(npair >= 2);   // (K >= 512: no zero-trip copies of the K loop, whose accumulator joins cost registers)
-#ifdef MMISS_EXPERIMENTS
-    // timing experiment (profiles/gemm_fp8_p256_r05.txt): do the workgroups' epilogues cost more because all 256 run them at once?
-    if (g.stagger > 0 && (blockIdx.x & 1))
-        for (int i = 0; i < g.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
 
     // ---- the ragged last row block, in front of everything (no LDS-DMA is in flight yet: ordinary loads, ordinary waits)
     if (g.ragged > 0) {
@@ -430,10 +425,9 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
         wq[nq][nf][4] = hi_[0]; wq[nq][nf][5] = hi_[1]; wq[nq][nf][6] = hi_[2]; wq[nq][nf][7] = hi_[3];     \
     }
 // 8 block-scaled MFMAs: weights = A operand (unit block scales), activations = B operand (scale byte 0 of sc[mf])
-// STG = the phase's two LDS-DMA pieces when they are issued from the MIDDLE of the MFMA part (Q256_STAGE_MID: after the first
-// four MFMAs — 24 of an MFMA's 32 cycles are free issue slots of the wave, and the partner half's read part, the longer side of
-// every barrier-to-barrier segment, loses its most expensive instructions), empty otherwise
-#define Q256_MMA(mq, nq, STG)                                                                                \
+// (The phase's two LDS-DMA pieces issued from the middle of the MFMA part, between the two sched_barriers, instead of in the
+// read part: measured in round 5 with a build variant since removed, equal or 1-3 % slower; profiles/gemm_fp8_p256_r05.txt.)
+#define Q256_MMA(mq, nq)                                                                                     \
     {                                                                                                       \
         __builtin_amdgcn_s_setprio(1);                                                                      \
         _Pragma("unroll") for (int nf = 0; nf < 2; ++nf) {                                                  \
@@ -442,7 +436,6 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
                     wq[nq][nf], am[mf], acc[(nq) * 2 + nf][(mq) * 4 + mf], 0, 0, 0, 0x7F7F7F7F, 0, sc[mf]); \
             if (nf == 0) {                                                                                  \
                 __builtin_amdgcn_sched_barrier(0);                                                          \
-                STG;                                                                                        \
                 __builtin_amdgcn_sched_barrier(0);                                                          \
             }                                                                                               \
         }                                                                                                   \
@@ -453,18 +446,9 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
                 asm volatile("" : Q256_PIN(acc[(nq) * 2 + nf][(mq) * 4 + mf]));                                \
         __builtin_amdgcn_s_setprio(0);                                                                      \
     }
-#ifdef Q256_STAGE_MID
-#define Q256_STG_READ(...)
-#define Q256_STG_MMA(...) Q256_STAGE(__VA_ARGS__)
-#define Q256_WADJ 2
-#else
-#define Q256_STG_READ(...) Q256_STAGE(__VA_ARGS__)
-#define Q256_STG_MMA(...)
-#define Q256_WADJ 0
-#endif
 // counted wait: 10 younger slot pieces stay in flight; POST: + the previous tile's epilogue operations; XS: + the pair's scale piece
 // (ODD: two scale pieces per pair)
-#define Q256_WAIT(POST, XS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(10 - Q256_WADJ + ((POST) ? EX : 0) + ((XS) ? 1 + ODD : 0)) : "memory")
+#define Q256_WAIT(POST, XS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(10 + ((POST) ? EX : 0) + ((XS) ? 1 + ODD : 0)) : "memory")
 #define Q256_BARRIER()                       \
     {                                        \
         __builtin_amdgcn_sched_barrier(0);   \
@@ -479,31 +463,29 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
     {                                                                                                       \
         Q256_READ_A(B, 0);                                                                                  \
         Q256_READ_W(B, 0);                                                                                  \
-        Q256_STG_READ(1, (B) ^ 1, oA1 + mA1, oW1, mA1 != 0); /* A m1 of K-tile t+1 */                       \
+        Q256_STAGE(1, (B) ^ 1, oA1 + mA1, oW1, mA1 != 0); /* A m1 of K-tile t+1 */                          \
         Q256_LATE_READS_DONE();                                                                             \
         Q256_WAIT(P0, X0);                /* retires W n1 of this K-tile */                                 \
         Q256_BARRIER();                                                                                     \
-        Q256_MMA(0, 0, Q256_STG_MMA(1, (B) ^ 1, oA1 + mA1, oW1, mA1 != 0));                                 \
+        Q256_MMA(0, 0);                                                                                     \
         Q256_BARRIER();                                                                                     \
         Q256_READ_W(B, 1);                                                                                  \
-        Q256_STG_READ(0, B, oA2, oW2, true);       /* A m0 of K-tile t+2 */                                 \
+        Q256_STAGE(0, B, oA2, oW2, true);          /* A m0 of K-tile t+2 */                                 \
         Q256_LATE_READS_DONE();                                                                             \
         Q256_WAIT(P1, X1);                /* retires A m1 of this K-tile */                                 \
         Q256_BARRIER();                                                                                     \
-        Q256_MMA(0, 1, Q256_STG_MMA(0, B, oA2, oW2, true));                                                 \
+        Q256_MMA(0, 1);                                                                                     \
         Q256_BARRIER();                                                                                     \
         if constexpr (!(HALF)) { Q256_READ_A(B, 1); }                                                       \
-        Q256_STG_READ(2, B, oA2, oW2, true);       /* W n0 of K-tile t+2; nothing new is read in the next phase: no wait */ \
+        Q256_STAGE(2, B, oA2, oW2, true);          /* W n0 of K-tile t+2; nothing new is read in the next phase: no wait */ \
         Q256_LATE_READS_DONE();                                                                             \
         Q256_BARRIER();                                                                                     \
-        if constexpr (!(HALF)) { Q256_MMA(1, 1, Q256_STG_MMA(2, B, oA2, oW2, true)); }                      \
-        else { Q256_STG_MMA(2, B, oA2, oW2, true); }                                                        \
+        if constexpr (!(HALF)) { Q256_MMA(1, 1); }                                                          \
         Q256_BARRIER();                                                                                     \
-        Q256_STG_READ(3, B, oA2, oW2, true);       /* W n1 of K-tile t+2 */                                 \
+        Q256_STAGE(3, B, oA2, oW2, true);          /* W n1 of K-tile t+2 */                                 \
         Q256_WAIT(P3, X3);                /* retires A m0 / W n0 of the next K-tile */                      \
         Q256_BARRIER();                                                                                     \
-        if constexpr (!(HALF)) { Q256_MMA(1, 0, Q256_STG_MMA(3, B, oA2, oW2, true)); }                      \
-        else { Q256_STG_MMA(3, B, oA2, oW2, true); }                                                        \
+        if constexpr (!(HALF)) { Q256_MMA(1, 0); }                                                          \
         Q256_BARRIER();                                                                                     \
         Q256_ADVANCE();                                                                                     \
     }
@@ -889,9 +871,6 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
 #undef Q256_BARRIER
 #undef Q256_LATE_READS_DONE
 #undef Q256_KTILE
-#undef Q256_STG_READ
-#undef Q256_STG_MMA
-#undef Q256_WADJ
 #undef Q256_ADVANCE
 #undef Q256_SCALE_PIECE
 #undef Q256_SCALE_PIECE2
@@ -943,9 +922,6 @@ static int launch_gemm256p8(hipStream_t st, int epi, Gemm8Args g, int xt = 0) {
     g.ragged = 0;
     if (g.M >= 512 && g.m_valid > g.M - 256 && g.m_valid <= g.M - 128 && mmiss_option("gemm_p256_ragged", 1) != 0)
         g.ragged = g.m_valid - (g.M - 256);
-#ifdef MMISS_EXPERIMENTS
-    g.stagger = mmiss_option("gemm_p256_stagger", 0);
-#endif
     if (!gemm256p8_xt_ok(epi, xt, g)) MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm256p8: extension %d of epilogue %d at M=%d N=%d K=%d", xt, epi, g.M, g.N, g.K);
     static const char* names[] = {"gemm_fp8_bias_p256", "gemm_fp8_qgelu_mx_p256", "", "gemm_fp8_bias_resid16_p256"};
     static const char* names_x[] = {"gemm_fp8_lnfold_bias_p256", "gemm_fp8_lnfold_qgelu_mx_p256", "", "gemm_fp8_bias_resid16_mxq_p256"};

@@ -256,16 +256,8 @@ struct ScanLds {
     static __host__ __device__ int round_up16(int x) { return (x + 15) & ~15; }
 };
 
-// A stored row is read ONCE per query block by one wave: a stream. MMISS_SCAN_NT marks the loads non-temporal so that a
-// scan does not push the towers' weights out of the 256 MB Infinity Cache between two requests (tools/scan_nt_ab.sh).
-__device__ __forceinline__ u32x4 scan_row_load(const u32x4* p) {
-#ifdef MMISS_SCAN_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-
+// (A stored row is read ONCE per query block by one wave, with plain loads: non-temporal ones, meant to keep the towers' weights in
+// the Infinity Cache between two requests, were tried with a build variant since removed and not adopted — no gain was recorded.)
 // FILT (filtered queries): per 16-row tile the wave reads the 16 tag words (fetched four tiles at a time, one word per lane, one
 // batch ahead, so that a sparse filter is not a chain of dependent tag loads), skips the tile when no query of the block admits
 // any of its rows, masks the row loads of the rows no query admits (their MFMA operand is zero), and drops every (row, query)
@@ -403,11 +395,11 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
                 for (int s = 0; s < NS; ++s) araw[s] = u32x4{0u, 0u, 0u, 0u};
                 if (live) {
 #pragma unroll
-                    for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp + byte0 + s * 64));
+                    for (int s = 0; s < NS; ++s) araw[s] = *reinterpret_cast<const u32x4*>(rp + byte0 + s * 64);
                 }
             } else {
 #pragma unroll
-                for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp + byte0 + s * 64));
+                for (int s = 0; s < NS; ++s) araw[s] = *reinterpret_cast<const u32x4*>(rp + byte0 + s * 64);
             }
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
@@ -443,11 +435,11 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
                 for (int s = 0; s < NS; ++s) araw[s] = u32x4{0u, 0u, 0u, 0u};
                 if (live) {
 #pragma unroll
-                    for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp8 + (span0 + s) * 64));
+                    for (int s = 0; s < NS; ++s) araw[s] = *reinterpret_cast<const u32x4*>(rp8 + (span0 + s) * 64);
                 }
             } else {
 #pragma unroll
-                for (int s = 0; s < NS; ++s) araw[s] = scan_row_load(reinterpret_cast<const u32x4*>(rp8 + (span0 + s) * 64));
+                for (int s = 0; s < NS; ++s) araw[s] = *reinterpret_cast<const u32x4*>(rp8 + (span0 + s) * 64);
             }
 #pragma unroll
             for (int s = 0; s < NS; ++s) {

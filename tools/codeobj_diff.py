@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Are the gfx950 kernels of two builds the same machine code? For refactors of the kernel headers that must not change
+the product: compares, kernel by kernel, the instruction sequences of csrc/api_encoder.o and csrc/api_index.o and the
+compiler's resource figures (csrc/*.resources.txt) of an OLD and a NEW build.
+
+    usage: python tools/codeobj_diff.py OLD/csrc NEW/csrc      (both built by `make -C .../csrc`; no GPU needed)
+
+Kernels are matched by demangled name through RENAMES (old -> new, for kernels whose template or argument lists changed);
+the match must be a bijection over all kernels of an object. ONE normalisation: the 32-bit literal of the s_add_u32 behind
+an s_getpc_b64 is a PC-relative distance to read-only data and moves when anything earlier in the code object changes size;
+kernels that needed it are listed. Exit status 0 = identical."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+# (pattern on the OLD demangled name, replacement): the kernels whose names changed when the compile-time experiment
+# parameters were removed — gemm256p_kernel<EPI, XP, STYLE = 0, DBG = 0> -> <EPI, XP>; gemm160p_kernel<EPI, VARIANT = 0, KT>
+# -> <EPI, KT>; attention_long_kernel(..., int dbg) -> (...)
+RENAMES = [
+    (r"gemm256p_kernel<(\d+), (\d+), 0, 0>", r"gemm256p_kernel<\1, \2>"),
+    (r"gemm160p_kernel<(\d+), 0, (\d+)>", r"gemm160p_kernel<\1, \2>"),
+    (r"(attention_long_kernel<.*>\(.*), int\)$", r"\1)"),
+]
+
+
+def rename(name):
+    for pat, rep in RENAMES:
+        name = re.sub(pat, rep, name)
+    return name
+
+
+def disassembly(csrc, obj):
+    """({demangled kernel name: [instruction text, ...]}, {mangled name: demangled name}) of the gfx950 code object in csrc/obj.o"""
+    with tempfile.TemporaryDirectory() as work:
+        subprocess.check_call(["cp", os.path.join(csrc, obj + ".o"), work])
+        subprocess.check_call([LLVM + "/llvm-objdump", "--offloading", obj + ".o"], cwd=work, stdout=subprocess.DEVNULL)
+        co = [f for f in os.listdir(work) if "gfx950" in f]
+        assert len(co) == 1, os.listdir(work)
+        text = subprocess.check_output([LLVM + "/llvm-objdump", "-d", "--demangle", co[0]], cwd=work, text=True)
+        raw = subprocess.check_output([LLVM + "/llvm-objdump", "-d", co[0]], cwd=work, text=True)
+    head = re.compile(r"^[0-9a-f]+ <(.+)>:$", re.M)
+    names = dict(zip(head.findall(raw), head.findall(text)))
+    kernels, cur = {}, None
+    for line in text.splitlines():
+        m = head.match(line)
+        if m:
+            assert m.group(1) not in kernels, m.group(1)
+            cur = kernels.setdefault(m.group(1), [])
+        elif cur is not None and line.startswith("\t"):
+            cur.append(line.split("//")[0].strip())
+    return kernels, names
+
+
+def mask_pc_literals(ins):
+    out, n = list(ins), 0
+    for i, text in enumerate(ins):
+        if text.startswith("s_getpc_b64"):
+            for j in range(i + 1, min(i + 3, len(ins))):
+                m = re.match(r"(s_add_u32 \S+ \S+ )0x[0-9a-f]+$", ins[j])
+                if m:
+                    out[j] = m.group(1) + "<pc-relative>"
+                    n += 1
+                    break
+    return out, n
+
+
+def resources(csrc, obj, names):
+    """{demangled kernel name: {figure: value}} of the compiler's kernel-resource-usage remarks"""
+    text = open(os.path.join(csrc, obj + ".resources.txt")).read()
+    out = {}
+    for b in re.split(r"remark: [^\n]*Function Name: ", text)[1:]:
+        out[names[b.split()[0]]] = dict(re.findall(r"remark:\s+([A-Za-z][^:\n]*): (\S+) \[-Rpass", b))
+    return out
+
+
+def main():
+    old_dir, new_dir = sys.argv[1], sys.argv[2]
+    bad = 0
+    for obj in ("api_encoder", "api_index"):
+        (old, old_names), (new, new_names) = disassembly(old_dir, obj), disassembly(new_dir, obj)
+        old_res, new_res = resources(old_dir, obj, old_names), resources(new_dir, obj, new_names)
+        mapped = {}
+        for k in old:
+            assert rename(k) not in mapped, ("two old kernels map to one name", k)
+            mapped[rename(k)] = k
+        only_old = sorted(set(mapped) - set(new))
+        only_new = sorted(set(new) - set(mapped))
+        renamed = sorted(k for k in mapped if mapped[k] != k and k in new)
+        masked, differ, res_differ = [], [], []
+        for k in sorted(set(mapped) & set(new)):
+            a, b = old[mapped[k]], new[k]
+            if a != b:
+                (ma, na), (mb, nb) = mask_pc_literals(a), mask_pc_literals(b)
+                if ma == mb and na == nb:
+                    masked.append(k)
+                else:
+                    differ.append(k)
+            ra, rb = old_res.get(mapped[k]), new_res.get(k)
+            if ra != rb or (ra is None) != (rb is None):
+                res_differ.append((k, ra, rb))
+        nres = sum(1 for k in new if k in new_res)
+        print(f"{obj}: {len(old)} kernels before, {len(new)} after; {len(renamed)} matched under a new name; "
+              f"{nres} with resource figures")
+        for k in masked:
+            print(f"  identical after masking PC-relative literals: {k}")
+        for k in only_old:
+            print(f"  ONLY BEFORE: {mapped[k]}")
+        for k in only_new:
+            print(f"  ONLY AFTER: {k}")
+        for k in differ:
+            print(f"  INSTRUCTIONS DIFFER: {k} ({len(old[mapped[k]])} vs {len(new[k])})")
+        for k, ra, rb in res_differ:
+            print(f"  RESOURCES DIFFER: {k}: {ra} vs {rb}")
+        bad += len(only_old) + len(only_new) + len(differ) + len(res_differ)
+    print("identical" if not bad else f"{bad} differences")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -18,9 +18,9 @@ import sys
 CLASSES = {
     "gemm_bf16_bias_resid": r"gemm16_kernelIDF16bLi160ELi3E",
     "gemm_bf16_bias_resid16": r"gemm16_kernelIDF16bLi160ELi9E",
-    # round 4: one symbol per K (gemm160p_kernel<9, 0, K/64>): out-projection and FC2 of the bs-256 step apart
-    "gemm_bf16_bias_resid16_p160_k768": r"gemm160p_kernel(ILi9ELi0ELi12E|<9, 0, 12>)",
-    "gemm_bf16_bias_resid16_p160_k3072": r"gemm160p_kernel(ILi9ELi0ELi48E|<9, 0, 48>)",
+    # round 4: one symbol per K (gemm160p_kernel<9, K/64>): out-projection and FC2 of the bs-256 step apart
+    "gemm_bf16_bias_resid16_p160_k768": r"gemm160p_kernel(ILi9ELi12E|<9, 12>)",
+    "gemm_bf16_bias_resid16_p160_k3072": r"gemm160p_kernel(ILi9ELi48E|<9, 48>)",
     "gemm_bf16_patch_p160": r"gemm160p_kernel(ILi4E|<4,)",
     "gemm_bf16_bias_resid_pruned": r"gemm16_kernelIDF16bLi128ELi3E",
     "gemm_bf16_bias_qgelu": r"gemm16_kernelIDF16bLi192ELi2E",

@@ -47,10 +47,10 @@ def pm(cls, col):
 ktot = sum(float(x["TotalDurationNs"]) for x in stats if "at::native" not in x["Name"]) / steps_traced / 1e6
 r, l, c = d["retrieval"], d["l14"], d["cpu_baseline"]
 q1, qk, f = r["Q1"], r["Q1024"], l["fp8"]
-rows = [("folded FC1 `gemm256p_kernel<8,3,0,0>` (persistent 256²)", "gemm_bf16_lnfold_qgelu_p256", r"gemm256p_kernel(ILi8E|<8,)", "gemm_bf16_lnfold_qgelu_p256"),
-        ("FC2 on the bf16 stream `gemm160p_kernel<9,0,48>` (160 × 256, one round)", "gemm_bf16_bias_resid16_p160_k3072", r"gemm160p_kernel(ILi9ELi0ELi48E|<9, 0, 48>)", "gemm_bf16_bias_resid16_p160_k3072"),
-        ("folded QKV `gemm256p_kernel<7,3,0,0>`", "gemm_bf16_lnfold_bias_p256", r"gemm256p_kernel(ILi7E|<7,)", "gemm_bf16_lnfold_bias_p256"),
-        ("out-projection `gemm160p_kernel<9,0,12>`", "gemm_bf16_bias_resid16_p160_k768", r"gemm160p_kernel(ILi9ELi0ELi12E|<9, 0, 12>)", "gemm_bf16_bias_resid16_p160_k768"),
+rows = [("folded FC1 `gemm256p_kernel<8,3>` (persistent 256²)", "gemm_bf16_lnfold_qgelu_p256", r"gemm256p_kernel(ILi8E|<8,)", "gemm_bf16_lnfold_qgelu_p256"),
+        ("FC2 on the bf16 stream `gemm160p_kernel<9,48>` (160 × 256, one round)", "gemm_bf16_bias_resid16_p160_k3072", r"gemm160p_kernel(ILi9ELi48E|<9, 48>)", "gemm_bf16_bias_resid16_p160_k3072"),
+        ("folded QKV `gemm256p_kernel<7,3>`", "gemm_bf16_lnfold_bias_p256", r"gemm256p_kernel(ILi7E|<7,)", "gemm_bf16_lnfold_bias_p256"),
+        ("out-projection `gemm160p_kernel<9,12>`", "gemm_bf16_bias_resid16_p160_k768", r"gemm160p_kernel(ILi9ELi12E|<9, 12>)", "gemm_bf16_bias_resid16_p160_k768"),
         ("`attention_heads_kernel<2,false,4>`", "attention", r"attention_heads_kernel", "attention")]
 table = ""
 for label, kname, rx, tcls in rows:
