@@ -21,8 +21,14 @@
 //     ~0.9 us here, two of them in flight (104 KB per CU) keep the prefetch distance of the 256 x 256 loop in time.
 //   * 20 A pieces of 8 rows for 8 waves: every wave issues THREE LDS-DMA operations for the A slot (waves 4-7: two pieces and a
 //     4-byte-per-lane filler into a dump area) and two per W slot — 7 per K-tile on every wave, so one counted wait serves all.
-//   * one tile per workgroup: the bf16 rows it adds to (its own output rows) and its bias are fetched BEFORE the K loop; the
-//     epilogue's transpose patches lie over staging buffer 0.
+//   * one tile per workgroup: the bf16 rows it adds to (its own output rows, 80 KB) are fetched UNDER the K loop, by the two
+//     stagings that have no K-tile left to fetch (issued during K-tiles nt - 2 and nt - 1; they used to wrap round and re-read
+//     K-tiles 0 and 1 for nobody) — same instructions, other descriptor and offsets — into the LDS slots those fill, behind the
+//     final vmcnt(0) and barrier that were always there; the epilogue reads them from LDS in the accumulator layout. Nothing
+//     of them is older than K-tile 0's pieces: they used to be 24 register loads in front of the prologue, which the
+//     prologue's first counted wait had to sit out (vector-memory operations retire in order) and which held 40 VGPRs
+//     through the loop. Only the bias (1 KB) is still requested ahead. The epilogue's transpose patches lie over the one
+//     staging buffer those two stagings do not fill, (nt - 1) % 3 (the patch-embedding GEMM: buffer 0).
 // Fragment layout and swizzle: gemm_bf16_p256.h.
 #pragma once
 #include "gemm_bf16_256.h"
@@ -59,15 +65,26 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     // ---- LDS-DMA sources, buffer form: one per-lane offset (row r_in of an 8-row piece, swizzled 16-byte chunk), everything
     // else scalar. A slot row r = tile row r; piece q = rows 8q .. 8q+7 at q * 1024. W slot row r = weight row
     // (r >> 5) * 64 + nq * 32 + (r & 31) (the 32 rows of n half nq of each of the four wave columns).
+    //
+    // Everything a staging operation READS is a run-time value — descriptor, per-lane offset, the seven scalar offsets — so
+    // that the residual GEMMs can point the two stagings past the last K-tile at their own old output rows (G160_NEXT_KTILE)
+    // through the SAME instructions: there is one copy of the K-tile body. Where it WRITES never changes.
+    constexpr bool RESID = (EPI == MMISS_EPI_BIAS_RESID_BF16);
+    static_assert(RESID || EPI == MMISS_EPI_PATCH_F32, "gemm160p_kernel: epilogue");
     const int r_in = lane >> 3, p = lane & 7;
-    const int lane_vo = (r_in * K + ((p ^ r_in) * 8)) * 2;
-    const __amdgpu_buffer_rsrc_t srdA = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Ab), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t srdW = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Wb), 0, 0x7fffffff, 0x00020000);
+    int lane_vo = (r_in * K + ((p ^ r_in) * 8)) * 2;
+    __amdgpu_buffer_rsrc_t srdA = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Ab), 0, 0x7fffffff, 0x00020000);
+    __amdgpu_buffer_rsrc_t srdW = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Wb), 0, 0x7fffffff, 0x00020000);
     const int row8 = 8 * K * 2;                 // bytes between two consecutive 8-row pieces
     const int a_so = wave * row8;               // A pieces w, w + 8 and (waves 0-3) w + 16
     const int a_dst = wave * 1024;
     const int w_so = ((wave >> 1) * 64 + (wave & 1) * 16) * K * 2;   // W slot rows 16w, 16w + 8; the n1 slot is 32 weight rows on
     const int w_dst = wave * 2048;
+    int xa0 = a_so, xa1 = a_so + 8 * row8, xa2 = a_so + 16 * row8, xaf = a_so;           // A pieces; the filler's source
+    int xw0 = w_so, xw1 = w_so + row8, xw2 = w_so + 4 * row8, xw3 = w_so + 5 * row8;     // W n0 (two pieces), W n1 (two)
+    int kstep = GEMM_BK * 2;                    // what ko2 advances by per K-tile
+// (the patch-embedding GEMM never re-points them: it keeps the expressions, and with them its instructions, as they were)
+#define G160_X(var, expr) (RESID ? (var) : (expr))
     char* const dump = smem + G160_DUMP + wave * 256;
 #define G160_BLDS(srd, so, dst) \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(dst), 16, lane_vo, so, 0, 0)
@@ -77,19 +94,45 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
 #define G160_STAGE_A(b2, ko)                                                                                 \
     {                                                                                                       \
         char* sl_ = smem + (b2) * G160_BUF + a_dst;                                                         \
-        G160_BLDS(srdA, a_so + (ko), sl_);                                                                  \
-        G160_BLDS(srdA, a_so + 8 * row8 + (ko), sl_ + 8 * 1024);                                            \
-        if (wave < 4) { G160_BLDS(srdA, a_so + 16 * row8 + (ko), sl_ + 16 * 1024); }                        \
-        else { G160_FILL(srdA, a_so + (ko)); }                                                              \
+        G160_BLDS(srdA, G160_X(xa0, a_so) + (ko), sl_);                                                     \
+        G160_BLDS(srdA, G160_X(xa1, a_so + 8 * row8) + (ko), sl_ + 8 * 1024);                               \
+        if (wave < 4) { G160_BLDS(srdA, G160_X(xa2, a_so + 16 * row8) + (ko), sl_ + 16 * 1024); }           \
+        else { G160_FILL(srdA, G160_X(xaf, a_so) + (ko)); }                                                 \
     }
 // the W slot of n half nq: TWO operations per wave
 #define G160_STAGE_W(b2, nq, ko)                                                                             \
     {                                                                                                       \
         char* sl_ = smem + (b2) * G160_BUF + G160_A_BYTES + (nq) * G160_W_BYTES + w_dst;                    \
-        const int so_ = w_so + (nq) * 4 * row8 + (ko);                                                      \
+        const int so_ = G160_X((nq) ? xw2 : xw0, w_so + (nq) * 4 * row8) + (ko);                            \
         G160_BLDS(srdW, so_, sl_);                                                                          \
-        G160_BLDS(srdW, so_ + row8, sl_ + 1024);                                                            \
+        G160_BLDS(srdW, G160_X(((nq) ? xw3 : xw1) + (ko), so_ + row8), sl_ + 1024);                         \
     }
+
+    // ---- the old rows of the residual GEMMs (the bf16 rows this workgroup adds to: its own output rows, nobody else touches
+    // them) ride in the two stagings that have no K-tile left to fetch — the ones issued during K-tiles nt - 2 and nt - 1, into
+    // buffers nt % 3 and (nt + 1) % 3 — and land behind the final vmcnt(0) and barrier that those stagings always had. Every
+    // wave fetches the rows of ITS OWN 80 x 64 block, as pieces of 16 rows x 64 bytes (32 columns): lane l reads 16 bytes of row
+    // l >> 2, chunk (l & 3) ^ (l >> 4) — the four rows that share a 64-byte quarter of the 256-byte bank row hold a column chunk
+    // at four different places, so the epilogue's 8-byte reads in the accumulator layout (16 rows x 2 half chunks per 32 lanes)
+    // touch every bank once. Piece (j, h) = row block j of five, column half h. The six operations that all eight waves issue as
+    // 16-byte pieces carry, in issue order (A, A, W0, W0, W1, W1): first staging (0,0) (0,1) (1,0) (1,1) (2,0) (2,1), second
+    // staging — ko2 = two row blocks on — (2,.) again, (3,0) (3,1) (4,0) (4,1). The third A operation (a piece on waves 0-3, the
+    // 4-byte filler on 4-7) re-reads piece (0,0) / (2,0): inside the tile like everything else, read by nobody.
+    const int rblk = 16 * ep.ldo * 2;           // bytes between two row blocks of the output
+    const int lane_vo_r = ((lane >> 2) * ep.ldo + (((lane & 3) ^ (lane >> 4)) * 8)) * 2;
+// after a K-tile's stagings: the next K-tile to stage, or (residual GEMMs) the old rows in place of K-tiles nt and nt + 1
+#define G160_NEXT_KTILE()                                                                                    \
+    if (++k2 == nt) {                                                                                       \
+        if constexpr (RESID) {                                                                              \
+            srdA = srdW = __builtin_amdgcn_make_buffer_rsrc(                                                \
+                reinterpret_cast<uint16_t*>(ep.out) + (size_t)(bm * 160 + wm * 80) * ep.ldo + bn * 256 + wn * 64, 0, 0x7fffffff, \
+                0x00020000);                                                                                \
+            lane_vo = lane_vo_r;                                                                            \
+            xa0 = 0; xa1 = 64; xa2 = 0; xaf = 0;                                                            \
+            xw0 = rblk; xw1 = rblk + 64; xw2 = 2 * rblk; xw3 = 2 * rblk + 64;                               \
+            ko2 = 0; kstep = 2 * rblk;                                                                      \
+        } else { k2 = 0; ko2 = 0; }                                                                         \
+    } else { ko2 += kstep; }
 
     // ---- fragment reads: one base per operand and k step + immediate (buffer, 16-row block)
     uint32_t ab[2], wb[2];
@@ -156,22 +199,13 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
         G160_BARRIER();                                                                                     \
         G160_MMA();                                                                                         \
         G160_BARRIER();                                                                                     \
-        if (++k2 == nt) { k2 = 0; ko2 = 0; } else { ko2 += GEMM_BK * 2; }                                   \
+        G160_NEXT_KTILE();                                                                                  \
     }
 
-    // ---- the bf16 rows this wave will add to (its own output rows: nobody else touches them), in the accumulator layout —
-    // 8 bytes per lane and 16 x 16 block, 40 registers — and its bias values: requested NOW, in front of the prologue's LDS-DMA,
-    // so that the epilogue of this one-tile workgroup starts without a memory round trip
-    constexpr bool RESID = (EPI == MMISS_EPI_BIAS_RESID_BF16);
-    static_assert(RESID || EPI == MMISS_EPI_PATCH_F32, "gemm160p_kernel: epilogue");
-    u32x2 resid[5][4];
+    // ---- this wave's bias values (1 KB per workgroup): requested NOW, in front of the prologue's LDS-DMA, so that the epilogue
+    // of this one-tile workgroup starts without a memory round trip
     f32x4 bias[4];
     if constexpr (RESID) {
-        const uint16_t* ob = reinterpret_cast<const uint16_t*>(ep.out) + (size_t)(bm * 160 + wm * 80 + fr) * ep.ldo + bn * 256 + wn * 64 + 4 * fg;
-#pragma unroll
-        for (int j = 0; j < 5; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) resid[j][i] = *reinterpret_cast<const u32x2*>(ob + (size_t)j * 16 * ep.ldo + i * 16);
 #pragma unroll
         for (int i = 0; i < 4; ++i) bias[i] = *reinterpret_cast<const f32x4*>(ep.bias + bn * 256 + wn * 64 + i * 16 + 4 * fg);
     }
@@ -186,13 +220,9 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     G160_STAGE_W(1, 1, GEMM_BK * 2);
     ko2 = (nt > 2) ? 2 * GEMM_BK * 2 : 0;   // (K >= 256: nt >= 4)
     asm volatile("s_waitcnt vmcnt(7)" ::: "memory");  // K-tile 0 has landed (younger: K-tile 1's seven)
-    // ... and with it the 24 ordinary loads above, which are older: their round trip ran beside the prologue's. Pinned here
+    // ... and with it the four bias loads above, which are older: their round trip ran beside the prologue's. Pinned here
     // so that the compiler's own wait for them sits in front of the K loop, not inside it.
     if constexpr (RESID) {
-#pragma unroll
-        for (int j = 0; j < 5; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(resid[j][i]));
 #pragma unroll
         for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(bias[i]));
     }
@@ -206,8 +236,11 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
         if (t + 2 < nt) G160_KTILE(2, 1);
     }
     if (wm == 0) G160_BARRIER();   // (the upper half's last barrier: the lower half is still one behind)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wrap-around staging of the last K-tiles has landed ...
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last two stagings (old rows / wrap-around) have landed ...
     G160_BARRIER();                // ... on every wave, and every wave has read its last fragments: the buffers are free
+    // the epilogue's transpose patches: the residual GEMMs' old rows sit in buffers nt % 3 and (nt + 1) % 3 now, so their
+    // patches lie over the third one, (nt - 1) % 3, the last one read; the patch-embedding GEMM keeps buffer 0
+    const int free_buf = RESID ? ((nt + 2) % 3) * G160_BUF : 0;
 
     if constexpr (EPI == MMISS_EPI_PATCH_F32) {
         // f32 rows: 16 rows x 32 columns at a time through the wave's 2 KB patch (16-byte chunks XOR-swizzled by the row), read back
@@ -216,7 +249,7 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
         asm volatile("" : "+v"(lane_e));
         const int efr = lane_e & 15, efg = lane_e >> 4;
         const int rrow = lane_e >> 3, rchunk = lane_e & 7;
-        char* patch = smem + wave * 2048;   // (over staging buffer 0)
+        char* patch = smem + free_buf + wave * 2048;
         float* outp = reinterpret_cast<float*>(ep.out);
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
@@ -252,10 +285,26 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
         const int efr = lane_e & 15, efg = lane_e >> 4;
         const int rrow = lane_e >> 3, rchunk = lane_e & 7;
         const __amdgpu_buffer_rsrc_t srdO = __builtin_amdgcn_make_buffer_rsrc(ep.out, 0, 0x7fffffff, 0x00020000);
-        char* patch = smem + wave * 2048;   // (over staging buffer 0)
+        char* patch = smem + free_buf + wave * 2048;
         const int wr_off = efr * 128, wr_sw = 2 * (efr & 7);
         const int col = bn * 256 + wn * 64 + rchunk * 8;
         const int dump_row = M - 1;
+        // the old rows, out of the slots the last two stagings filled, in the accumulator layout: 8 bytes per lane and 16 x 16 block
+        u32x2 resid[5][4];
+        {
+            const char* const st0 = smem + (nt % 3) * G160_BUF;         // the staging issued during K-tile nt - 2
+            const char* const st1 = smem + ((nt + 1) % 3) * G160_BUF;   // ... during K-tile nt - 1
+            const int rd = efr * 64 + ((((efg >> 1) ^ (efr >> 2)) << 4) | ((efg & 1) << 3));
+#pragma unroll
+            for (int j = 0; j < 5; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int h = i >> 1;
+                    const char* piece = j == 0 ? st0 + a_dst + h * 8 * 1024
+                                               : (j < 3 ? st0 : st1) + G160_A_BYTES + ((j - 1) & 1) * G160_W_BYTES + w_dst + h * 1024;
+                    resid[j][i] = *reinterpret_cast<const u32x2*>(piece + (rd ^ ((i & 1) << 5)));
+                }
+        }
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
 #pragma unroll
@@ -312,6 +361,8 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
 #undef G160_BARRIER
 #undef G160_LATE_READS_DONE
 #undef G160_KTILE
+#undef G160_NEXT_KTILE
+#undef G160_X
 
 // can the residual GEMM on the bf16 stream run on this tile? (the tile must divide the padded rows / the columns; 32-bit offsets)
 static inline bool gemm160p_ok(int M, int N, int K) {
