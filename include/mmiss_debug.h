@@ -35,6 +35,23 @@ int mmiss_dbg_layernorm(int device, void* hip_stream, const float* x, const floa
 int mmiss_dbg_attention(int device, void* hip_stream, const void* qkv, void* ctx, int32_t B, int32_t T,
                         int32_t H, int32_t causal);
 
+/* the pooled-query form of the short-sequence attention (the pruned last layer): ctxc bf16 [B, H*64] row b = the attention
+ * output of query row pool_row[b] - b*T of item b (pool_row int32 [B]: global token rows). Only where mmiss_dbg_attention runs the
+ * several-heads kernel (T <= 128; B * H large enough, or option att_hpb forced): MMISS_ERR_UNSUPPORTED elsewhere. */
+int mmiss_dbg_attention_pooled(int device, void* hip_stream, const void* qkv, const int32_t* pool_row, void* ctxc, int32_t B,
+                               int32_t T, int32_t H, int32_t causal);
+
+/* the pooled rows' out-projection: out f32 [M,N] = f32(rows_bf16[rowmap[m]]) + A W^T + bias (rows_bf16 bf16 [*, N], rowmap
+ * int32 [M]); `out` is only written. M <= 320, N % 16 == 0, K % 128 == 0 (the skinny kernel). */
+int mmiss_dbg_gemm_resid_rows(int device, void* hip_stream, const void* A, const void* W, float* out, const float* bias,
+                              const void* rows_bf16, const int32_t* rowmap, int32_t M, int32_t N, int32_t K);
+
+/* the patch-embedding GEMM reading the f32 pixels itself (csrc/gemm_bf16_p160.h): pixels f32 [B,3,S,S], W bf16 [d, 3*P*P],
+ * pos f32 [G*G+1, d] -> out f32 [B*(G*G+1), d] rows b*(G*G+1) + 1 + patch = patch . W^T + pos[1 + patch]; the CLS rows (token 0)
+ * are not written. P = 16 or 32, d % 256 == 0. The same bits as mmiss_dbg_im2col + mmiss_dbg_gemm(MMISS_EPI_PATCH_F32). */
+int mmiss_dbg_patch_from_pixels(int device, void* hip_stream, const float* pixels, const void* W, float* out, const float* pos,
+                                int32_t B, int32_t S, int32_t P, int32_t d);
+
 /* pixels f32 [B,3,S,S] -> patches bf16 [B*G*G, Kp] (k = c*P*P + ky*P + kx, zero padded to Kp) */
 int mmiss_dbg_im2col(int device, void* hip_stream, const float* pixels, void* out, int32_t B, int32_t S,
                      int32_t P, int32_t Kp);

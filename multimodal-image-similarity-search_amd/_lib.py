@@ -108,6 +108,9 @@ SIGNATURES = {
     "mmiss_dbg_layernorm": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float]),
     "mmiss_dbg_attention": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _I32]),
     "mmiss_dbg_im2col": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _I32]),
+    "mmiss_dbg_patch_from_pixels": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32]),
+    "mmiss_dbg_attention_pooled": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _I32, _I32]),
+    "mmiss_dbg_gemm_resid_rows": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32]),
     "mmiss_dbg_encoder_record_taps": (_I, [_P, _I]),
     "mmiss_dbg_encoder_set_fuse_ln": (_I, [_P, _I]),
     "mmiss_dbg_set_option": (_I, [C.c_char_p, _I]),

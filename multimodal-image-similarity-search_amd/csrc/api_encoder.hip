@@ -602,21 +602,37 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
         qkv.c = &L.cqkv; qkv.W8 = &L.wqkv8; qkv.s8 = &L.sqkv; qkv.W8f = &L.wqkv8f; qkv.s8f = &L.sqkvf; qkv.c16 = &L.cqkv16; qkv.out = qkv.out8 = tw.qkv.p;
         MM_TRY(run_wide(st, tw, P, P.qkv, qkv, eps));
         const bool last_pruned = P.prune && l == tw.layers - 1;
-        if (P.out8 && !last_pruned)
+        // The pruned last layer where the attention is the several-heads kernel and the out-projection the skinny one: the
+        // attention computes the pooled query's tile only and stores that row straight into ctxc, and the out-projection reads
+        // its old residual row through pool_row (from xb, widened, or from x) — no gather launch, no other ctx row written.
+        // Option pooled_tail = 0: the full attention and the gather.
+        GemmEpi ep_out{};
+        ep_out.out = tw.xc.p; ep_out.bias = L.bo.as<float>(); ep_out.ldo = d; ep_out.m_valid = B;
+        const bool pooled = last_pruned && attention_pooled_ok(B, tw.T, tw.heads) &&
+                            gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, B, d, d, ep_out) && mmiss_option("pooled_tail", 1) != 0;
+        if (pooled)
+            MM_TRY(launch_attention_pooled(st, tw.qkv.p, tw.ctxc.p, tw.pool_row.as<int32_t>(), B, tw.T, tw.heads, P.causal));
+        else if (P.out8 && !last_pruned)
             MM_TRY(launch_attention_mx(st, tw.qkv.p, tw.ctx8.as<uint8_t>(), tw.ctxs.as<uint8_t>(), mx_scale_row_bytes(d), B, tw.T, tw.heads));
         else
             MM_TRY(launch_attention(st, tw.qkv.p, tw.ctx.p, B, tw.T, tw.heads, P.causal));
         if (last_pruned) {
             const int Bp = (int)round_up(B, 128);
-            const int grid = (B * d / 4 + 255) / 256;
-            // pooled rows of the attention output (bf16) and of the residual stream (f32, or widened bf16) in ONE launch
-            hipLaunchKernelGGL(gather_pooled_kernel, dim3(grid), dim3(256), 0, st, tw.ctx.as<uint16_t>(), tw.ctxc.as<uint16_t>(),
-                               P.resid16 ? nullptr : tw.x.as<float>(), P.resid16 ? tw.xb.as<uint16_t>() : nullptr,
-                               tw.xc.as<float>(), tw.pool_row.as<int32_t>(), B, d);
-            MM_HIP(hipGetLastError());
+            if (pooled) {
+                if (P.resid16) ep_out.resid16_rows = tw.xb.as<uint16_t>();
+                else ep_out.resid32_rows = tw.x.as<float>();
+                ep_out.resid_rowmap = tw.pool_row.as<int32_t>();
+            } else {
+                const int grid = (B * d / 4 + 255) / 256;
+                MM_PROF("gather_pooled", st, 0.0, (double)B * d * (P.resid16 ? 10 : 12));
+                // pooled rows of the attention output (bf16) and of the residual stream (f32, or widened bf16) in ONE launch
+                hipLaunchKernelGGL(gather_pooled_kernel, dim3(grid), dim3(256), 0, st, tw.ctx.as<uint16_t>(), tw.ctxc.as<uint16_t>(),
+                                   P.resid16 ? nullptr : tw.x.as<float>(), P.resid16 ? tw.xb.as<uint16_t>() : nullptr,
+                                   tw.xc.as<float>(), tw.pool_row.as<int32_t>(), B, d);
+                MM_HIP(hipGetLastError());
+            }
+            MM_TRY(launch_gemm(st, MMISS_EPI_BIAS_RESID_F32, 128, tw.ctxc.p, L.wo.p, ep_out, Bp, d, d));
             GemmEpi ep{};
-            ep.out = tw.xc.p; ep.bias = L.bo.as<float>(); ep.ldo = d; ep.m_valid = B;
-            MM_TRY(launch_gemm(st, MMISS_EPI_BIAS_RESID_F32, 128, tw.ctxc.p, L.wo.p, ep, Bp, d, d));
             MM_TRY(launch_layernorm(st, tw.xc.as<float>(), L.ln2g.as<float>(), L.ln2b.as<float>(), tw.hc.p, true, nullptr,
                                     B, d, eps));
             ep = GemmEpi{};
@@ -676,25 +692,37 @@ int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B
     const int Mpatch = B * e->G * e->G;
     const int bm_p = gemm_pick_bm(Mpatch, d);
     const int Mpp = (int)round_up(Mpatch, bm_p);
-    MM_TRY(launch_im2col(st, pix_dev, src_u8, e->patches.p, B, S, P, e->Kp));
+    // round 3: the patch GEMM on the 160 x 256 tile of gemm_bf16_p160.h when that grid is about one round of the chip and K is long;
+    // f32 pixels, patch 16 or 32 and no K padding: that kernel reads the pixels itself and there is no im2col pass (option
+    // patch_from_pixels = 0: the bf16 copy first, as u8 / RGB inputs, patch 14 and the other batch sizes always do)
+    const int M160 = (int)round_up(Mpatch, 160);
+    const int64_t tiles160 = (int64_t)(M160 / 160) * (d / 256);
+    const bool patch_p160 = mmiss_option("gemm_p160", 1) != 0 && (d % 256) == 0 && gemm160p_ok(M160, d, e->Kp) && tiles160 >= 200 &&
+                            tiles160 <= 256 && e->Kp >= 2048;
+    const bool from_pixels = patch_p160 && !src_u8 && gemm160p_pix_ok(pix_dev, B, S, P, M160, d, e->Kp) &&
+                             mmiss_option("patch_from_pixels", 1) != 0;
+    if (!from_pixels) MM_TRY(launch_im2col(st, pix_dev, src_u8, e->patches.p, B, S, P, e->Kp));
+    // On the bf16 residual stream (pruned last layer, no taps) the layers read xb and the statistics only and the head reads
+    // the compact rows xc: the pre-LayerNorm then keeps its f32 rows to itself and makes the CLS rows as it goes
+    const bool lean_pre = plan.embed == EmbedOut::Stats64 && plan.resid16 && plan.prune && mmiss_option("prelayernorm_lean", 1) != 0;
     // (Stats16: the CLS rows come with the pre-LayerNorm below, prelayernorm_skinny_kernel)
-    if (plan.embed != EmbedOut::Stats16)
+    if (plan.embed != EmbedOut::Stats16 && !lean_pre) {
+        MM_PROF("cls_rows", st, (double)B * d, 12.0 * B * d);
         hipLaunchKernelGGL(cls_rows_kernel, dim3((B * d + 255) / 256), dim3(256), 0, st, tw.x.as<float>(),
                            e->cls.as<float>(), tw.pos.as<float>(), B, tw.T, d);
+    }
     GemmEpi ep{};
     ep.out = tw.x.p; ep.aux = tw.pos.as<float>(); ep.ldo = d; ep.m_valid = Mpatch; ep.p0 = e->G * e->G; ep.p1 = tw.T;
     if (gemm_splitk_candidate((int64_t)(Mpp / bm_p) * (d / GEMM_BN), e->Kp)) {
         MM_TRY(tw.splitk.ensure((size_t)8 * Mpp * d * 4));
         ep.splitk_ws = tw.splitk.as<float>(); ep.splitk_ws_bytes = tw.splitk.bytes;
     }
-    {   // round 3: on the 160 x 256 tile of gemm_bf16_p160.h when that grid is about one round of the chip and K is long
-        const int M160 = (int)round_up(Mpatch, 160);
-        const int64_t tiles = (int64_t)(M160 / 160) * (d / 256);
-        if (mmiss_option("gemm_p160", 1) != 0 && (d % 256) == 0 && gemm160p_ok(M160, d, e->Kp) && tiles >= 200 && tiles <= 256 && e->Kp >= 2048)
-            MM_TRY(launch_gemm160p_patch(st, e->patches.p, e->patch_w.p, ep, M160, d, e->Kp));
-        else
-            MM_TRY(launch_gemm(st, MMISS_EPI_PATCH_F32, bm_p, e->patches.p, e->patch_w.p, ep, Mpp, d, e->Kp));
-    }
+    if (from_pixels)
+        MM_TRY(launch_gemm160p_patch_pix(st, pix_dev, e->patch_w.p, ep, B, S, P, M160, d, e->Kp));
+    else if (patch_p160)
+        MM_TRY(launch_gemm160p_patch(st, e->patches.p, e->patch_w.p, ep, M160, d, e->Kp));
+    else
+        MM_TRY(launch_gemm(st, MMISS_EPI_PATCH_F32, bm_p, e->patches.p, e->patch_w.p, ep, Mpp, d, e->Kp));
     // pre_layrnorm, in place on the fp32 residual stream (HF:modeling_clip.py:640), with what the plan's first layer wants
     const int M = plan.M;
     if (plan.embed == EmbedOut::Stats16) {   // + CLS rows, xb and the 16-column statistics, in one launch
@@ -703,10 +731,17 @@ int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B
                            tw.pos.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(),
                            M, tw.T, d, e->cfg.ln_eps);
         MM_HIP(hipGetLastError());
+    } else if (lean_pre) {   // xb and the 64-column statistics; CLS rows made here, no f32 write-back
+        MM_PROF("layernorm", st, 10.0 * M * d, (double)M * d * 6);
+        hipLaunchKernelGGL(layernorm_stats_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->pre_g.as<float>(),
+                           e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(), M, d, d / 64, e->cfg.ln_eps,
+                           e->cls.as<float>(), tw.pos.as<float>(), tw.T);
+        MM_HIP(hipGetLastError());
     } else if (plan.embed == EmbedOut::Stats64) {   // + xb and the 64-column statistics
         MM_PROF("layernorm", st, 10.0 * M * d, (double)M * d * 10);
-        hipLaunchKernelGGL(layernorm_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->pre_g.as<float>(),
-                           e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(), M, d, d / 64, e->cfg.ln_eps);
+        hipLaunchKernelGGL(layernorm_stats_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->pre_g.as<float>(),
+                           e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(), M, d, d / 64, e->cfg.ln_eps,
+                           (const float*)nullptr, (const float*)nullptr, 1);
         MM_HIP(hipGetLastError());
     } else {
         MM_TRY(launch_layernorm(st, tw.x.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.x.p, false, nullptr, M, d,
@@ -1469,6 +1504,35 @@ extern "C" int mmiss_dbg_attention(int device, void* hip_stream, const void* qkv
     if (!qkv || !ctx) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_attention: null pointer");
     MM_TRY(mmiss_use_device(device));
     return launch_attention(reinterpret_cast<hipStream_t>(hip_stream), qkv, ctx, B, T, H, causal != 0);
+}
+
+extern "C" int mmiss_dbg_attention_pooled(int device, void* hip_stream, const void* qkv, const int32_t* pool_row, void* ctxc,
+                                          int32_t B, int32_t T, int32_t H, int32_t causal) {
+    if (!qkv || !pool_row || !ctxc) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_attention_pooled: null pointer");
+    MM_TRY(mmiss_use_device(device));
+    return launch_attention_pooled(reinterpret_cast<hipStream_t>(hip_stream), qkv, ctxc, pool_row, B, T, H, causal != 0);
+}
+
+extern "C" int mmiss_dbg_gemm_resid_rows(int device, void* hip_stream, const void* A, const void* W, float* out, const float* bias,
+                                         const void* rows_bf16, const int32_t* rowmap, int32_t M, int32_t N, int32_t K) {
+    if (!A || !W || !out || !bias || !rows_bf16 || !rowmap) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_resid_rows: null pointer");
+    MM_TRY(mmiss_use_device(device));
+    GemmEpi ep{};
+    ep.out = out; ep.bias = bias; ep.ldo = N; ep.m_valid = M;
+    ep.resid16_rows = reinterpret_cast<const uint16_t*>(rows_bf16); ep.resid_rowmap = rowmap;
+    return launch_gemm(reinterpret_cast<hipStream_t>(hip_stream), MMISS_EPI_BIAS_RESID_F32, 128, A, W, ep, (int)round_up(M, 128), N, K);
+}
+
+extern "C" int mmiss_dbg_patch_from_pixels(int device, void* hip_stream, const float* pixels, const void* W, float* out,
+                                           const float* pos, int32_t B, int32_t S, int32_t P, int32_t d) {
+    if (!pixels || !W || !out || !pos) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_patch_from_pixels: null pointer");
+    if (P <= 0 || S <= 0 || S % P || B <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_patch_from_pixels: B=%d S=%d P=%d", B, S, P);
+    MM_TRY(mmiss_use_device(device));
+    const int G = S / P;
+    GemmEpi ep{};
+    ep.out = out; ep.aux = pos; ep.ldo = d; ep.m_valid = B * G * G; ep.p0 = G * G; ep.p1 = G * G + 1;
+    return launch_gemm160p_patch_pix(reinterpret_cast<hipStream_t>(hip_stream), pixels, W, ep, B, S, P, (int)round_up(B * G * G, 160), d,
+                                     3 * P * P);
 }
 
 extern "C" int mmiss_dbg_im2col(int device, void* hip_stream, const float* pixels, void* out, int32_t B, int32_t S,

@@ -328,19 +328,30 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(const uint16_t* __rest
 // pre_layrnorm for the large calls: LayerNorm in place on the f32 rows AND, in the same pass, what row_stats_kernel would
 // produce from the result — the bf16 copy of the new rows (xb) and their (sum, sumsq) in statistics slot 0 of `parts`
 // (the others zero). One launch and one 39 MB read less per ViT-B/32 step. d <= 1024, d % 4 == 0.
+// LEAN (the bf16 residual stream: the layers read xb and the statistics, nobody reads the f32 rows again): the f32 write-back
+// is skipped (39 MB per ViT-B/32 step), and row 0 of every item is class_embedding + position_embedding[0] computed HERE
+// (cls_rows_kernel's sum, as prelayernorm_skinny_kernel does), so that launch goes away too. Same arithmetic, same bits.
+template <bool LEAN>
 __global__ __launch_bounds__(256) void layernorm_stats_kernel(float* __restrict__ x, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, uint16_t* __restrict__ xb,
-                                                              float* __restrict__ stats, int M, int d, int parts, float eps) {
+                                                              float* __restrict__ stats, int M, int d, int parts, float eps,
+                                                              const float* __restrict__ cls = nullptr,
+                                                              const float* __restrict__ pos = nullptr, int T = 1) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= M) return;
     float* xr = x + (size_t)r * d;
+    const bool is_cls = LEAN && (r % T) == 0;
     f32x4 v[4];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int c = (i * 64 + lane) * 4;
-        v[i] = (c < d) ? *reinterpret_cast<const f32x4*>(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < d) {
+            if (is_cls) v[i] = *reinterpret_cast<const f32x4*>(cls + c) + *reinterpret_cast<const f32x4*>(pos + c);
+            else v[i] = *reinterpret_cast<const f32x4*>(xr + c);
+        }
         s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     }
     const float mean = wave_sum(s) / (float)d;
@@ -366,7 +377,7 @@ __global__ __launch_bounds__(256) void layernorm_stats_kernel(float* __restrict_
             f32x4 y;
 #pragma unroll
             for (int e = 0; e < 4; ++e) y[e] = (v[i][e] - mean) * rstd * g[e] + bb[e];
-            *reinterpret_cast<f32x4*>(xr + c) = y;
+            if constexpr (!LEAN) *reinterpret_cast<f32x4*>(xr + c) = y;
             u32x2 pk;
             pk[0] = pack_bf16x2(y[0], y[1]);
             pk[1] = pack_bf16x2(y[2], y[3]);
@@ -487,7 +498,7 @@ __device__ __forceinline__ float att_max_over_lane_groups(float v);
 template <int NKP, bool CAUSAL, bool MXOUT = false>
 __device__ __forceinline__ void attention_onepass_tile(const char* sK, const char* sV, const bf16x8 (&qf)[2], int q, int T,
                                                        int fr, int fg, uint16_t* orow, uint8_t* o8row = nullptr, uint8_t* srow = nullptr,
-                                                       int h = 0) {
+                                                       int h = 0, int only_q = -1) {
     f32x4 sacc[2 * NKP];
     float mx = -INFINITY;
 #pragma unroll
@@ -574,7 +585,7 @@ __device__ __forceinline__ void attention_onepass_tile(const char* sK, const cha
                 if (fg == 0) srow[mx_scale_offset(2 * h + blk)] = (uint8_t)e8;
             }
         }
-    } else if (q < T) {
+    } else if (q < T && (only_q < 0 || q == only_q)) {   // (only_q: the pooled-query form keeps one row of the tile)
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             u32x2 pk;
@@ -852,11 +863,17 @@ __global__ __launch_bounds__(512) void attention_long_kernel(const uint16_t* __r
 // Q/K/V global loads, LDS writes, barrier, 1 us of arithmetic, store - 3072 workgroups of 20 KB each. Here the K/V image of
 // head h+1 (and its Q fragments) is in flight in registers while head h is computed from LDS (two LDS images, one barrier
 // per head), so a workgroup pays the load latency once instead of HPB times. Same arithmetic, bit-identical output.
+// POOLED (the pruned last layer: one query row per item leaves it): only the 16-query tile that holds row pool_row[b] is
+// computed — by the wave that owns it in the full form — from the same K/V images, and only that row is stored, into the
+// compact ctx [B, H * 64] at row b. No Q rows of the other tiles are read and no other ctx row is written: half the bytes.
+// The tile's arithmetic is the full form's, so the row has the same bits.
 // ------------------------------------------------------------------------------------------------
-template <int NKP, bool CAUSAL, int HPB, bool MXOUT = false>
+template <int NKP, bool CAUSAL, int HPB, bool MXOUT = false, bool POOLED = false>
 __global__ __launch_bounds__(256) void attention_heads_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ ctx,
                                                               int T, int H, uint8_t* __restrict__ ctx8 = nullptr,
-                                                              uint8_t* __restrict__ ctxs = nullptr, int ld_s = 0) {
+                                                              uint8_t* __restrict__ ctxs = nullptr, int ld_s = 0,
+                                                              const int32_t* __restrict__ pool_row = nullptr) {
+    static_assert(!(POOLED && MXOUT), "the pooled-query form writes bf16");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TP = NKP * 32;
     constexpr int IMG = TP * (128 + ATT_VSTRIDE);  // one K + V image
@@ -904,7 +921,15 @@ __global__ __launch_bounds__(256) void attention_heads_kernel(const uint16_t* __
     };
 
     bf16x8 qf[2], qn[2];
-    load_q(h0, wave, qf);
+    int pq = 0, pqt = wave;   // POOLED: the item's pooled query and its tile (every wave stages K/V, one wave computes)
+    if constexpr (POOLED) {
+        pq = __builtin_amdgcn_readfirstlane(pool_row[b]) - b * T;
+        pq = pq < 0 ? 0 : (pq >= T ? T - 1 : pq);
+        pqt = pq >> 4;
+    }
+    const bool my_tile = !POOLED || wave == (pqt & 3);
+    if constexpr (POOLED) { if (my_tile) load_q(h0, pqt, qf); }
+    else load_q(h0, wave, qf);
     load_head(h0);
     store_head(0);
     __syncthreads();
@@ -912,11 +937,17 @@ __global__ __launch_bounds__(256) void attention_heads_kernel(const uint16_t* __
     for (int hh = 0; hh < HPB; ++hh) {
         const int h = h0 + hh, cur = hh & 1;
         if (hh + 1 < HPB) {  // next head's operands fly during this head's arithmetic
-            load_q(h + 1, wave, qn);
+            if constexpr (POOLED) { if (my_tile) load_q(h + 1, pqt, qn); }
+            else load_q(h + 1, wave, qn);
             load_head(h + 1);
         }
         const char* sK = smem + cur * IMG;
         const char* sV = sK + TP * 128;
+        if constexpr (POOLED) {
+            if (my_tile)
+                attention_onepass_tile<NKP, CAUSAL>(sK, sV, qf, pqt * 16 + fr, T, fr, fg, ctx + (size_t)b * dmodel + h * 64 + 4 * fg,
+                                                    nullptr, nullptr, 0, pq);
+        } else
         for (int qt = wave; qt < nqt; qt += 4) {
             const int q = qt * 16 + fr;
             if (qt != wave) load_q(h, qt, qf);  // (T > 64: a wave's second tile)
@@ -1086,6 +1117,25 @@ static int launch_attention_heads(hipStream_t st, const void* qkv, void* ctx, in
     return MMISS_OK;
 }
 
+// the pooled-query form of attention_heads_kernel: ctxc [B, H * 64] row b = the attention output of query pool_row[b] - b * T
+template <int NKP, int HPB>
+static int launch_attention_heads_pooled(hipStream_t st, const void* qkv, void* ctxc, const int32_t* pool_row, int B, int T, int H,
+                                         bool causal) {
+    const int lds = 2 * NKP * 32 * (128 + ATT_VSTRIDE);
+    const dim3 grid(B * (H / HPB));
+    if (causal) {
+        MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&attention_heads_kernel<NKP, true, HPB, false, true>), lds));
+        hipLaunchKernelGGL((attention_heads_kernel<NKP, true, HPB, false, true>), grid, dim3(256), lds, st, (const uint16_t*)qkv,
+                           (uint16_t*)ctxc, T, H, (uint8_t*)nullptr, (uint8_t*)nullptr, 0, pool_row);
+    } else {
+        MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&attention_heads_kernel<NKP, false, HPB, false, true>), lds));
+        hipLaunchKernelGGL((attention_heads_kernel<NKP, false, HPB, false, true>), grid, dim3(256), lds, st, (const uint16_t*)qkv,
+                           (uint16_t*)ctxc, T, H, (uint8_t*)nullptr, (uint8_t*)nullptr, 0, pool_row);
+    }
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
 template <int NKP>
 static int launch_attention_heads_hpb(hipStream_t st, int hpb, const void* qkv, void* ctx, int B, int T, int H, bool causal) {
     switch (hpb) {
@@ -1140,22 +1190,55 @@ static int launch_attention_mx_short(hipStream_t st, const void* qkv, uint8_t* c
     }
 }
 
+// heads per workgroup of the short-sequence kernel (attention_heads_kernel), 1 = one (item, head) per workgroup (attention_kernel):
+// several while >= 512 workgroups remain. Option att_hpb: 0 = automatic, 1 = never, 2/3/4/6 = forced (if it divides H)
+static int attention_pick_hpb(int B, int H) {
+    int hpb = mmiss_option("att_hpb", 0);
+    if (hpb == 0) {
+        hpb = 1;
+        for (int c : {4, 6, 3, 2})  // B = 256, T = 50, H = 12: 1 head 19.3 us, 2: 17.5, 3: 17.2, 4: 16.2, 6: 16.8 (4.9 TB/s)
+            if (H % c == 0 && (int64_t)B * (H / c) >= 512) { hpb = c; break; }
+    }
+    return ((hpb == 2 || hpb == 3 || hpb == 4 || hpb == 6) && H % hpb == 0) ? hpb : 1;
+}
+
+// The pruned last layer's attention: does launch_attention pick attention_heads_kernel at this shape? Then its pooled-query
+// form can run instead (launch_attention_pooled); every other kernel keeps the full attention and the gather behind it.
+static bool attention_pooled_ok(int B, int T, int H) {
+    return B > 0 && T > 0 && T <= 128 && H > 0 && attention_pick_hpb(B, H) > 1;
+}
+static int launch_attention_pooled(hipStream_t st, const void* qkv, void* ctxc, const int32_t* pool_row, int B, int T, int H,
+                                   bool causal) {
+    if (!attention_pooled_ok(B, T, H) || !pool_row) MM_FAIL(MMISS_ERR_UNSUPPORTED, "attention (pooled query): B=%d T=%d H=%d", B, T, H);
+    // one query per (item, head): its scores and its output, and the K/V rows the tile reads
+    MM_PROF("attention", st, 4.0 * B * H * (double)T * 64, ((double)B * T * H * 64 * 2 + (double)B * H * 64 * 2) * 2);
+    auto heads = [&](auto nkp_tag) -> int {
+        constexpr int NKP = decltype(nkp_tag)::value;
+        switch (attention_pick_hpb(B, H)) {
+            case 2: return launch_attention_heads_pooled<NKP, 2>(st, qkv, ctxc, pool_row, B, T, H, causal);
+            case 3: return launch_attention_heads_pooled<NKP, 3>(st, qkv, ctxc, pool_row, B, T, H, causal);
+            case 4: return launch_attention_heads_pooled<NKP, 4>(st, qkv, ctxc, pool_row, B, T, H, causal);
+            default: return launch_attention_heads_pooled<NKP, 6>(st, qkv, ctxc, pool_row, B, T, H, causal);
+        }
+    };
+    switch ((T + 31) / 32) {
+        case 1: return heads(std::integral_constant<int, 1>{});
+        case 2: return heads(std::integral_constant<int, 2>{});
+        case 3: return heads(std::integral_constant<int, 3>{});
+        default: return heads(std::integral_constant<int, 4>{});
+    }
+}
+
 static int launch_attention(hipStream_t st, const void* qkv, void* ctx, int B, int T, int H, bool causal) {
     if (B <= 0) return MMISS_OK;
     if (T <= 0 || T > 288 || H <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "attention: T=%d (1..288), H=%d", T, H);
     const int nkp = (T + 31) / 32;
     // algorithmic flops: QK^T and PV, unpadded, full (non-causal) count as SURVEY.md §8(d) does
     MM_PROF("attention", st, 4.0 * B * H * (double)T * T * 64, (double)B * T * H * 64 * 2 * 4);
-    // short sequences, large batch: several heads per workgroup (attention_heads_kernel) while >= 512 workgroups remain.
-    // Option att_hpb: 0 = automatic, 1 = never, 2/3/4/6 = forced (if it divides H)
+    // short sequences, large batch: several heads per workgroup (attention_heads_kernel), attention_pick_hpb
     if (nkp <= 4) {
-        int hpb = mmiss_option("att_hpb", 0);
-        if (hpb == 0) {
-            hpb = 1;
-            for (int c : {4, 6, 3, 2})  // B = 256, T = 50, H = 12: 1 head 19.3 us, 2: 17.5, 3: 17.2, 4: 16.2, 6: 16.8 (4.9 TB/s)
-                if (H % c == 0 && (int64_t)B * (H / c) >= 512) { hpb = c; break; }
-        }
-        if ((hpb == 2 || hpb == 3 || hpb == 4 || hpb == 6) && H % hpb == 0) {
+        const int hpb = attention_pick_hpb(B, H);
+        if (hpb > 1) {
             switch (nkp) {
                 case 1: return launch_attention_heads_hpb<1>(st, hpb, qkv, ctx, B, T, H, causal);
                 case 2: return launch_attention_heads_hpb<2>(st, hpb, qkv, ctx, B, T, H, causal);

@@ -44,6 +44,13 @@ struct GemmEpi {
     // LNFOLD epilogues of the persistent kernel, K > 768: (mean, rstd) of every row FINISHED, [M][2] (ln_finalize_kernel) —
     // the raw partials of a 256-row tile (K / 64 x 8 bytes per row) no longer fit beside the staging buffers
     const float* ln_final;
+    // BIAS_RESID_F32 on the skinny kernel (the pruned last layer's out-projection): if set, the OLD residual row of output row m
+    // is row resid_rowmap[m] of ANOTHER buffer (stride ldo) — f32 rows, or bf16 rows widened — not row m of `out`, which is only written
+    const float* resid32_rows;
+    const uint16_t* resid16_rows;
+    const int32_t* resid_rowmap;
+    // PATCH straight from the pixels (gemm_bf16_p160.h): the A operand is the f32 image [B,3,pix_S,pix_S], patches of side pix_P
+    int pix_S, pix_P, pix_bytes;
 };
 
 #define MMISS_EPI_GROUPMAX_F32 5  // internal: out f32 [M, N/16] = max over the lane's 16 n (see decode below)
@@ -854,6 +861,7 @@ static int launch_gemm(hipStream_t st, int epi, int bm, const void* A, const voi
             return launch_gemm_skinny(st, epi, A, W, ep, mv0, N, K);
         }
     }
+    if (ep.resid_rowmap) MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm: M=%d N=%d K=%d: row-mapped residual rows are read by the skinny kernel only", M, N, K);
     if (bm == 0) bm = 128;
     if (M <= 0 || N <= 0 || K <= 0 || (M % bm) || (N % GEMM_BN) || (K % GEMM_BK))
         MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm: M=%d N=%d K=%d must be multiples of %d/%d/%d", M, N, K, bm, GEMM_BN,

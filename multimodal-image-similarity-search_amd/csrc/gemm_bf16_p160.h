@@ -29,9 +29,21 @@
 //     prologue's first counted wait had to sit out (vector-memory operations retire in order) and which held 40 VGPRs
 //     through the loop. Only the bias (1 KB) is still requested ahead. The epilogue's transpose patches lie over the one
 //     staging buffer those two stagings do not fill, (nt - 1) % 3 (the patch-embedding GEMM: buffer 0).
+//   * the patch-embedding GEMM straight from the f32 pixels (MMISS_EPI_PATCH_PIX_F32): its A operand is the [B,3,S,S] image,
+//     not an im2col copy. Tile row r is patch (img, py, px), K index k is (c, ky, kx), so a 64-wide K-tile of a row is 64 / P
+//     pixel-row segments of P floats. The A slot's 8-row pieces keep their owners and their swizzle; a lane fetches 16 bytes of the K-tile's
+//     first and of its second 32 floats (eight lanes: 128 contiguous bytes), converts with im2col_kernel's pack_bf16x2 and writes
+//     the two half chunks where the LDS-DMA would have put them. hipcc drains vmcnt(0) at the first use of an ordinary load's result while LDS-DMA is in
+//     flight, so these loads are inline asm it does not count, their destinations named by the counted wait in front of their
+//     first use. Two register sets: K-tile t + 2's pixels are requested in phase 0 of K-tile t and written to LDS in phase 1
+//     of K-tile t + 1 (a K-tile and a half of latency cover), read from K-tile t + 2 on. A wave has 6 loads + 4 LDS-DMA in
+//     flight per K-tile: the waits are vmcnt(10). Same K order in every accumulator and the same epilogue as the bf16 form.
 // Fragment layout and swizzle: gemm_bf16_p256.h.
 #pragma once
 #include "gemm_bf16_256.h"
+
+// internal: MMISS_EPI_PATCH_F32 with the A operand read from the f32 pixels (ep.pix_S, ep.pix_P, ep.pix_bytes); gemm160p_kernel only
+#define MMISS_EPI_PATCH_PIX_F32 10
 
 #define G160_A_BYTES 20480                  // 160 rows x 128 B
 #define G160_W_BYTES 16384                  // 128 rows x 128 B
@@ -70,7 +82,9 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     // that the residual GEMMs can point the two stagings past the last K-tile at their own old output rows (G160_NEXT_KTILE)
     // through the SAME instructions: there is one copy of the K-tile body. Where it WRITES never changes.
     constexpr bool RESID = (EPI == MMISS_EPI_BIAS_RESID_BF16);
-    static_assert(RESID || EPI == MMISS_EPI_PATCH_F32, "gemm160p_kernel: epilogue");
+    constexpr bool PIX = (EPI == MMISS_EPI_PATCH_PIX_F32);
+    constexpr bool PATCH = (EPI == MMISS_EPI_PATCH_F32) || PIX;
+    static_assert(RESID || PATCH, "gemm160p_kernel: epilogue");
     const int r_in = lane >> 3, p = lane & 7;
     int lane_vo = (r_in * K + ((p ^ r_in) * 8)) * 2;
     __amdgpu_buffer_rsrc_t srdA = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Ab), 0, 0x7fffffff, 0x00020000);
@@ -133,6 +147,68 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
             ko2 = 0; kstep = 2 * rblk;                                                                      \
         } else { k2 = 0; ko2 = 0; }                                                                         \
     } else { ko2 += kstep; }
+
+    // ---- PIX: the A slot from the f32 pixels. Piece j of this wave (rows 8 (wave + 8 j) + r_in; waves 4-7 have no third piece
+    // and fetch their second one again, unused, so that every wave issues six loads per K-tile) at per-lane byte offset pvo[j]
+    // = pixel (img, c = 0, py * P + dky, px * P + kx) of its row's patch, dky / kx = where chunk p lies in the K-tile's
+    // 64 / P pixel-row segments; K-tile kt adds the scalar offset of (c, ky0). Pad rows read the last valid row's patch.
+    u32x4 srdP = {0u, 0u, 0u, 0u};
+    int pvo[3] = {0, 0, 0};
+    u32x4 pa[2][6];
+    int pix_S = 0, pix_tshift = 0, pix_rows = 0, pix_half = 0;
+    if constexpr (PIX) {
+        const uint64_t a64 = (uint64_t)A;
+        srdP = u32x4{(uint32_t)a64, (uint32_t)(a64 >> 32) & 0xffffu, (uint32_t)ep.pix_bytes, 0x00020000u};
+        const int S = ep.pix_S, P = ep.pix_P, G = S / P, GG = ep.p0;
+        pix_S = S;
+        pix_tshift = P == 32 ? 4 : 2;   // K-tiles per channel = P * P / 64
+        pix_rows = 64 / P;              // pixel rows per K-tile
+        // a lane's two loads are floats 4 p .. 4 p + 3 of the K-tile's first and second 32: eight lanes read 128 contiguous
+        // bytes of one patch row (P = 32: one pixel-row segment; P = 16: two of 64 bytes)
+        const int dky = P == 32 ? 0 : (p >> 2), kx = P == 32 ? p * 4 : (p & 3) * 4;
+        pix_half = (P == 32 ? 1 : 2) * S * 4;   // bytes from the first 32 floats of a K-tile to the second
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int q = wave + 8 * ((j == 2 && wave >= 4) ? 1 : j);
+            int m = bm * 160 + q * 8 + r_in;
+            m = m < ep.m_valid ? m : ep.m_valid - 1;
+            const int img = m / GG, pr = m - img * GG, py = pr / G, px = pr - py * G;
+            pvo[j] = (((img * 3) * S + py * P + dky) * S + px * P + kx) * 4;
+        }
+    }
+// six loads of K-tile kt into register set `set` (not counted by the compiler: G160_PIX_WRITE's wait names them)
+#define G160_PIX_LOAD(set, kt)                                                                               \
+    {                                                                                                       \
+        const int c_ = (kt) >> pix_tshift;                                                                  \
+        const int so_ = (c_ * pix_S + ((kt) - (c_ << pix_tshift)) * pix_rows) * pix_S * 4;                  \
+        const int so2_ = so_ + pix_half;                                                                    \
+        _Pragma("unroll") for (int j = 0; j < 3; ++j)                                                       \
+            asm volatile("buffer_load_dwordx4 %0, %2, %3, %4 offen\n\tbuffer_load_dwordx4 %1, %2, %3, %5 offen" \
+                         : "=&v"(pa[set][2 * j]), "=&v"(pa[set][2 * j + 1])                                 \
+                         : "v"(pvo[j]), "s"(srdP), "s"(so_), "s"(so2_)                                      \
+                         : "memory");                                                                       \
+    }
+// register set `set` has landed once at most `cnt` younger operations are in flight: convert, write the A slot of buffer b2
+#define G160_PIX_WRITE(set, b2, cnt)                                                                         \
+    {                                                                                                       \
+        asm volatile("s_waitcnt vmcnt(" #cnt ")"                                                            \
+                     : "+v"(pa[set][0]), "+v"(pa[set][1]), "+v"(pa[set][2]), "+v"(pa[set][3]), "+v"(pa[set][4]), "+v"(pa[set][5]) \
+                     :: "memory");                                                                          \
+        /* floats 4 p .. of the first 32 are half (p & 1) of chunk p >> 1, of the second 32 of chunk 4 + (p >> 1) */ \
+        const int ao_ = (b2) * G160_BUF + a_dst + r_in * 128 + (((p >> 1) ^ r_in) << 4) + ((p & 1) << 3);   \
+        _Pragma("unroll") for (int j = 0; j < 3; ++j) {                                                     \
+            const u32x4 lo_ = pa[set][2 * j], hi_ = pa[set][2 * j + 1];                                     \
+            u32x2 pl_, ph_;                                                                                 \
+            pl_[0] = pack_bf16x2(__uint_as_float(lo_[0]), __uint_as_float(lo_[1]));                         \
+            pl_[1] = pack_bf16x2(__uint_as_float(lo_[2]), __uint_as_float(lo_[3]));                         \
+            ph_[0] = pack_bf16x2(__uint_as_float(hi_[0]), __uint_as_float(hi_[1]));                         \
+            ph_[1] = pack_bf16x2(__uint_as_float(hi_[2]), __uint_as_float(hi_[3]));                         \
+            if (j < 2 || wave < 4) {                                                                        \
+                *reinterpret_cast<u32x2*>(smem + ao_ + j * 8 * 1024) = pl_;                                 \
+                *reinterpret_cast<u32x2*>(smem + (ao_ ^ 64) + j * 8 * 1024) = ph_;                          \
+            }                                                                                               \
+        }                                                                                                   \
+    }
 
     // ---- fragment reads: one base per operand and k step + immediate (buffer, 16-row block)
     uint32_t ab[2], wb[2];
@@ -202,6 +278,30 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
         G160_NEXT_KTILE();                                                                                  \
     }
 
+// PIX, K-tile t (even / odd: SET = 0 / 1) out of buffer B: phase 0 requests K-tile t + 2's pixels into set SET, phase 1 converts
+// K-tile t + 1's (set SET ^ 1, requested a K-tile and a half ago; younger: K-tile t + 1's four W pieces and the six loads just
+// issued) into the A slot of buffer B1 = (B + 1) % 3 — last read during K-tile t - 2, first read after this phase's barriers
+// on either wave half — and stages K-tile t + 2's W slots by LDS-DMA as ever. The closing wait retires K-tile t + 1's W pieces
+// (younger: six loads and four pieces of K-tile t + 2) and every wave's LDS writes.
+#define G160_KTILE_PIX(B, B1, B2, SET)                                                                       \
+    {                                                                                                       \
+        G160_READ(B, 0);                                                                                    \
+        G160_PIX_LOAD(SET, k2);                                                                             \
+        G160_LATE_READS_DONE();                                                                             \
+        G160_BARRIER();                                                                                     \
+        G160_MMA();                                                                                         \
+        G160_BARRIER();                                                                                     \
+        G160_READ(B, 1);                                                                                    \
+        G160_PIX_WRITE((SET) ^ 1, B1, 10);                                                                  \
+        G160_STAGE_W(B2, 0, ko2);                                                                           \
+        G160_STAGE_W(B2, 1, ko2);                                                                           \
+        asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");                                        \
+        G160_BARRIER();                                                                                     \
+        G160_MMA();                                                                                         \
+        G160_BARRIER();                                                                                     \
+        G160_NEXT_KTILE();                                                                                  \
+    }
+
     // ---- this wave's bias values (1 KB per workgroup): requested NOW, in front of the prologue's LDS-DMA, so that the epilogue
     // of this one-tile workgroup starts without a memory round trip
     f32x4 bias[4];
@@ -212,6 +312,17 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
 
     // prologue: K-tiles 0 and 1 into buffers 0 and 1 (14 operations per wave)
     int ko2 = 0, k2 = 2;
+    if constexpr (PIX) {   // 20 operations: K-tile 0's pixels are converted here, K-tile 1's in phase 1 of K-tile 0
+        G160_PIX_LOAD(0, 0);
+        G160_STAGE_W(0, 0, 0);
+        G160_STAGE_W(0, 1, 0);
+        G160_PIX_LOAD(1, 1);
+        G160_STAGE_W(1, 0, GEMM_BK * 2);
+        G160_STAGE_W(1, 1, GEMM_BK * 2);
+        G160_PIX_WRITE(0, 0, 14);   // (younger than K-tile 0's loads: 4 + 6 + 4)
+        ko2 = 2 * GEMM_BK * 2;
+        asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");  // K-tile 0's W pieces (younger: K-tile 1's ten), the A writes
+    } else {
     G160_STAGE_A(0, 0);
     G160_STAGE_W(0, 0, 0);
     G160_STAGE_W(0, 1, 0);
@@ -220,6 +331,7 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     G160_STAGE_W(1, 1, GEMM_BK * 2);
     ko2 = (nt > 2) ? 2 * GEMM_BK * 2 : 0;   // (K >= 256: nt >= 4)
     asm volatile("s_waitcnt vmcnt(7)" ::: "memory");  // K-tile 0 has landed (younger: K-tile 1's seven)
+    }
     // ... and with it the four bias loads above, which are older: their round trip ran beside the prologue's. Pinned here
     // so that the compiler's own wait for them sits in front of the K loop, not inside it.
     if constexpr (RESID) {
@@ -229,11 +341,23 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     G160_BARRIER();
     if (wm == 1) G160_BARRIER();  // the lower half runs one barrier behind from here on
 
+    if constexpr (PIX) {
+#pragma unroll 1   // three buffers x two register sets: nt % 6 == 0 (12 K-tiles at P = 16, 48 at P = 32)
+        for (int t = 0; t < nt; t += 6) {
+            G160_KTILE_PIX(0, 1, 2, 0);
+            G160_KTILE_PIX(1, 2, 0, 1);
+            G160_KTILE_PIX(2, 0, 1, 0);
+            G160_KTILE_PIX(0, 1, 2, 1);
+            G160_KTILE_PIX(1, 2, 0, 0);
+            G160_KTILE_PIX(2, 0, 1, 1);
+        }
+    } else {
 #pragma unroll 1   // (nt may be a compile-time constant, KT: the loop stays a loop — one copy of the K-tile triple)
     for (int t = 0; t < nt; t += 3) {
         G160_KTILE(0, 2);
         if (t + 1 < nt) G160_KTILE(1, 0);
         if (t + 2 < nt) G160_KTILE(2, 1);
+    }
     }
     if (wm == 0) G160_BARRIER();   // (the upper half's last barrier: the lower half is still one behind)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last two stagings (old rows / wrap-around) have landed ...
@@ -242,7 +366,7 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     // patches lie over the third one, (nt - 1) % 3, the last one read; the patch-embedding GEMM keeps buffer 0
     const int free_buf = RESID ? ((nt + 2) % 3) * G160_BUF : 0;
 
-    if constexpr (EPI == MMISS_EPI_PATCH_F32) {
+    if constexpr (PATCH) {
         // f32 rows: 16 rows x 32 columns at a time through the wave's 2 KB patch (16-byte chunks XOR-swizzled by the row), read back
         // as whole 128-byte row segments; patch row m of the GEMM is token 1 + m % p0 of item m / p0, the position row is added
         int lane_e = lane;
@@ -361,6 +485,9 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
 #undef G160_BARRIER
 #undef G160_LATE_READS_DONE
 #undef G160_KTILE
+#undef G160_KTILE_PIX
+#undef G160_PIX_LOAD
+#undef G160_PIX_WRITE
 #undef G160_NEXT_KTILE
 #undef G160_X
 
@@ -409,6 +536,31 @@ static int launch_gemm160p_patch(hipStream_t st, const void* A, const void* W, c
     MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_PATCH_F32>), G160_LDS));
     hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_PATCH_F32>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, st,
                        reinterpret_cast<const __bf16*>(A), reinterpret_cast<const __bf16*>(W), M, N, K, ep);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+// The same GEMM with the A operand read straight from the f32 pixels [B,3,S,S] (no im2col pass): K = 3 P^2, P = 16 or 32,
+// ep.p0 = (S / P)^2 patches per item. The same bits as im2col + launch_gemm160p_patch. The class's bytes name the pixels.
+static inline bool gemm160p_pix_ok(const void* pixels, int B, int S, int P, int M, int N, int K) {
+    if (!(P == 16 || P == 32) || S <= 0 || (S % P) || K != 3 * P * P || !gemm160p_ok(M, N, K)) return false;
+    const int G = S / P;
+    if ((int64_t)B * G * G > M || ((uintptr_t)pixels & 15)) return false;
+    return (int64_t)B * 3 * S * S * 4 < (1LL << 31);   // 32-bit byte offsets into the image
+}
+static int launch_gemm160p_patch_pix(hipStream_t st, const void* pixels, const void* W, const GemmEpi& ep0, int B, int S, int P, int M,
+                                     int N, int K) {
+    if (!gemm160p_pix_ok(pixels, B, S, P, M, N, K)) MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm160p_patch_pix: B=%d S=%d P=%d M=%d N=%d K=%d", B, S, P, M, N, K);
+    GemmEpi ep = ep0;
+    const int G = S / P;
+    if (!ep.out || !ep.aux || ep.p0 != G * G || ep.p1 <= 0 || ep.ldo < N || ep.m_valid != B * G * G)
+        MM_FAIL(MMISS_ERR_ARG, "gemm160p_patch_pix: missing operand");
+    ep.pix_S = S; ep.pix_P = P; ep.pix_bytes = (int)((int64_t)B * 3 * S * S * 4);
+    const int mv = ep.m_valid;
+    MM_PROF("gemm_bf16_patch_p160", st, 2.0 * mv * N * K, 4.0 * (double)B * 3 * S * S + 2.0 * (double)N * K + 4.0 * (double)mv * N);
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm160p_kernel<MMISS_EPI_PATCH_PIX_F32>), G160_LDS));
+    hipLaunchKernelGGL((gemm160p_kernel<MMISS_EPI_PATCH_PIX_F32>), dim3((M / 160) * (N / 256)), dim3(512), G160_LDS, st,
+                       reinterpret_cast<const __bf16*>(pixels), reinterpret_cast<const __bf16*>(W), M, N, K, ep);
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }

@@ -71,9 +71,21 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const __bf16* __re
     f32x4 pre_bias = f32x4{0.f, 0.f, 0.f, 0.f}, pre_cv = f32x4{0.f, 0.f, 0.f, 0.f}, pre_res = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (HAS_BIAS) pre_bias = *reinterpret_cast<const f32x4*>(ep.bias + n_pre);
     if constexpr (FOLD) pre_cv = *reinterpret_cast<const f32x4*>(ep.aux + n_pre);
+    // the old residual values of row m, columns n .. n + 3: row m of the f32 output, or (ep.resid_rowmap) row
+    // ep.resid_rowmap[m] of another buffer: f32 rows, or bf16 rows widened
+    auto old_resid = [&](int m, int n) -> f32x4 {
+        if (ep.resid_rowmap) {
+            const size_t o = (size_t)ep.resid_rowmap[m] * ep.ldo + n;
+            if (!ep.resid16_rows) return *reinterpret_cast<const f32x4*>(ep.resid32_rows + o);
+            const u32x2 r = *reinterpret_cast<const u32x2*>(ep.resid16_rows + o);
+            return f32x4{__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xFFFF0000u), __uint_as_float(r[1] << 16),
+                         __uint_as_float(r[1] & 0xFFFF0000u)};
+        }
+        return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(ep.out) + (size_t)m * ep.ldo + n);
+    };
     if constexpr (EPI == MMISS_EPI_BIAS_RESID_F32) {
         const int m = m_base + wave * 16 + fr;
-        if (wave < MT && m < M) pre_res = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(ep.out) + (size_t)m * ep.ldo + n_pre);
+        if (wave < MT && m < M) pre_res = old_resid(m, n_pre);
     }
 
     // U k-steps per trip: every load of the trip (U weight fragments from HBM/MALL, U*MT activation fragments from L2)
@@ -121,8 +133,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const __bf16* __re
                 // a row, fixed xor order, one writer -> deterministic. [M][N/16][2]: the next folded skinny GEMM sums them.
                 float rs = 0.f, rq = 0.f;
                 if (m < M) {
-                    const f32x4 oldv = (t == wave) ? pre_res
-                                                   : *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(ep.out) + (size_t)m * ep.ldo + n);
+                    const f32x4 oldv = (t == wave) ? pre_res : old_resid(m, n);
                     const f32x4 nv = oldv + v + pre_bias;
                     rs = (nv[0] + nv[1]) + (nv[2] + nv[3]);
                     rq = (nv[0] * nv[0] + nv[1] * nv[1]) + (nv[2] * nv[2] + nv[3] * nv[3]);
@@ -172,7 +183,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const __bf16* __re
         } else if constexpr (EPI == MMISS_EPI_BIAS_RESID_F32) {
             v += pre_bias;
             float* p = reinterpret_cast<float*>(ep.out) + (size_t)m * ep.ldo + n;
-            v = ((t == wave) ? pre_res : *reinterpret_cast<const f32x4*>(p)) + v;
+            v = ((t == wave) ? pre_res : old_resid(m, n)) + v;
             *reinterpret_cast<f32x4*>(p) = v;
             if (ep.xb_out) {  // bf16 copy of the new residual rows: the A operand of the next folded GEMM
                 u32x2 pk;
