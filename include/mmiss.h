@@ -111,12 +111,17 @@ int mmiss_encoder_finalize(mmiss_encoder* enc);
  * the attention kernel's MXFP8 output; the attention arithmetic, LayerNorm statistics and the projection head keep their
  * precision, and the residual stream is the same as under MMISS_PREC_BF16: bf16 in calls of at least ~6000 token rows, f32
  * below. Measured 1 - cos vs the fp32 reference arithmetic: 5e-4 at full ViT-L/14 depth, 6e-4 on ViT-B/32 at batch 256
- * (seeded Gaussian weights; asserted at 1e-3). NOT covered by that bar: a checkpoint with residual OUTLIER channels. An e4m3
- * weight keeps three mantissa bits at any magnitude, so the weight column that meets a channel of magnitude 300 carries a
- * rounding error comparable to the signal of all ordinary channels: with +300 / -180 channels planted, ViT-L/14 (width 1024)
- * measures 6.7e-4 — inside — but ViT-B/32 (width 768) 1.15e-3 — OUTSIDE the tolerance (tests/test_headline_gpu.py prints
- * both; MMISS_PREC_BF16 holds 5e-5 on the same weights). MMISS_PREC_FP8 is therefore an OPT-IN, to be verified per checkpoint
- * against the default path (bench.py prints that gap); the default is MMISS_PREC_BF16. The TEXT tower stays on the bf16
+ * (seeded Gaussian weights; asserted at 1e-3). A checkpoint with residual OUTLIER channels needs mmiss_encoder_calibrate (below)
+ * to be covered by that bar. An e4m3 weight keeps three mantissa bits at any magnitude, so the weight column that meets a
+ * channel of magnitude 300 carries a rounding error comparable to the signal of all ordinary channels: with +300 / -180
+ * channels planted, an UNCALIBRATED handle measures 6.7e-4 on ViT-L/14 (width 1024) — inside — but 1.15e-3 on ViT-B/32
+ * (width 768) — OUTSIDE the tolerance (tests/test_headline_gpu.py prints both; MMISS_PREC_BF16 holds 5e-5 on the same weights);
+ * uncalibrated handles behave exactly as before. After mmiss_encoder_calibrate on a few dozen other images the constant part
+ * of every LayerNorm output goes round the fp8 operands and the same ViT-B/32 weights are held to 1e-3
+ * (tests/test_fp8_calibration_gpu.py asserts it and prints the figures; the CPU emulation tools/fp8_calib_sim.py gives
+ * 1.25e-3 -> 6.2e-4, outliers on the CLS row only 7.8e-4 -> 7.3e-4, no outliers 6.4e-4 -> 6.6e-4; profiles/fp8_calibration.txt).
+ * MMISS_PREC_FP8 stays an OPT-IN, to be verified per checkpoint against the default path (bench.py prints that gap); the
+ * default is MMISS_PREC_BF16. The TEXT tower stays on the bf16
  * kernels under this setting: its fp8 form measures 3.3-3.9e-3, outside the 1e-3 tolerance (three mantissa bits put ~5 %
  * noise on every GEMM output and the text stream is built almost entirely from GEMM outputs).
  * mmiss_encoder_set_tower_precision switches ONE tower (MMISS_TOWER_VISION / MMISS_TOWER_TEXT) to MMISS_PREC_BF16 or
@@ -128,6 +133,36 @@ enum { MMISS_PREC_BF16 = 0, MMISS_PREC_FP8 = 1, MMISS_PREC_BF16_F32RESID = 2 };
 enum { MMISS_TOWER_VISION = 0, MMISS_TOWER_TEXT = 1 };
 int mmiss_encoder_set_precision(mmiss_encoder* enc, int32_t precision);
 int mmiss_encoder_set_tower_precision(mmiss_encoder* enc, int32_t tower, int32_t precision);
+/*
+ * Calibrated activation centring for MMISS_PREC_FP8 on the VISION tower (the outlier-channel regime above). The constant part
+ * of a LayerNorm output does not have to pass through fp8:  LN(x) W^T + b = (LN(x) - mu) W^T + (b + W mu).
+ * mmiss_encoder_calibrate runs ONE pass of the vision tower over `pixels` (f32 [B,3,S,S], host or device, as for
+ * mmiss_encode_image; 1 <= B <= max_batch_image; after finalize) in the bf16 arithmetic whatever precision is set, on every
+ * token row of every layer, and reduces the OUTPUT of each of the 2 * v_layers LayerNorm sites (LN1 -> QKV, LN2 -> FC1) over
+ * all B * T rows to a per-channel mean and population variance (f64 sums in a fixed order). mu_c = mean_c where
+ * mean_c^2 >= var_c — the channel's constant part is at least as large as its varying part — and 0 elsewhere (centring a channel
+ * that is large on one token row only would hurt the other rows). From then on the fp8 QKV / FC1 of this handle run the same
+ * LayerNorm -> MXFP8 and GEMM kernels on beta' = beta - mu and b' = b + W_bf16 mu (f32, fixed order): the same launches, no
+ * kernel changed. Explicit, one-shot, deterministic: the same weights, pixels and B give the same bits. Use images that look
+ * like the ones to be encoded; 16-64 are enough (the statistics are over B * T rows).
+ * The stored calibration: cleared by mmiss_encoder_calibration_clear, by any mmiss_encoder_set_weight of a vision-tower tensor
+ * and by mmiss_encoder_finalize; no effect on the text tower, on the bf16 settings, or on calls below the fp8 row threshold
+ * (they run the bf16 kernels); NOT used under option fp8_ln_fold = 1 (gamma folded into the fp8 weights: that GEMM has no beta).
+ * Errors (MMISS_ERR_ARG, with a message): a call before finalize, B outside 1 .. max_batch_image, a null pointer, a table of
+ * the wrong length.
+ *   _info   out[0] = sites (2 * v_layers; 0 when uncalibrated), out[1] = v_hidden, out[2] = centred channels over all sites,
+ *           out[3] = rows seen (B * T; 0 for a table installed with _set)
+ *   _get    the mu table, f32 [2 * v_layers, v_hidden], site order layer 0 LN1, layer 0 LN2, layer 1 LN1, ...; *written = floats
+ *           copied (0 when uncalibrated); cap smaller than the table -> MMISS_ERR_ARG
+ *   _set    installs a table (n = 2 * v_layers * v_hidden) and derives beta' / b' from it with the same kernels: a server
+ *           calibrates once, stores the table and restores it at start — bit-identical embeddings.
+ * No reference analogue (the reference runs fp32 on the CPU, backend/app/utils.py:77).
+ */
+int mmiss_encoder_calibrate(mmiss_encoder* enc, const float* pixels, int32_t B);
+int mmiss_encoder_calibration_clear(mmiss_encoder* enc);
+int mmiss_encoder_calibration_info(mmiss_encoder* enc, int64_t out[4]);
+int mmiss_encoder_calibration_get(mmiss_encoder* enc, float* mu, int64_t cap, int64_t* written);
+int mmiss_encoder_calibration_set(mmiss_encoder* enc, const float* mu, int64_t n);
 /*
  * use_own != 0 (the default after create): calls run on the handle's private stream and return after the
  * work has finished (host-synchronous). use_own == 0: calls are enqueued on the caller's hipStream_t

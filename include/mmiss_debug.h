@@ -129,6 +129,15 @@ int mmiss_dbg_gemm8_time(int device, int epi, int bm, const void* A8, const void
 /* process-wide integer tuning knob (A/B experiments from tools/): e.g. "scan_group" = 8 | 16 */
 int mmiss_dbg_set_option(const char* key, int value);
 
+/* the calibration kernels in isolation (csrc/calibrate_kernels.h). ln_colstats: x f32 [M,d] (bf16 when x_is_bf16) -> column statistics
+ * of LayerNorm(x; gamma, beta) over the M rows: mean_out, var_out f64 [d] (population variance), mu_out f32 [d] (the mean where
+ * mean^2 >= var, else 0), centred_out int32 [1]; M >= 1, d <= 1024, d % 4 == 0; synchronises the stream (it frees its scratch).
+ * bias_fold: out f32 [N] = bias + W mu, W bf16 [N,K], mu f32 [K], f32 accumulation in a fixed order. */
+int mmiss_dbg_ln_colstats(int device, void* hip_stream, const void* x, int32_t x_is_bf16, const float* gamma, const float* beta,
+                          int32_t M, int32_t d, float eps, double* mean_out, double* var_out, float* mu_out, int32_t* centred_out);
+int mmiss_dbg_bias_fold(int device, void* hip_stream, const void* w_bf16, const float* bias, const float* mu, int32_t N, int32_t K,
+                        float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,11 @@ SIGNATURES = {
     "mmiss_encoder_finalize": (_I, [_P]),
     "mmiss_encoder_set_precision": (_I, [_P, _I32]),
     "mmiss_encoder_set_tower_precision": (_I, [_P, _I32, _I32]),
+    "mmiss_encoder_calibrate": (_I, [_P, _P, _I32]),
+    "mmiss_encoder_calibration_clear": (_I, [_P]),
+    "mmiss_encoder_calibration_info": (_I, [_P, C.POINTER(_I64)]),
+    "mmiss_encoder_calibration_get": (_I, [_P, _P, _I64, C.POINTER(_I64)]),
+    "mmiss_encoder_calibration_set": (_I, [_P, _P, _I64]),
     "mmiss_encoder_set_stream": (_I, [_P, _P, _I32]),
     "mmiss_encode_image": (_I, [_P, _P, _I32, _P]),
     "mmiss_encode_image_u8": (_I, [_P, _P, _I32, _P]),
@@ -123,6 +128,8 @@ SIGNATURES = {
     "mmiss_dbg_quant16_mxfp8_stats": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32]),
     "mmiss_dbg_quantize_weights_fp8_csum": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32]),
     "mmiss_dbg_gemm8_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
+    "mmiss_dbg_ln_colstats": (_I, [_I, _P, _P, _I32, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P]),
+    "mmiss_dbg_bias_fold": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _P]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
 

@@ -10,6 +10,7 @@
 #include "host_stager.h"
 #include "encoder_kernels.h"
 #include "preprocess_kernels.h"
+#include "calibrate_kernels.h"
 #include <map>
 #include <set>
 
@@ -56,6 +57,7 @@ struct LayerW {
     DevBuf wqkv8, sqkv, w1_8, s1, w2_8, s2;       // fp8 path: e4m3 weights + per-output-channel f32 scales
     DevBuf wo8, so;                               // ... of the out-projection (used when the attention output is MXFP8)
     DevBuf wqkv8f, sqkvf, cqkv16, w1_8f, s1f, c1_16;  // fp8 path with the LayerNorm folded in (hidden 1024): e4m3 of the gamma-folded weights, scales, f16 row sums
+    DevBuf ln1b_c, bqkv_c, ln2b_c, b1_c;          // calibrated fp8 path: beta' = beta - mu, b' = b + W mu of LN1 -> QKV and LN2 -> FC1 (calibrate_kernels.h)
 };
 
 struct Tower {
@@ -76,6 +78,11 @@ struct Tower {
     DevBuf h8, hs, u8, us;    // fp8 path: MXFP8 LayerNorm output / FC1 output (e4m3 bytes + permuted E8M0 block scales)
     DevBuf ctx8, ctxs;        // fp8 path: MXFP8 attention output (the out-projection's A operand)
     bool fp8_ready = false;   // fp8 weights built for this tower
+    // mmiss_encoder_calibrate (vision tower): mu f32 [2 * layers, hidden] (site 2l = LN1 of layer l, 2l + 1 = LN2), the centred
+    // channels per site, the f64 partials of the collection pass; `calibrated`: the beta' / b' of every layer are current
+    DevBuf cal_mu, cal_cnt, cal_part;
+    bool calibrated = false;
+    int64_t cal_rows = 0, cal_centred = 0;
     bool pooled_compact = false;
     int last_B = 0, last_T = 0;
     int64_t tap_stride = 0;  // floats per recorded tap
@@ -103,6 +110,7 @@ struct mmiss_encoder {
     std::mutex mu;
     bool finalized = false;
     bool record_taps = false;
+    bool collecting = false;   // inside mmiss_encoder_calibrate: the vision tower's plan is the collection pass
     // How LayerNorm1/2 reach the QKV / FC1 GEMMs:
     //   0 separate LayerNorm kernels (x f32 -> h bf16);
     //   (1, normalised while the f32 rows were staged as the A operand, was removed in round 4: every one of the 18-24
@@ -279,6 +287,7 @@ struct LayerPlan {
     bool resid16 = false;   // the residual stream is the bf16 rows xb (no f32 stream)
     bool sfold = false;     // one request: skinny GEMMs with the LayerNorm folded in (16-column statistics)
     bool prune = false;     // the last layer runs on the pooled rows only
+    bool collect = false;   // the calibration pass: bf16 arithmetic, unpruned, column statistics of every LayerNorm output
     EmbedOut embed = EmbedOut::Nothing;
     GemmPick qkv{}, out{}, fc1{}, fc2{};
 };
@@ -289,6 +298,8 @@ int plan_layers(const mmiss_encoder* e, const Tower& tw, int B, bool causal, Lay
     const int d = tw.hidden, M = B * tw.T;
     P = LayerPlan{};
     P.B = B; P.M = M; P.causal = causal;
+    P.collect = e->collecting && &tw == &e->vis;
+    const bool all_rows = e->record_taps || P.collect;   // every layer on every token row
     const int fold_min_rows = mmiss_option("ln_fold_min_rows", 6000);
     // LayerNorm placement: set_fuse_ln, else option ln_mode, else automatic: folded (2) from `ln_fold_min_rows` rows while the
     // hidden size allows it (ViT-L/14's 1024 folds since round 4: finished row statistics in front of the persistent GEMM;
@@ -300,7 +311,7 @@ int plan_layers(const mmiss_encoder* e, const Tower& tw, int B, bool causal, Lay
         const int max_hidden = mmiss_option("ln_fold_1024", 1) != 0 ? 1024 : 768;
         mode = forced >= 0 ? forced : ((M >= fold_min_rows && d <= max_hidden) ? 2 : 0);
     }
-    P.fp8 = e->fp8_tower[&tw == &e->txt ? 1 : 0] && tw.fp8_ready && tw.h8.p && M >= mmiss_option("fp8_min_rows", 1024);
+    P.fp8 = !P.collect && e->fp8_tower[&tw == &e->txt ? 1 : 0] && tw.fp8_ready && tw.h8.p && M >= mmiss_option("fp8_min_rows", 1024);
     if (P.fp8) mode = 0;  // the fp8 GEMMs take their A operand from the MXFP8 LayerNorm kernel
     const bool plain = mode == 0;
     P.fold = mode == 2;
@@ -385,7 +396,7 @@ int plan_layers(const mmiss_encoder* e, const Tower& tw, int B, bool causal, Lay
     // Only the pooled row of every item (token 0 / first EOS) leaves the last layer (HF:modeling_clip.py:650-651,
     // 561-581), and rows do not mix after the attention: out-proj, LN2 and the MLP of the LAST layer run on those B
     // rows only (compacted). Kept off while taps are recorded so the tests can compare every row of every layer.
-    P.prune = !e->record_taps;
+    P.prune = !all_rows;
     // bf16 residual stream for the large calls (needs the pruned last layer, i.e. no taps): the residual GEMMs
     // read-modify-write the bf16 rows; in the folded mode these rows are the A operand of the next GEMM as well, in the
     // separate-LayerNorm mode (hidden > 768: ViT-L/14) the LayerNorm kernel reads them. Default under MMISS_PREC_BF16 from
@@ -443,7 +454,7 @@ int plan_layers(const mmiss_encoder* e, const Tower& tw, int B, bool causal, Lay
     // the vision embedding stage's pre-LayerNorm: one request at a time (the layers run in the skinny folded mode) CLS rows,
     // pre_layrnorm and the mode's entry statistics are ONE launch behind the patch GEMM (option embed_fused = 0: off); when
     // the layers want the bf16 copy and the row statistics (folded LayerNorm, bf16 residual stream) the LayerNorm writes them
-    if (&tw == &e->vis && !e->record_taps) {
+    if (&tw == &e->vis && !all_rows) {
         if (P.sfold && d <= 1024 && (d % 16) == 0 && mmiss_option("embed_fused", 1) != 0)
             P.embed = EmbedOut::Stats16;
         else if (d % 128 == 0 && r16mode && mmiss_option("prelayernorm_stats", 1) != 0)
@@ -468,12 +479,18 @@ struct WideRole {
     const DevBuf *Wf, *bf, *c;        // the LayerNorm folded in: gamma-folded weights, bias b', row sums c (fold, sfold)
     const DevBuf *W8, *s8;            // fp8 weights, per-channel scales
     const DevBuf *W8f, *s8f, *c16;    // fp8 of the folded weights, scales, f16 row sums (fold8)
+    const DevBuf *beta_c, *b_c;       // the calibrated fp8 path's beta' and b'
+    int site;                         // 2 * layer (QKV) / 2 * layer + 1 (FC1): the row of the calibration table
     void *out, *out8;                 // bf16 [M, N]; on the fp8 path bf16 (QKV) or e4m3 + MXFP8 scales (FC1)
     uint8_t* out8_scale;
 };
 
 int run_wide(hipStream_t st, Tower& tw, const LayerPlan& P, GemmPick k, const WideRole& r, float eps) {
     const int d = tw.hidden, M = P.M, N = r.N;
+    if (P.collect)   // this site's LayerNorm output over all M rows -> mu, beta' (the f32 stream: the pass is unpruned)
+        MM_TRY(launch_ln_colstats(st, tw.x.p, false, r.g->as<float>(), r.beta->as<float>(), tw.cal_part.as<double>(), M, d, eps,
+                                  tw.cal_mu.as<float>() + (size_t)r.site * d, r.beta_c->as<float>(), tw.cal_cnt.as<int32_t>() + r.site,
+                                  nullptr, nullptr));
     if (is_fp8(k.kind)) {
         Gemm8Args g{};
         if (k.kind == GemmKind::P256Fp8Xt) {   // A = the raw rows as MXFP8 + statistics, the bf16 rows for a ragged block
@@ -481,10 +498,14 @@ int run_wide(hipStream_t st, Tower& tw, const LayerPlan& P, GemmPick k, const Wi
             g.ln_stats = tw.stats.as<float>(); g.x16 = tw.xb.as<uint16_t>(); g.ln_eps = eps;
             g.W = r.W8f->as<uint8_t>(); g.wscale = r.s8f->as<float>(); g.bias = r.bf->as<float>(); g.c16 = r.c16->as<uint16_t>();
         } else {
-            MM_TRY(launch_layernorm_mxfp8(st, P.resid16 ? tw.xb.p : tw.x.p, P.resid16, r.g->as<float>(), r.beta->as<float>(),
+            // calibrated: the same two kernels on beta' = beta - mu and b' = b + W mu (the constant part of the LayerNorm output
+            // goes round the fp8 operands; no launch more, none changed)
+            const DevBuf* beta = tw.calibrated ? r.beta_c : r.beta;
+            const DevBuf* bias = tw.calibrated ? r.b_c : r.b;
+            MM_TRY(launch_layernorm_mxfp8(st, P.resid16 ? tw.xb.p : tw.x.p, P.resid16, r.g->as<float>(), beta->as<float>(),
                                           tw.h8.as<uint8_t>(), tw.hs.as<uint8_t>(), M, d, eps));
             g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
-            g.W = r.W8->as<uint8_t>(); g.wscale = r.s8->as<float>(); g.bias = r.b->as<float>();
+            g.W = r.W8->as<uint8_t>(); g.wscale = r.s8->as<float>(); g.bias = bias->as<float>();
         }
         g.out = r.out8;
         if (r.out8_scale) { g.out_scale = r.out8_scale; g.ld_os = mx_scale_row_bytes(N); }
@@ -600,6 +621,7 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
         WideRole qkv{};
         qkv.N = 3 * d; qkv.g = &L.ln1g; qkv.beta = &L.ln1b; qkv.W = &L.wqkv; qkv.b = &L.bqkv; qkv.Wf = &L.wqkv_f; qkv.bf = &L.bqkv_f;
         qkv.c = &L.cqkv; qkv.W8 = &L.wqkv8; qkv.s8 = &L.sqkv; qkv.W8f = &L.wqkv8f; qkv.s8f = &L.sqkvf; qkv.c16 = &L.cqkv16; qkv.out = qkv.out8 = tw.qkv.p;
+        qkv.beta_c = &L.ln1b_c; qkv.b_c = &L.bqkv_c; qkv.site = 2 * l;
         MM_TRY(run_wide(st, tw, P, P.qkv, qkv, eps));
         const bool last_pruned = P.prune && l == tw.layers - 1;
         // The pruned last layer where the attention is the several-heads kernel and the out-projection the skinny one: the
@@ -652,6 +674,7 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
         fc1.N = tw.mlp; fc1.gelu = true; fc1.g = &L.ln2g; fc1.beta = &L.ln2b; fc1.W = &L.w1; fc1.b = &L.b1; fc1.Wf = &L.w1_f; fc1.bf = &L.b1_f;
         fc1.c = &L.c1; fc1.W8 = &L.w1_8; fc1.s8 = &L.s1; fc1.W8f = &L.w1_8f; fc1.s8f = &L.s1f; fc1.c16 = &L.c1_16;
         fc1.out = tw.u.p; fc1.out8 = tw.u8.p; fc1.out8_scale = tw.us.as<uint8_t>();
+        fc1.beta_c = &L.ln2b_c; fc1.b_c = &L.b1_c; fc1.site = 2 * l + 1;
         MM_TRY(run_wide(st, tw, P, P.fc1, fc1, eps));
         ResidRole fc2{};
         fc2.K = tw.mlp; fc2.A = tw.u.p; fc2.A8 = tw.u8.as<uint8_t>(); fc2.As = tw.us.as<uint8_t>();
@@ -1025,6 +1048,8 @@ extern "C" int mmiss_encoder_set_weight(mmiss_encoder* enc, const char* hf_key, 
     }
     MM_HIP(hipStreamSynchronize(st));
     enc->seen.insert(hf_key);
+    if (strncmp(hf_key, "vision_model.", 13) == 0 || strncmp(hf_key, "visual_projection.", 18) == 0)
+        enc->vis.calibrated = false;   // the calibration belongs to the weights it was measured on
     if (used) *used = 1;
     return MMISS_OK;
 }
@@ -1062,6 +1087,7 @@ extern "C" int mmiss_encoder_finalize(mmiss_encoder* enc) {
     MM_HIP(hipGetLastError());
     MM_HIP(hipStreamSynchronize(enc->own_stream));
     if (enc->fp8_tower[0] || enc->fp8_tower[1]) MM_TRY(build_fp8_weights(enc));
+    enc->vis.calibrated = false;
     enc->finalized = true;
     return MMISS_OK;
 }
@@ -1228,6 +1254,133 @@ extern "C" int mmiss_encode_image(mmiss_encoder* enc, const float* pixels, int32
 
 extern "C" int mmiss_encode_image_u8(mmiss_encoder* enc, const uint8_t* pixels_u8, int32_t B, float* out) {
     return encode_image_impl(enc, pixels_u8, true, B, out);
+}
+
+// ------------------------------------------------------------------------------------------------ fp8 calibration
+// (caller holds enc->mu, device current) buffers of the calibration: the table, the per-site counts, beta' / b' of every layer
+static int ensure_calibration_bufs(mmiss_encoder* enc) {
+    Tower& tw = enc->vis;
+    const int d = tw.hidden, sites = 2 * tw.layers;
+    MM_TRY(tw.cal_mu.ensure((size_t)sites * d * 4));
+    MM_TRY(tw.cal_cnt.ensure((size_t)sites * 4));
+    for (LayerW& L : tw.L) {
+        MM_TRY(L.ln1b_c.ensure((size_t)d * 4)); MM_TRY(L.bqkv_c.ensure((size_t)3 * d * 4));
+        MM_TRY(L.ln2b_c.ensure((size_t)d * 4)); MM_TRY(L.b1_c.ensure((size_t)tw.mlp * 4));
+    }
+    return MMISS_OK;
+}
+
+// (caller holds enc->mu) cal_mu and the beta' of every site are on the device: b' = b + W_bf16 mu per site, the counts to the host
+static int finish_calibration(mmiss_encoder* enc, hipStream_t st, int64_t rows) {
+    Tower& tw = enc->vis;
+    const int d = tw.hidden, sites = 2 * tw.layers;
+    for (int l = 0; l < tw.layers; ++l) {
+        LayerW& L = tw.L[l];
+        MM_TRY(launch_bias_fold(st, L.wqkv.p, L.bqkv.as<float>(), tw.cal_mu.as<float>() + (size_t)(2 * l) * d, L.bqkv_c.as<float>(), 3 * d, d));
+        MM_TRY(launch_bias_fold(st, L.w1.p, L.b1.as<float>(), tw.cal_mu.as<float>() + (size_t)(2 * l + 1) * d, L.b1_c.as<float>(), tw.mlp, d));
+    }
+    std::vector<int32_t> cnt((size_t)sites);
+    MM_HIP(hipMemcpyAsync(cnt.data(), tw.cal_cnt.p, (size_t)sites * 4, hipMemcpyDeviceToHost, st));
+    MM_HIP(hipStreamSynchronize(st));
+    tw.cal_centred = 0;
+    for (int32_t c : cnt) tw.cal_centred += c;
+    tw.cal_rows = rows;
+    tw.calibrated = true;
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_encoder_calibrate(mmiss_encoder* enc, const float* pixels, int32_t B) {
+    if (!enc) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibrate: enc is null");
+    std::lock_guard<std::mutex> lk(enc->mu);
+    if (!enc->finalized) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibrate: enc is not finalized (mmiss_encoder_finalize comes first)");
+    const int maxb = enc->cfg.max_batch_image, S = enc->cfg.v_image, P = enc->cfg.proj_dim;
+    if (B < 1 || B > maxb) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibrate: B = %d outside 1 .. max_batch_image = %d", B, maxb);
+    if (!pixels) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibrate: pixels is null");
+    MM_TRY(mmiss_use_device(enc->device));
+    hipStream_t st = enc->stream();
+    Tower& tw = enc->vis;
+    MM_TRY(ensure_tower_ws(enc, tw, maxb, P));
+    if (!enc->patches.p) {
+        const int64_t Mpp = round_up((int64_t)maxb * enc->G * enc->G, 128) + 192;
+        MM_TRY(alloc_zero(enc->patches, (size_t)Mpp * enc->Kp * 2));
+    }
+    MM_TRY(ensure_calibration_bufs(enc));
+    MM_TRY(tw.cal_part.ensure(cal_partial_bytes(B * tw.T, tw.hidden)));
+    const void* src = pixels;
+    if (!mmiss_is_device_ptr(pixels)) {
+        const size_t bytes = (size_t)B * 3 * S * S * 4;
+        MM_TRY(enc->pix_stage.ensure((size_t)maxb * 3 * S * S * 4));
+        MM_TRY(enc_h2d(enc, enc->pix_stage.p, pixels, bytes, st));
+        src = enc->pix_stage.p;
+    }
+    tw.calibrated = false;
+    enc->collecting = true;   // ONE pass in the bf16 arithmetic on every token row of every layer (plan_layers: collect)
+    const int rc = encode_image_chunk(enc, src, false, B, tw.out_stage.as<float>(), st);
+    enc->collecting = false;
+    if (rc != MMISS_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    return finish_calibration(enc, st, (int64_t)B * tw.T);
+}
+
+extern "C" int mmiss_encoder_calibration_clear(mmiss_encoder* enc) {
+    if (!enc) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_clear: enc is null");
+    std::lock_guard<std::mutex> lk(enc->mu);
+    enc->vis.calibrated = false;
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_encoder_calibration_info(mmiss_encoder* enc, int64_t out[4]) {
+    if (!enc || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_info: null argument");
+    std::lock_guard<std::mutex> lk(enc->mu);
+    const Tower& tw = enc->vis;
+    out[0] = tw.calibrated ? 2 * tw.layers : 0;
+    out[1] = tw.hidden;
+    out[2] = tw.calibrated ? tw.cal_centred : 0;
+    out[3] = tw.calibrated ? tw.cal_rows : 0;
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_encoder_calibration_get(mmiss_encoder* enc, float* mu, int64_t cap, int64_t* written) {
+    if (!enc || !mu || !written) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_get: null argument");
+    std::lock_guard<std::mutex> lk(enc->mu);
+    Tower& tw = enc->vis;
+    *written = 0;
+    if (!tw.calibrated) return MMISS_OK;
+    const int64_t n = (int64_t)2 * tw.layers * tw.hidden;
+    if (cap < n) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_get: cap = %lld, the table holds 2 * v_layers * v_hidden = %lld floats", (long long)cap, (long long)n);
+    MM_TRY(mmiss_use_device(enc->device));
+    hipStream_t st = enc->stream();
+    MM_HIP(hipMemcpyAsync(mu, tw.cal_mu.p, (size_t)n * 4, mmiss_is_device_ptr(mu) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    MM_HIP(hipStreamSynchronize(st));
+    *written = n;
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_encoder_calibration_set(mmiss_encoder* enc, const float* mu, int64_t n) {
+    if (!enc) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_set: enc is null");
+    if (!mu) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_set: mu is null");
+    std::lock_guard<std::mutex> lk(enc->mu);
+    if (!enc->finalized) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_set: enc is not finalized (mmiss_encoder_finalize comes first)");
+    Tower& tw = enc->vis;
+    const int d = tw.hidden;
+    const int64_t want = (int64_t)2 * tw.layers * d;
+    if (n != want) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_set: n = %lld, the table holds 2 * v_layers * v_hidden = %lld floats", (long long)n, (long long)want);
+    MM_TRY(mmiss_use_device(enc->device));
+    hipStream_t st = enc->stream();
+    MM_TRY(ensure_calibration_bufs(enc));
+    tw.calibrated = false;
+    MM_HIP(hipMemcpyAsync(tw.cal_mu.p, mu, (size_t)n * 4, mmiss_is_device_ptr(mu) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    for (int l = 0; l < tw.layers; ++l) {
+        LayerW& L = tw.L[l];
+        hipLaunchKernelGGL(beta_centre_kernel, dim3(1), dim3(256), 0, st, L.ln1b.as<float>(), tw.cal_mu.as<float>() + (size_t)(2 * l) * d,
+                           L.ln1b_c.as<float>(), tw.cal_cnt.as<int32_t>() + 2 * l, d);
+        hipLaunchKernelGGL(beta_centre_kernel, dim3(1), dim3(256), 0, st, L.ln2b.as<float>(), tw.cal_mu.as<float>() + (size_t)(2 * l + 1) * d,
+                           L.ln2b_c.as<float>(), tw.cal_cnt.as<int32_t>() + 2 * l + 1, d);
+    }
+    MM_HIP(hipGetLastError());
+    return finish_calibration(enc, st, 0);   // (rows seen: none, the table was measured elsewhere)
 }
 
 // raw RGB8 images of any size: resize (shortest edge, bicubic) + centre crop on the GPU, then the uint8 encode path
@@ -1588,6 +1741,29 @@ extern "C" int mmiss_dbg_gemm_split_time(int device, int epi, int bm, const void
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(fork); (void)hipEventDestroy(join);
     (void)hipStreamDestroy(s0); (void)hipStreamDestroy(s1);
     return MMISS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ calibration kernels in isolation
+// x f32 (or bf16 when x_is_bf16) [M,d] -> the column statistics of LayerNorm(x; gamma, beta): mean_out, var_out f64 [d] (population
+// variance), mu_out f32 [d] (the mean where mean^2 >= var, else 0), centred_out int32 [1]
+extern "C" int mmiss_dbg_ln_colstats(int device, void* hip_stream, const void* x, int32_t x_is_bf16, const float* gamma, const float* beta,
+                                     int32_t M, int32_t d, float eps, double* mean_out, double* var_out, float* mu_out, int32_t* centred_out) {
+    if (!x || !gamma || !beta || !mean_out || !var_out || !mu_out || !centred_out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_ln_colstats: null pointer");
+    if (M < 1) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_ln_colstats: M = %d", M);
+    MM_TRY(mmiss_use_device(device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    DevBuf part;   // (debug entry only: allocated and freed around the call)
+    MM_TRY(part.alloc(cal_partial_bytes(M, d)));
+    MM_TRY(launch_ln_colstats(st, x, x_is_bf16 != 0, gamma, beta, part.as<double>(), M, d, eps, mu_out, nullptr, centred_out, mean_out, var_out));
+    MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_dbg_bias_fold(int device, void* hip_stream, const void* w_bf16, const float* bias, const float* mu, int32_t N, int32_t K,
+                                   float* out) {
+    if (!w_bf16 || !bias || !mu || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_bias_fold: null pointer");
+    MM_TRY(mmiss_use_device(device));
+    return launch_bias_fold(reinterpret_cast<hipStream_t>(hip_stream), w_bf16, bias, mu, out, N, K);
 }
 
 // ------------------------------------------------------------------------------------------------ fp8 kernels in isolation

@@ -347,6 +347,52 @@ class ClipEncoder:
             _lib.check(self._lib.mmiss_encode_text(self._h, _lib.ptr(ids), B, T, _lib.ptr(out)))
         return out
 
+    # ------------------------------------------------------------------ fp8 calibration
+    def calibrate(self, pixels) -> dict:
+        """Measure the constant part of every LayerNorm output of the vision tower on `pixels` (float32 [B,3,S,S], numpy or a
+        torch tensor on this GPU, 1 <= B <= max_batch_image) and centre it out of the fp8 operands: from then on the "fp8"
+        setting holds the 1e-3 bar on checkpoints with residual outlier channels too (mmiss_encoder_calibrate). One pass in the
+        bf16 arithmetic; deterministic; the bf16 settings, small calls and the text tower are not affected. Returns
+        calibration_info()."""
+        s = self.shape
+        if tuple(pixels.shape[1:]) != (3, s.v_image, s.v_image):
+            raise ValueError(f"pixels must be [B,3,{s.v_image},{s.v_image}], got {tuple(pixels.shape)}")
+        if not _is_torch(pixels):
+            pixels = np.ascontiguousarray(pixels, dtype=np.float32)
+        else:
+            pixels = (pixels if str(pixels.dtype) == "torch.float32" else pixels.float()).contiguous()
+        with self._call_lock:  # stream hand-over + call are one unit per handle
+            self._sync_stream(pixels)
+            _lib.check(self._lib.mmiss_encoder_calibrate(self._h, _lib.ptr(pixels), int(pixels.shape[0])))
+        return self.calibration_info()
+
+    def clear_calibration(self) -> None:
+        _lib.check(self._lib.mmiss_encoder_calibration_clear(self._h))
+
+    def calibration_info(self) -> dict:
+        """sites (2 * v_layers, 0 when uncalibrated), hidden, centred (channels with mu != 0 over all sites), rows (seen)."""
+        out = (C.c_int64 * 4)()
+        _lib.check(self._lib.mmiss_encoder_calibration_info(self._h, out))
+        return {"sites": int(out[0]), "hidden": int(out[1]), "centred": int(out[2]), "rows": int(out[3])}
+
+    def get_calibration(self) -> np.ndarray:
+        """The mu table, float32 [2 * v_layers, v_hidden] (layer 0 LN1, layer 0 LN2, layer 1 LN1, ...); [0, v_hidden] when
+        uncalibrated. Store it and hand it to set_calibration at the next start."""
+        s = self.shape
+        mu = np.empty((2 * s.v_layers, s.v_hidden), dtype=np.float32)
+        w = C.c_int64(0)
+        with self._call_lock:
+            _lib.check(self._lib.mmiss_encoder_set_stream(self._h, None, 1))
+            _lib.check(self._lib.mmiss_encoder_calibration_get(self._h, mu.ctypes.data, mu.size, C.byref(w)))
+        return mu[: w.value // s.v_hidden]
+
+    def set_calibration(self, mu) -> None:
+        """Install a table from get_calibration(): the same embeddings, bit for bit, as the handle it was measured on."""
+        mu = np.ascontiguousarray(mu, dtype=np.float32)
+        with self._call_lock:
+            _lib.check(self._lib.mmiss_encoder_set_stream(self._h, None, 1))
+            _lib.check(self._lib.mmiss_encoder_calibration_set(self._h, mu.ctypes.data, mu.size))
+
     # ------------------------------------------------------------------ debug
     def record_taps(self, on: bool = True):
         _lib.check(self._lib.mmiss_dbg_encoder_record_taps(self._h, 1 if on else 0))
