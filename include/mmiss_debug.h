@@ -31,6 +31,34 @@ int mmiss_dbg_gemm(int device, void* hip_stream, int epi, int variant, const voi
 int mmiss_dbg_layernorm(int device, void* hip_stream, const float* x, const float* gamma, const float* beta,
                         void* out, int32_t out_bf16, int32_t M, int32_t d, float eps);
 
+/* The LayerNorm chain around the LayerNorm-folded GEMMs, one kernel per call with the encoder's own grid formulas. Shapes a
+ * kernel does not take, M < 1 among them, are refused with MMISS_ERR_UNSUPPORTED.
+ * layernorm16: the LayerNorm of a bf16 residual stream, x_bf16 [M,d] -> out_bf16 [M,d]; d % 8 == 0, d <= 1024. */
+int mmiss_dbg_layernorm16(int device, void* hip_stream, const void* x_bf16, const float* gamma, const float* beta, void* out_bf16,
+                          int32_t M, int32_t d, float eps);
+/* mmiss_dbg_layernorm with gathered input rows: out row r = LayerNorm(x row rowmap[r]) (rowmap int32 [M]: the pooling of the head) */
+int mmiss_dbg_layernorm_gather(int device, void* hip_stream, const float* x, const float* gamma, const float* beta, void* out,
+                               int32_t out_bf16, const int32_t* rowmap, int32_t M, int32_t d, float eps);
+/* pre-LayerNorm of the large calls: x f32 [M,d] normalised IN PLACE, xb bf16 [M,d] = its bf16 copy, stats f32 [M][parts][2] = (sum,
+ * sumsq) of the new row in slot 0, zeros in the others. lean != 0: x is only read, and row t = 0 of every T rows is taken as
+ * cls + pos[0] (cls, pos f32 [d]) instead of x. d % 4 == 0, d <= 1024, parts >= 1. */
+int mmiss_dbg_prelayernorm_stats(int device, void* hip_stream, float* x, const float* gamma, const float* beta, void* xb, float* stats,
+                                 int32_t M, int32_t d, int32_t parts, float eps, int32_t lean, const float* cls, const float* pos,
+                                 int32_t T);
+/* pre-LayerNorm of one request: rows t = 0 of every T rows = cls + pos[0], LayerNorm in place on x f32 [M,d], xb bf16 [M,d],
+ * stats16 f32 [M][d/16][2] = (sum, sumsq) per 16 columns of the new rows. d % 16 == 0, d <= 1024. */
+int mmiss_dbg_prelayernorm_skinny(int device, void* hip_stream, float* x, const float* cls, const float* pos, const float* gamma,
+                                  const float* beta, void* xb, float* stats16, int32_t M, int32_t T, int32_t d, float eps);
+/* stats f32 [M][parts][2]: slot 0 = (sum, sumsq) of row r of x f32 [M,d], the others zero; xb_or_null: the rows' bf16 copy. d % 4 == 0 */
+int mmiss_dbg_row_stats(int device, void* hip_stream, const float* x, float* stats, void* xb_or_null, int32_t M, int32_t d,
+                        int32_t parts);
+/* out f32 [M][2] = (mean, rstd) of every row from its `parts` partial (sum, sumsq) (stats f32 [M][parts][2], 16-byte aligned) of
+ * d columns in all: var = max(sumsq / d - mean^2, 0), rstd = 1 / sqrt(var + eps). parts even, >= 2. */
+int mmiss_dbg_ln_finalize(int device, void* hip_stream, const float* stats, float* out, int32_t M, int32_t parts, int32_t d, float eps);
+/* LayerNorm folding: wf bf16 [N,K] = bf16(f32(w) gamma[k]), c f32 [N] = sum_k wf[n,k], bf f32 [N] = bias[n] + sum_k beta[k] w[n,k] */
+int mmiss_dbg_fold_ln_weights(int device, void* hip_stream, const void* w_bf16, const float* gamma, const float* beta,
+                              const float* bias, void* wf, float* c, float* bf, int32_t N, int32_t K);
+
 /* qkv bf16 [B*T, 3*H*64] -> ctx bf16 [B*T, H*64]; softmax(QK^T/8 (+causal)) V per (b, head) */
 int mmiss_dbg_attention(int device, void* hip_stream, const void* qkv, void* ctx, int32_t B, int32_t T,
                         int32_t H, int32_t causal);

@@ -111,6 +111,13 @@ SIGNATURES = {
     "mmiss_dbg_gemm_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32,
                                  C.POINTER(C.c_float)]),
     "mmiss_dbg_layernorm": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float]),
+    "mmiss_dbg_layernorm16": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32, C.c_float]),
+    "mmiss_dbg_layernorm_gather": (_I, [_I, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, C.c_float]),
+    "mmiss_dbg_prelayernorm_stats": (_I, [_I, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _I32]),
+    "mmiss_dbg_prelayernorm_skinny": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float]),
+    "mmiss_dbg_row_stats": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _I32]),
+    "mmiss_dbg_ln_finalize": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, C.c_float]),
+    "mmiss_dbg_fold_ln_weights": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32]),
     "mmiss_dbg_attention": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _I32]),
     "mmiss_dbg_im2col": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _I32]),
     "mmiss_dbg_patch_from_pixels": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32]),

@@ -1666,6 +1666,92 @@ extern "C" int mmiss_dbg_attention_pooled(int device, void* hip_stream, const vo
     return launch_attention_pooled(reinterpret_cast<hipStream_t>(hip_stream), qkv, ctxc, pool_row, B, T, H, causal != 0);
 }
 
+// The LayerNorm chain around the folded GEMMs, kernel by kernel: the launches of embed_image / run_layers /
+// mmiss_encoder_finalize with the same grid formulas, on caller-owned buffers.
+extern "C" int mmiss_dbg_layernorm16(int device, void* hip_stream, const void* x_bf16, const float* gamma, const float* beta,
+                                     void* out_bf16, int32_t M, int32_t d, float eps) {
+    if (!x_bf16 || !gamma || !beta || !out_bf16) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_layernorm16: null pointer");
+    if (M <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "layernorm16: M=%d", M);
+    MM_TRY(mmiss_use_device(device));
+    return launch_layernorm16(reinterpret_cast<hipStream_t>(hip_stream), reinterpret_cast<const uint16_t*>(x_bf16), gamma, beta,
+                              out_bf16, M, d, eps);
+}
+
+extern "C" int mmiss_dbg_layernorm_gather(int device, void* hip_stream, const float* x, const float* gamma, const float* beta,
+                                          void* out, int32_t out_bf16, const int32_t* rowmap, int32_t M, int32_t d, float eps) {
+    if (!x || !gamma || !beta || !out || !rowmap) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_layernorm_gather: null pointer");
+    if (M <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "layernorm_gather: M=%d", M);
+    MM_TRY(mmiss_use_device(device));
+    return launch_layernorm(reinterpret_cast<hipStream_t>(hip_stream), x, gamma, beta, out, out_bf16 != 0, rowmap, M, d, eps);
+}
+
+extern "C" int mmiss_dbg_prelayernorm_stats(int device, void* hip_stream, float* x, const float* gamma, const float* beta, void* xb,
+                                            float* stats, int32_t M, int32_t d, int32_t parts, float eps, int32_t lean,
+                                            const float* cls, const float* pos, int32_t T) {
+    if (!x || !gamma || !beta || !xb || !stats || (lean && (!cls || !pos)))
+        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_prelayernorm_stats: null pointer");
+    if (M <= 0 || d <= 0 || d % 4 || d > 1024 || parts < 1 || (lean && T < 1))
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "prelayernorm_stats: M=%d d=%d (d%%4==0, d<=1024) parts=%d T=%d", M, d, parts, T);
+    MM_TRY(mmiss_use_device(device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    if (lean)
+        hipLaunchKernelGGL(layernorm_stats_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, x, gamma, beta,
+                           reinterpret_cast<uint16_t*>(xb), stats, M, d, parts, eps, cls, pos, T);
+    else
+        hipLaunchKernelGGL(layernorm_stats_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, x, gamma, beta,
+                           reinterpret_cast<uint16_t*>(xb), stats, M, d, parts, eps, (const float*)nullptr, (const float*)nullptr, 1);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_dbg_prelayernorm_skinny(int device, void* hip_stream, float* x, const float* cls, const float* pos,
+                                             const float* gamma, const float* beta, void* xb, float* stats16, int32_t M, int32_t T,
+                                             int32_t d, float eps) {
+    if (!x || !cls || !pos || !gamma || !beta || !xb || !stats16) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_prelayernorm_skinny: null pointer");
+    if (M <= 0 || T < 1 || d <= 0 || d % 16 || d > 1024)
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "prelayernorm_skinny: M=%d T=%d d=%d (d%%16==0, d<=1024)", M, T, d);
+    MM_TRY(mmiss_use_device(device));
+    hipLaunchKernelGGL(prelayernorm_skinny_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), x, cls,
+                       pos, gamma, beta, reinterpret_cast<uint16_t*>(xb), stats16, M, T, d, eps);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_dbg_row_stats(int device, void* hip_stream, const float* x, float* stats, void* xb_or_null, int32_t M, int32_t d,
+                                   int32_t parts) {
+    if (!x || !stats) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_row_stats: null pointer");
+    if (M <= 0 || d <= 0 || d % 4 || parts < 1) MM_FAIL(MMISS_ERR_UNSUPPORTED, "row_stats: M=%d d=%d (d%%4==0) parts=%d", M, d, parts);
+    MM_TRY(mmiss_use_device(device));
+    hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), x, stats,
+                       reinterpret_cast<uint16_t*>(xb_or_null), M, d, parts);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_dbg_ln_finalize(int device, void* hip_stream, const float* stats, float* out, int32_t M, int32_t parts, int32_t d,
+                                     float eps) {
+    if (!stats || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_ln_finalize: null pointer");
+    // (the kernel reads the partials of a row as 16-byte pairs of (sum, sumsq): an even count, rows 16-byte aligned)
+    if (M <= 0 || d <= 0 || parts < 2 || parts % 2 || (reinterpret_cast<uintptr_t>(stats) & 15))
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "ln_finalize: M=%d d=%d parts=%d (even, >= 2; stats 16-byte aligned)", M, d, parts);
+    MM_TRY(mmiss_use_device(device));
+    hipLaunchKernelGGL(ln_finalize_kernel, dim3((M * 8 + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), stats, out,
+                       M, parts, d, eps);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_dbg_fold_ln_weights(int device, void* hip_stream, const void* w_bf16, const float* gamma, const float* beta,
+                                         const float* bias, void* wf, float* c, float* bf, int32_t N, int32_t K) {
+    if (!w_bf16 || !gamma || !beta || !bias || !wf || !c || !bf) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_fold_ln_weights: null pointer");
+    if (N <= 0 || K <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "fold_ln_weights: N=%d K=%d", N, K);
+    MM_TRY(mmiss_use_device(device));
+    hipLaunchKernelGGL(fold_ln_weights_kernel, dim3((N + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream),
+                       reinterpret_cast<const uint16_t*>(w_bf16), gamma, beta, bias, reinterpret_cast<uint16_t*>(wf), c, bf, N, K);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
 extern "C" int mmiss_dbg_gemm_resid_rows(int device, void* hip_stream, const void* A, const void* W, float* out, const float* bias,
                                          const void* rows_bf16, const int32_t* rowmap, int32_t M, int32_t N, int32_t K) {
     if (!A || !W || !out || !bias || !rows_bf16 || !rowmap) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_resid_rows: null pointer");

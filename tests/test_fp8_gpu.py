@@ -128,7 +128,8 @@ def test_layernorm_mxfp8_from_bf16_rows(env, d):
 def test_attention_with_mxfp8_output(env, B, T, H):
     """The fp8 vision tower's attention writes its output as MXFP8 (the out-projection's A operand on the fp8 GEMM): the
     dequantised bytes must equal the bf16-output kernel's rows up to the e4m3 rounding of a block — 2^-4 of the block's
-    largest magnitude — and the bf16 kernel itself is held against torch in tests/test_kernels_gpu.py."""
+    largest magnitude — and the bf16 kernels themselves are held against torch: attention_kernel and the long kernels in
+    tests/test_kernels_gpu.py, attention_heads_kernel (the (256, 50, 12) case here) in tests/test_attention_heads_gpu.py."""
     torch, _lib, lib, fo = env
     g = torch.Generator(device="cuda").manual_seed(B * 1000 + T)
     qkv = torch.randn(B * T, 3 * H * 64, device="cuda", generator=g).to(torch.bfloat16)
