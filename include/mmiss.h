@@ -71,8 +71,12 @@ int mmiss_device_count(int* count);
  * Shape-parametric CLIP (two towers + projections). Defaults of HF CLIPConfig() are ViT-B/32
  * (HF:configuration_clip.py:47-54,97-105,160). The reference HEAD loads a ViT-L/14 LongCLIP with
  * text_ctx = 248 (backend/app/utils.py:16-17,41-45); both are instances of this struct.
- * head_dim = hidden / heads must be 64; hidden and mlp must be multiples of 128.
+ * head_dim = hidden / heads must be 64; hidden (<= 1024) and mlp must be multiples of 128. A tower has at most
+ * MMISS_MAX_TOKENS tokens: (v_image / v_patch)^2 + 1 and t_ctx — a 32 x 32 patch grid plus the class token, e.g. ViT-L/14 at
+ * 448 px; ViT-L/14 at 336 px has 577. Up to 288 tokens the attention holds a head's keys in LDS, above it walks them in chunks.
  */
+#define MMISS_MAX_TOKENS 1025
+
 typedef struct mmiss_clip_config {
     int32_t struct_size;   /* = sizeof(mmiss_clip_config), ABI guard */
     int32_t v_hidden, v_layers, v_heads, v_mlp, v_patch, v_image; /* 768,12,12,3072,32,224 */

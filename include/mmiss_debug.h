@@ -59,9 +59,14 @@ int mmiss_dbg_ln_finalize(int device, void* hip_stream, const float* stats, floa
 int mmiss_dbg_fold_ln_weights(int device, void* hip_stream, const void* w_bf16, const float* gamma, const float* beta,
                               const float* bias, void* wf, float* c, float* bf, int32_t N, int32_t K);
 
-/* qkv bf16 [B*T, 3*H*64] -> ctx bf16 [B*T, H*64]; softmax(QK^T/8 (+causal)) V per (b, head) */
+/* qkv bf16 [B*T, 3*H*64] -> ctx bf16 [B*T, H*64]; softmax(QK^T/8 (+causal)) V per (b, head); 1 <= T <= MMISS_MAX_TOKENS (1025) */
 int mmiss_dbg_attention(int device, void* hip_stream, const void* qkv, void* ctx, int32_t B, int32_t T,
                         int32_t H, int32_t causal);
+/* the key-chunked kernel (csrc/attention_tiled.h), which mmiss_dbg_attention / mmiss_dbg_attention_mx run above 288 tokens, at
+ * any 1 <= T <= MMISS_MAX_TOKENS. ctx8 == NULL: bf16 rows into ctx [B*T, H*64]. Otherwise MXFP8 into ctx8 / ctx_scale as
+ * mmiss_dbg_attention_mx writes them (ctx unused; causal must be 0). At T <= 288 the bits are the long-sequence kernel's. */
+int mmiss_dbg_attention_tiled(int device, void* hip_stream, const void* qkv, void* ctx, void* ctx8, void* ctx_scale, int32_t B,
+                              int32_t T, int32_t H, int32_t causal);
 
 /* the pooled-query form of the short-sequence attention (the pruned last layer): ctxc bf16 [B, H*64] row b = the attention
  * output of query row pool_row[b] - b*T of item b (pool_row int32 [B]: global token rows). Only where mmiss_dbg_attention runs the
@@ -127,8 +132,8 @@ int mmiss_dbg_layernorm_mxfp8(int device, void* hip_stream, const float* x, cons
 int mmiss_dbg_layernorm16_mxfp8(int device, void* hip_stream, const void* x_bf16, const float* gamma, const float* beta,
                                 void* out8, void* out_scale, int32_t M, int32_t d, float eps);
 /* attention whose output leaves the kernel as MXFP8 (the fp8 out-projection's A operand): qkv bf16 [B*T, 3*H*64] -> ctx8 e4m3
- * [B*T, H*64] + ctx_scale (permuted E8M0, 16 * ceil(H*64 / 512) bytes per row); non-causal, 1 <= T <= 288 (round 6: the one-pass
- * kernels for T <= 128 too) */
+ * [B*T, H*64] + ctx_scale (permuted E8M0, 16 * ceil(H*64 / 512) bytes per row); non-causal, 1 <= T <= MMISS_MAX_TOKENS
+ * (1025; round 6: the one-pass kernels for T <= 128 too; above 288: the key-chunked kernel) */
 int mmiss_dbg_attention_mx(int device, void* hip_stream, const void* qkv, void* ctx8, void* ctx_scale, int32_t B, int32_t T,
                            int32_t H);
 /* epi: 0 out bf16 = acc * wscale[n] + bias[n]; 1 out e4m3 + out_scale = mx(quick_gelu(.)); 2 out f32 += . ; bm = 128 | 160 | 192 */

@@ -119,6 +119,7 @@ SIGNATURES = {
     "mmiss_dbg_ln_finalize": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, C.c_float]),
     "mmiss_dbg_fold_ln_weights": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32]),
     "mmiss_dbg_attention": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _I32]),
+    "mmiss_dbg_attention_tiled": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32]),
     "mmiss_dbg_im2col": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _I32]),
     "mmiss_dbg_patch_from_pixels": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32]),
     "mmiss_dbg_attention_pooled": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _I32, _I32]),

@@ -925,8 +925,9 @@ extern "C" int mmiss_encoder_create(const mmiss_clip_config* cfg, int device, mm
         MM_FAIL(MMISS_ERR_ARG, "image size %d not a multiple of patch %d", cfg->v_image, cfg->v_patch);
     if (cfg->proj_dim <= 0 || cfg->proj_dim % 128) MM_FAIL(MMISS_ERR_UNSUPPORTED, "proj_dim %d must be a multiple of 128", cfg->proj_dim);
     const int G = cfg->v_image / cfg->v_patch;
-    if (G * G + 1 > 288 || cfg->t_ctx > 288 || cfg->t_ctx <= 0)
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "sequence length > 288 tokens is not supported by the attention kernel");
+    if (G * G + 1 > MMISS_MAX_TOKENS || cfg->t_ctx > MMISS_MAX_TOKENS || cfg->t_ctx <= 0)
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "sequence length %d (vision) / %d (text): the attention kernels take 1..%d tokens", G * G + 1,
+                cfg->t_ctx, MMISS_MAX_TOKENS);
     if (cfg->t_vocab <= 0) MM_FAIL(MMISS_ERR_ARG, "bad vocab size");
     MM_TRY(mmiss_use_device(device));
 
@@ -1666,6 +1667,24 @@ extern "C" int mmiss_dbg_attention_pooled(int device, void* hip_stream, const vo
     return launch_attention_pooled(reinterpret_cast<hipStream_t>(hip_stream), qkv, ctxc, pool_row, B, T, H, causal != 0);
 }
 
+// attention_tiled_kernel at any 1 <= T <= MMISS_MAX_TOKENS (the product routes T <= 288 to the other kernels): bf16 rows into ctx,
+// or with ctx8 != NULL MXFP8 into ctx8 / ctx_scale (non-causal)
+extern "C" int mmiss_dbg_attention_tiled(int device, void* hip_stream, const void* qkv, void* ctx, void* ctx8, void* ctx_scale,
+                                         int32_t B, int32_t T, int32_t H, int32_t causal) {
+    if (!qkv || (!ctx8 && !ctx) || (ctx8 && !ctx_scale)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_attention_tiled: null pointer");
+    if (T <= 0 || T > MMISS_MAX_TOKENS || H <= 0 || B < 0 || (ctx8 && causal))
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "mmiss_dbg_attention_tiled: B=%d T=%d (1..%d) H=%d causal=%d%s", B, T, MMISS_MAX_TOKENS, H, causal,
+                ctx8 ? " (MXFP8 output is non-causal)" : "");
+    MM_TRY(mmiss_use_device(device));
+    if (B == 0) return MMISS_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    if (ctx8)
+        return launch_attention_tiled<false, true>(st, qkv, nullptr, reinterpret_cast<uint8_t*>(ctx8), reinterpret_cast<uint8_t*>(ctx_scale),
+                                                   mx_scale_row_bytes(H * 64), B, T, H);
+    return causal ? launch_attention_tiled<true, false>(st, qkv, ctx, nullptr, nullptr, 0, B, T, H)
+                  : launch_attention_tiled<false, false>(st, qkv, ctx, nullptr, nullptr, 0, B, T, H);
+}
+
 // The LayerNorm chain around the folded GEMMs, kernel by kernel: the launches of embed_image / run_layers /
 // mmiss_encoder_finalize with the same grid formulas, on caller-owned buffers.
 extern "C" int mmiss_dbg_layernorm16(int device, void* hip_stream, const void* x_bf16, const float* gamma, const float* beta,
@@ -1874,7 +1893,7 @@ extern "C" int mmiss_dbg_layernorm16_mxfp8(int device, void* hip_stream, const v
 }
 
 // qkv bf16 [B*T, 3*H*64] -> the attention output as MXFP8: ctx8 e4m3 [B*T, H*64] + permuted E8M0 scales [B*T, 16 * ceil(H*64 / 512)]
-// (non-causal; T <= 128: the one-pass kernels, 129 <= T <= 288: the long-sequence form)
+// (non-causal; T <= 128: the one-pass kernels, 129 <= T <= 288: the long-sequence form, above up to MMISS_MAX_TOKENS: key chunks)
 extern "C" int mmiss_dbg_attention_mx(int device, void* hip_stream, const void* qkv, void* ctx8, void* ctx_scale, int32_t B,
                                       int32_t T, int32_t H) {
     if (!qkv || !ctx8 || !ctx_scale) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_attention_mx: null pointer");

@@ -966,6 +966,9 @@ __global__ __launch_bounds__(256) void attention_heads_kernel(const uint16_t* __
     }
 }
 
+// K4 above 288 tokens (up to MMISS_MAX_TOKENS): the keys in chunks through two LDS images, attention_tiled_kernel
+#include "attention_tiled.h"
+
 // ------------------------------------------------------------------------------------------------
 // K8 tail / a7: out[r] = y[r] / ||y[r]||_2, fp32, no epsilon (backend/app/utils.py:78,98).
 // One wave per row.
@@ -1069,15 +1072,17 @@ static int launch_attention_long(hipStream_t st, const void* qkv, void* ctx, uin
     }
 }
 
-// attention writing MXFP8: non-causal only (the vision tower), 1..288 keys (round 6: the one-pass kernels too — ViT-B/32's 50 keys)
-static bool attention_mx_ok(int T, int H) { return T > 0 && T <= 288 && H > 0; }
+// attention writing MXFP8: non-causal only (the vision tower), 1..MMISS_MAX_TOKENS keys (round 6: the one-pass kernels too —
+// ViT-B/32's 50 keys; above 288 keys: attention_tiled_kernel)
+static bool attention_mx_ok(int T, int H) { return T > 0 && T <= MMISS_MAX_TOKENS && H > 0; }
 static int launch_attention_mx_short(hipStream_t st, const void* qkv, uint8_t* ctx8, uint8_t* ctxs, int ld_s, int B, int T, int H);
 static int launch_attention_mx(hipStream_t st, const void* qkv, uint8_t* ctx8, uint8_t* ctxs, int ld_s, int B, int T, int H) {
     if (B <= 0) return MMISS_OK;
     if (!attention_mx_ok(T, H) || !ctx8 || !ctxs || ld_s < mx_scale_row_bytes(H * 64))
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "attention (MXFP8 output): T=%d (1..288), H=%d", T, H);
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "attention (MXFP8 output): T=%d (1..%d), H=%d", T, MMISS_MAX_TOKENS, H);
     MM_PROF("attention_mx", st, 4.0 * B * H * (double)T * T * 64, (double)B * T * H * 64 * (2 * 3 + 1));
     if (T <= 128) return launch_attention_mx_short(st, qkv, ctx8, ctxs, ld_s, B, T, H);
+    if (T > 288) return launch_attention_tiled<false, true>(st, qkv, nullptr, ctx8, ctxs, ld_s, B, T, H);
     return launch_attention_long<false, true>(st, qkv, nullptr, ctx8, ctxs, ld_s, B, T, H);
 }
 
@@ -1231,7 +1236,8 @@ static int launch_attention_pooled(hipStream_t st, const void* qkv, void* ctxc, 
 
 static int launch_attention(hipStream_t st, const void* qkv, void* ctx, int B, int T, int H, bool causal) {
     if (B <= 0) return MMISS_OK;
-    if (T <= 0 || T > 288 || H <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "attention: T=%d (1..288), H=%d", T, H);
+    if (T <= 0 || T > MMISS_MAX_TOKENS || H <= 0)
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "attention: T=%d (1..%d), H=%d", T, MMISS_MAX_TOKENS, H);
     const int nkp = (T + 31) / 32;
     // algorithmic flops: QK^T and PV, unpadded, full (non-causal) count as SURVEY.md §8(d) does
     MM_PROF("attention", st, 4.0 * B * H * (double)T * T * 64, (double)B * T * H * 64 * 2 * 4);
@@ -1253,6 +1259,9 @@ static int launch_attention(hipStream_t st, const void* qkv, void* ctx, int B, i
         case 3: return launch_attention_nkp<3>(st, qkv, ctx, B, T, H, causal);
         case 4: return launch_attention_nkp<4>(st, qkv, ctx, B, T, H, causal);
     }
+    if (T > 288)   // the K/V image of a head no longer fits in LDS: key chunks (attention_tiled.h)
+        return causal ? launch_attention_tiled<true, false>(st, qkv, ctx, nullptr, nullptr, 0, B, T, H)
+                      : launch_attention_tiled<false, false>(st, qkv, ctx, nullptr, nullptr, 0, B, T, H);
     return causal ? launch_attention_long<true, false>(st, qkv, ctx, nullptr, nullptr, 0, B, T, H)
                   : launch_attention_long<false, false>(st, qkv, ctx, nullptr, nullptr, 0, B, T, H);
 }

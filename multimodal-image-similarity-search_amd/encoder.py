@@ -82,6 +82,10 @@ class ClipShape:
 VIT_B32 = ClipShape()
 LONGCLIP_L14 = ClipShape(v_hidden=1024, v_layers=24, v_heads=16, v_mlp=4096, v_patch=14, v_image=224,
                          t_hidden=768, t_layers=12, t_heads=12, t_mlp=3072, t_ctx=248, proj_dim=768)
+# openai/clip-vit-large-patch14-336: the L/14 towers at 336 px, 24 x 24 + 1 = 577 vision tokens (above 288 tokens the attention
+# walks the keys in chunks, csrc/attention_tiled.h; the limit is 1025), the stock 77-token text tower
+VIT_L14_336 = ClipShape(v_hidden=1024, v_layers=24, v_heads=16, v_mlp=4096, v_patch=14, v_image=336,
+                        t_hidden=768, t_layers=12, t_heads=12, t_mlp=3072, t_ctx=77, proj_dim=768)
 
 
 def _is_torch(x) -> bool:
