@@ -171,6 +171,18 @@ int mmiss_dbg_ln_colstats(int device, void* hip_stream, const void* x, int32_t x
 int mmiss_dbg_bias_fold(int device, void* hip_stream, const void* w_bf16, const float* bias, const float* mu, int32_t N, int32_t K,
                         float* out);
 
+/* the resize step's tables in isolation (csrc/preprocess_kernels.h): the host geometry of one H x W image at crop size S, and one
+ * resize_coeffs_kernel launch with the grid, block and pool layout of the encoder's own call. geometry: HOST int32 [6] = new_h,
+ * new_w, top, left, ksx, ksy. pool int32 [(ksx + ksy) * S] = kx [ksx][S] then ky [S][ksy] (fixed point, 22 bits), bounds int32
+ * [4][S] = xmin, xcnt, ymin, ycnt of the crop window's S columns / rows. pool == bounds == NULL: only the geometry, nothing is
+ * launched and no device is needed. Refused like an encoder call: edges outside 1..65536, more than 4096 taps (and S outside
+ * 1..16384). Synchronises the stream. */
+int mmiss_dbg_resize_coeffs(int device, void* hip_stream, int32_t H, int32_t W, int32_t S, int32_t* geometry, int32_t* pool,
+                            int32_t* bounds);
+/* which resize_crop_kernel<KMAX> a launch over a blob of blob_bytes whose images need at most max_ksx horizontal taps runs:
+ * 12 or 24 (taps in registers), 0 (generic). The return value is the answer, not a status. */
+int mmiss_dbg_resize_crop_variant(int64_t blob_bytes, int32_t max_ksx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,8 @@ SIGNATURES = {
     "mmiss_dbg_gemm8_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
     "mmiss_dbg_ln_colstats": (_I, [_I, _P, _P, _I32, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P]),
     "mmiss_dbg_bias_fold": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _P]),
+    "mmiss_dbg_resize_coeffs": (_I, [_I, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "mmiss_dbg_resize_crop_variant": (_I, [_I64, _I32]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
 

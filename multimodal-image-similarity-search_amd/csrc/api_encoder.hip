@@ -854,6 +854,7 @@ int resize_chunk(mmiss_encoder* e, const uint8_t* rgb, bool rgb_dev, int64_t rgb
     }
     int64_t pool = 0, lo = INT64_MAX, hi = 0;
     int max_ksx = 0;
+    bool any_vfirst = false;
     for (int i = 0; i < nb; ++i) {
         const int H = heights[b0 + i], W = widths[b0 + i];
         const int64_t off = offsets[b0 + i];
@@ -870,6 +871,7 @@ int resize_chunk(mmiss_encoder* e, const uint8_t* rgb, bool rgb_dev, int64_t rgb
                     d.ksx, d.ksy);
         d.src_off = off;
         max_ksx = d.ksx > max_ksx ? d.ksx : max_ksx;
+        any_vfirst = any_vfirst || resize_vertical_first(H, W, d.new_h);
         d.kx_off = pool; pool += (int64_t)d.ksx * S;
         d.ky_off = pool; pool += (int64_t)d.ksy * S;
         lo = off < lo ? off : lo;
@@ -899,7 +901,7 @@ int resize_chunk(mmiss_encoder* e, const uint8_t* rgb, bool rgb_dev, int64_t rgb
     {
         MM_PROF("resize_crop", st, 0.0, (double)(hi - lo) + (double)nb * S * S * 3);
         launch_resize_crop(st, max_ksx, src, (rgb_dev && !staged) ? rgb_bytes : hi - lo, e->rz_desc.as<ResizeDesc>(), e->rz_pool.as<int32_t>(),
-                           e->rz_bounds.as<int32_t>(), dst_dev, S, nb);
+                           e->rz_bounds.as<int32_t>(), dst_dev, S, nb, any_vfirst);
         MM_HIP(hipGetLastError());
     }
     return MMISS_OK;
@@ -1870,6 +1872,43 @@ extern "C" int mmiss_dbg_bias_fold(int device, void* hip_stream, const void* w_b
     MM_TRY(mmiss_use_device(device));
     return launch_bias_fold(reinterpret_cast<hipStream_t>(hip_stream), w_bf16, bias, mu, out, N, K);
 }
+
+// ------------------------------------------------------------------------------------------------ resize tables in isolation
+// resize_geometry + one resize_coeffs_kernel launch for a single descriptor, with resize_chunk's grid, block and pool layout
+extern "C" int mmiss_dbg_resize_coeffs(int device, void* hip_stream, int32_t H, int32_t W, int32_t S, int32_t* geometry,
+                                       int32_t* pool, int32_t* bounds) {
+    if (!geometry) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_resize_coeffs: null geometry");
+    if ((pool == nullptr) != (bounds == nullptr)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_resize_coeffs: pool and bounds go together");
+    if (S < 1 || S > (1 << 14)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_resize_coeffs: S = %d outside 1..16384", S);
+    if (H < 1 || W < 1 || H > (1 << 16) || W > (1 << 16))
+        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_resize_coeffs: size %d x %d outside 1..65536", W, H);
+    ResizeDesc d;
+    resize_geometry(H, W, S, d);
+    if (d.ksx > 4096 || d.ksy > 4096)
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "mmiss_dbg_resize_coeffs: %d x %d -> %d needs %d / %d filter taps (limit 4096)", W, H, S, d.ksx,
+                d.ksy);
+    d.src_off = 0;
+    d.kx_off = 0;
+    d.ky_off = (int64_t)d.ksx * S;
+    const int32_t g[6] = {d.new_h, d.new_w, d.top, d.left, d.ksx, d.ksy};
+    memcpy(geometry, g, sizeof(g));
+    if (!pool) return MMISS_OK;
+    MM_TRY(mmiss_use_device(device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    ResizeDesc* dd = nullptr;
+    MM_HIP(hipMalloc(reinterpret_cast<void**>(&dd), sizeof(ResizeDesc)));
+    hipError_t err = hipMemcpyAsync(dd, &d, sizeof(ResizeDesc), hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(resize_coeffs_kernel, dim3(1, 2), dim3(256), 0, st, dd, pool, bounds, S);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // the descriptor is freed below, and is read from this stack frame
+    (void)hipFree(dd);
+    MM_HIP(err);
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_dbg_resize_crop_variant(int64_t blob_bytes, int32_t max_ksx) { return resize_crop_variant(blob_bytes, max_ksx); }
 
 // ------------------------------------------------------------------------------------------------ fp8 kernels in isolation
 extern "C" int mmiss_dbg_quantize_weights_fp8(int device, void* hip_stream, const void* w_bf16, void* w8, float* scale,

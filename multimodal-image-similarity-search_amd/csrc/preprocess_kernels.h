@@ -8,30 +8,27 @@
 //             center = (xx+0.5)*scale, weights bicubic((x+xmin-center+0.5)/filterscale) normalised by their sum
 //             (IEEE double), rounded half-away-from-zero to 22-bit fixed point;
 //   a pass    out = clip8((2^21 + sum pixel*k) >> 22); horizontal pass first, its result ROUNDED TO UINT8, then
-//             the vertical pass.
-// Two kernels:
+//             the vertical pass;
+//   order     Image.resize (PIL/Image.py, 12.2) turns the passes round when H > 100 W and the height shrinks: vertical over the
+//             full width first, horizontal second. The intermediate image is uint8 either way, so the order changes bytes.
+// Three kernels:
 //   resize_coeffs_kernel   one thread per (image, axis, output index inside the crop window): the fixed-point taps,
 //                          computed on the device in double with contraction off (same operation order as Pillow);
 //   resize_crop_kernel     one block per (16 output rows, 256 output columns, image): streams the source rows its
 //                          rows need; a thread computes the horizontally resampled uint8 RGB of its column for the
 //                          row and feeds it to the 16 x 3 vertical accumulators it owns, so the intermediate image
-//                          never exists in memory. Only the crop window is computed.
+//                          never exists in memory. Only the crop window is computed;
+//   resize_crop_vfirst_kernel  the vertical-first order, for the images Pillow runs that way (at most 655 px wide, more than 100
+//                          times as tall): one block per output row, the vertically resampled uint8 row in LDS. Rare and plain;
+//                          it lives in preprocess_vfirst.hip, a translation unit of its own.
 // Integer work bound by byte loads of the source (each source row is read once per 16-row tile it contributes to);
 // at the sizes of the reference's uploads (<= a few MP) the whole batch costs a fraction of one encoder layer.
+// Tests: tests/test_preprocess_gpu.py (mixed batches up to 19 taps, goldens: <12> and <24>); tests/test_resize_paths_gpu.py
+// (<0> and the 11|13, 23|25 routing, partial row / column tiles, many vertical chunks, saturation in <24> and <0>, the source
+// routes, resize_coeffs_kernel's tables and resize_geometry against the oracle); tests/test_resize_paths_cpu.py pins their inputs.
 #pragma once
 #include "common.h"
-
-struct ResizeDesc {
-    int64_t src_off;        // byte offset of the image (tightly packed RGB8, row stride 3*W) inside the source blob
-    int32_t H, W;           // source size
-    int32_t new_h, new_w;   // resized size (shortest edge = S)
-    int32_t top, left;      // centre-crop offsets inside the resized image
-    int32_t ksx, ksy;       // taps reserved per output index (Pillow's ksize) on x / y
-    int64_t kx_off, ky_off; // int32 offsets into the coefficient pool: kx[tap][S] (tap-major), ky[S][ksy]
-};
-
-#define MMISS_RESIZE_PRECISION_BITS 22
-#define MMISS_RESIZE_ROWS 16
+#include "preprocess_common.h"
 
 __device__ __forceinline__ double pil_bicubic(double x) {
 #pragma clang fp contract(off)
@@ -79,11 +76,6 @@ __global__ void resize_coeffs_kernel(const ResizeDesc* __restrict__ desc, int32_
         bnd[i] = xmin;
         bnd[S + i] = xmax;
     }
-}
-
-__device__ __forceinline__ int clip8_fixed(int32_t v) {
-    v >>= MMISS_RESIZE_PRECISION_BITS;  // arithmetic shift, as Pillow's clip8
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
 // grid (ceil(S/16), ceil(S/256), B), block 256: a thread owns one output COLUMN (3 channels) of the tile's 16 rows.
@@ -222,16 +214,27 @@ __global__ __launch_bounds__(256) void resize_crop_kernel(const uint8_t* __restr
         }
 }
 
+// Which resize_crop_kernel<KMAX> a launch runs: 12 / 24 = the register-tap kernels (4-byte loads: the blob must hold 4 bytes),
+// 0 = the generic one. max_ksx = the largest ksx of the launch's images.
+static inline int resize_crop_variant(int64_t blob_bytes, int max_ksx) {
+    if (blob_bytes >= 4 && max_ksx <= 12) return 12;
+    if (blob_bytes >= 4 && max_ksx <= 24) return 24;
+    return 0;
+}
+
 static inline void launch_resize_crop(hipStream_t st, int max_ksx, const uint8_t* src, int64_t blob_bytes,
                                       const ResizeDesc* desc, const int32_t* pool, const int32_t* bounds, uint8_t* dst,
-                                      int S, int nb) {
+                                      int S, int nb, bool any_vertical_first) {
     const dim3 grid((S + MMISS_RESIZE_ROWS - 1) / MMISS_RESIZE_ROWS, (S + 255) / 256, nb), block(256);
-    if (blob_bytes >= 4 && max_ksx <= 12)
+    const int variant = resize_crop_variant(blob_bytes, max_ksx);
+    if (variant == 12)
         hipLaunchKernelGGL(resize_crop_kernel<12>, grid, block, 0, st, src, blob_bytes, desc, pool, bounds, dst, S);
-    else if (blob_bytes >= 4 && max_ksx <= 24)
+    else if (variant == 24)
         hipLaunchKernelGGL(resize_crop_kernel<24>, grid, block, 0, st, src, blob_bytes, desc, pool, bounds, dst, S);
     else
         hipLaunchKernelGGL(resize_crop_kernel<0>, grid, block, 0, st, src, blob_bytes, desc, pool, bounds, dst, S);
+    if (any_vertical_first)  // rewrites the crops of those images in Pillow's order for them
+        launch_resize_crop_vfirst(st, src, desc, pool, bounds, dst, S, nb);
 }
 
 // Host geometry, the arithmetic of HF's get_resize_output_image_size (shortest edge -> S, long edge

@@ -11,7 +11,10 @@ reference pins only `Pillow>=10` in requirements.txt; 12.2 is installed here). I
     normalised by their sum; all in IEEE double;
   * 8-bit path: weights become 22-bit fixed point, round-half-away-from-zero (`normalize_coeffs_8bpc`); a pass
     computes clip8((2^21 + sum pixel * k) >> 22) per channel; horizontal pass first, then vertical, with the
-    intermediate image rounded to uint8.
+    intermediate image rounded to uint8;
+  * `Image.resize` itself (PIL/Image.py) turns the two passes round for very tall images: when height > 100 * width and
+    the height shrinks, it resamples vertically over the full width first and horizontally second (`vertical_first`).
+    The intermediate image is uint8 either way, so the order changes bytes.
 
 Pinned against the real Pillow in tests/test_resize_oracle_cpu.py (bit-exact on a sweep of sizes, up- and
 down-scaling), so parity of the GPU kernel with this file is parity with what the reference calls.
@@ -85,13 +88,26 @@ def output_geometry(h: int, w: int, size: int):
     return new_h, new_w, (new_h - size) // 2, (new_w - size) // 2
 
 
+def vertical_first(h: int, w: int, new_h: int) -> bool:
+    """Image.resize's own rule (PIL/Image.py, 12.2): the vertical pass runs first on images more than 100 times as tall as wide
+    whose height shrinks."""
+    return h > w * 100 and new_h < h
+
+
+def _resample(rgb, bx, kx, by, ky, top, rows, left, cols):
+    if vertical_first(rgb.shape[0], rgb.shape[1], len(by)):
+        tmp = _pass(np.ascontiguousarray(rgb), by, ky, top, rows)                                      # vertical, full width
+        return _pass(np.ascontiguousarray(tmp.transpose(1, 0, 2)), bx, kx, left, cols).transpose(1, 0, 2)
+    tmp = _pass(np.ascontiguousarray(rgb.transpose(1, 0, 2)), bx, kx, left, cols).transpose(1, 0, 2)   # horizontal
+    return _pass(np.ascontiguousarray(tmp), by, ky, top, rows)                                         # vertical
+
+
 def resize_bicubic_u8(rgb: np.ndarray, new_h: int, new_w: int) -> np.ndarray:
     """uint8 [H,W,3] -> uint8 [new_h,new_w,3], the whole resized image (Image.resize((new_w,new_h), BICUBIC))."""
     h, w, _ = rgb.shape
     _, bx, kx = precompute_coeffs(w, new_w)
     _, by, ky = precompute_coeffs(h, new_h)
-    tmp = _pass(np.ascontiguousarray(rgb.transpose(1, 0, 2)), bx, kx, 0, new_w).transpose(1, 0, 2)  # horizontal
-    return _pass(np.ascontiguousarray(tmp), by, ky, 0, new_h)                                       # vertical
+    return np.ascontiguousarray(_resample(rgb, bx, kx, by, ky, 0, new_h, 0, new_w))
 
 
 def resize_crop_u8(rgb: np.ndarray, size: int = 224) -> np.ndarray:
@@ -102,5 +118,4 @@ def resize_crop_u8(rgb: np.ndarray, size: int = 224) -> np.ndarray:
         raise ValueError("centre crop larger than the resized image")
     _, bx, kx = precompute_coeffs(w, new_w)
     _, by, ky = precompute_coeffs(h, new_h)
-    tmp = _pass(np.ascontiguousarray(rgb.transpose(1, 0, 2)), bx, kx, left, size).transpose(1, 0, 2)
-    return _pass(np.ascontiguousarray(tmp), by, ky, top, size)
+    return np.ascontiguousarray(_resample(rgb, bx, kx, by, ky, top, size, left, size))

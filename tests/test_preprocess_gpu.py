@@ -1,6 +1,9 @@
 """SURVEY §8(f) N2 on the GPU: CLIPImageProcessor's resize (shortest edge, bicubic) + centre crop as HIP kernels,
 bit-exact against oracle/resize_oracle.py (itself pinned bit-exact against Pillow in test_resize_oracle_cpu.py) and
-against the committed HF-processor goldens; then the raw-RGB encode entry point against the uint8 one."""
+against the committed HF-processor goldens; then the raw-RGB encode entry point against the uint8 one.
+Up to 19 taps and crop sizes that are multiples of 16 here; the generic kernel, the tap-count routing, partial tiles, many vertical
+chunks, saturation at many taps, the source routes, the vertical-first pass order and the coefficient tables themselves live in
+test_resize_paths_gpu.py."""
 import os
 
 import numpy as np

@@ -1,5 +1,7 @@
 """Pins oracle/resize_oracle.py (the restatement of Pillow's 8-bit bicubic resample) against the real Pillow that the
-reference's CLIPProcessor calls (backend/app/utils.py:76 -> HF:image_processing_clip.py:23-34), bit for bit."""
+reference's CLIPProcessor calls (backend/app/utils.py:76 -> HF:image_processing_clip.py:23-34), bit for bit.
+Sizes up to 2000 x 1500 at S = 224 here; the sizes of the kernel-path tests (up to 3000 x 4000 and 65536-px edges, S = 8 .. 336), the
+pass order of very tall images, int32 headroom and the library's host geometry are pinned in test_resize_paths_cpu.py."""
 import os
 import sys
 
