@@ -21,8 +21,7 @@
 // The arithmetic of the 16 full tiles is attention_long_kernel's, instruction for instruction: their output bits are equal.
 // The last query's sums are associated differently (nine partial sums merged): equal within the test's tolerance.
 #pragma once
-#include "common.h"
-#include "gemm_fp8.h"
+#include "attention_common.h"
 
 typedef float ats_f32x2 __attribute__((ext_vector_type(2)));
 
@@ -34,15 +33,6 @@ typedef float ats_f32x2 __attribute__((ext_vector_type(2)));
 #define ATS_PART (2 * ATS_IMG)                 // 2 areas of partial softmaxes of the last query
 #define ATS_QTAIL (ATS_PART + 2 * ATS_PSZ)     // 2 x 256 B: the last query's row (twice), by one 4-byte piece
 #define ATS_LDS (ATS_QTAIL + 512)
-
-__device__ __forceinline__ float ats_max_over_lane_groups(float v) {   // max over lanes l, l ^ 16, l ^ 32, l ^ 48
-    uint32_t u = __float_as_uint(v);
-    auto r32 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    v = mm_max2(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-    u = __float_as_uint(v);
-    auto r16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    return mm_max2(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-}
 
 // one 1 KB (16 B per lane) / 256 B (4 B per lane) piece global -> LDS. Inline asm on purpose: behind the builtin hipcc puts an
 // s_waitcnt vmcnt in front of the first transposing LDS read that follows (it cannot tell the two images apart) — a drain
@@ -170,7 +160,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
         // lm is lane-local here: some lane's maximum passes the threshold exactly when the query's does, so the exchange over
         // the four lanes of a query is only needed in the (rare) step that raises an offset
         if (__any(lm > s.m + thr_raw)) {
-            lm = ats_max_over_lane_groups(lm);
+            lm = att_max_over_lane_groups(lm);
             const float mn = (lm > s.m + thr_raw) ? lm : s.m;
             const float alpha = __builtin_amdgcn_exp2f((s.m - mn) * c_exp);
             s.m = mn;
@@ -205,7 +195,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) s.oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf, s.oacc[dt], 0, 0, 0);
     };
-    // the 16 queries of a tile leave as bf16 rows or as MXFP8 (attention_long_kernel's epilogue)
+    // the 16 queries of a tile leave as bf16 rows or as MXFP8 (bf16: att_store_bf16_row; the MXFP8 form is this kernel's own, attention_common.h says why)
     auto emit = [&](const f32x4 (&oacc)[4], float inv, int b, int h, int q) {
         if constexpr (MXOUT) {
             const size_t row = (size_t)b * T + (q < T ? q : 0);
@@ -218,7 +208,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(oacc[2 * blk + i][r]));
-                amax = ats_max_over_lane_groups(amax) * inv;
+                amax = att_max_over_lane_groups(amax) * inv;
                 int e8;
                 float sinv;
                 mx_scale_of(amax, e8, sinv);
@@ -232,14 +222,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
                 }
             }
         } else if (q < T) {
-            uint16_t* orow = ctx + ((size_t)b * T + q) * dmodel + h * 64 + 4 * fg;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                u32x2 pk;
-                pk[0] = pack_bf16x2(oacc[dt][0] * inv, oacc[dt][1] * inv);
-                pk[1] = pack_bf16x2(oacc[dt][2] * inv, oacc[dt][3] * inv);
-                *reinterpret_cast<u32x2*>(orow + dt * 16) = pk;
-            }
+            att_store_bf16_row(oacc, inv, ctx + ((size_t)b * T + q) * dmodel + h * 64 + 4 * fg);
         }
     };
     // the last query of pair (b, h): nine partial softmaxes over disjoint key ranges (area `par`), merged by one wave

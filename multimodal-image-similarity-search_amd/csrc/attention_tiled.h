@@ -1,5 +1,6 @@
 // attention_tiled.h — K4 above 288 tokens (ViT-L/14@336 and ViT-B/16@384: 577 tokens, L/14@448: 1025): the keys arrive in
-// chunks. Included by encoder_kernels.h behind attention_long_kernel, whose LDS layouts, helpers and arithmetic it restates.
+// chunks. Part of the attention header family (attention_kernels.h): the LDS layouts, the staging pieces, the key-pair step
+// and the epilogues are attention_common.h's, shared with attention_long_kernel.
 //
 // attention_long_kernel stages the whole K/V image of an (item, head) in LDS — 272 B per key, 78 KB at 288 padded keys, more
 // than a CU has at 577. Here:
@@ -18,6 +19,7 @@
 //     query tile lies beyond ceil(T / 16) stages its share of every chunk and meets every barrier; it only skips the key
 //     steps and the store. There is no early return.
 #pragma once
+#include "attention_common.h"
 
 #define ATT_TILED_CHUNK 128                                        // keys per LDS image (a multiple of 32)
 #define ATT_TILED_IMG (ATT_TILED_CHUNK * (128 + ATT_VSTRIDE))      // one K + V image
@@ -35,8 +37,6 @@ __global__ __launch_bounds__(512) void attention_tiled_kernel(const uint16_t* __
     const int dmodel = H * 64, ld = 3 * dmodel;
     const int fr = lane & 15, fg = lane >> 4;
     const int nqt = (T + 15) >> 4;
-    const float c_exp = 0.125f * 1.4426950408889634f;
-    const float thr_raw = 8.0f / c_exp;              // deferred rescale: the offset may lag the maximum by 8 binary orders
     // per-lane constants of the LDS addresses inside an image (krow & 7 = fr & 7: a key tile starts at a multiple of 16 rows)
     const int kb0 = fr * 128 + ((fg ^ (fr & 7)) << 4);
     const int kb1 = fr * 128 + (((4 + fg) ^ (fr & 7)) << 4);
@@ -61,33 +61,24 @@ __global__ __launch_bounds__(512) void attention_tiled_kernel(const uint16_t* __
     auto load_chunk = [&](int ch) {
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
-            const int idx = tid + i * (NW * 64), row = ch * C + (idx >> 3), c = idx & 7;
-            kr[i] = u32x4{0u, 0u, 0u, 0u};
-            vr[i] = u32x4{0u, 0u, 0u, 0u};
-            if (row < T) {
-                kr[i] = *reinterpret_cast<const u32x4*>(base + (size_t)row * ld + dmodel + c * 8);
-                vr[i] = *reinterpret_cast<const u32x4*>(base + (size_t)row * ld + 2 * dmodel + c * 8);
-            }
+            const int idx = tid + i * (NW * 64);
+            const AttKV t = att_load_kv_piece(base, ld, dmodel, ch * C + (idx >> 3), idx & 7, T);
+            kr[i] = t.k;
+            vr[i] = t.v;
         }
     };
     auto store_chunk = [&](int buf) {
         char* sK = smem + buf * IMG;
-        char* sV = sK + C * 128;
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
-            const int idx = tid + i * (NW * 64), row = idx >> 3, c = idx & 7;   // row < C
-            *reinterpret_cast<u32x4*>(sK + row * 128 + ((c ^ (row & 7)) << 4)) = kr[i];
-            *reinterpret_cast<u32x4*>(sV + row * ATT_VSTRIDE + (c << 4)) = vr[i];
+            const int idx = tid + i * (NW * 64);   // row idx >> 3 < C
+            att_store_kv_piece(sK, sK + C * 128, idx >> 3, idx & 7, kr[i], vr[i]);
         }
     };
 
     bf16x8 qf[2];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        u32x4 raw = {0u, 0u, 0u, 0u};
-        if (q < T) raw = *reinterpret_cast<const u32x4*>(base + (size_t)q * ld + s * 32 + fg * 8);
-        qf[s] = __builtin_bit_cast(bf16x8, raw);
-    }
+    for (int s = 0; s < 2; ++s) qf[s] = att_load_q(base, ld, q, T, s, fg);
     load_chunk(0);
     store_chunk(0);
     __syncthreads();
@@ -124,64 +115,14 @@ __global__ __launch_bounds__(512) void attention_tiled_kernel(const uint16_t* __
             }
             return a;
         };
-        // one step = two key tiles (the 32 keys of one PV MFMA); an odd last tile is a step of its own (second tile -inf)
-        auto step = [&](int ks, auto pair_tag) {
-            constexpr bool PAIR = decltype(pair_tag)::value;
-            f32x4 p0 = score_tile(2 * ks), p1;
-            if constexpr (PAIR) p1 = score_tile(2 * ks + 1);
-            else p1 = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            if constexpr (PAIR) mm_mfma_settle("+v"(p0), "+v"(p1));   // (the asm maxima below read MFMA results: common.h)
-            else mm_mfma_settle("+v"(p0));
-            float lm = mm_max3(p0[0], p0[1], p0[2]);
-            if constexpr (PAIR) lm = mm_max3(mm_max3(lm, p0[3], p1[0]), p1[1], mm_max2(p1[2], p1[3]));
-            else lm = mm_max2(lm, p0[3]);
-            lm = att_max_over_lane_groups(lm);   // the same value in the four lanes of a query
-            if (__any(lm > m + thr_raw)) {       // (m = -inf at the first step: taken, alpha = 0 on zeros)
-                const float mn = (lm > m + thr_raw) ? lm : m;
-                const float alpha = __builtin_amdgcn_exp2f((m - mn) * c_exp);   // 1 where the offset stays; exp2(-inf) = 0
-                m = mn;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) oacc[dt][r] *= alpha;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) lacc[r] *= alpha;
-            }
-            const float mc = m * c_exp;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p0[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(p0[r], c_exp, -mc));
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(p1[r], c_exp, -mc));
-            // B fragment of O^T = V^T P^T: element j < 4 = key 32 ks + 4 fg + j, j >= 4 = key 32 ks + 16 + 4 fg + (j - 4)
-            u32x4 praw;
-            praw[0] = pack_bf16x2(p0[0], p0[1]);
-            praw[1] = pack_bf16x2(p0[2], p0[3]);
-            praw[2] = pack_bf16x2(p1[0], p1[1]);
-            praw[3] = pack_bf16x2(p1[2], p1[3]);
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, praw);
-            lacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf, lacc, 0, 0, 0);
-            const char* vks = img + vb + ks * (32 * ATT_VSTRIDE);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const char* a0 = vks + dt * 32;
-                const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                    (__attribute__((address_space(3))) bf16x4*)(a0));
-                const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                    (__attribute__((address_space(3))) bf16x4*)(a0 + 16 * ATT_VSTRIDE));
-                bf16x8 vf;
-                vf[0] = v0[0]; vf[1] = v0[1]; vf[2] = v0[2]; vf[3] = v0[3];
-                vf[4] = v1[0]; vf[5] = v1[1]; vf[6] = v1[2]; vf[7] = v1[3];
-                oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[dt], 0, 0, 0);
-            }
-        };
         if (active) {
             // this wave's key tiles inside the chunk: [0, nt), odd only in the wave's last chunk
             int nt = kt_end - kt0;
             nt = nt < 0 ? 0 : (nt > CT ? CT : nt);
             const int npairs = nt >> 1;
 #pragma unroll 1
-            for (int ks = 0; ks < npairs; ++ks) step(ks, std::true_type{});
-            if (nt & 1) step(npairs, std::false_type{});
+            for (int ks = 0; ks < npairs; ++ks) att_key_pair_step<true>(score_tile, ks, img + vb + ks * (32 * ATT_VSTRIDE), ones, m, lacc, oacc);
+            if (nt & 1) att_key_pair_step<false>(score_tile, npairs, img + vb + npairs * (32 * ATT_VSTRIDE), ones, m, lacc, oacc);
         }
         if (more) store_chunk((ch + 1) & 1);         // image (ch + 1) & 1 was last read before the previous barrier
         __syncthreads();
@@ -191,38 +132,9 @@ __global__ __launch_bounds__(512) void attention_tiled_kernel(const uint16_t* __
         const float inv = 1.0f / lacc[0];
         if constexpr (MXOUT) {
             const size_t row = (size_t)b * T + (q < T ? q : 0);
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {
-                float o[2][4];
-                float amax = 0.f;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        o[i][r] = oacc[2 * blk + i][r] * inv;
-                        amax = fmaxf(amax, fabsf(o[i][r]));
-                    }
-                amax = att_max_over_lane_groups(amax);
-                int e8;
-                float sinv;
-                mx_scale_of(amax, e8, sinv);
-                if (q < T) {
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        *reinterpret_cast<uint32_t*>(ctx8 + row * dmodel + h * 64 + (2 * blk + i) * 16 + 4 * fg) =
-                            pack_fp8x4(o[i][0] * sinv, o[i][1] * sinv, o[i][2] * sinv, o[i][3] * sinv);
-                    if (fg == 0) ctxs[row * ld_s + mx_scale_offset(2 * h + blk)] = (uint8_t)e8;
-                }
-            }
+            att_store_mx_row(oacc, inv, q < T, ctx8 + row * dmodel + h * 64 + 4 * fg, ctxs + row * ld_s, h, fg);
         } else if (q < T) {
-            uint16_t* orow = ctx + ((size_t)b * T + q) * dmodel + h * 64 + 4 * fg;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                u32x2 pk;
-                pk[0] = pack_bf16x2(oacc[dt][0] * inv, oacc[dt][1] * inv);
-                pk[1] = pack_bf16x2(oacc[dt][2] * inv, oacc[dt][3] * inv);
-                *reinterpret_cast<u32x2*>(orow + dt * 16) = pk;
-            }
+            att_store_bf16_row(oacc, inv, ctx + ((size_t)b * T + q) * dmodel + h * 64 + 4 * fg);
         }
     }
 }

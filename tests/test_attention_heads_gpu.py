@@ -1,4 +1,4 @@
-"""attention_heads_kernel (encoder_kernels.h: several heads of one item per workgroup, T <= 128 — the kernel every layer of both
+"""attention_heads_kernel (attention_kernels.h: several heads of one item per workgroup, T <= 128 — the kernel every layer of both
 towers runs at batch 256) against torch's fp32 softmax on the whole tensor, under the per-element bound of
 tests/test_kernels_gpu.py::_attn_ref. Every instantiation <NKP, CAUSAL, HPB, MXOUT, POOLED> the launchers can pick:
 

@@ -67,7 +67,7 @@ def cat():
 @contextlib.contextmanager
 def _option(_lib, key, value, default):
     """The C API can set an option but not read one (include/mmiss_debug.h), so what is restored is the default the launcher itself
-    names: att_hpb 0 (encoder_kernels.h: attention_pick_hpb), attention_stream_min_pairs 256 (attention_stream.h:
+    names: att_hpb 0 (attention_kernels.h: attention_pick_hpb), attention_stream_min_pairs 256 (attention_stream.h:
     attention_stream_ok) — as tests/test_attention_heads_gpu.py::_forced does. tests/test_mxfp8_edges_cpu.py holds
     these two numbers against the sources, so a changed default in csrc/ fails here instead of leaking into later tests."""
     _lib.set_option(key, value)

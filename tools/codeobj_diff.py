@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Are the gfx950 kernels of two builds the same machine code? For refactors of the kernel headers that must not change
-the product: compares, kernel by kernel, the instruction sequences of csrc/api_encoder.o and csrc/api_index.o and the
+the product: compares, kernel by kernel, the instruction sequences of csrc/api_encoder.o, csrc/api_index.o and csrc/preprocess_vfirst.o and the
 compiler's resource figures (csrc/*.resources.txt) of an OLD and a NEW build.
 
     usage: python tools/codeobj_diff.py OLD/csrc NEW/csrc      (both built by `make -C .../csrc`; no GPU needed)
@@ -8,7 +8,9 @@ compiler's resource figures (csrc/*.resources.txt) of an OLD and a NEW build.
 Kernels are matched by demangled name through RENAMES (old -> new, for kernels whose template or argument lists changed);
 the match must be a bijection over all kernels of an object. ONE normalisation: the 32-bit literal of the s_add_u32 behind
 an s_getpc_b64 is a PC-relative distance to read-only data and moves when anything earlier in the code object changes size;
-kernels that needed it are listed. Exit status 0 = identical."""
+kernels that needed it are listed. For a kernel whose instructions differ, the opcodes whose counts differ follow
+(before -> after): equal counts say the same instructions in another order or with other registers. Exit status 0 = identical."""
+import collections
 import os
 import re
 import subprocess
@@ -17,14 +19,9 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 
-# (pattern on the OLD demangled name, replacement): the kernels whose names changed when the compile-time experiment
-# parameters were removed — gemm256p_kernel<EPI, XP, STYLE = 0, DBG = 0> -> <EPI, XP>; gemm160p_kernel<EPI, VARIANT = 0, KT>
-# -> <EPI, KT>; attention_long_kernel(..., int dbg) -> (...)
-RENAMES = [
-    (r"gemm256p_kernel<(\d+), (\d+), 0, 0>", r"gemm256p_kernel<\1, \2>"),
-    (r"gemm160p_kernel<(\d+), 0, (\d+)>", r"gemm160p_kernel<\1, \2>"),
-    (r"(attention_long_kernel<.*>\(.*), int\)$", r"\1)"),
-]
+# (pattern on the OLD demangled name, replacement): for a refactor that changes kernels' template or argument lists. Empty
+# between such refactors: a stale rule maps kernels that kept their names onto names that do not exist.
+RENAMES = []
 
 
 def rename(name):
@@ -50,7 +47,7 @@ def disassembly(csrc, obj):
         if m:
             assert m.group(1) not in kernels, m.group(1)
             cur = kernels.setdefault(m.group(1), [])
-        elif cur is not None and line.startswith("\t"):
+        elif cur is not None and line.startswith("\t") and line.strip() != "...":   # ("...": zero padding behind a kernel's end)
             cur.append(line.split("//")[0].strip())
     return kernels, names
 
@@ -68,6 +65,12 @@ def mask_pc_literals(ins):
     return out, n
 
 
+def opcode_count_differences(a, b):
+    """'opcode before->after, ...' over the opcodes whose counts differ between instruction lists a and b"""
+    ca, cb = (collections.Counter(text.split()[0] for text in ins if text) for ins in (a, b))
+    return ", ".join(f"{op} {ca[op]}->{cb[op]}" for op in sorted(set(ca) | set(cb)) if ca[op] != cb[op])
+
+
 def resources(csrc, obj, names):
     """{demangled kernel name: {figure: value}} of the compiler's kernel-resource-usage remarks"""
     text = open(os.path.join(csrc, obj + ".resources.txt")).read()
@@ -80,7 +83,7 @@ def resources(csrc, obj, names):
 def main():
     old_dir, new_dir = sys.argv[1], sys.argv[2]
     bad = 0
-    for obj in ("api_encoder", "api_index"):
+    for obj in ("api_encoder", "api_index", "preprocess_vfirst"):
         (old, old_names), (new, new_names) = disassembly(old_dir, obj), disassembly(new_dir, obj)
         old_res, new_res = resources(old_dir, obj, old_names), resources(new_dir, obj, new_names)
         mapped = {}
@@ -113,6 +116,7 @@ def main():
             print(f"  ONLY AFTER: {k}")
         for k in differ:
             print(f"  INSTRUCTIONS DIFFER: {k} ({len(old[mapped[k]])} vs {len(new[k])})")
+            print(f"    opcode counts: {opcode_count_differences(old[mapped[k]], new[k]) or 'equal'}")
         for k, ra, rb in res_differ:
             print(f"  RESOURCES DIFFER: {k}: {ra} vs {rb}")
         bad += len(only_old) + len(only_new) + len(differ) + len(res_differ)
