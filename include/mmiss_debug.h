@@ -183,6 +183,18 @@ int mmiss_dbg_resize_coeffs(int device, void* hip_stream, int32_t H, int32_t W, 
  * 12 or 24 (taps in registers), 0 (generic). The return value is the answer, not a status. */
 int mmiss_dbg_resize_crop_variant(int64_t blob_bytes, int32_t max_ksx);
 
+/* The plan a query call of Q queries and this k (filtered != 0: a filtered one) would follow on the index as it stands, and the
+ * plan of the widen pass if `flagged` (0 .. Q) of its queries were flagged: the query path's own planning functions, evaluated
+ * on the host. Launches nothing, changes nothing, needs no device. out is a HOST int32 [24]; fields that do not apply are 0:
+ *   [0] dense   [1] dense8   [2] big   [3] strip_v3   [4] sample   [5] kp (k')   [6] pages
+ *   dense first pass:  [7] Mq   [8] Npad   [9] ns_tiles (the sample, when [4])   [10] strip (when [2])   [16] splits of select_topk
+ *                      [23] groups per split
+ *   scan first pass:   [11] nqt   [12] cap   [13] slabs   [14] tiles_per_block   [15] qtiles
+ *   [17] the merge that ends the first pass runs in two levels
+ *   widen pass:        [18] 1 = strip score GEMM, 0 = scan;  GEMM: [22] strip;  scan: [19] nqt  [20] slabs  [21] tiles_per_block */
+struct mmiss_index;
+int mmiss_dbg_index_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int32_t filtered, int32_t flagged, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,7 @@ SIGNATURES = {
     "mmiss_dbg_bias_fold": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _P]),
     "mmiss_dbg_resize_coeffs": (_I, [_I, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_dbg_resize_crop_variant": (_I, [_I64, _I32]),
+    "mmiss_dbg_index_plan": (_I, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
 
@@ -232,3 +233,16 @@ def prof_read() -> list:
     buf = C.create_string_buffer(1 << 16)
     check(load().mmiss_prof_read(buf, len(buf)))
     return json.loads(buf.value.decode())
+
+
+INDEX_PLAN_FIELDS = ("dense", "dense8", "big", "strip_v3", "sample", "kp", "pages", "Mq", "Npad", "ns_tiles", "strip", "nqt", "cap",
+                     "slabs", "tiles_per_block", "qtiles", "splits", "merge_two_level", "sweep_gemm", "sweep_nqt", "sweep_slabs",
+                     "sweep_tiles_per_block", "sweep_strip", "groups_per_split")
+
+
+def index_plan(handle, Q: int, k: int, filtered: bool = False, flagged: int = 0) -> dict:
+    """mmiss_dbg_index_plan as a dict: the path a query call of this shape would take on the index `handle` as it stands (and the
+    widen pass's, were `flagged` of its queries flagged). Nothing is launched."""
+    out = (_I32 * 24)()
+    check(load().mmiss_dbg_index_plan(handle, int(Q), int(k), 1 if filtered else 0, int(flagged), out))
+    return dict(zip(INDEX_PLAN_FIELDS, (int(v) for v in out)))

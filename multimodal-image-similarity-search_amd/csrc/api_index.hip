@@ -271,9 +271,12 @@ int launch_scan(mmiss_index* ix, hipStream_t st, const ScanArgs& a, const ScanPl
 
 // merge L per-slab lists of every query into its candidate page; above 64 lists in two levels so that a single
 // query (the API path) is not merged by one lone workgroup
+constexpr int MERGE_LISTS_PER_BLOCK = 32;   // lists per first-level merge block
+bool merge_two_level(int L) { return L > mmiss_option("merge_two_level_min", 64); }
+
 int launch_merge(mmiss_index* ix, hipStream_t st, MergeArgs m) {
-    if (m.L > mmiss_option("merge_two_level_min", 64)) {
-        const int per = 32;
+    if (merge_two_level(m.L)) {
+        const int per = MERGE_LISTS_PER_BLOCK;
         const int S = (m.L + per - 1) / per;
         MM_TRY(ix->lists2_s.ensure((size_t)S * m.Q * m.kp * 4));
         MM_TRY(ix->lists2_r.ensure((size_t)S * m.Q * m.kp * 4));
@@ -748,6 +751,12 @@ int launch_strip_gemm(mmiss_index* ix, hipStream_t st, bool v3, const void* qs, 
     return launch_gemm256_strip<_Float16>(st, qs, ix->rows.p, ep, M, N, ix->dim, strip, flt);
 }
 
+// the widen pass's threshold pass over the index for Qf flagged queries: the strip score GEMM (true) or the streaming scan
+// (see sweep_queries)
+bool sweep_uses_gemm(const mmiss_index* ix, bool filt, int Qf) {
+    return !filt && strip_gemm_rows(ix) && strip_v3(ix) && Qf > mmiss_option("sweep_gemm_min_q", 64);
+}
+
 // The widen pass for the queries of `pd` listed in `which` (original indices): ONE threshold pass over the index for all of
 // them (thr_q = c_k - eps_q, left in ix->thr by the first pass's re-rank), the canonical re-rank of the rows it collected, and
 // the exhaustive pass for the lists that overflowed. Results overwrite the queries' rows of pd's outputs. Returns with the
@@ -759,7 +768,7 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const mmiss_index::Pending& p
     // the score GEMM for an f16 index once the flagged queries fill a quarter of a 256-query tile (it costs about what 1.2
     // streaming scans cost, and a scan serves 64 queries), the scan otherwise
     // (filtered queries: always the scan, whose FILT form collects admitted rows only; the score GEMM has no filtered epilogue)
-    const bool gemm = !pd.filt && strip_gemm_rows(ix) && strip_v3(ix) && Qf > mmiss_option("sweep_gemm_min_q", 64);
+    const bool gemm = sweep_uses_gemm(ix, pd.filt, Qf);
     const int Qfp = (int)round_up(Qf, 256);
     MM_TRY(ix->swp_cnt.ensure((size_t)Qfp * 4));
     MM_TRY(ix->swp_list.ensure((size_t)Qf * SWEEP_CAP * 4));
@@ -1002,6 +1011,17 @@ int upload_queries(mmiss_index* ix, hipStream_t st, const float* queries, int Q)
     return MMISS_OK;
 }
 
+// blocks per query of select_topk over ng group maxima: about 1024 blocks per call, every block at least one unit of
+// SELECT_UNIT groups, 32 at the most
+int select_splits(int ng, int Q) {
+    const int units = (ng + SELECT_UNIT - 1) / SELECT_UNIT;
+    int splits = (1024 + Q - 1) / Q;
+    if (splits > units) splits = units;
+    if (splits > 32) splits = 32;
+    if (splits < 1) splits = 1;
+    return splits;
+}
+
 // The dense first pass: the score GEMM writes the maximum of every group of 16 rows per query, select_topk / merge_lists keep
 // the k' best groups per query as its candidates (threshold-filtered sample form: see plan_query).
 int dense_pass(mmiss_index* ix, hipStream_t st, const QueryPlan& p, int Q) {
@@ -1019,11 +1039,7 @@ int dense_pass(mmiss_index* ix, hipStream_t st, const QueryPlan& p, int Q) {
         if (p.big) MM_TRY(launch_strip_gemm(ix, st, p.strip_v3, ix->qs.p, ep, p.Mq, (int)p.Ndense, p.strip, nullptr));
         else MM_TRY((launch_gemm_inst<_Float16, 128, MMISS_EPI_GROUPMAX_F32>(st, ix->qs.p, ix->rows.p, ep, p.Mq, (int)p.Npad, D)));
     }
-    const int units = (ng + 1023) / 1024;
-    int splits = (1024 + Q - 1) / Q;
-    if (splits > units) splits = units;
-    if (splits > 32) splits = 32;
-    if (splits < 1) splits = 1;
+    const int splits = select_splits(ng, Q);
     MM_TRY(ix->lists_s.ensure((size_t)splits * Q * kp * 4));
     MM_TRY(ix->lists_r.ensure((size_t)splits * Q * kp * 4));
     SelectArgs sa{};
@@ -1257,6 +1273,45 @@ extern "C" int mmiss_index_guard_stats(mmiss_index* ix, int64_t out[4]) {
     if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_guard_stats: null argument");
     std::lock_guard<std::mutex> lk(ix->mu);
     out[0] = ix->stat_queries; out[1] = ix->stat_flagged; out[2] = ix->stat_rounds; out[3] = ix->stat_pages;
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: the plan a query call of this shape would follow on the index as it stands. Host arithmetic only: the functions
+// the query path itself calls, nothing launched, no state changed.
+extern "C" int mmiss_dbg_index_plan(mmiss_index* ix, int32_t Q, int32_t k, int32_t filtered, int32_t flagged, int32_t* out) {
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_plan: null argument");
+    if (Q <= 0 || k <= 0 || flagged < 0 || flagged > Q) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_plan: Q=%d k=%d flagged=%d", Q, k, flagged);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (int i = 0; i < 24; ++i) out[i] = 0;
+    const int64_t N = ix->count;
+    const bool filt = filtered != 0;
+    QueryPlan p;
+    MM_TRY(plan_query(ix, Q, k, filt, p));
+    auto i32 = [](int64_t v) { return (int32_t)std::min<int64_t>(v, INT32_MAX); };
+    out[0] = p.dense; out[1] = p.dense8; out[2] = p.dense && p.big; out[3] = p.strip_v3; out[4] = p.sample;
+    out[5] = p.kp; out[6] = p.pages;
+    if (N <= 0) return MMISS_OK;   // (an empty index: no pass at all)
+    if (p.dense) {
+        out[7] = p.Mq; out[8] = i32(p.Npad); out[9] = i32(p.ns_tiles); out[10] = p.strip;
+        const int ng = (int)(p.Ndense / 16);
+        out[16] = select_splits(ng, Q);
+        out[17] = merge_two_level(p.sample ? 1 : out[16]);   // (sample form: the last merge reads the one seed list)
+        out[23] = select_split_groups(ng, out[16]);
+    } else {
+        const ScanPlan sp = plan_scan(ix->dim, ix->qelt(), Q, p.kp, N);
+        out[11] = sp.nqt; out[12] = sp.cap; out[13] = sp.slabs; out[14] = sp.tiles_per_block; out[15] = sp.qtiles;
+        out[17] = merge_two_level(sp.slabs);
+    }
+    if (flagged > 0) {
+        if (sweep_uses_gemm(ix, filt, flagged)) {
+            const int64_t nbn = round_up(N, 256) / 256;
+            out[18] = 1;
+            out[22] = strip_length((int)round_up(flagged, 256), nbn, nbn);
+        } else {
+            const ScanPlan sp = plan_sweep(ix->dim, ix->qelt(), flagged, N);
+            out[19] = sp.nqt; out[20] = sp.slabs; out[21] = sp.tiles_per_block;
+        }
+    }
     return MMISS_OK;
 }
 

@@ -595,17 +595,24 @@ __device__ __forceinline__ void lane_list_insert(float& ls, int& lr, float xs, i
     else if (lane == p) { ls = xs; lr = xr; }
 }
 
+// columns per block of select_topk_kernel when ng columns are dealt to nsplit blocks, in units of SELECT_UNIT columns (block y
+// takes [y * span, (y + 1) * span) cut at ng)
+constexpr int SELECT_UNIT = 1024;
+__host__ __device__ inline int select_split_groups(int ng, int nsplit) {
+    const int units = (ng + SELECT_UNIT - 1) / SELECT_UNIT;
+    const int upb = (units + nsplit - 1) / nsplit;
+    return upb * SELECT_UNIT;
+}
+
 __global__ __launch_bounds__(256) void select_topk_kernel(SelectArgs a) {
     __shared__ float ms[4][32];
     __shared__ int mr[4][32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x;
-    const int nsplit = gridDim.y;
-    // this block's column range, in units of 1024 columns
-    const int units = (a.ng + 1023) / 1024;
-    const int upb = (units + nsplit - 1) / nsplit;
-    const int c_begin = blockIdx.y * upb * 1024;
-    int c_end = c_begin + upb * 1024;
+    // this block's column range
+    const int span = select_split_groups(a.ng, gridDim.y);
+    const int c_begin = blockIdx.y * span;
+    int c_end = c_begin + span;
     if (c_end > a.ng) c_end = a.ng;
     const float* row = a.G + (size_t)q * a.ldg;
 

@@ -370,7 +370,7 @@ def test_attention_long_form_rescale_branch(env, causal):
 def test_attention_257_keys_last_query_every_key_counts(env, B, H):
     """The 257th query of ViT-L/14 takes its own code path in both long kernels (the odd last key tile; in the streaming kernel
     it is split by keys over nine waves and recombined), so it is compared ALONE, on data where losing any single key shows:
-    V = +-8 in every component, mild scores, so a dropped key moves every output by ~8/257 = 0.03 — six times the bound —
+    V = +-8 in every component, mild scores, so a dropped key moves every output by ~8/257 = 0.03 — two times the bound —
     which the test checks of its own reference first (the bound must be able to fail)."""
     torch, _lib, lib = env
     T = 257
