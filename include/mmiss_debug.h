@@ -52,6 +52,19 @@ int mmiss_dbg_prelayernorm_skinny(int device, void* hip_stream, float* x, const 
 /* stats f32 [M][parts][2]: slot 0 = (sum, sumsq) of row r of x f32 [M,d], the others zero; xb_or_null: the rows' bf16 copy. d % 4 == 0 */
 int mmiss_dbg_row_stats(int device, void* hip_stream, const float* x, float* stats, void* xb_or_null, int32_t M, int32_t d,
                         int32_t parts);
+/* The folded chain of one request (M <= 128 rows, <= 320 when N <= 1024; N % 16 == 0, K % 128 == 0), where LayerNorm1 / 2 run inside
+ * the skinny GEMM (csrc/gemm_skinny.h). Each entry is the encoder's own launch; where the skinny kernel would not run, it returns
+ * MMISS_ERR_UNSUPPORTED, launches nothing and never falls back to a tiled kernel.
+ * row_stats16: stats16 f32 [M][d/16][2] = (sum, sumsq) per 16 columns of x f32 [M,d], xb bf16 [M,d] = the rows' bf16 copy. d % 16 == 0 */
+int mmiss_dbg_row_stats16(int device, void* hip_stream, const float* x, float* stats16, void* xb, int32_t M, int32_t d);
+/* epi 7 / 8 (LayerNorm folded into W; 8: + QuickGELU): out bf16 [M,N] = rstd_m (A Wf^T - mean_m c) + bf, (mean, rstd) of row m from
+ * stats16 f32 [M][K/16][2] (16-byte aligned); A bf16 [M,K], Wf bf16 [N,K], c, bf f32 [N] as mmiss_dbg_fold_ln_weights writes them */
+int mmiss_dbg_gemm_skinny_fold(int device, void* hip_stream, int epi, const void* A, const void* Wf, void* out, const float* bf,
+                               const float* c, const float* stats16, float eps, int32_t M, int32_t N, int32_t K);
+/* x f32 [M,N] += A W^T + bias IN PLACE; stats16_out (optional) f32 [M][N/16][2] = (sum, sumsq) of the new rows per 16 columns,
+ * xb_out (optional) bf16 [M,N] = their bf16 copy: what the next folded skinny GEMM reads */
+int mmiss_dbg_gemm_skinny_resid(int device, void* hip_stream, const void* A, const void* W, float* x, const float* bias,
+                                float* stats16_out, void* xb_out, int32_t M, int32_t N, int32_t K);
 /* out f32 [M][2] = (mean, rstd) of every row from its `parts` partial (sum, sumsq) (stats f32 [M][parts][2], 16-byte aligned) of
  * d columns in all: var = max(sumsq / d - mean^2, 0), rstd = 1 / sqrt(var + eps). parts even, >= 2. */
 int mmiss_dbg_ln_finalize(int device, void* hip_stream, const float* stats, float* out, int32_t M, int32_t parts, int32_t d, float eps);

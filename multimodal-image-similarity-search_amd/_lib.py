@@ -116,6 +116,9 @@ SIGNATURES = {
     "mmiss_dbg_prelayernorm_stats": (_I, [_I, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _I32]),
     "mmiss_dbg_prelayernorm_skinny": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, C.c_float]),
     "mmiss_dbg_row_stats": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _I32]),
+    "mmiss_dbg_row_stats16": (_I, [_I, _P, _P, _P, _P, _I32, _I32]),
+    "mmiss_dbg_gemm_skinny_fold": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _I32, _I32]),
+    "mmiss_dbg_gemm_skinny_resid": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32]),
     "mmiss_dbg_ln_finalize": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, C.c_float]),
     "mmiss_dbg_fold_ln_weights": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32]),
     "mmiss_dbg_attention": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _I32]),

@@ -1749,6 +1749,47 @@ extern "C" int mmiss_dbg_row_stats(int device, void* hip_stream, const float* x,
     return MMISS_OK;
 }
 
+// The one-request folded chain (P.sfold), kernel by kernel: the launches of run_layers / run_wide / run_resid on caller-owned
+// buffers. None of the three falls back to a tiled kernel: where the skinny path would not run they refuse.
+extern "C" int mmiss_dbg_row_stats16(int device, void* hip_stream, const float* x, float* stats16, void* xb, int32_t M, int32_t d) {
+    if (!x || !stats16 || !xb) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_row_stats16: null pointer");
+    if (M <= 0 || d <= 0 || d % 16) MM_FAIL(MMISS_ERR_UNSUPPORTED, "row_stats16: M=%d d=%d (d%%16==0)", M, d);
+    MM_TRY(mmiss_use_device(device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    MM_PROF("row_stats", st, 3.0 * M * d, 6.0 * M * d);
+    hipLaunchKernelGGL(skinny_row_stats16_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, stats16, reinterpret_cast<uint16_t*>(xb), M, d);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_dbg_gemm_skinny_fold(int device, void* hip_stream, int epi, const void* A, const void* Wf, void* out, const float* bf,
+                                          const float* c, const float* stats16, float eps, int32_t M, int32_t N, int32_t K) {
+    if (!A || !Wf || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_skinny_fold: null pointer");
+    // (the kernel reads a row's partials, c and b' as 16-byte vectors)
+    if ((reinterpret_cast<uintptr_t>(stats16) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(bf)) & 15)
+        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_skinny_fold: stats16, c and bf must be 16-byte aligned");
+    if (epi != MMISS_EPI_LNFOLD_BF16 && epi != MMISS_EPI_LNFOLD_QGELU_BF16)
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm_skinny_fold: epilogue %d (7 or 8)", epi);
+    if (M <= 0 || N <= 0 || K <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm_skinny_fold: M=%d N=%d K=%d", M, N, K);
+    MM_TRY(mmiss_use_device(device));
+    GemmEpi ep{};
+    ep.out = out; ep.bias = bf; ep.aux = c; ep.ldo = N; ep.m_valid = M;
+    ep.ln_stats = stats16; ep.ln_eps = eps; ep.ln_parts = K / 16; ep.stats16 = 1;
+    return launch_gemm_skinny_fold(reinterpret_cast<hipStream_t>(hip_stream), epi, A, Wf, ep, M, N, K);
+}
+
+extern "C" int mmiss_dbg_gemm_skinny_resid(int device, void* hip_stream, const void* A, const void* W, float* x, const float* bias,
+                                           float* stats16_out, void* xb_out, int32_t M, int32_t N, int32_t K) {
+    if (!A || !W || !x || !bias) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_skinny_resid: null pointer");
+    GemmEpi ep{};
+    ep.out = x; ep.bias = bias; ep.ldo = N; ep.m_valid = M;
+    ep.stats_out = stats16_out; ep.xb_out = xb_out; ep.stats16 = 1;
+    if (M <= 0 || N <= 0 || K <= 0 || !gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, M, N, K, ep))
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm_skinny_resid: M=%d N=%d K=%d is not a skinny GEMM", M, N, K);
+    MM_TRY(mmiss_use_device(device));
+    return launch_gemm(reinterpret_cast<hipStream_t>(hip_stream), MMISS_EPI_BIAS_RESID_F32, 128, A, W, ep, (int)round_up(M, 128), N, K);
+}
+
 extern "C" int mmiss_dbg_ln_finalize(int device, void* hip_stream, const float* stats, float* out, int32_t M, int32_t parts, int32_t d,
                                      float eps) {
     if (!stats || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_ln_finalize: null pointer");
