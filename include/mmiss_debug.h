@@ -31,8 +31,9 @@ int mmiss_dbg_gemm(int device, void* hip_stream, int epi, int variant, const voi
 int mmiss_dbg_layernorm(int device, void* hip_stream, const float* x, const float* gamma, const float* beta,
                         void* out, int32_t out_bf16, int32_t M, int32_t d, float eps);
 
-/* The LayerNorm chain around the LayerNorm-folded GEMMs, one kernel per call with the encoder's own grid formulas. Shapes a
- * kernel does not take, M < 1 among them, are refused with MMISS_ERR_UNSUPPORTED.
+/* The LayerNorm chain around the LayerNorm-folded GEMMs, one kernel per call: each entry calls the launcher the encoder itself
+ * calls (the launch_* function beside the kernel), which also makes the checks. Shapes a kernel does not take, M < 1 among them,
+ * are refused with MMISS_ERR_UNSUPPORTED.
  * layernorm16: the LayerNorm of a bf16 residual stream, x_bf16 [M,d] -> out_bf16 [M,d]; d % 8 == 0, d <= 1024. */
 int mmiss_dbg_layernorm16(int device, void* hip_stream, const void* x_bf16, const float* gamma, const float* beta, void* out_bf16,
                           int32_t M, int32_t d, float eps);
@@ -185,7 +186,7 @@ int mmiss_dbg_bias_fold(int device, void* hip_stream, const void* w_bf16, const 
                         float* out);
 
 /* the resize step's tables in isolation (csrc/preprocess_kernels.h): the host geometry of one H x W image at crop size S, and one
- * resize_coeffs_kernel launch with the grid, block and pool layout of the encoder's own call. geometry: HOST int32 [6] = new_h,
+ * resize_coeffs_kernel launch through the encoder's own launcher, with the pool layout of the encoder's own call. geometry: HOST int32 [6] = new_h,
  * new_w, top, left, ksx, ksy. pool int32 [(ksx + ksy) * S] = kx [ksx][S] then ky [S][ksy] (fixed point, 22 bits), bounds int32
  * [4][S] = xmin, xcnt, ymin, ycnt of the crop window's S columns / rows. pool == bounds == NULL: only the geometry, nothing is
  * launched and no device is needed. Refused like an encoder call: edges outside 1..65536, more than 4096 taps (and S outside

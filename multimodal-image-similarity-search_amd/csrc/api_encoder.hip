@@ -16,41 +16,6 @@
 
 namespace {
 
-// f32 [R,C] -> bf16 rows of stride ldd (dst pre-zeroed where ldd > C)
-__global__ void convert_2d_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t R, int C,
-                                       int ldd) {
-    const int64_t total = R * C;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = i / C;
-        const int c = (int)(i - r * C);
-        bf16_t v = (bf16_t)src[i];
-        dst[r * ldd + c] = __builtin_bit_cast(uint16_t, v);
-    }
-}
-
-// The pruned last layer's two gathers in one launch: ctxc row r = ctx row rowmap[r] (bf16), xc row r = the residual row
-// rowmap[r] as f32 — copied from x32, or widened from x16 when the stream is bf16. d % 4 == 0.
-__global__ void gather_pooled_kernel(const uint16_t* __restrict__ ctx, uint16_t* __restrict__ ctxc, const float* __restrict__ x32,
-                                     const uint16_t* __restrict__ x16, float* __restrict__ xc, const int32_t* __restrict__ rowmap,
-                                     int n, int d) {
-    const int chunks = d >> 2;
-    const int64_t total = (int64_t)n * chunks;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int r = (int)(i / chunks), c = (int)(i - (int64_t)r * chunks);
-        const size_t so = (size_t)rowmap[r] * d + (size_t)c * 4, dofs = (size_t)r * d + (size_t)c * 4;
-        *reinterpret_cast<u32x2*>(ctxc + dofs) = *reinterpret_cast<const u32x2*>(ctx + so);
-        f32x4 o;
-        if (x16) {
-            const u32x2 v = *reinterpret_cast<const u32x2*>(x16 + so);
-            o[0] = __uint_as_float(v[0] << 16); o[1] = __uint_as_float(v[0] & 0xFFFF0000u);
-            o[2] = __uint_as_float(v[1] << 16); o[3] = __uint_as_float(v[1] & 0xFFFF0000u);
-        } else {
-            o = *reinterpret_cast<const f32x4*>(x32 + so);
-        }
-        *reinterpret_cast<f32x4*>(xc + dofs) = o;
-    }
-}
-
 struct LayerW {
     DevBuf wqkv, bqkv, wo, bo, ln1g, ln1b, ln2g, ln2b, w1, b1, w2, b2;
     DevBuf wqkv_f, cqkv, bqkv_f, w1_f, c1, b1_f;  // LayerNorm folded into the QKV / FC1 weights (finalize)
@@ -527,10 +492,7 @@ int run_wide(hipStream_t st, Tower& tw, const LayerPlan& P, GemmPick k, const Wi
         }
         ep.ln_parts = d / 64;
         if (k.kind == GemmKind::P256 && P.fold_final) {   // partial (sum, sumsq) per 64 columns -> (mean, rstd) per row
-            MM_PROF("ln_finalize", st, 4.0 * M * (d / 64), (double)M * ((d / 64) * 8 + 8));
-            hipLaunchKernelGGL(ln_finalize_kernel, dim3((M * 8 + 255) / 256), dim3(256), 0, st, tw.stats.as<float>(),
-                               tw.stats_final.as<float>(), M, d / 64, d, eps);
-            MM_HIP(hipGetLastError());
+            MM_TRY(launch_ln_finalize(st, tw.stats.as<float>(), tw.stats_final.as<float>(), M, d / 64, d, eps));
             ep.ln_final = tw.stats_final.as<float>();
         }
     } else if (P.resid16) {
@@ -598,24 +560,12 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
     MM_TRY(tap(0));
     tw.pooled_compact = false;
     // entry statistics of the first layer's LayerNorm, unless the embedding stage already left them
-    if (P.sfold && P.embed != EmbedOut::Stats16) {
-        MM_PROF("row_stats", st, 3.0 * M * d, 6.0 * M * d);
-        hipLaunchKernelGGL(skinny_row_stats16_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), tw.stats.as<float>(),
-                           tw.xb.as<uint16_t>(), M, d);
-        MM_HIP(hipGetLastError());
-    }
-    if ((P.fold || P.resid16) && P.embed != EmbedOut::Stats64) {  // (separate-LayerNorm mode with a bf16 stream: only the bf16 copy is used)
-        MM_PROF("row_stats", st, 3.0 * M * d, (P.fold ? 6.0 : 4.0) * M * d);
-        hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), tw.stats.as<float>(),
-                           tw.xb.as<uint16_t>(), M, d, d / 64);
-        MM_HIP(hipGetLastError());
-    }
-    if (P.fold8) {
-        MM_PROF("quant16_mxfp8_stats", st, 3.0 * M * d, 3.0 * M * d);
-        hipLaunchKernelGGL(quant16_mxfp8_stats_1024_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.xb.as<uint16_t>(), tw.h8.as<uint8_t>(),
-                           tw.hs.as<uint8_t>(), tw.stats.as<float>(), M, mx_scale_row_bytes(d));
-        MM_HIP(hipGetLastError());
-    }
+    if (P.sfold && P.embed != EmbedOut::Stats16)
+        MM_TRY(launch_row_stats16(st, tw.x.as<float>(), tw.stats.as<float>(), tw.xb.as<uint16_t>(), M, d));
+    if ((P.fold || P.resid16) && P.embed != EmbedOut::Stats64)  // (separate-LayerNorm mode with a bf16 stream: only the bf16 copy is used)
+        MM_TRY(launch_row_stats(st, tw.x.as<float>(), tw.stats.as<float>(), tw.xb.as<uint16_t>(), M, d, d / 64, P.fold));
+    if (P.fold8)
+        MM_TRY(launch_quant16_mxfp8_stats(st, tw.xb.as<uint16_t>(), tw.h8.as<uint8_t>(), tw.hs.as<uint8_t>(), tw.stats.as<float>(), M, d));
     for (int l = 0; l < tw.layers; ++l) {
         LayerW& L = tw.L[l];
         WideRole qkv{};
@@ -645,13 +595,8 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
                 else ep_out.resid32_rows = tw.x.as<float>();
                 ep_out.resid_rowmap = tw.pool_row.as<int32_t>();
             } else {
-                const int grid = (B * d / 4 + 255) / 256;
-                MM_PROF("gather_pooled", st, 0.0, (double)B * d * (P.resid16 ? 10 : 12));
-                // pooled rows of the attention output (bf16) and of the residual stream (f32, or widened bf16) in ONE launch
-                hipLaunchKernelGGL(gather_pooled_kernel, dim3(grid), dim3(256), 0, st, tw.ctx.as<uint16_t>(), tw.ctxc.as<uint16_t>(),
-                                   P.resid16 ? nullptr : tw.x.as<float>(), P.resid16 ? tw.xb.as<uint16_t>() : nullptr,
-                                   tw.xc.as<float>(), tw.pool_row.as<int32_t>(), B, d);
-                MM_HIP(hipGetLastError());
+                MM_TRY(launch_gather_pooled(st, tw.ctx.as<uint16_t>(), tw.ctxc.as<uint16_t>(), P.resid16 ? nullptr : tw.x.as<float>(),
+                                            P.resid16 ? tw.xb.as<uint16_t>() : nullptr, tw.xc.as<float>(), tw.pool_row.as<int32_t>(), B, d));
             }
             MM_TRY(launch_gemm(st, MMISS_EPI_BIAS_RESID_F32, 128, tw.ctxc.p, L.wo.p, ep_out, Bp, d, d));
             GemmEpi ep{};
@@ -698,13 +643,7 @@ int run_head(mmiss_encoder* e, Tower& tw, int B, float* out_dev, hipStream_t st)
     GemmEpi ep{};
     ep.out = tw.proj_out.p; ep.ldo = P; ep.m_valid = B;
     MM_TRY(launch_gemm(st, MMISS_EPI_F32, 0, tw.pooled.p, tw.proj.p, ep, Bp, P, d));
-    {
-        MM_PROF("l2norm_rows", st, 3.0 * B * P, 8.0 * B * P);
-        hipLaunchKernelGGL(l2norm_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, st, tw.proj_out.as<float>(), out_dev, B,
-                           P, P);
-    }
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
+    return launch_l2norm_rows(st, tw.proj_out.as<float>(), out_dev, B, P, P);
 }
 
 int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B, float* out_dev, hipStream_t st) {
@@ -729,11 +668,8 @@ int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B
     // the compact rows xc: the pre-LayerNorm then keeps its f32 rows to itself and makes the CLS rows as it goes
     const bool lean_pre = plan.embed == EmbedOut::Stats64 && plan.resid16 && plan.prune && mmiss_option("prelayernorm_lean", 1) != 0;
     // (Stats16: the CLS rows come with the pre-LayerNorm below, prelayernorm_skinny_kernel)
-    if (plan.embed != EmbedOut::Stats16 && !lean_pre) {
-        MM_PROF("cls_rows", st, (double)B * d, 12.0 * B * d);
-        hipLaunchKernelGGL(cls_rows_kernel, dim3((B * d + 255) / 256), dim3(256), 0, st, tw.x.as<float>(),
-                           e->cls.as<float>(), tw.pos.as<float>(), B, tw.T, d);
-    }
+    if (plan.embed != EmbedOut::Stats16 && !lean_pre)
+        MM_TRY(launch_cls_rows(st, tw.x.as<float>(), e->cls.as<float>(), tw.pos.as<float>(), B, tw.T, d));
     GemmEpi ep{};
     ep.out = tw.x.p; ep.aux = tw.pos.as<float>(); ep.ldo = d; ep.m_valid = Mpatch; ep.p0 = e->G * e->G; ep.p1 = tw.T;
     if (gemm_splitk_candidate((int64_t)(Mpp / bm_p) * (d / GEMM_BN), e->Kp)) {
@@ -749,30 +685,18 @@ int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B
     // pre_layrnorm, in place on the fp32 residual stream (HF:modeling_clip.py:640), with what the plan's first layer wants
     const int M = plan.M;
     if (plan.embed == EmbedOut::Stats16) {   // + CLS rows, xb and the 16-column statistics, in one launch
-        MM_PROF("layernorm", st, 12.0 * M * d, (double)M * d * 10);
-        hipLaunchKernelGGL(prelayernorm_skinny_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->cls.as<float>(),
-                           tw.pos.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(),
-                           M, tw.T, d, e->cfg.ln_eps);
-        MM_HIP(hipGetLastError());
-    } else if (lean_pre) {   // xb and the 64-column statistics; CLS rows made here, no f32 write-back
-        MM_PROF("layernorm", st, 10.0 * M * d, (double)M * d * 6);
-        hipLaunchKernelGGL(layernorm_stats_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->pre_g.as<float>(),
-                           e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(), M, d, d / 64, e->cfg.ln_eps,
-                           e->cls.as<float>(), tw.pos.as<float>(), tw.T);
-        MM_HIP(hipGetLastError());
-    } else if (plan.embed == EmbedOut::Stats64) {   // + xb and the 64-column statistics
-        MM_PROF("layernorm", st, 10.0 * M * d, (double)M * d * 10);
-        hipLaunchKernelGGL(layernorm_stats_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, tw.x.as<float>(), e->pre_g.as<float>(),
-                           e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(), M, d, d / 64, e->cfg.ln_eps,
-                           (const float*)nullptr, (const float*)nullptr, 1);
-        MM_HIP(hipGetLastError());
+        MM_TRY(launch_prelayernorm_skinny(st, tw.x.as<float>(), e->cls.as<float>(), tw.pos.as<float>(), e->pre_g.as<float>(),
+                                          e->pre_b.as<float>(), tw.xb.as<uint16_t>(), tw.stats.as<float>(), M, tw.T, d, e->cfg.ln_eps));
+    } else if (plan.embed == EmbedOut::Stats64) {   // + xb and the 64-column statistics; lean: CLS rows made here, no f32 write-back
+        MM_TRY(launch_layernorm_stats(st, tw.x.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.xb.as<uint16_t>(),
+                                      tw.stats.as<float>(), M, d, d / 64, e->cfg.ln_eps, lean_pre, e->cls.as<float>(), tw.pos.as<float>(), tw.T));
     } else {
         MM_TRY(launch_layernorm(st, tw.x.as<float>(), e->pre_g.as<float>(), e->pre_b.as<float>(), tw.x.p, false, nullptr, M, d,
                                 e->cfg.ln_eps));
     }
     if (tw.pool_B < B || tw.pool_T != tw.T) {  // token 0 of every image: the same table until the shape changes
         const int nb = tw.ws_batch > B ? tw.ws_batch : B;
-        hipLaunchKernelGGL(vision_pool_rows_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, tw.pool_row.as<int32_t>(), nb, tw.T);
+        MM_TRY(launch_vision_pool_rows(st, tw.pool_row.as<int32_t>(), nb, tw.T));
         tw.pool_B = nb;
         tw.pool_T = tw.T;
     }
@@ -790,11 +714,10 @@ int encode_text_chunk(mmiss_encoder* e, const int32_t* ids_dev, int B, int T, fl
     tw.T = T;  // shorter-than-ctx sequences run at their own length (positions 0..T-1)
     LayerPlan plan;
     int rc = plan_layers(e, tw, B, true, plan);
-    if (rc == MMISS_OK) {
-        hipLaunchKernelGGL(text_embed_kernel, dim3(B), dim3(256), 0, st, ids_dev, e->tok.as<float>(), tw.pos.as<float>(),
-                           tw.x.as<float>(), tw.pool_row.as<int32_t>(), T, d, e->cfg.t_vocab, e->cfg.eos_token_id);
-        rc = run_layers(e, tw, plan, st);
-    }
+    if (rc == MMISS_OK)
+        rc = launch_text_embed(st, ids_dev, e->tok.as<float>(), tw.pos.as<float>(), tw.x.as<float>(), tw.pool_row.as<int32_t>(), B, T, d,
+                               e->cfg.t_vocab, e->cfg.eos_token_id);
+    if (rc == MMISS_OK) rc = run_layers(e, tw, plan, st);
     if (rc == MMISS_OK) rc = run_head(e, tw, B, out_dev, st);
     tw.T = savedT;
     tw.last_B = B;
@@ -892,12 +815,7 @@ int resize_chunk(mmiss_encoder* e, const uint8_t* rgb, bool rgb_dev, int64_t rgb
     MM_TRY(e->rz_bounds.ensure((size_t)nb * 4 * S * 4));
     MM_HIP(hipMemcpyAsync(e->rz_desc.p, e->rz_host, sizeof(ResizeDesc) * (size_t)nb, hipMemcpyHostToDevice, st));
     MM_HIP(hipEventRecord(e->rz_copied, st));
-    {
-        MM_PROF("resize_coeffs", st, 0.0, (double)pool * 4);
-        hipLaunchKernelGGL(resize_coeffs_kernel, dim3(nb, 2), dim3(256), 0, st, e->rz_desc.as<ResizeDesc>(),
-                           e->rz_pool.as<int32_t>(), e->rz_bounds.as<int32_t>(), S);
-        MM_HIP(hipGetLastError());
-    }
+    MM_TRY(launch_resize_coeffs(st, e->rz_desc.as<ResizeDesc>(), e->rz_pool.as<int32_t>(), e->rz_bounds.as<int32_t>(), S, nb, pool));
     {
         MM_PROF("resize_crop", st, 0.0, (double)(hi - lo) + (double)nb * S * S * 3);
         launch_resize_crop(st, max_ksx, src, (rgb_dev && !staged) ? rgb_bytes : hi - lo, e->rz_desc.as<ResizeDesc>(), e->rz_pool.as<int32_t>(),
@@ -1040,10 +958,7 @@ extern "C" int mmiss_encoder_set_weight(mmiss_encoder* enc, const char* hf_key, 
     }
     if (s.bf16) {
         uint16_t* dst = s.dst->as<uint16_t>() + s.dst_row_off * s.ldd;
-        const int grid = (int)((numel + 255) / 256 < 4096 ? (numel + 255) / 256 : 4096);
-        hipLaunchKernelGGL(convert_2d_bf16_kernel, dim3(grid), dim3(256), 0, st, src, dst, s.rows, (int)s.cols,
-                           (int)s.ldd);
-        MM_HIP(hipGetLastError());
+        MM_TRY(launch_convert_2d_bf16(st, src, dst, s.rows, (int)s.cols, (int)s.ldd));
     } else {
         // 1-D slots use dst_row_off as an element offset (ldd may be 0 for fused biases)
         float* dst = s.dst->as<float>() + (s.rows == 1 ? s.dst_row_off : s.dst_row_off * s.ldd);
@@ -1079,15 +994,12 @@ extern "C" int mmiss_encoder_finalize(mmiss_encoder* enc) {
         for (LayerW& L : tw->L) {
             MM_TRY(L.wqkv_f.alloc((size_t)3 * d * d * 2)); MM_TRY(L.cqkv.alloc((size_t)3 * d * 4)); MM_TRY(L.bqkv_f.alloc((size_t)3 * d * 4));
             MM_TRY(L.w1_f.alloc((size_t)tw->mlp * d * 2)); MM_TRY(L.c1.alloc((size_t)tw->mlp * 4)); MM_TRY(L.b1_f.alloc((size_t)tw->mlp * 4));
-            hipLaunchKernelGGL(fold_ln_weights_kernel, dim3((3 * d + 3) / 4), dim3(256), 0, enc->own_stream, L.wqkv.as<uint16_t>(),
-                               L.ln1g.as<float>(), L.ln1b.as<float>(), L.bqkv.as<float>(), L.wqkv_f.as<uint16_t>(),
-                               L.cqkv.as<float>(), L.bqkv_f.as<float>(), 3 * d, d);
-            hipLaunchKernelGGL(fold_ln_weights_kernel, dim3((tw->mlp + 3) / 4), dim3(256), 0, enc->own_stream, L.w1.as<uint16_t>(),
-                               L.ln2g.as<float>(), L.ln2b.as<float>(), L.b1.as<float>(), L.w1_f.as<uint16_t>(),
-                               L.c1.as<float>(), L.b1_f.as<float>(), tw->mlp, d);
+            MM_TRY(launch_fold_ln_weights(enc->own_stream, L.wqkv.as<uint16_t>(), L.ln1g.as<float>(), L.ln1b.as<float>(), L.bqkv.as<float>(),
+                                          L.wqkv_f.as<uint16_t>(), L.cqkv.as<float>(), L.bqkv_f.as<float>(), 3 * d, d));
+            MM_TRY(launch_fold_ln_weights(enc->own_stream, L.w1.as<uint16_t>(), L.ln2g.as<float>(), L.ln2b.as<float>(), L.b1.as<float>(),
+                                          L.w1_f.as<uint16_t>(), L.c1.as<float>(), L.b1_f.as<float>(), tw->mlp, d));
         }
     }
-    MM_HIP(hipGetLastError());
     MM_HIP(hipStreamSynchronize(enc->own_stream));
     if (enc->fp8_tower[0] || enc->fp8_tower[1]) MM_TRY(build_fp8_weights(enc));
     enc->vis.calibrated = false;
@@ -1104,19 +1016,13 @@ static int build_fp8_weights(mmiss_encoder* enc) {
         auto quant = [&](DevBuf& wb, DevBuf& w8, DevBuf& sc, int N, int K) -> int {
             MM_TRY(w8.alloc((size_t)N * K));
             MM_TRY(sc.alloc((size_t)N * 4));
-            hipLaunchKernelGGL(quantize_weights_fp8_kernel, dim3((N + 3) / 4), dim3(256), 0, st, wb.as<uint16_t>(),
-                               w8.as<uint8_t>(), sc.as<float>(), N, K);
-            MM_HIP(hipGetLastError());
-            return MMISS_OK;
+            return launch_quantize_weights_fp8(st, wb.as<uint16_t>(), w8.as<uint8_t>(), sc.as<float>(), N, K);
         };
         auto quant_fold = [&](DevBuf& wf, DevBuf& w8, DevBuf& sc, DevBuf& c16, int N, int K) -> int {
             MM_TRY(w8.alloc((size_t)N * K));
             MM_TRY(sc.alloc((size_t)N * 4));
             MM_TRY(c16.alloc((size_t)N * 2));
-            hipLaunchKernelGGL(quantize_weights_fp8_csum_kernel, dim3((N + 3) / 4), dim3(256), 0, st, wf.as<uint16_t>(), w8.as<uint8_t>(),
-                               sc.as<float>(), c16.as<uint16_t>(), N, K);
-            MM_HIP(hipGetLastError());
-            return MMISS_OK;
+            return launch_quantize_weights_fp8_csum(st, wf.as<uint16_t>(), w8.as<uint8_t>(), sc.as<float>(), c16.as<uint16_t>(), N, K);
         };
         for (LayerW& L : tw->L) {
             MM_TRY(quant(L.wqkv, L.wqkv8, L.sqkv, 3 * d, d));
@@ -1377,12 +1283,11 @@ extern "C" int mmiss_encoder_calibration_set(mmiss_encoder* enc, const float* mu
     MM_HIP(hipMemcpyAsync(tw.cal_mu.p, mu, (size_t)n * 4, mmiss_is_device_ptr(mu) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     for (int l = 0; l < tw.layers; ++l) {
         LayerW& L = tw.L[l];
-        hipLaunchKernelGGL(beta_centre_kernel, dim3(1), dim3(256), 0, st, L.ln1b.as<float>(), tw.cal_mu.as<float>() + (size_t)(2 * l) * d,
-                           L.ln1b_c.as<float>(), tw.cal_cnt.as<int32_t>() + 2 * l, d);
-        hipLaunchKernelGGL(beta_centre_kernel, dim3(1), dim3(256), 0, st, L.ln2b.as<float>(), tw.cal_mu.as<float>() + (size_t)(2 * l + 1) * d,
-                           L.ln2b_c.as<float>(), tw.cal_cnt.as<int32_t>() + 2 * l + 1, d);
+        MM_TRY(launch_beta_centre(st, L.ln1b.as<float>(), tw.cal_mu.as<float>() + (size_t)(2 * l) * d, L.ln1b_c.as<float>(),
+                                  tw.cal_cnt.as<int32_t>() + 2 * l, d));
+        MM_TRY(launch_beta_centre(st, L.ln2b.as<float>(), tw.cal_mu.as<float>() + (size_t)(2 * l + 1) * d, L.ln2b_c.as<float>(),
+                                  tw.cal_cnt.as<int32_t>() + 2 * l + 1, d));
     }
-    MM_HIP(hipGetLastError());
     return finish_calibration(enc, st, 0);   // (rows seen: none, the table was measured elsewhere)
 }
 
@@ -1546,7 +1451,7 @@ extern "C" int mmiss_encoder_tap(mmiss_encoder* enc, int tower, int what, float*
         n = (int64_t)B * d;
         if (n > cap) n = cap;
         MM_TRY(tmp.alloc((size_t)n * 4));
-        hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(256), dim3(256), 0, st, tw.pooled.as<uint16_t>(), tmp.as<float>(), n);
+        MM_TRY(launch_bf16_to_f32(st, tw.pooled.as<uint16_t>(), tmp.as<float>(), n));
         MM_HIP(hipStreamSynchronize(st));
         MM_HIP(hipMemcpy(out, tmp.p, (size_t)n * 4, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     } else if (what == 101) {
@@ -1560,494 +1465,4 @@ extern "C" int mmiss_encoder_tap(mmiss_encoder* enc, int tower, int what, float*
     return MMISS_OK;
 }
 
-// ================================================================================================ debug ABI
-// ms per launch of run() on st over `iters` launches, after three warm-up launches; the events are destroyed on every path
-template <typename Run>
-static int time_launches(hipStream_t st, int iters, Run&& run, float* ms_per_launch) {
-    struct Events {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    MM_HIP(hipEventCreate(&ev.e0));
-    MM_HIP(hipEventCreate(&ev.e1));
-    for (int i = 0; i < 3; ++i) MM_TRY(run());
-    MM_HIP(hipEventRecord(ev.e0, st));
-    for (int i = 0; i < iters; ++i) MM_TRY(run());
-    MM_HIP(hipEventRecord(ev.e1, st));
-    MM_HIP(hipEventSynchronize(ev.e1));
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    *ms_per_launch = ms / iters;
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_gemm(int device, void* hip_stream, int epi, int variant, const void* A, const void* W,
-                              void* out, const float* bias, const float* aux, int32_t M, int32_t N, int32_t K,
-                              int32_t p0, int32_t p1) {
-    if (!A || !W || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    GemmEpi ep{};
-    ep.out = out; ep.bias = bias; ep.aux = aux; ep.ldo = N; ep.m_valid = M; ep.p0 = p0; ep.p1 = p1;
-    static DevBuf dbg_splitk;  // debug entry only: scratch so that the split-K path can be exercised
-    if ((int64_t)M * N <= (1 << 22)) {
-        MM_TRY(dbg_splitk.ensure((size_t)8 * M * N * 4));
-        ep.splitk_ws = dbg_splitk.as<float>(); ep.splitk_ws_bytes = dbg_splitk.bytes;
-    }
-    if (variant == 256) return launch_gemm256(reinterpret_cast<hipStream_t>(hip_stream), epi, A, W, ep, M, N, K);
-    if (variant > 1000) MM_FAIL(MMISS_ERR_UNSUPPORTED, "GEMM variant %d (ring pipeline / BM x 256 tiles) was removed in round 4: measured slower, profiles/gemm_variants_r01.md", variant);
-    return launch_gemm(reinterpret_cast<hipStream_t>(hip_stream), epi, variant, A, W, ep, M, N, K);
-}
-
-// the persistent 256 x 256 kernel in isolation (gemm_bf16_p256.h): epi 1 / 2 (bias, bias + QuickGELU) or 7 / 8 (the same
-// behind a folded LayerNorm: ln_stats [M][K/64][2], aux = c [N], bias = b' [N]); iters > 0 also times it
-extern "C" int mmiss_dbg_gemm_p256(int device, void* hip_stream, int epi, const void* A, const void* W, void* out,
-                                   const float* bias, const float* aux, const float* ln_stats, float ln_eps, int32_t M,
-                                   int32_t N, int32_t K, int32_t m_valid, int32_t iters, float* ms_per_launch) {
-    if (!A || !W || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_p256: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    GemmEpi ep{};
-    ep.out = out; ep.bias = bias; ep.aux = aux; ep.ldo = N; ep.m_valid = m_valid;
-    ep.ln_stats = ln_stats; ep.ln_parts = K / 64; ep.ln_eps = ln_eps;
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    auto run = [&]() -> int { return launch_gemm256p(st, epi, A, W, ep, M, N, K); };
-    if (iters <= 0 || !ms_per_launch) return run();
-    return time_launches(st, iters, run, ms_per_launch);
-}
-
-// the residual GEMM on a bf16 stream (out = bf16(f32(out) + A W^T + bias), in place; stats_out [M][N/64][2] optional) in
-// isolation: variant 0 = the 160 x 256 tile on the staggered loop (gemm160p_kernel), 128 / 160 / 192 = the 128-column kernel
-// with that tile height; iters > 0 also times it (the stream keeps accumulating: only the time means anything then)
-extern "C" int mmiss_dbg_gemm_resid16(int device, void* hip_stream, int variant, const void* A, const void* W, void* out,
-                                      const float* bias, float* stats_out, int32_t M, int32_t N, int32_t K, int32_t m_valid,
-                                      int32_t iters, float* ms_per_launch) {
-    if (!A || !W || !out || !bias) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_resid16: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    GemmEpi ep{};
-    ep.out = out; ep.bias = bias; ep.ldo = N; ep.m_valid = m_valid; ep.stats_out = stats_out;
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    auto run = [&]() -> int {
-        return variant == 0 ? launch_gemm160p(st, A, W, ep, M, N, K) : launch_gemm_resid16(st, variant, A, W, ep, M, N, K);
-    };
-    if (iters <= 0 || !ms_per_launch) return run();
-    return time_launches(st, iters, run, ms_per_launch);
-}
-
-extern "C" int mmiss_dbg_gemm_time(int device, int epi, int variant, const void* A, const void* W, void* out,
-                                   const float* bias, const float* aux, int32_t M, int32_t N, int32_t K, int32_t p0,
-                                   int32_t p1, int32_t iters, float* ms_per_launch) {
-    if (!A || !W || !out || !ms_per_launch || iters <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_time: bad argument");
-    MM_TRY(mmiss_use_device(device));
-    GemmEpi ep{};
-    ep.out = out; ep.bias = bias; ep.aux = aux; ep.ldo = N; ep.m_valid = M; ep.p0 = p0; ep.p1 = p1;
-    auto run = [&]() -> int {
-        if (variant == 256) return launch_gemm256(nullptr, epi, A, W, ep, M, N, K);
-        if (variant > 1000) MM_FAIL(MMISS_ERR_UNSUPPORTED, "GEMM variant %d was removed in round 4", variant);
-        return launch_gemm(nullptr, epi, variant, A, W, ep, M, N, K);
-    };
-    return time_launches(nullptr, iters, run, ms_per_launch);
-}
-
-extern "C" int mmiss_dbg_layernorm(int device, void* hip_stream, const float* x, const float* gamma, const float* beta,
-                                   void* out, int32_t out_bf16, int32_t M, int32_t d, float eps) {
-    if (!x || !gamma || !beta || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_layernorm: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    return launch_layernorm(reinterpret_cast<hipStream_t>(hip_stream), x, gamma, beta, out, out_bf16 != 0, nullptr, M, d,
-                            eps);
-}
-
-extern "C" int mmiss_dbg_attention(int device, void* hip_stream, const void* qkv, void* ctx, int32_t B, int32_t T,
-                                   int32_t H, int32_t causal) {
-    if (!qkv || !ctx) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_attention: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    return launch_attention(reinterpret_cast<hipStream_t>(hip_stream), qkv, ctx, B, T, H, causal != 0);
-}
-
-extern "C" int mmiss_dbg_attention_pooled(int device, void* hip_stream, const void* qkv, const int32_t* pool_row, void* ctxc,
-                                          int32_t B, int32_t T, int32_t H, int32_t causal) {
-    if (!qkv || !pool_row || !ctxc) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_attention_pooled: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    return launch_attention_pooled(reinterpret_cast<hipStream_t>(hip_stream), qkv, ctxc, pool_row, B, T, H, causal != 0);
-}
-
-// attention_tiled_kernel at any 1 <= T <= MMISS_MAX_TOKENS (the product routes T <= 288 to the other kernels): bf16 rows into ctx,
-// or with ctx8 != NULL MXFP8 into ctx8 / ctx_scale (non-causal)
-extern "C" int mmiss_dbg_attention_tiled(int device, void* hip_stream, const void* qkv, void* ctx, void* ctx8, void* ctx_scale,
-                                         int32_t B, int32_t T, int32_t H, int32_t causal) {
-    if (!qkv || (!ctx8 && !ctx) || (ctx8 && !ctx_scale)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_attention_tiled: null pointer");
-    if (T <= 0 || T > MMISS_MAX_TOKENS || H <= 0 || B < 0 || (ctx8 && causal))
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "mmiss_dbg_attention_tiled: B=%d T=%d (1..%d) H=%d causal=%d%s", B, T, MMISS_MAX_TOKENS, H, causal,
-                ctx8 ? " (MXFP8 output is non-causal)" : "");
-    MM_TRY(mmiss_use_device(device));
-    if (B == 0) return MMISS_OK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    if (ctx8)
-        return launch_attention_tiled<false, true>(st, qkv, nullptr, reinterpret_cast<uint8_t*>(ctx8), reinterpret_cast<uint8_t*>(ctx_scale),
-                                                   mx_scale_row_bytes(H * 64), B, T, H);
-    return causal ? launch_attention_tiled<true, false>(st, qkv, ctx, nullptr, nullptr, 0, B, T, H)
-                  : launch_attention_tiled<false, false>(st, qkv, ctx, nullptr, nullptr, 0, B, T, H);
-}
-
-// The LayerNorm chain around the folded GEMMs, kernel by kernel: the launches of embed_image / run_layers /
-// mmiss_encoder_finalize with the same grid formulas, on caller-owned buffers.
-extern "C" int mmiss_dbg_layernorm16(int device, void* hip_stream, const void* x_bf16, const float* gamma, const float* beta,
-                                     void* out_bf16, int32_t M, int32_t d, float eps) {
-    if (!x_bf16 || !gamma || !beta || !out_bf16) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_layernorm16: null pointer");
-    if (M <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "layernorm16: M=%d", M);
-    MM_TRY(mmiss_use_device(device));
-    return launch_layernorm16(reinterpret_cast<hipStream_t>(hip_stream), reinterpret_cast<const uint16_t*>(x_bf16), gamma, beta,
-                              out_bf16, M, d, eps);
-}
-
-extern "C" int mmiss_dbg_layernorm_gather(int device, void* hip_stream, const float* x, const float* gamma, const float* beta,
-                                          void* out, int32_t out_bf16, const int32_t* rowmap, int32_t M, int32_t d, float eps) {
-    if (!x || !gamma || !beta || !out || !rowmap) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_layernorm_gather: null pointer");
-    if (M <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "layernorm_gather: M=%d", M);
-    MM_TRY(mmiss_use_device(device));
-    return launch_layernorm(reinterpret_cast<hipStream_t>(hip_stream), x, gamma, beta, out, out_bf16 != 0, rowmap, M, d, eps);
-}
-
-extern "C" int mmiss_dbg_prelayernorm_stats(int device, void* hip_stream, float* x, const float* gamma, const float* beta, void* xb,
-                                            float* stats, int32_t M, int32_t d, int32_t parts, float eps, int32_t lean,
-                                            const float* cls, const float* pos, int32_t T) {
-    if (!x || !gamma || !beta || !xb || !stats || (lean && (!cls || !pos)))
-        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_prelayernorm_stats: null pointer");
-    if (M <= 0 || d <= 0 || d % 4 || d > 1024 || parts < 1 || (lean && T < 1))
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "prelayernorm_stats: M=%d d=%d (d%%4==0, d<=1024) parts=%d T=%d", M, d, parts, T);
-    MM_TRY(mmiss_use_device(device));
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    if (lean)
-        hipLaunchKernelGGL(layernorm_stats_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, x, gamma, beta,
-                           reinterpret_cast<uint16_t*>(xb), stats, M, d, parts, eps, cls, pos, T);
-    else
-        hipLaunchKernelGGL(layernorm_stats_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, x, gamma, beta,
-                           reinterpret_cast<uint16_t*>(xb), stats, M, d, parts, eps, (const float*)nullptr, (const float*)nullptr, 1);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_prelayernorm_skinny(int device, void* hip_stream, float* x, const float* cls, const float* pos,
-                                             const float* gamma, const float* beta, void* xb, float* stats16, int32_t M, int32_t T,
-                                             int32_t d, float eps) {
-    if (!x || !cls || !pos || !gamma || !beta || !xb || !stats16) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_prelayernorm_skinny: null pointer");
-    if (M <= 0 || T < 1 || d <= 0 || d % 16 || d > 1024)
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "prelayernorm_skinny: M=%d T=%d d=%d (d%%16==0, d<=1024)", M, T, d);
-    MM_TRY(mmiss_use_device(device));
-    hipLaunchKernelGGL(prelayernorm_skinny_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), x, cls,
-                       pos, gamma, beta, reinterpret_cast<uint16_t*>(xb), stats16, M, T, d, eps);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_row_stats(int device, void* hip_stream, const float* x, float* stats, void* xb_or_null, int32_t M, int32_t d,
-                                   int32_t parts) {
-    if (!x || !stats) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_row_stats: null pointer");
-    if (M <= 0 || d <= 0 || d % 4 || parts < 1) MM_FAIL(MMISS_ERR_UNSUPPORTED, "row_stats: M=%d d=%d (d%%4==0) parts=%d", M, d, parts);
-    MM_TRY(mmiss_use_device(device));
-    hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), x, stats,
-                       reinterpret_cast<uint16_t*>(xb_or_null), M, d, parts);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-// The one-request folded chain (P.sfold), kernel by kernel: the launches of run_layers / run_wide / run_resid on caller-owned
-// buffers. None of the three falls back to a tiled kernel: where the skinny path would not run they refuse.
-extern "C" int mmiss_dbg_row_stats16(int device, void* hip_stream, const float* x, float* stats16, void* xb, int32_t M, int32_t d) {
-    if (!x || !stats16 || !xb) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_row_stats16: null pointer");
-    if (M <= 0 || d <= 0 || d % 16) MM_FAIL(MMISS_ERR_UNSUPPORTED, "row_stats16: M=%d d=%d (d%%16==0)", M, d);
-    MM_TRY(mmiss_use_device(device));
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    MM_PROF("row_stats", st, 3.0 * M * d, 6.0 * M * d);
-    hipLaunchKernelGGL(skinny_row_stats16_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, stats16, reinterpret_cast<uint16_t*>(xb), M, d);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_gemm_skinny_fold(int device, void* hip_stream, int epi, const void* A, const void* Wf, void* out, const float* bf,
-                                          const float* c, const float* stats16, float eps, int32_t M, int32_t N, int32_t K) {
-    if (!A || !Wf || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_skinny_fold: null pointer");
-    // (the kernel reads a row's partials, c and b' as 16-byte vectors)
-    if ((reinterpret_cast<uintptr_t>(stats16) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(bf)) & 15)
-        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_skinny_fold: stats16, c and bf must be 16-byte aligned");
-    if (epi != MMISS_EPI_LNFOLD_BF16 && epi != MMISS_EPI_LNFOLD_QGELU_BF16)
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm_skinny_fold: epilogue %d (7 or 8)", epi);
-    if (M <= 0 || N <= 0 || K <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm_skinny_fold: M=%d N=%d K=%d", M, N, K);
-    MM_TRY(mmiss_use_device(device));
-    GemmEpi ep{};
-    ep.out = out; ep.bias = bf; ep.aux = c; ep.ldo = N; ep.m_valid = M;
-    ep.ln_stats = stats16; ep.ln_eps = eps; ep.ln_parts = K / 16; ep.stats16 = 1;
-    return launch_gemm_skinny_fold(reinterpret_cast<hipStream_t>(hip_stream), epi, A, Wf, ep, M, N, K);
-}
-
-extern "C" int mmiss_dbg_gemm_skinny_resid(int device, void* hip_stream, const void* A, const void* W, float* x, const float* bias,
-                                           float* stats16_out, void* xb_out, int32_t M, int32_t N, int32_t K) {
-    if (!A || !W || !x || !bias) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_skinny_resid: null pointer");
-    GemmEpi ep{};
-    ep.out = x; ep.bias = bias; ep.ldo = N; ep.m_valid = M;
-    ep.stats_out = stats16_out; ep.xb_out = xb_out; ep.stats16 = 1;
-    if (M <= 0 || N <= 0 || K <= 0 || !gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, M, N, K, ep))
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm_skinny_resid: M=%d N=%d K=%d is not a skinny GEMM", M, N, K);
-    MM_TRY(mmiss_use_device(device));
-    return launch_gemm(reinterpret_cast<hipStream_t>(hip_stream), MMISS_EPI_BIAS_RESID_F32, 128, A, W, ep, (int)round_up(M, 128), N, K);
-}
-
-extern "C" int mmiss_dbg_ln_finalize(int device, void* hip_stream, const float* stats, float* out, int32_t M, int32_t parts, int32_t d,
-                                     float eps) {
-    if (!stats || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_ln_finalize: null pointer");
-    // (the kernel reads the partials of a row as 16-byte pairs of (sum, sumsq): an even count, rows 16-byte aligned)
-    if (M <= 0 || d <= 0 || parts < 2 || parts % 2 || (reinterpret_cast<uintptr_t>(stats) & 15))
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "ln_finalize: M=%d d=%d parts=%d (even, >= 2; stats 16-byte aligned)", M, d, parts);
-    MM_TRY(mmiss_use_device(device));
-    hipLaunchKernelGGL(ln_finalize_kernel, dim3((M * 8 + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), stats, out,
-                       M, parts, d, eps);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_fold_ln_weights(int device, void* hip_stream, const void* w_bf16, const float* gamma, const float* beta,
-                                         const float* bias, void* wf, float* c, float* bf, int32_t N, int32_t K) {
-    if (!w_bf16 || !gamma || !beta || !bias || !wf || !c || !bf) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_fold_ln_weights: null pointer");
-    if (N <= 0 || K <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "fold_ln_weights: N=%d K=%d", N, K);
-    MM_TRY(mmiss_use_device(device));
-    hipLaunchKernelGGL(fold_ln_weights_kernel, dim3((N + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream),
-                       reinterpret_cast<const uint16_t*>(w_bf16), gamma, beta, bias, reinterpret_cast<uint16_t*>(wf), c, bf, N, K);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_gemm_resid_rows(int device, void* hip_stream, const void* A, const void* W, float* out, const float* bias,
-                                         const void* rows_bf16, const int32_t* rowmap, int32_t M, int32_t N, int32_t K) {
-    if (!A || !W || !out || !bias || !rows_bf16 || !rowmap) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_resid_rows: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    GemmEpi ep{};
-    ep.out = out; ep.bias = bias; ep.ldo = N; ep.m_valid = M;
-    ep.resid16_rows = reinterpret_cast<const uint16_t*>(rows_bf16); ep.resid_rowmap = rowmap;
-    return launch_gemm(reinterpret_cast<hipStream_t>(hip_stream), MMISS_EPI_BIAS_RESID_F32, 128, A, W, ep, (int)round_up(M, 128), N, K);
-}
-
-extern "C" int mmiss_dbg_patch_from_pixels(int device, void* hip_stream, const float* pixels, const void* W, float* out,
-                                           const float* pos, int32_t B, int32_t S, int32_t P, int32_t d) {
-    if (!pixels || !W || !out || !pos) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_patch_from_pixels: null pointer");
-    if (P <= 0 || S <= 0 || S % P || B <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_patch_from_pixels: B=%d S=%d P=%d", B, S, P);
-    MM_TRY(mmiss_use_device(device));
-    const int G = S / P;
-    GemmEpi ep{};
-    ep.out = out; ep.aux = pos; ep.ldo = d; ep.m_valid = B * G * G; ep.p0 = G * G; ep.p1 = G * G + 1;
-    return launch_gemm160p_patch_pix(reinterpret_cast<hipStream_t>(hip_stream), pixels, W, ep, B, S, P, (int)round_up(B * G * G, 160), d,
-                                     3 * P * P);
-}
-
-extern "C" int mmiss_dbg_im2col(int device, void* hip_stream, const float* pixels, void* out, int32_t B, int32_t S,
-                                int32_t P, int32_t Kp) {
-    if (!pixels || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_im2col: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    return launch_im2col(reinterpret_cast<hipStream_t>(hip_stream), pixels, false, out, B, S, P, Kp);
-}
-
-
-// Experiment (tools/gemm_split_test.py): one GEMM over M rows vs two half-M GEMMs back to back vs the two halves on
-// two streams joined by events. ms[0..2] = milliseconds per GEMM-equivalent.
-extern "C" int mmiss_dbg_gemm_split_time(int device, int epi, int bm, const void* A, const void* W, void* out,
-                                         const float* bias, int32_t M, int32_t N, int32_t K, int32_t iters, float* ms) {
-    if (!A || !W || !out || !ms || iters <= 0 || (M % (2 * bm))) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_split_time: bad argument");
-    MM_TRY(mmiss_use_device(device));
-    hipStream_t s0, s1;
-    MM_HIP(hipStreamCreateWithFlags(&s0, hipStreamNonBlocking));
-    MM_HIP(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
-    hipEvent_t e0, e1, fork, join;
-    MM_HIP(hipEventCreate(&e0)); MM_HIP(hipEventCreate(&e1));
-    MM_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming)); MM_HIP(hipEventCreateWithFlags(&join, hipEventDisableTiming));
-    const int out_elt = (epi == MMISS_EPI_BIAS_BF16 || epi == MMISS_EPI_BIAS_QGELU_BF16) ? 2 : 4;
-    const int Mh = M / 2;
-    auto full = [&](hipStream_t s) -> int {
-        GemmEpi ep{}; ep.out = out; ep.bias = bias; ep.ldo = N; ep.m_valid = M;
-        return launch_gemm(s, epi, bm, A, W, ep, M, N, K);
-    };
-    auto half = [&](hipStream_t s, int which) -> int {
-        GemmEpi ep{}; ep.out = (char*)out + (size_t)which * Mh * N * out_elt; ep.bias = bias; ep.ldo = N; ep.m_valid = Mh;
-        return launch_gemm(s, epi, bm, (const char*)A + (size_t)which * Mh * K * 2, W, ep, Mh, N, K);
-    };
-    for (int mode = 0; mode < 3; ++mode) {
-        for (int it = -3; it < iters; ++it) {
-            if (it == 0) MM_HIP(hipEventRecord(e0, s0));
-            if (mode == 0) { MM_TRY(full(s0)); }
-            else if (mode == 1) { MM_TRY(half(s0, 0)); MM_TRY(half(s0, 1)); }
-            else {
-                MM_HIP(hipEventRecord(fork, s0));
-                MM_HIP(hipStreamWaitEvent(s1, fork, 0));
-                MM_TRY(half(s0, 0));
-                MM_TRY(half(s1, 1));
-                MM_HIP(hipEventRecord(join, s1));
-                MM_HIP(hipStreamWaitEvent(s0, join, 0));
-            }
-        }
-        MM_HIP(hipEventRecord(e1, s0));
-        MM_HIP(hipEventSynchronize(e1));
-        float t = 0.f;
-        MM_HIP(hipEventElapsedTime(&t, e0, e1));
-        ms[mode] = t / iters;
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(fork); (void)hipEventDestroy(join);
-    (void)hipStreamDestroy(s0); (void)hipStreamDestroy(s1);
-    return MMISS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ calibration kernels in isolation
-// x f32 (or bf16 when x_is_bf16) [M,d] -> the column statistics of LayerNorm(x; gamma, beta): mean_out, var_out f64 [d] (population
-// variance), mu_out f32 [d] (the mean where mean^2 >= var, else 0), centred_out int32 [1]
-extern "C" int mmiss_dbg_ln_colstats(int device, void* hip_stream, const void* x, int32_t x_is_bf16, const float* gamma, const float* beta,
-                                     int32_t M, int32_t d, float eps, double* mean_out, double* var_out, float* mu_out, int32_t* centred_out) {
-    if (!x || !gamma || !beta || !mean_out || !var_out || !mu_out || !centred_out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_ln_colstats: null pointer");
-    if (M < 1) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_ln_colstats: M = %d", M);
-    MM_TRY(mmiss_use_device(device));
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    DevBuf part;   // (debug entry only: allocated and freed around the call)
-    MM_TRY(part.alloc(cal_partial_bytes(M, d)));
-    MM_TRY(launch_ln_colstats(st, x, x_is_bf16 != 0, gamma, beta, part.as<double>(), M, d, eps, mu_out, nullptr, centred_out, mean_out, var_out));
-    MM_HIP(hipStreamSynchronize(st));
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_bias_fold(int device, void* hip_stream, const void* w_bf16, const float* bias, const float* mu, int32_t N, int32_t K,
-                                   float* out) {
-    if (!w_bf16 || !bias || !mu || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_bias_fold: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    return launch_bias_fold(reinterpret_cast<hipStream_t>(hip_stream), w_bf16, bias, mu, out, N, K);
-}
-
-// ------------------------------------------------------------------------------------------------ resize tables in isolation
-// resize_geometry + one resize_coeffs_kernel launch for a single descriptor, with resize_chunk's grid, block and pool layout
-extern "C" int mmiss_dbg_resize_coeffs(int device, void* hip_stream, int32_t H, int32_t W, int32_t S, int32_t* geometry,
-                                       int32_t* pool, int32_t* bounds) {
-    if (!geometry) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_resize_coeffs: null geometry");
-    if ((pool == nullptr) != (bounds == nullptr)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_resize_coeffs: pool and bounds go together");
-    if (S < 1 || S > (1 << 14)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_resize_coeffs: S = %d outside 1..16384", S);
-    if (H < 1 || W < 1 || H > (1 << 16) || W > (1 << 16))
-        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_resize_coeffs: size %d x %d outside 1..65536", W, H);
-    ResizeDesc d;
-    resize_geometry(H, W, S, d);
-    if (d.ksx > 4096 || d.ksy > 4096)
-        MM_FAIL(MMISS_ERR_UNSUPPORTED, "mmiss_dbg_resize_coeffs: %d x %d -> %d needs %d / %d filter taps (limit 4096)", W, H, S, d.ksx,
-                d.ksy);
-    d.src_off = 0;
-    d.kx_off = 0;
-    d.ky_off = (int64_t)d.ksx * S;
-    const int32_t g[6] = {d.new_h, d.new_w, d.top, d.left, d.ksx, d.ksy};
-    memcpy(geometry, g, sizeof(g));
-    if (!pool) return MMISS_OK;
-    MM_TRY(mmiss_use_device(device));
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    ResizeDesc* dd = nullptr;
-    MM_HIP(hipMalloc(reinterpret_cast<void**>(&dd), sizeof(ResizeDesc)));
-    hipError_t err = hipMemcpyAsync(dd, &d, sizeof(ResizeDesc), hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(resize_coeffs_kernel, dim3(1, 2), dim3(256), 0, st, dd, pool, bounds, S);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(st);  // the descriptor is freed below, and is read from this stack frame
-    (void)hipFree(dd);
-    MM_HIP(err);
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_resize_crop_variant(int64_t blob_bytes, int32_t max_ksx) { return resize_crop_variant(blob_bytes, max_ksx); }
-
-// ------------------------------------------------------------------------------------------------ fp8 kernels in isolation
-extern "C" int mmiss_dbg_quantize_weights_fp8(int device, void* hip_stream, const void* w_bf16, void* w8, float* scale,
-                                              int32_t N, int32_t K) {
-    if (!w_bf16 || !w8 || !scale || N <= 0 || K <= 0 || (K % 4)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_quantize_weights_fp8: bad argument");
-    MM_TRY(mmiss_use_device(device));
-    hipLaunchKernelGGL(quantize_weights_fp8_kernel, dim3((N + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream),
-                       reinterpret_cast<const uint16_t*>(w_bf16), reinterpret_cast<uint8_t*>(w8), scale, N, K);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-// bf16 rows in (the bf16 residual stream): d = 512 / 1024 take the wide kernel of round 4, other d the first form
-extern "C" int mmiss_dbg_layernorm16_mxfp8(int device, void* hip_stream, const void* x_bf16, const float* gamma, const float* beta,
-                                           void* out8, void* out_scale, int32_t M, int32_t d, float eps) {
-    if (!x_bf16 || !gamma || !beta || !out8 || !out_scale) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_layernorm16_mxfp8: null pointer");
-    if (M <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_layernorm16_mxfp8: M = %d", M);
-    MM_TRY(mmiss_use_device(device));
-    return launch_layernorm_mxfp8(reinterpret_cast<hipStream_t>(hip_stream), x_bf16, true, gamma, beta,
-                                  reinterpret_cast<uint8_t*>(out8), reinterpret_cast<uint8_t*>(out_scale), M, d, eps);
-}
-
-// qkv bf16 [B*T, 3*H*64] -> the attention output as MXFP8: ctx8 e4m3 [B*T, H*64] + permuted E8M0 scales [B*T, 16 * ceil(H*64 / 512)]
-// (non-causal; T <= 128: the one-pass kernels, 129 <= T <= 288: the long-sequence form, above up to MMISS_MAX_TOKENS: key chunks)
-extern "C" int mmiss_dbg_attention_mx(int device, void* hip_stream, const void* qkv, void* ctx8, void* ctx_scale, int32_t B,
-                                      int32_t T, int32_t H) {
-    if (!qkv || !ctx8 || !ctx_scale) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_attention_mx: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    return launch_attention_mx(reinterpret_cast<hipStream_t>(hip_stream), qkv, reinterpret_cast<uint8_t*>(ctx8),
-                               reinterpret_cast<uint8_t*>(ctx_scale), mx_scale_row_bytes(H * 64), B, T, H);
-}
-
-extern "C" int mmiss_dbg_layernorm_mxfp8(int device, void* hip_stream, const float* x, const float* gamma, const float* beta,
-                                         void* out8, void* out_scale, int32_t M, int32_t d, float eps) {
-    if (!x || !gamma || !beta || !out8 || !out_scale) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_layernorm_mxfp8: null pointer");
-    MM_TRY(mmiss_use_device(device));
-    return launch_layernorm_mxfp8(reinterpret_cast<hipStream_t>(hip_stream), x, false, gamma, beta, reinterpret_cast<uint8_t*>(out8),
-                                  reinterpret_cast<uint8_t*>(out_scale), M, d, eps);
-}
-
-extern "C" int mmiss_dbg_gemm8(int device, void* hip_stream, int epi, int bm, const void* A8, const void* As, const void* W8,
-                               const float* wscale, const float* bias, void* out, void* out_scale, int32_t M, int32_t N,
-                               int32_t K) {
-    MM_TRY(mmiss_use_device(device));
-    Gemm8Args g{};
-    g.A = reinterpret_cast<const uint8_t*>(A8); g.As = reinterpret_cast<const uint8_t*>(As); g.ld_as = mx_scale_row_bytes(K);
-    g.W = reinterpret_cast<const uint8_t*>(W8); g.wscale = wscale; g.bias = bias; g.out = out;
-    g.out_scale = reinterpret_cast<uint8_t*>(out_scale); g.ld_os = mx_scale_row_bytes(N);
-    g.M = M; g.N = N; g.K = K; g.ldo = N; g.m_valid = M;
-    if (bm >= 256) {   // the persistent 256 x 256 kernel (gemm_fp8_p256.h); bm = 256 + v: only the first v rows are valid
-        if (bm > 256) g.m_valid = bm - 256 < M ? bm - 256 : M;
-        return launch_gemm256p8(reinterpret_cast<hipStream_t>(hip_stream), epi, g);
-    }
-    return launch_gemm8(reinterpret_cast<hipStream_t>(hip_stream), epi, bm, g);
-}
-
-extern "C" int mmiss_dbg_gemm8_xt(int device, void* hip_stream, int epi, int xt, const void* A8, const void* As, const void* W8,
-                                  const float* wscale, const float* bias, void* out, void* out_scale, int32_t M, int32_t N, int32_t K,
-                                  int32_t m_valid, const void* c16, const float* ln_stats, const void* x16, float ln_eps,
-                                  void* q_out, void* q_scale, float* stats_out) {
-    MM_TRY(mmiss_use_device(device));
-    Gemm8Args g{};
-    g.A = reinterpret_cast<const uint8_t*>(A8); g.As = reinterpret_cast<const uint8_t*>(As); g.ld_as = mx_scale_row_bytes(K);
-    g.W = reinterpret_cast<const uint8_t*>(W8); g.wscale = wscale; g.bias = bias; g.out = out;
-    g.out_scale = reinterpret_cast<uint8_t*>(out_scale); g.ld_os = mx_scale_row_bytes(N);
-    g.M = M; g.N = N; g.K = K; g.ldo = N; g.m_valid = m_valid > 0 && m_valid < M ? m_valid : M;
-    g.c16 = reinterpret_cast<const uint16_t*>(c16); g.ln_stats = ln_stats; g.x16 = reinterpret_cast<const uint16_t*>(x16); g.ln_eps = ln_eps;
-    g.q_out = reinterpret_cast<uint8_t*>(q_out); g.q_scale = reinterpret_cast<uint8_t*>(q_scale); g.ld_qs = mx_scale_row_bytes(N);
-    g.stats_out = stats_out;
-    return launch_gemm256p8(reinterpret_cast<hipStream_t>(hip_stream), epi, g, xt);
-}
-
-extern "C" int mmiss_dbg_quant16_mxfp8_stats(int device, void* hip_stream, const void* x_bf16, void* out8, void* out_scale,
-                                             float* stats, int32_t M, int32_t d) {
-    if (!x_bf16 || !out8 || !out_scale || !stats || M <= 0 || d != 1024) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_quant16_mxfp8_stats: bad argument (d must be 1024)");
-    MM_TRY(mmiss_use_device(device));
-    hipLaunchKernelGGL(quant16_mxfp8_stats_1024_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream),
-                       reinterpret_cast<const uint16_t*>(x_bf16), reinterpret_cast<uint8_t*>(out8), reinterpret_cast<uint8_t*>(out_scale),
-                       stats, M, mx_scale_row_bytes(d));
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_quantize_weights_fp8_csum(int device, void* hip_stream, const void* w_bf16, void* w8, float* scale, void* c16,
-                                                   int32_t N, int32_t K) {
-    if (!w_bf16 || !w8 || !scale || !c16 || N <= 0 || K <= 0 || (K % 4)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_quantize_weights_fp8_csum: bad argument");
-    MM_TRY(mmiss_use_device(device));
-    hipLaunchKernelGGL(quantize_weights_fp8_csum_kernel, dim3((N + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream),
-                       reinterpret_cast<const uint16_t*>(w_bf16), reinterpret_cast<uint8_t*>(w8), scale, reinterpret_cast<uint16_t*>(c16), N, K);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-extern "C" int mmiss_dbg_gemm8_time(int device, int epi, int bm, const void* A8, const void* As, const void* W8,
-                                    const float* wscale, const float* bias, void* out, void* out_scale, int32_t M, int32_t N,
-                                    int32_t K, int32_t iters, float* ms_per_launch) {
-    if (!ms_per_launch || iters <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm8_time: bad argument");
-    MM_TRY(mmiss_use_device(device));
-    auto run = [&]() -> int { return mmiss_dbg_gemm8(device, nullptr, epi, bm, A8, As, W8, wscale, bias, out, out_scale, M, N, K); };
-    return time_launches(nullptr, iters, run, ms_per_launch);
-}
+#include "api_encoder_debug.h"

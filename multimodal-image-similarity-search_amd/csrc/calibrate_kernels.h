@@ -217,3 +217,9 @@ static int launch_bias_fold(hipStream_t st, const void* w_bf16, const float* bia
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }
+
+static int launch_beta_centre(hipStream_t st, const float* beta, const float* mu, float* beta_out, int32_t* centred, int d) {
+    hipLaunchKernelGGL(beta_centre_kernel, dim3(1), dim3(256), 0, st, beta, mu, beta_out, centred, d);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}

@@ -504,7 +504,48 @@ __global__ void bf16_to_f32_kernel(const uint16_t* __restrict__ src, float* __re
         dst[i] = bf16_bits_to_f32(src[i]);
 }
 
+namespace {   // (the two kernels below keep the internal linkage they had in api_encoder.hip)
+
+// f32 [R,C] -> bf16 rows of stride ldd (dst pre-zeroed where ldd > C)
+__global__ void convert_2d_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t R, int C,
+                                       int ldd) {
+    const int64_t total = R * C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / C;
+        const int c = (int)(i - r * C);
+        bf16_t v = (bf16_t)src[i];
+        dst[r * ldd + c] = __builtin_bit_cast(uint16_t, v);
+    }
+}
+
+// The pruned last layer's two gathers in one launch: ctxc row r = ctx row rowmap[r] (bf16), xc row r = the residual row
+// rowmap[r] as f32 — copied from x32, or widened from x16 when the stream is bf16. d % 4 == 0.
+__global__ void gather_pooled_kernel(const uint16_t* __restrict__ ctx, uint16_t* __restrict__ ctxc, const float* __restrict__ x32,
+                                     const uint16_t* __restrict__ x16, float* __restrict__ xc, const int32_t* __restrict__ rowmap,
+                                     int n, int d) {
+    const int chunks = d >> 2;
+    const int64_t total = (int64_t)n * chunks;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / chunks), c = (int)(i - (int64_t)r * chunks);
+        const size_t so = (size_t)rowmap[r] * d + (size_t)c * 4, dofs = (size_t)r * d + (size_t)c * 4;
+        *reinterpret_cast<u32x2*>(ctxc + dofs) = *reinterpret_cast<const u32x2*>(ctx + so);
+        f32x4 o;
+        if (x16) {
+            const u32x2 v = *reinterpret_cast<const u32x2*>(x16 + so);
+            o[0] = __uint_as_float(v[0] << 16); o[1] = __uint_as_float(v[0] & 0xFFFF0000u);
+            o[2] = __uint_as_float(v[1] << 16); o[3] = __uint_as_float(v[1] & 0xFFFF0000u);
+        } else {
+            o = *reinterpret_cast<const f32x4*>(x32 + so);
+        }
+        *reinterpret_cast<f32x4*>(xc + dofs) = o;
+    }
+}
+
+}  // namespace
+
 // ------------------------------------------------------------------------------------------------ launchers
+// One per kernel: its preconditions, its profile record (where the encoder has always had one), the launch, the error check.
+// The encoder (api_encoder.hip) and the debug ABI (api_encoder_debug.h) launch through these and nowhere else.
 static int launch_layernorm(hipStream_t st, const float* x, const float* g, const float* b, void* out, bool out_bf16,
                             const int32_t* rowmap, int M, int d, float eps) {
     if (d % 4 || d > 1024 || d <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "layernorm: d=%d (need d%%4==0, d<=1024)", d);
@@ -542,6 +583,108 @@ static int launch_im2col(hipStream_t st, const void* pixels, bool src_u8, void* 
         hipLaunchKernelGGL(im2col_kernel<true>, dim3(grid), dim3(256), 0, st, pixels, (uint16_t*)out, B, S, P, Kp);
     else
         hipLaunchKernelGGL(im2col_kernel<false>, dim3(grid), dim3(256), 0, st, pixels, (uint16_t*)out, B, S, P, Kp);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_cls_rows(hipStream_t st, float* x, const float* cls, const float* pos, int B, int T, int d) {
+    MM_PROF("cls_rows", st, (double)B * d, 12.0 * B * d);
+    hipLaunchKernelGGL(cls_rows_kernel, dim3((B * d + 255) / 256), dim3(256), 0, st, x, cls, pos, B, T, d);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_prelayernorm_skinny(hipStream_t st, float* x, const float* cls, const float* pos, const float* g, const float* b, uint16_t* xb,
+                                      float* stats16, int M, int T, int d, float eps) {
+    if (M <= 0 || T < 1 || d <= 0 || d % 16 || d > 1024) MM_FAIL(MMISS_ERR_UNSUPPORTED, "prelayernorm_skinny: M=%d T=%d d=%d (d%%16==0, d<=1024)", M, T, d);
+    MM_PROF("layernorm", st, 12.0 * M * d, (double)M * d * 10);
+    hipLaunchKernelGGL(prelayernorm_skinny_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, cls, pos, g, b, xb, stats16, M, T, d, eps);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+// lean: x is only read and the CLS rows are made here from cls + pos, one per T rows; otherwise cls, pos and T are not used
+static int launch_layernorm_stats(hipStream_t st, float* x, const float* g, const float* b, uint16_t* xb, float* stats, int M, int d, int parts,
+                                  float eps, bool lean, const float* cls, const float* pos, int T) {
+    if (M <= 0 || d <= 0 || d % 4 || d > 1024 || parts < 1 || (lean && T < 1))
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "prelayernorm_stats: M=%d d=%d (d%%4==0, d<=1024) parts=%d T=%d", M, d, parts, T);
+    MM_PROF("layernorm", st, 10.0 * M * d, (double)M * d * (lean ? 6 : 10));
+    const dim3 grid((M + 3) / 4), block(256);
+    if (lean) hipLaunchKernelGGL(layernorm_stats_kernel<true>, grid, block, 0, st, x, g, b, xb, stats, M, d, parts, eps, cls, pos, T);
+    else hipLaunchKernelGGL(layernorm_stats_kernel<false>, grid, block, 0, st, x, g, b, xb, stats, M, d, parts, eps, (const float*)nullptr, (const float*)nullptr, 1);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_ln_finalize(hipStream_t st, const float* stats, float* out, int M, int parts, int d, float eps) {
+    // (the kernel reads the partials of a row as 16-byte pairs of (sum, sumsq): an even count, rows 16-byte aligned)
+    if (M <= 0 || d <= 0 || parts < 2 || parts % 2 || (reinterpret_cast<uintptr_t>(stats) & 15))
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "ln_finalize: M=%d d=%d parts=%d (even, >= 2; stats 16-byte aligned)", M, d, parts);
+    MM_PROF("ln_finalize", st, 4.0 * M * parts, (double)M * (parts * 8 + 8));
+    hipLaunchKernelGGL(ln_finalize_kernel, dim3((M * 8 + 255) / 256), dim3(256), 0, st, stats, out, M, parts, d, eps);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+// stats_read = false: the separate-LayerNorm mode on a bf16 stream, where only the bf16 copy is used (the byte model leaves the statistics out)
+static int launch_row_stats(hipStream_t st, const float* x, float* stats, uint16_t* xb_or_null, int M, int d, int parts, bool stats_read) {
+    if (M <= 0 || d <= 0 || d % 4 || parts < 1) MM_FAIL(MMISS_ERR_UNSUPPORTED, "row_stats: M=%d d=%d (d%%4==0) parts=%d", M, d, parts);
+    MM_PROF("row_stats", st, 3.0 * M * d, (stats_read ? 6.0 : 4.0) * M * d);
+    hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, stats, xb_or_null, M, d, parts);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_fold_ln_weights(hipStream_t st, const uint16_t* w, const float* gamma, const float* beta, const float* bias, uint16_t* wf,
+                                  float* c, float* bf, int N, int K) {
+    if (N <= 0 || K <= 0) MM_FAIL(MMISS_ERR_UNSUPPORTED, "fold_ln_weights: N=%d K=%d", N, K);
+    hipLaunchKernelGGL(fold_ln_weights_kernel, dim3((N + 3) / 4), dim3(256), 0, st, w, gamma, beta, bias, wf, c, bf, N, K);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_text_embed(hipStream_t st, const int32_t* ids, const float* tok, const float* pos, float* x, int32_t* pool_row, int B, int T,
+                             int d, int vocab, int eos_id) {
+    if (B <= 0 || T < 1 || d <= 0 || d % 4 || vocab < 1) MM_FAIL(MMISS_ERR_UNSUPPORTED, "text_embed: B=%d T=%d d=%d (d%%4==0) vocab=%d", B, T, d, vocab);
+    hipLaunchKernelGGL(text_embed_kernel, dim3(B), dim3(256), 0, st, ids, tok, pos, x, pool_row, T, d, vocab, eos_id);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_vision_pool_rows(hipStream_t st, int32_t* pool_row, int B, int T) {
+    hipLaunchKernelGGL(vision_pool_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, st, pool_row, B, T);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+// pooled rows of the attention output (bf16) and of the residual stream (x32, or x16 widened: exactly one of the two) in ONE launch
+static int launch_gather_pooled(hipStream_t st, const uint16_t* ctx, uint16_t* ctxc, const float* x32, const uint16_t* x16, float* xc,
+                                const int32_t* rowmap, int n, int d) {
+    if (n <= 0 || d <= 0 || d % 4 || !x32 == !x16) MM_FAIL(MMISS_ERR_UNSUPPORTED, "gather_pooled: n=%d d=%d (d%%4==0; one of x32 / x16)", n, d);
+    MM_PROF("gather_pooled", st, 0.0, (double)n * d * (x16 ? 10 : 12));
+    hipLaunchKernelGGL(gather_pooled_kernel, dim3((n * d / 4 + 255) / 256), dim3(256), 0, st, ctx, ctxc, x32, x16, xc, rowmap, n, d);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_l2norm_rows(hipStream_t st, const float* y, float* out, int B, int D, int ldy) {
+    MM_PROF("l2norm_rows", st, 3.0 * B * D, 8.0 * B * D);
+    hipLaunchKernelGGL(l2norm_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, st, y, out, B, D, ldy);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_convert_2d_bf16(hipStream_t st, const float* src, uint16_t* dst, int64_t R, int C, int ldd) {
+    if (R <= 0 || C <= 0 || ldd < C) MM_FAIL(MMISS_ERR_ARG, "convert_2d_bf16: R=%lld C=%d ldd=%d", (long long)R, C, ldd);
+    const int64_t blocks = (R * C + 255) / 256;
+    hipLaunchKernelGGL(convert_2d_bf16_kernel, dim3((int)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, src, dst, R, C, ldd);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_bf16_to_f32(hipStream_t st, const uint16_t* src, float* dst, int64_t n) {
+    if (n <= 0) return MMISS_OK;
+    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(256), dim3(256), 0, st, src, dst, n);
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }

@@ -759,3 +759,26 @@ static int launch_layernorm_mxfp8(hipStream_t st, const void* x, bool x_bf16, co
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }
+
+// (the weight quantisers read a row as 8-byte groups of four: K % 4 == 0)
+static int launch_quantize_weights_fp8(hipStream_t st, const uint16_t* w, uint8_t* w8, float* scale, int N, int K) {
+    if (N <= 0 || K <= 0 || (K % 4)) MM_FAIL(MMISS_ERR_ARG, "quantize_weights_fp8: bad argument (N=%d K=%d, K %% 4 == 0)", N, K);
+    hipLaunchKernelGGL(quantize_weights_fp8_kernel, dim3((N + 3) / 4), dim3(256), 0, st, w, w8, scale, N, K);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_quantize_weights_fp8_csum(hipStream_t st, const uint16_t* w, uint8_t* w8, float* scale, uint16_t* c16, int N, int K) {
+    if (N <= 0 || K <= 0 || (K % 4)) MM_FAIL(MMISS_ERR_ARG, "quantize_weights_fp8_csum: bad argument (N=%d K=%d, K %% 4 == 0)", N, K);
+    hipLaunchKernelGGL(quantize_weights_fp8_csum_kernel, dim3((N + 3) / 4), dim3(256), 0, st, w, w8, scale, c16, N, K);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+static int launch_quant16_mxfp8_stats(hipStream_t st, const uint16_t* x16, uint8_t* out8, uint8_t* out_scale, float* stats, int M, int d) {
+    if (M <= 0 || d != 1024) MM_FAIL(MMISS_ERR_ARG, "quant16_mxfp8_stats: bad argument (M=%d d=%d; d must be 1024)", M, d);
+    MM_PROF("quant16_mxfp8_stats", st, 3.0 * M * d, 3.0 * M * d);
+    hipLaunchKernelGGL(quant16_mxfp8_stats_1024_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x16, out8, out_scale, stats, M, mx_scale_row_bytes(d));
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}

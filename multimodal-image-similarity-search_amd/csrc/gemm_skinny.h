@@ -312,3 +312,11 @@ static __global__ __launch_bounds__(256) void skinny_row_stats16_kernel(const fl
         }
     }
 }
+
+static int launch_row_stats16(hipStream_t st, const float* x, float* stats16, uint16_t* xb, int M, int d) {
+    if (M <= 0 || d <= 0 || d % 16) MM_FAIL(MMISS_ERR_UNSUPPORTED, "row_stats16: M=%d d=%d (d%%16==0)", M, d);
+    MM_PROF("row_stats", st, 3.0 * M * d, 6.0 * M * d);
+    hipLaunchKernelGGL(skinny_row_stats16_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, stats16, xb, M, d);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}

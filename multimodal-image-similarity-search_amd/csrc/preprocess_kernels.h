@@ -237,6 +237,14 @@ static inline void launch_resize_crop(hipStream_t st, int max_ksx, const uint8_t
         launch_resize_crop_vfirst(st, src, desc, pool, bounds, dst, S, nb);
 }
 
+// pool_ints: the taps the nb descriptors address in pool (the profile's byte count)
+static int launch_resize_coeffs(hipStream_t st, const ResizeDesc* desc, int32_t* pool, int32_t* bounds, int S, int nb, int64_t pool_ints) {
+    MM_PROF("resize_coeffs", st, 0.0, (double)pool_ints * 4);
+    hipLaunchKernelGGL(resize_coeffs_kernel, dim3(nb, 2), dim3(256), 0, st, desc, pool, bounds, S);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
 // Host geometry, the arithmetic of HF's get_resize_output_image_size (shortest edge -> S, long edge
 // int(S * long / short)) and centre crop ((new - S) // 2), and Pillow's ksize.
 static inline int resize_ksize(int in_size, int out_size) {

@@ -67,6 +67,14 @@ def test_product_package_never_imports_the_oracle():
                 assert "import oracle" not in text and "from oracle" not in text, f
 
 
+def test_encoder_files_launch_through_launchers_only():
+    """Every kernel the encoder runs is launched by the launch_* function beside it in its header (preconditions, profile
+    record, error check), and the debug ABI calls the same function: neither file launches a kernel itself."""
+    for f in ("api_encoder.hip", "api_encoder_debug.h"):
+        text = open(os.path.join(ROOT, "multimodal-image-similarity-search_amd", "csrc", f)).read()
+        assert "hipLaunchKernelGGL" not in text, f
+
+
 def test_persistent_gemm_kernels_do_not_spill():
     """The persistent GEMM counts its own vector-memory operations (s_waitcnt vmcnt(N) with N = loads it leaves in flight):
     a register spill is a scratch load / store the count does not know about — correct only by over-waiting, and measured
