@@ -12,7 +12,10 @@ identity (contiguous: a query's winners fill one or two 16-row tiles — one wav
 filtered_corpus(N, D, k, seed, contiguous, mirrored): 2k rows per query. k DECOYS (a from 0.97 down to 0.90) carry the bit the
 query excludes, k WINNERS (a from 0.88 down to 0.75) the bit it requires; query j requires bit j % 62 and excludes bit 63, so
 the queries of one call use different masks. Slots 0..k-1 of a query's 2k are the decoys, or, mirrored, the winners: over the
-two corpora every position hosts an admitted winner once and a better-scoring excluded row once."""
+two corpora every position hosts an admitted winner once and a better-scoring excluded row once.
+
+ghosts(p, G, kind), tiny_live and plateau (below) serve test_dead_rows_cpu.py and test_index_dead_rows_gpu.py: the hostile rows
+an emptied index keeps behind its count, and the live sets on which such a row would show."""
 import functools
 from typing import NamedTuple, Optional
 
@@ -127,6 +130,90 @@ def expected(orc, p: Planted, stored, labels, k, full: bool, which=None):
     return ol, od, oc
 
 
+# ---------------------------------------------------------------------------------------------- dead rows behind count
+# (test_dead_rows_cpu.py pins what follows, test_index_dead_rows_gpu.py leaves these rows behind the live ones)
+GHOST_LABEL0 = 10 ** 12          # ghost row r is added under GHOST_LABEL0 + r: disjoint from (and above) every live label
+GHOST_KINDS = ("twin", "nonfinite", "plateau")
+
+
+def capacity_for(N):
+    """the capacity an index created for N rows gets (1024 doubled until it holds them) = the rows a ghost corpus must fill"""
+    G = 1024
+    while G < N:
+        G *= 2
+    return G
+
+
+def ghost_owner(p: Planted, G) -> np.ndarray:
+    """int64 [G]: the query whose direction ghost row r copies, (r - N) mod Qt: behind N the queries take turns"""
+    return (np.arange(G, dtype=np.int64) - p.rows.shape[0]) % p.n_queries
+
+
+def ghosts(p: Planted, G, kind) -> np.ndarray:
+    """float32 [G, D]: the rows that fill an index of capacity G before it is emptied and the live corpus p is added; rows [N, G)
+    stay behind count. twin: row r is 3 q^_j, j = ghost_owner(p, G)[r], cosine 1.0 to query j against its best live row's 0.95
+    (a decoy's 0.97). nonfinite: the same, but of every three rows one is all NaN, all +inf or all zero (in turn), stored as
+    whatever the normalisation makes of it. plateau: every row is the first row query 0 owns (plateau(): the tied row)."""
+    assert kind in GHOST_KINDS and G >= p.rows.shape[0]
+    if kind == "plateau":
+        return np.repeat(p.rows[p.rows_of(0)[:1]], G, axis=0)
+    q64 = p.queries.astype(np.float64)
+    qh = q64 / np.linalg.norm(q64, axis=1, keepdims=True)
+    rows = (3.0 * qh[ghost_owner(p, G)]).astype(np.float32)
+    if kind == "nonfinite":
+        r = np.arange(G)
+        for i, v in enumerate((np.nan, np.inf, 0.0)):
+            rows[(r % 3 == 0) & (r // 3 % 3 == i)] = v
+    return rows
+
+
+def ghost_labels(G) -> np.ndarray:
+    return GHOST_LABEL0 + np.arange(G, dtype=np.int64)
+
+
+TINY_QUERIES = 200
+
+
+@functools.lru_cache(maxsize=None)
+def tiny_live(n_live, D, seed) -> Planted:
+    """n_live random rows and TINY_QUERIES random queries: no planted winners (owner 0 holds every row; k = n_live). With
+    k >= n_live a query's results are ALL live rows, those of negative cosine included, which a dead row scoring 0 outranks."""
+    rng = _philox(seed)
+    rows = (3.0 * rng.standard_normal((n_live, D))).astype(np.float32)
+    queries = rng.standard_normal((TINY_QUERIES, D), dtype=np.float32)
+    every = np.arange(n_live, dtype=np.int64)
+    none = np.empty(0, np.int64)
+    return Planted(rows, queries, np.zeros(n_live, np.int64), every, n_live, n_live, (every,) + (none,) * (TINY_QUERIES - 1))
+
+
+PLATEAU_OTHERS = 3
+
+
+@functools.lru_cache(maxsize=None)
+def plateau(N, D, seed) -> Planted:
+    """N rows of which N - PLATEAU_OTHERS are byte-identical (query 0 owns them, rank = their order) and three, at the two ends
+    and in the middle, are random (query 1 owns them). Queries: the tied row's direction, its opposite plus a little noise (every
+    tied row at the same NEGATIVE cosine, below a dead fp8 row's score 0), a random one, and one of the three other rows. For
+    each of them the tied rows share one distance, so the answer's order is decided by the labels alone."""
+    rng = _philox(seed)
+    tied = rng.standard_normal(D)
+    rows = np.repeat((3.0 * tied / np.linalg.norm(tied))[None].astype(np.float32), N, axis=0)
+    others = np.array([0, N // 2, N - 1])
+    rows[others] = (3.0 * rng.standard_normal((PLATEAU_OTHERS, D))).astype(np.float32)
+    queries = np.stack([tied, -tied + 0.1 * rng.standard_normal(D), rng.standard_normal(D), rows[others[1]]]).astype(np.float32)
+    owner = np.zeros(N, np.int64)
+    owner[others] = 1
+    rank = np.empty(N, np.int64)
+    rank[owner == 0] = np.arange(N - PLATEAU_OTHERS)
+    rank[others] = np.arange(PLATEAU_OTHERS)
+    return Planted(rows, queries, owner, rank, N - PLATEAU_OTHERS, N - PLATEAU_OTHERS, _by_owner(owner, queries.shape[0]))
+
+
+def not_excluded(p: Planted) -> np.ndarray:
+    """ascending row ids a query of a filtered corpus admits when it only excludes (require = None): every row but the decoys"""
+    return np.nonzero((p.tags & p.exclude[0]) == 0)[0]
+
+
 # ---------------------------------------------------------------------------------------------- the corpora the GPU tests use
 SEED = 5
 D = 128              # the positional structure of the scan and the 128-query score GEMM does not depend on D
@@ -137,3 +224,9 @@ LAYOUTS = {"scattered": False, "contiguous": True}
 # (N, D, k) of every unfiltered corpus, each in both layouts, and of every filtered pair of corpora
 PLAIN = [(N_SCAN, D, 10), (N_SCAN, D, 24), (N_SCAN, D, 100), (N_DENSE, D, 10), (N_DENSE, D_STRIP, 10), (N_SAMPLE, D_STRIP, 10)]
 FILTERED = [(N_SCAN, D, 10), (N_SAMPLE, D, 10)]
+# the dead-row tests: the unfiltered and filtered corpora above that they put ghosts behind (scattered layout), the tiny live
+# sets, and the tie plateau of more rows than a widened query may collect (8192)
+GHOSTED = [(N_SCAN, D, 10), (N_SCAN, D, 24), (N_SCAN, D, 100), (N_DENSE, D, 10), (N_DENSE, D_STRIP, 10), (N_SAMPLE, D_STRIP, 10)]
+GHOSTED_FILTERED = [(N_SCAN, D, 10)]
+TINY_LIVE = (1, 3, 19)
+N_PLATEAU = 9003

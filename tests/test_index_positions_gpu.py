@@ -12,175 +12,21 @@ functions the query path itself calls, not from formulas restated here.
 Expected answers: the oracle over the whole index at N = 4099 and for every filtered query (over its admitted rows), the oracle
 restricted to a query's own planted rows at N >= 20011 (equal to the full one: test_planted_rows_cpu.py). Ids, distance bits
 and counts of every query are compared; no case is left out."""
-import functools
-from typing import NamedTuple
-
 import numpy as np
 import pytest
 
 import planted_rows as pr
+from index_query_cases import ALL_DTYPES, Case, load_mods
+from index_query_cases import dense_names as _dense_names, run as _run, scan_names as _scan_names
 
 pytestmark = pytest.mark.gpu
 
-DEFAULTS = {"scan_max_slabs": 1024, "scan_group": 8, "score_strip": 0, "score_strip_v3": 1, "score_filter": 1, "guard_force": 0}
-WIDEN_KERNELS = {"sweep_scan_f32", "sweep_scan_f16", "sweep_scan_f8", "sweep_gemm_f16", "sweep_gemm_f8", "canonical_scan"}
 LAYOUT_IDS = list(pr.LAYOUTS)
-ALL_DTYPES = ["f32", "f16", "f8"]
 
 
 @pytest.fixture(scope="module")
 def mods():
-    import mmiss_amd  # noqa: F401
-    from mmiss_amd import _lib
-    from mmiss_amd.index import FlatIndex
-    from oracle import retrieval_oracle as ro
-    from oracle import retrieval_oracle_c as roc
-
-    return FlatIndex, ro, roc, _lib
-
-
-def _labels(N):
-    return np.arange(N, dtype=np.int64) * 3 + 5
-
-
-class Case(NamedTuple):
-    """one corpus of planted_rows (they are cached there: every test on a case shares the arrays)"""
-    N: int
-    D: int
-    k: int
-    layout: str
-    filtered: bool = False
-    mirrored: bool = False
-
-    def corpus(self):
-        if self.filtered:
-            return pr.filtered_corpus(self.N, self.D, self.k, pr.SEED, pr.LAYOUTS[self.layout], self.mirrored)
-        return pr.corpus(self.N, self.D, self.k, pr.SEED, pr.LAYOUTS[self.layout])
-
-
-@functools.lru_cache(maxsize=None)
-def _expected(case, dtype):
-    """computed once per corpus and storage dtype, shared by every test on it, never modified"""
-    from oracle import retrieval_oracle as ro
-    from oracle import retrieval_oracle_c as roc
-
-    p = case.corpus()
-    stored = ro.normalize_rows(p.rows, dtype)
-    out = pr.expected(roc, p, stored, _labels(case.N), case.k, full=case.N <= pr.FULL_ORACLE_MAX_N)
-    for a in out:
-        a.setflags(write=False)
-    return out
-
-
-def _where(row, plan):
-    """the structural position of a row, from the plan of the call that should have found it"""
-    tile, s = row // 16, [f"row {row}", f"row%16 {row % 16}", f"tile%4 {row // 16 % 4}"]
-    if plan["tiles_per_block"]:
-        s.append(f"slab {tile // plan['tiles_per_block']} (tile {tile % plan['tiles_per_block']} of {plan['tiles_per_block']})")
-    if plan["sweep_tiles_per_block"]:
-        s.append(f"sweep slab {tile // plan['sweep_tiles_per_block']}")
-    if plan["groups_per_split"]:
-        # a group of the score GEMM's maxima is 4 rows of each 16-row quarter of a 64-row block (groupmax_row, csrc/gemm_bf16.h)
-        group = row // 64 * 4 + row % 16 // 4
-        s.append(f"group {group}, split {group // plan['groups_per_split']} (group {group % plan['groups_per_split']} of it)")
-    if plan["dense"] and plan["big"]:
-        t256, first = row // 256, plan["ns_tiles"] if plan["sample"] else 0     # (the appending launch starts behind the sample)
-        if t256 >= first:
-            s.append(f"256-row tile {t256}, strip {(t256 - first) // max(1, plan['strip'])} (tile {(t256 - first) % max(1, plan['strip'])} of it)")
-        if plan["sample"]:
-            s.append(f"{'behind' if t256 >= first else 'in'} the sample of {first} tiles")
-    elif plan["dense"]:
-        s.append(f"128-row tile {row // 128}")
-    if plan["sweep_gemm"]:
-        s.append(f"sweep strip {row // 256 // max(1, plan['sweep_strip'])}")
-    return ", ".join(s)
-
-
-def _compare(got, exp, plan, what):
-    gl, gd, gc = got
-    el, ed, ec = exp
-    bad = np.nonzero((gl != el).any(1) | (gd.view(np.uint32) != ed.view(np.uint32)).any(1) | (gc != ec))[0]
-    if bad.size == 0:
-        return
-    lines = [f"{what}: {bad.size} of {gl.shape[0]} queries differ from the oracle; the winners that are missing:"]
-    for j in bad[:24]:
-        missing = sorted(set(el[j][el[j] >= 0].tolist()) - set(gl[j].tolist()))
-        for lab in missing:
-            lines.append(f"  query {j}: {_where((lab - 5) // 3, plan)}")
-        if not missing:
-            lines.append(f"  query {j}: same ids; counts {gc[j]} / {ec[j]}, order or distance bits differ")
-    print("\n".join(lines))
-    pytest.fail("\n".join(lines[:12]))
-
-
-def _run(mods, case, dtype, Q, *, options=None, widen=False, plan_check=None, kernels=(), extra_calls=(), what=""):
-    """Add the corpus (labels 3 r + 5), issue its queries Q per call (the last call is short; extra_calls: further (first, Q)
-    calls), compare every answer with the oracle's. Returns (labels, distances, counts, plan)."""
-    FlatIndex, ro, roc, _lib = mods
-    p, N, D, k, filtered = case.corpus(), case.N, case.D, case.k, case.filtered
-    options = dict(options or {})
-    if widen:
-        options["guard_force"] = 1
-    labels = _labels(N)
-    idx = FlatIndex(D, dtype, capacity=N)
-    try:
-        for o, v in options.items():
-            _lib.set_option(o, v)
-        idx.add(p.rows, labels)
-        if filtered:
-            idx.set_tags(labels, p.tags)
-        plan = _lib.index_plan(idx._h, Q, k, filtered, Q if widen else 0)
-        print(f"{what} plan(Q={Q}, k={k}): " + ", ".join(f"{f}={v}" for f, v in plan.items() if v))
-        if plan_check:
-            plan_check(plan)
-        Qt = p.n_queries
-        gl = np.empty((Qt, k), np.int64)
-        gd = np.empty((Qt, k), np.float32)
-        gc = np.empty(Qt, np.int32)
-
-        def call(j0, n):
-            sl = slice(j0, min(j0 + n, Qt))
-            if filtered:
-                return idx.query(p.queries[sl], k, require=p.require[sl], exclude=p.exclude[sl])
-            return idx.query(p.queries[sl], k)
-
-        _lib.prof_reset()
-        _lib.prof_enable(True)
-        before = idx.guard_stats()
-        try:
-            for j0 in range(0, Qt, Q):
-                gl[j0:j0 + Q], gd[j0:j0 + Q], gc[j0:j0 + Q] = call(j0, Q)
-            extras = [(j0, n, call(j0, n)) for j0, n in extra_calls]
-        finally:
-            _lib.prof_enable(False)
-        after = idx.guard_stats()
-        ran = {r["kernel"] for r in _lib.prof_read()}
-    finally:
-        for o in options:
-            _lib.set_option(o, DEFAULTS[o])
-        idx.close()
-    exp = _expected(case, dtype)
-    _compare((gl, gd, gc), exp, plan, what)
-    for j0, n, got in extras:
-        _compare(got, tuple(a[j0:j0 + n] for a in exp), plan, f"{what} extra call of {n} from query {j0}")
-    nq = Qt + sum(min(j0 + n, Qt) - j0 for j0, n in extra_calls)
-    delta = {s: after[s] - before[s] for s in after}
-    assert delta["queries"] == nq, delta
-    if filtered:   # no decoy in any answer
-        decoy_labels = labels[p.decoy]
-        assert not np.isin(gl, decoy_labels).any()
-    if widen:
-        assert delta["widened"] == nq and delta["exhaustive"] == 0, delta
-    else:
-        assert delta["widened"] == 0 and delta["rounds"] == 0 and delta["exhaustive"] == 0, delta
-        assert not (ran & WIDEN_KERNELS), ran
-    for name in kernels:
-        assert name in ran, (name, ran)
-    return gl, gd, gc, plan
-
-
-def _scan_names(dtype):
-    return ("scan_topk_" + dtype, "merge_lists", "rerank")
+    return load_mods()
 
 
 # ================================================================================================ first pass: streaming scan
@@ -282,10 +128,6 @@ def test_filtered_scan(mods, dtype, Q, nqt, slabs, layout):
 
 
 # ================================================================================================ first pass: score GEMM
-def _dense_names(dtype, sample=False):
-    return ("score_gemm_" + dtype + ("_sample" if sample else ""), "select_topk", "merge_lists", "rerank")
-
-
 @pytest.mark.parametrize("layout", LAYOUT_IDS)
 @pytest.mark.parametrize("Q", [40, 128])
 def test_score_gemm_128_query_tile(mods, Q, layout):
