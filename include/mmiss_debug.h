@@ -27,6 +27,22 @@ int mmiss_dbg_gemm(int device, void* hip_stream, int epi, int variant, const voi
                    void* out, const float* bias, const float* aux, int32_t M, int32_t N, int32_t K,
                    int32_t p0, int32_t p1);
 
+/* mmiss_dbg_gemm with what the encoder's calls add. m_valid (1 .. M): rows >= m_valid are computed but not stored (under PATCH
+ * no output row is written for them). Epilogue 3 only: stats_out (optional) f32 [M][N/64][2] = (sum, sumsq) of the new f32 rows
+ * per 64 columns, xb_out (optional) bf16 [M,N] = their bf16 copy; either one keeps the call off the split-K path. Epilogues 7 / 8
+ * (LayerNorm folded into W; 8: + QuickGELU): out bf16 [M,N] = rstd_m (A W^T - mean_m c) + b', aux = c f32 [N], bias = b' f32 [N],
+ * (mean, rstd) of row m from ln_stats f32 [M][K/64][2] = partial (sum, sumsq) per 64 columns (16-byte aligned) and ln_eps;
+ * variant 0 / 128 / 160 / 192: the 128-column tile of that height, always on two staging buffers and 4 waves; 256: the
+ * 256 x 256 tile. Refuses what the launchers refuse; no other kernel stands in. */
+int mmiss_dbg_gemm_ex(int device, void* hip_stream, int epi, int variant, const void* A, const void* W, void* out,
+                      const float* bias, const float* aux, int32_t M, int32_t N, int32_t K, int32_t p0, int32_t p1,
+                      int32_t m_valid, float* stats_out, void* xb_out, const float* ln_stats, float ln_eps);
+/* which form of the 128-column tile kernel a launch of epilogues 0 .. 4 at tile height bm (0 = 128) over M x N x K in `splits`
+ * K slices (1 = no split-K) runs under the current options: 10 * staging buffers (2 | 3) + waves per workgroup (4 | 8), or 0
+ * where the shape is no such launch. The launcher's own choice, evaluated on the host: the return value is the answer, not
+ * a status; launches nothing, needs no device. */
+int mmiss_dbg_gemm_form(int32_t bm, int32_t M, int32_t N, int32_t K, int32_t splits);
+
 /* LayerNorm over the last dim: x f32 [M,d] -> out (bf16 if out_bf16 else f32) [M,d]; may be in place for f32 */
 int mmiss_dbg_layernorm(int device, void* hip_stream, const float* x, const float* gamma, const float* beta,
                         void* out, int32_t out_bf16, int32_t M, int32_t d, float eps);

@@ -106,6 +106,8 @@ SIGNATURES = {
     "mmiss_prof_read": (_I, [C.c_char_p, C.c_size_t]),
     # mmiss_debug.h
     "mmiss_dbg_gemm": (_I, [_I, _P, _I, _I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32]),
+    "mmiss_dbg_gemm_ex": (_I, [_I, _P, _I, _I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, C.c_float]),
+    "mmiss_dbg_gemm_form": (_I, [_I32, _I32, _I32, _I32, _I32]),
     "mmiss_dbg_gemm_p256": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _I32, _I32, _I32, _I32, _P]),
     "mmiss_dbg_gemm_resid16": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "mmiss_dbg_gemm_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32,
@@ -236,6 +238,13 @@ def prof_read() -> list:
     buf = C.create_string_buffer(1 << 16)
     check(load().mmiss_prof_read(buf, len(buf)))
     return json.loads(buf.value.decode())
+
+
+def gemm_form(bm: int, M: int, N: int, K: int, splits: int = 1):
+    """mmiss_dbg_gemm_form as (staging buffers, waves) of the 128-column tile kernel under the current options; None where the
+    shape is no launch of it. Nothing is launched."""
+    v = load().mmiss_dbg_gemm_form(int(bm), int(M), int(N), int(K), int(splits))
+    return divmod(v, 10) if v else None
 
 
 INDEX_PLAN_FIELDS = ("dense", "dense8", "big", "strip_v3", "sample", "kp", "pages", "Mq", "Npad", "ns_tiles", "strip", "nqt", "cap",

@@ -30,6 +30,16 @@ static int time_launches(hipStream_t st, int iters, Run&& run, float* ms_per_lau
     return MMISS_OK;
 }
 
+// debug entries only: scratch so that the split-K path can be exercised (mmiss_dbg_gemm and mmiss_dbg_gemm_ex share it)
+static int dbg_splitk_scratch(GemmEpi& ep, int32_t M, int32_t N) {
+    static DevBuf dbg_splitk;
+    if (M > 0 && N > 0 && (int64_t)M * N <= (1 << 22)) {
+        MM_TRY(dbg_splitk.ensure((size_t)8 * M * N * 4));
+        ep.splitk_ws = dbg_splitk.as<float>(); ep.splitk_ws_bytes = dbg_splitk.bytes;
+    }
+    return MMISS_OK;
+}
+
 extern "C" int mmiss_dbg_gemm(int device, void* hip_stream, int epi, int variant, const void* A, const void* W,
                               void* out, const float* bias, const float* aux, int32_t M, int32_t N, int32_t K,
                               int32_t p0, int32_t p1) {
@@ -37,14 +47,51 @@ extern "C" int mmiss_dbg_gemm(int device, void* hip_stream, int epi, int variant
     MM_TRY(mmiss_use_device(device));
     GemmEpi ep{};
     ep.out = out; ep.bias = bias; ep.aux = aux; ep.ldo = N; ep.m_valid = M; ep.p0 = p0; ep.p1 = p1;
-    static DevBuf dbg_splitk;  // debug entry only: scratch so that the split-K path can be exercised
-    if ((int64_t)M * N <= (1 << 22)) {
-        MM_TRY(dbg_splitk.ensure((size_t)8 * M * N * 4));
-        ep.splitk_ws = dbg_splitk.as<float>(); ep.splitk_ws_bytes = dbg_splitk.bytes;
-    }
+    MM_TRY(dbg_splitk_scratch(ep, M, N));
     if (variant == 256) return launch_gemm256(reinterpret_cast<hipStream_t>(hip_stream), epi, A, W, ep, M, N, K);
     if (variant > 1000) MM_FAIL(MMISS_ERR_UNSUPPORTED, "GEMM variant %d (ring pipeline / BM x 256 tiles) was removed in round 4: measured slower, profiles/gemm_variants_r01.md", variant);
     return launch_gemm(reinterpret_cast<hipStream_t>(hip_stream), epi, variant, A, W, ep, M, N, K);
+}
+
+// mmiss_dbg_gemm with the pad-row mask, the residual epilogue's by-products and the folded epilogues: 0 .. 4 through launch_gemm
+// (variant 256: launch_gemm256), 7 / 8 through launch_gemm_fold (variant 256: launch_gemm256). The launchers decide what runs.
+extern "C" int mmiss_dbg_gemm_ex(int device, void* hip_stream, int epi, int variant, const void* A, const void* W, void* out,
+                                 const float* bias, const float* aux, int32_t M, int32_t N, int32_t K, int32_t p0, int32_t p1,
+                                 int32_t m_valid, float* stats_out, void* xb_out, const float* ln_stats, float ln_eps) {
+    if (!A || !W || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_ex: null pointer");
+    const bool fold = epi == MMISS_EPI_LNFOLD_BF16 || epi == MMISS_EPI_LNFOLD_QGELU_BF16;
+    if (!fold && (epi < 0 || epi > 4)) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_ex: epilogue %d", epi);
+    if (m_valid < 1 || m_valid > M) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_ex: m_valid=%d outside 1..M=%d", m_valid, M);
+    if ((epi >= MMISS_EPI_BIAS_BF16 && epi <= MMISS_EPI_BIAS_RESID_F32 && !bias) || (fold && (!bias || !aux || !ln_stats)) ||
+        (epi == MMISS_EPI_PATCH_F32 && (!aux || p0 <= 0 || p1 < p0 + 1)))
+        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_ex: epilogue %d lacks an operand", epi);
+    if ((stats_out || xb_out) && epi != MMISS_EPI_BIAS_RESID_F32)
+        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_ex: stats_out / xb_out belong to the f32 residual epilogue, not %d", epi);
+    if (ln_stats && !fold) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_gemm_ex: ln_stats belong to epilogues 7 / 8, not %d", epi);
+    if (variant > 1000) MM_FAIL(MMISS_ERR_UNSUPPORTED, "GEMM variant %d was removed in round 4", variant);
+    MM_TRY(mmiss_use_device(device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    GemmEpi ep{};
+    ep.out = out; ep.bias = bias; ep.aux = aux; ep.ldo = N; ep.m_valid = m_valid; ep.p0 = p0; ep.p1 = p1;
+    ep.stats_out = stats_out; ep.xb_out = xb_out;
+    if (fold) {
+        ep.ln_stats = ln_stats; ep.ln_parts = K / 64; ep.ln_eps = ln_eps;
+        if (variant == 256) return launch_gemm256(st, epi, A, W, ep, M, N, K);
+        return launch_gemm_fold(st, epi, variant, A, W, ep, M, N, K);
+    }
+    MM_TRY(dbg_splitk_scratch(ep, M, N));
+    if (variant == 256) return launch_gemm256(st, epi, A, W, ep, M, N, K);
+    return launch_gemm(st, epi, variant, A, W, ep, M, N, K);
+}
+
+// the gemm16_kernel form launch_gemm_stages picks under the current options: 10 * staging buffers + waves (0: no such launch)
+extern "C" int mmiss_dbg_gemm_form(int32_t bm, int32_t M, int32_t N, int32_t K, int32_t splits) {
+    if (bm == 0) bm = 128;
+    if ((bm != 128 && bm != 160 && bm != 192) || M <= 0 || N <= 0 || K <= 0 || splits < 1 || (M % bm) || (N % GEMM_BN) ||
+        (K % (splits * GEMM_BK)))
+        return 0;
+    const Gemm16Form f = gemm16_form(bm, (int64_t)(M / bm) * (N / GEMM_BN) * splits, K, splits);
+    return f.bufs * 10 + f.waves;
 }
 
 // the persistent 256 x 256 kernel in isolation (gemm_bf16_p256.h): epi 1 / 2 (bias, bias + QuickGELU) or 7 / 8 (the same

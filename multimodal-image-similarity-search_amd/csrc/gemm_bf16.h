@@ -150,6 +150,9 @@ __device__ __forceinline__ void ln_row_stats(const GemmEpi& ep, int64_t row, flo
     rstd = 1.0f / sqrtf(var + ep.ln_eps);
 }
 
+// what the loop above covers: an even number of partials, 16 at the most (hidden % 128 == 0, hidden <= 1024)
+static inline bool ln_row_stats_ok(int parts) { return parts >= 2 && (parts & 1) == 0 && parts <= 16; }
+
 template <int EPI, int JT>
 // stat_part / stat_parts (folded LayerNorm only): the stat_parts waves that share these rows (same wm) share ONE stat_area
 // and each finalises 1/stat_parts of the rows' statistics; a workgroup barrier publishes them (all waves call the epilogue).
@@ -696,8 +699,9 @@ static int launch_gemm_inst(hipStream_t st, const void* A, const void* W, const 
 static int launch_gemm_fold(hipStream_t st, int epi, int bm, const void* A, const void* W, const GemmEpi& ep, int M, int N,
                             int K) {
     if (bm == 0) bm = 128;
+    // (ln_row_stats reads a row's partials as pairs, 8 pairs at the most: K % 128 == 0, K <= 1024)
     if (M <= 0 || N <= 0 || K <= 0 || (M % bm) || (N % GEMM_BN) || (K % GEMM_BK) || !ep.ln_stats || !ep.aux || !ep.bias ||
-        ep.ln_parts * 64 != K)
+        ep.ln_parts * 64 != K || !ln_row_stats_ok(ep.ln_parts))
         MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm_fold: M=%d N=%d K=%d bm=%d parts=%d", M, N, K, bm, ep.ln_parts);
     const int mv = ep.m_valid < M ? ep.m_valid : M;
     const double bytes = 2.0 * ((double)mv * K + (double)N * K) + 2.0 * (double)mv * N;
@@ -739,22 +743,29 @@ static int launch_gemm_resid16(hipStream_t st, int bm, const void* A, const void
 
 // Two or three staging buffers: a grid of at most 256 workgroups puts one workgroup on a CU whatever its LDS footprint,
 // so the deeper pipeline costs no occupancy there and hides the load latency the second workgroup would have hidden.
+// The form of gemm16_kernel a grid of `wgs` workgroups (the K slices of a split launch counted) runs at tile height bm: the one
+// choice, read by launch_gemm_stages and by mmiss_dbg_gemm_form.
+struct Gemm16Form { int bufs, waves; };   // staging buffers (2 | 3), waves per workgroup (4 | 8)
+static inline Gemm16Form gemm16_form(int bm, int64_t wgs, int K, int splits) {
+    if (wgs <= 256 && K / splits >= 4 * GEMM_BK && mmiss_option("gemm_s3", 1) != 0)
+        return {3, (bm == 128 && mmiss_option("gemm_w8", 1) != 0) ? 8 : 4};
+    // the 8-wave form (two buffers) also while the grid is at most one round of 2 workgroups per CU, where many CUs
+    // still hold a single workgroup (bs 128: 2.10 -> 2.03 ms, bs 192: 2.60 -> 2.55 ms per encode)
+    if (bm == 128 && wgs <= mmiss_option("gemm_w8_max_wgs", 512)) return {2, 8};
+    return {2, 4};
+}
+
 template <typename IN, int BM, int EPI>
 static int launch_gemm_stages(hipStream_t st, const void* A, const void* W, const GemmEpi& ep, int M, int N, int K,
                               int splits = 1) {
-    const int64_t wgs = (int64_t)(M / BM) * (N / GEMM_BN) * splits;
-    if (wgs <= 256 && K / splits >= 4 * GEMM_BK && mmiss_option("gemm_s3", 1) != 0) {
-        if constexpr (BM == 128) {
-            if (mmiss_option("gemm_w8", 1) != 0) return launch_gemm_inst<IN, BM, EPI, false, 2, true, 4>(st, A, W, ep, M, N, K, splits);
-        }
-        return launch_gemm_inst<IN, BM, EPI, false, 2, true>(st, A, W, ep, M, N, K, splits);
-    }
+    const Gemm16Form f = gemm16_form(BM, (int64_t)(M / BM) * (N / GEMM_BN) * splits, K, splits);
     if constexpr (BM == 128) {
-        // the 8-wave form (two buffers) also while the grid is at most one round of 2 workgroups per CU, where many CUs
-        // still hold a single workgroup (bs 128: 2.10 -> 2.03 ms, bs 192: 2.60 -> 2.55 ms per encode)
-        if (wgs <= mmiss_option("gemm_w8_max_wgs", 512)) return launch_gemm_inst<IN, BM, EPI, false, 2, false, 4>(st, A, W, ep, M, N, K, splits);
+        if (f.waves == 8)
+            return f.bufs == 3 ? launch_gemm_inst<IN, BM, EPI, false, 2, true, 4>(st, A, W, ep, M, N, K, splits)
+                               : launch_gemm_inst<IN, BM, EPI, false, 2, false, 4>(st, A, W, ep, M, N, K, splits);
     }
-    return launch_gemm_inst<IN, BM, EPI>(st, A, W, ep, M, N, K, splits);
+    return f.bufs == 3 ? launch_gemm_inst<IN, BM, EPI, false, 2, true>(st, A, W, ep, M, N, K, splits)
+                       : launch_gemm_inst<IN, BM, EPI>(st, A, W, ep, M, N, K, splits);
 }
 
 template <typename IN, int EPI>

@@ -400,7 +400,7 @@ static int launch_gemm256(hipStream_t st, int epi, const void* A, const void* W,
     const bool fold = epi == MMISS_EPI_LNFOLD_BF16 || epi == MMISS_EPI_LNFOLD_QGELU_BF16;
     static const char* names[] = {"gemm_bf16_f32", "gemm_bf16_bias", "gemm_bf16_bias_qgelu", "gemm_bf16_bias_resid"};
     if (!fold && (epi < 0 || epi > 3)) MM_FAIL(MMISS_ERR_ARG, "gemm256: bad epilogue %d", epi);
-    if (fold && (!ep.ln_stats || !ep.aux || !ep.bias || ep.ln_parts * 64 != K))
+    if (fold && (!ep.ln_stats || !ep.aux || !ep.bias || ep.ln_parts * 64 != K || !ln_row_stats_ok(ep.ln_parts)))
         MM_FAIL(MMISS_ERR_UNSUPPORTED, "gemm256 fold: K=%d parts=%d", K, ep.ln_parts);
     const int out_elt = (epi == MMISS_EPI_BIAS_BF16 || epi == MMISS_EPI_BIAS_QGELU_BF16 || fold) ? 2 : 4;
     const int mv = ep.m_valid < M ? ep.m_valid : M;
