@@ -225,6 +225,25 @@ int mmiss_dbg_resize_crop_variant(int64_t blob_bytes, int32_t max_ksx);
 struct mmiss_index;
 int mmiss_dbg_index_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int32_t filtered, int32_t flagged, int32_t* out);
 
+
+/* The path one chunk of an encode call would take on the handle as it stands and under the options as they stand: B items
+ * (1 .. the tower's max_batch) on `tower` (MMISS_TOWER_*), T tokens per item for the text tower (the vision tower's is fixed: pass 0).
+ * The encoder's own planning functions, evaluated on the host; no kernel is launched. Like an encode call it allocates the tower's
+ * workspaces (zero-filled) if they do not exist yet, because the plan depends on which of them there are. out is a HOST int32 [32]:
+ *   [0] fold   [1] fold_final   [2] fp8   [3] fold8   [4] out8   [5] resid16   [6] sfold   [7] prune
+ *   [8] embed: 0 nothing, 1 xb + 64-column statistics, 2 xb + 16-column statistics (one request)
+ *   [9],[10] kernel and tile height of the QKV GEMM   [11],[12] out-projection   [13],[14] FC1   [15],[16] FC2
+ *        kernel: 0 BM x 128 tile (the launcher takes the skinny kernel for few rows), 1 256 x 256 tile, 2 persistent 256 x 256,
+ *        3 160 x 256 residual, 4 skinny with the LayerNorm folded in, 5 fp8 BM x 128 tile, 6 persistent fp8, 7 persistent fp8 with
+ *        the LayerNorm folded in
+ *   [17] the pruned last layer runs the pooled-query tail   [18] FC2 is a split-K candidate   [19] M = B * T
+ *   vision only: [20] lean pre-LayerNorm   [21],[22] kernel and tile height of the patch GEMM   [23] it is a split-K candidate
+ *   the attention kernel (the token count picks the family: up to 128 one pass, up to 288 long, above it key chunks):
+ *   [24] heads per workgroup of the one-pass kernels (attention_pick_hpb; it applies up to 128 tokens)
+ *   [25] the shape may run on the streaming kernel (attention_stream_ok; option attention_stream = 0 keeps the long kernel)
+ *   [26..31] 0 */
+int mmiss_dbg_encoder_plan(struct mmiss_encoder* enc, int32_t tower, int32_t B, int32_t T, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,7 @@ SIGNATURES = {
     "mmiss_dbg_resize_coeffs": (_I, [_I, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_dbg_resize_crop_variant": (_I, [_I64, _I32]),
     "mmiss_dbg_index_plan": (_I, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
+    "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
 
@@ -258,3 +259,22 @@ def index_plan(handle, Q: int, k: int, filtered: bool = False, flagged: int = 0)
     out = (_I32 * 24)()
     check(load().mmiss_dbg_index_plan(handle, int(Q), int(k), 1 if filtered else 0, int(flagged), out))
     return dict(zip(INDEX_PLAN_FIELDS, (int(v) for v in out)))
+
+
+ENCODER_PLAN_FIELDS = ("fold", "fold_final", "fp8", "fold8", "out8", "resid16", "sfold", "prune", "embed", "qkv", "qkv_bm", "out", "out_bm",
+                       "fc1", "fc1_bm", "fc2", "fc2_bm", "pooled_tail", "fc2_splitk", "M", "lean_pre", "patch", "patch_bm", "patch_splitk",
+                       "att_hpb", "att_stream")
+GEMM_KINDS = ("Tile", "Tile256", "P256", "P160", "Skinny", "Fp8Tile", "P256Fp8", "P256Fp8Xt")
+EMBED_OUTS = ("Nothing", "Stats64", "Stats16")
+
+
+def encoder_plan(handle, tower: int, B: int, T: int = 0) -> dict:
+    """mmiss_dbg_encoder_plan as a dict: the path one chunk of B items (T tokens each on the text tower) would take on the encoder
+    `handle` as it stands, under the options as they stand; GEMM kernels and `embed` by name. No kernel is launched."""
+    out = (_I32 * 32)()
+    check(load().mmiss_dbg_encoder_plan(handle, int(tower), int(B), int(T), out))
+    plan = dict(zip(ENCODER_PLAN_FIELDS, (int(v) for v in out)))
+    for k in ("qkv", "out", "fc1", "fc2", "patch"):
+        plan[k] = GEMM_KINDS[plan[k]]
+    plan["embed"] = EMBED_OUTS[plan["embed"]]
+    return plan

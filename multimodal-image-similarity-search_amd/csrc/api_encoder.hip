@@ -428,6 +428,39 @@ int plan_layers(const mmiss_encoder* e, const Tower& tw, int B, bool causal, Lay
     return MMISS_OK;
 }
 
+// The decisions of a call that plan_layers does not take (run_layers and encode_image_chunk take them), each in one function that
+// mmiss_dbg_encoder_plan reports from as well.
+// The pruned last layer on the pooled query's tile only: several-heads attention kernel, skinny out-projection (run_layers)
+static bool pooled_tail_planned(const Tower& tw, const LayerPlan& P) {
+    const GemmEpi probe{};
+    return P.prune && attention_pooled_ok(P.B, tw.T, tw.heads) && gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, P.B, tw.hidden, tw.hidden, probe) &&
+           mmiss_option("pooled_tail", 1) != 0;
+}
+// FC2 may split K: its grid on the BM x 128 tile is far below the CU count (run_layers makes the scratch)
+static bool fc2_splitk_planned(const Tower& tw, int M) {
+    return gemm_splitk_candidate((int64_t)((M + 127) / 128) * (tw.hidden / GEMM_BN), tw.mlp);
+}
+// The pre-LayerNorm keeps its f32 rows to itself and makes the CLS rows as it goes (encode_image_chunk)
+static bool lean_prelayernorm_planned(const LayerPlan& P) {
+    return P.embed == EmbedOut::Stats64 && P.resid16 && P.prune && mmiss_option("prelayernorm_lean", 1) != 0;
+}
+// The patch GEMM of B images: the BM x 128 tile at height bm over Mpp rows (split-K scratch when `splitk`), or the 160 x 256 tile
+// of gemm_bf16_p160.h over M160 rows when that grid is about one round of the chip and K is long
+struct PatchPlan { int Mpatch, bm, Mpp, M160; bool p160, splitk; };
+static PatchPlan plan_patch(const mmiss_encoder* e, int B) {
+    const int d = e->vis.hidden;
+    PatchPlan pp{};
+    pp.Mpatch = B * e->G * e->G;
+    pp.bm = gemm_pick_bm(pp.Mpatch, d);
+    pp.Mpp = (int)round_up(pp.Mpatch, pp.bm);
+    pp.M160 = (int)round_up(pp.Mpatch, 160);
+    const int64_t tiles160 = (int64_t)(pp.M160 / 160) * (d / 256);
+    pp.p160 = mmiss_option("gemm_p160", 1) != 0 && (d % 256) == 0 && gemm160p_ok(pp.M160, d, e->Kp) && tiles160 >= 200 &&
+              tiles160 <= 256 && e->Kp >= 2048;
+    pp.splitk = gemm_splitk_candidate((int64_t)(pp.Mpp / pp.bm) * (d / GEMM_BN), e->Kp);
+    return pp;
+}
+
 // an fp8 GEMM on the planned kernel, M rows padded to its tile height (xt: the folded-LayerNorm form of P256Fp8Xt)
 static int launch_gemm8_pick(hipStream_t st, GemmPick k, int epi, Gemm8Args g, int M, int xt) {
     if (k.kind == GemmKind::Fp8Tile) { g.M = (int)round_up(M, k.bm); return launch_gemm8(st, epi, k.bm, g); }
@@ -549,7 +582,7 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
     const int d = tw.hidden, M = P.M, B = P.B;
     const float eps = e->cfg.ln_eps;
     // split-K scratch for the narrow long-K GEMM (FC2) while its grid is far below the CU count
-    if (gemm_splitk_candidate((int64_t)((M + 127) / 128) * (d / GEMM_BN), tw.mlp))
+    if (fc2_splitk_planned(tw, M))
         MM_TRY(tw.splitk.ensure((size_t)8 * (round_up(M, 128) + 192) * d * 4));  // any tile height's row padding
     auto tap = [&](int which) -> int {
         if (e->record_taps && tw.taps.p)
@@ -580,8 +613,7 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
         // Option pooled_tail = 0: the full attention and the gather.
         GemmEpi ep_out{};
         ep_out.out = tw.xc.p; ep_out.bias = L.bo.as<float>(); ep_out.ldo = d; ep_out.m_valid = B;
-        const bool pooled = last_pruned && attention_pooled_ok(B, tw.T, tw.heads) &&
-                            gemm_skinny_ok(MMISS_EPI_BIAS_RESID_F32, B, d, d, ep_out) && mmiss_option("pooled_tail", 1) != 0;
+        const bool pooled = last_pruned && pooled_tail_planned(tw, P);
         if (pooled)
             MM_TRY(launch_attention_pooled(st, tw.qkv.p, tw.ctxc.p, tw.pool_row.as<int32_t>(), B, tw.T, tw.heads, P.causal));
         else if (P.out8 && !last_pruned)
@@ -651,28 +683,24 @@ int encode_image_chunk(mmiss_encoder* e, const void* pix_dev, bool src_u8, int B
     LayerPlan plan;
     MM_TRY(plan_layers(e, tw, B, false, plan));
     const int d = tw.hidden, S = e->cfg.v_image, P = e->cfg.v_patch;
-    const int Mpatch = B * e->G * e->G;
-    const int bm_p = gemm_pick_bm(Mpatch, d);
-    const int Mpp = (int)round_up(Mpatch, bm_p);
-    // round 3: the patch GEMM on the 160 x 256 tile of gemm_bf16_p160.h when that grid is about one round of the chip and K is long;
-    // f32 pixels, patch 16 or 32 and no K padding: that kernel reads the pixels itself and there is no im2col pass (option
-    // patch_from_pixels = 0: the bf16 copy first, as u8 / RGB inputs, patch 14 and the other batch sizes always do)
-    const int M160 = (int)round_up(Mpatch, 160);
-    const int64_t tiles160 = (int64_t)(M160 / 160) * (d / 256);
-    const bool patch_p160 = mmiss_option("gemm_p160", 1) != 0 && (d % 256) == 0 && gemm160p_ok(M160, d, e->Kp) && tiles160 >= 200 &&
-                            tiles160 <= 256 && e->Kp >= 2048;
+    const PatchPlan pp = plan_patch(e, B);
+    const int Mpatch = pp.Mpatch, bm_p = pp.bm, Mpp = pp.Mpp, M160 = pp.M160;
+    // the patch GEMM on the 160 x 256 tile (plan_patch) with f32 pixels, patch 16 or 32 and no K padding: that kernel reads the
+    // pixels itself and there is no im2col pass (option patch_from_pixels = 0: the bf16 copy first, as u8 / RGB inputs, patch 14
+    // and the other batch sizes always do)
+    const bool patch_p160 = pp.p160;
     const bool from_pixels = patch_p160 && !src_u8 && gemm160p_pix_ok(pix_dev, B, S, P, M160, d, e->Kp) &&
                              mmiss_option("patch_from_pixels", 1) != 0;
     if (!from_pixels) MM_TRY(launch_im2col(st, pix_dev, src_u8, e->patches.p, B, S, P, e->Kp));
     // On the bf16 residual stream (pruned last layer, no taps) the layers read xb and the statistics only and the head reads
     // the compact rows xc: the pre-LayerNorm then keeps its f32 rows to itself and makes the CLS rows as it goes
-    const bool lean_pre = plan.embed == EmbedOut::Stats64 && plan.resid16 && plan.prune && mmiss_option("prelayernorm_lean", 1) != 0;
+    const bool lean_pre = lean_prelayernorm_planned(plan);
     // (Stats16: the CLS rows come with the pre-LayerNorm below, prelayernorm_skinny_kernel)
     if (plan.embed != EmbedOut::Stats16 && !lean_pre)
         MM_TRY(launch_cls_rows(st, tw.x.as<float>(), e->cls.as<float>(), tw.pos.as<float>(), B, tw.T, d));
     GemmEpi ep{};
     ep.out = tw.x.p; ep.aux = tw.pos.as<float>(); ep.ldo = d; ep.m_valid = Mpatch; ep.p0 = e->G * e->G; ep.p1 = tw.T;
-    if (gemm_splitk_candidate((int64_t)(Mpp / bm_p) * (d / GEMM_BN), e->Kp)) {
+    if (pp.splitk) {
         MM_TRY(tw.splitk.ensure((size_t)8 * Mpp * d * 4));
         ep.splitk_ws = tw.splitk.as<float>(); ep.splitk_ws_bytes = tw.splitk.bytes;
     }

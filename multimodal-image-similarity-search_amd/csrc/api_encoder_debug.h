@@ -502,3 +502,46 @@ extern "C" int mmiss_dbg_gemm8_time(int device, int epi, int bm, const void* A8,
     auto run = [&]() -> int { return mmiss_dbg_gemm8(device, nullptr, epi, bm, A8, As, W8, wscale, bias, out, out_scale, M, N, K); };
     return time_launches(nullptr, iters, run, ms_per_launch);
 }
+
+// mmiss_debug.h: the path an encode call of this shape would take on the handle as it stands and under the options as they stand.
+// Host arithmetic only: plan_layers and the functions run_layers / encode_image_chunk themselves decide by; no kernel is launched.
+// Like an encode call it first makes sure the tower's workspaces exist (zero-filled): the plan reads which of them there are.
+extern "C" int mmiss_dbg_encoder_plan(mmiss_encoder* enc, int32_t tower, int32_t B, int32_t T, int32_t* out) {
+    if (!enc || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_encoder_plan: null argument");
+    if (tower != MMISS_TOWER_VISION && tower != MMISS_TOWER_TEXT) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_encoder_plan: unknown tower %d", tower);
+    std::lock_guard<std::mutex> lk(enc->mu);
+    if (!enc->finalized) MM_FAIL(MMISS_ERR_STATE, "mmiss_dbg_encoder_plan before mmiss_encoder_finalize");
+    const bool text = tower == MMISS_TOWER_TEXT;
+    Tower& tw = text ? enc->txt : enc->vis;
+    const int maxb = text ? enc->cfg.max_batch_text : enc->cfg.max_batch_image;
+    if (B < 1 || B > maxb) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_encoder_plan: B = %d outside 1 .. max_batch = %d (one chunk of a call)", B, maxb);
+    if (text ? (T < 1 || T > enc->cfg.t_ctx) : (T != 0 && T != tw.T))
+        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_encoder_plan: T = %d (text: 1 .. %d; vision: 0 or %d)", T, enc->cfg.t_ctx, enc->vis.T);
+    for (int i = 0; i < 32; ++i) out[i] = 0;
+    MM_TRY(mmiss_use_device(enc->device));
+    MM_TRY(ensure_tower_ws(enc, tw, maxb, enc->cfg.proj_dim));
+    const int savedT = tw.T;
+    if (text) tw.T = T;   // as encode_text_chunk sets it
+    LayerPlan P;
+    const int rc = plan_layers(enc, tw, B, text, P);
+    if (rc == MMISS_OK) {
+        out[0] = P.fold; out[1] = P.fold_final; out[2] = P.fp8; out[3] = P.fold8; out[4] = P.out8; out[5] = P.resid16;
+        out[6] = P.sfold; out[7] = P.prune; out[8] = (int)P.embed;
+        const GemmPick picks[4] = {P.qkv, P.out, P.fc1, P.fc2};
+        for (int i = 0; i < 4; ++i) { out[9 + 2 * i] = (int)picks[i].kind; out[10 + 2 * i] = picks[i].bm; }
+        out[17] = pooled_tail_planned(tw, P);
+        out[18] = fc2_splitk_planned(tw, P.M);
+        out[19] = P.M;
+        out[24] = attention_pick_hpb(B, tw.heads);
+        out[25] = attention_stream_ok(B, tw.T, tw.heads, text);
+        if (!text) {
+            const PatchPlan pp = plan_patch(enc, B);
+            out[20] = lean_prelayernorm_planned(P);
+            out[21] = (int)(pp.p160 ? GemmKind::P160 : GemmKind::Tile);
+            out[22] = pp.p160 ? 160 : pp.bm;
+            out[23] = pp.splitk;
+        }
+    }
+    tw.T = savedT;
+    return rc;
+}

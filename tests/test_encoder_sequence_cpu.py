@@ -1,0 +1,127 @@
+"""What test_encoder_sequence_gpu.py relies on, established on the host (tests/encoder_sequence_cases.py): every poison covers the
+rows its victim's tiles can read, the NaN poisons provably reach the end of a tower, the victims are finite, the twin poison is
+another input, and the pooled-position table is the oracle's."""
+import functools
+import glob
+import os
+import re
+
+import numpy as np
+import pytest
+
+from oracle import clip_oracle as co
+import encoder_sequence_cases as sc
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(shape, tower, call):
+    case = sc.Case("", "", shape, tower, call, ())
+    return sc.oracle_embed(case, call)
+
+
+def _plain(call):
+    """The call without what the oracle does not see (options, expectations): one oracle run per distinct input."""
+    return sc.Call(call.kind, call.B, call.T, (), (), call.trim, call.via, call.seed)
+
+
+def test_case_names_are_unique_and_every_plan_row_has_cases():
+    names = [c.name for c in sc.CASES]
+    assert len(names) == len(set(names))
+    assert {c.plan for c in sc.CASES} == set("abcdefghijk")          # (l): CHUNK_CASES
+    for c in sc.CASES:
+        assert len(c.poisons) == 2 and c.victim.kind == "victim" and all(p.kind in ("nan", "twin") for p in c.poisons), c.name
+        assert {k for call in (c.victim,) + c.poisons for k, _ in call.opts} <= set(sc.OPTION_DEFAULTS), c.name
+        assert c.victim.expect, c.name + ": a victim pins its plan"
+
+
+def test_option_defaults_are_the_call_sites():
+    """_options() restores OPTION_DEFAULTS after a call: each value must be the default every mmiss_option call site of that key
+    passes, or a restored option would change the path of every later test in the process."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "multimodal-image-similarity-search_amd", "csrc")
+    text = "".join(open(f).read() for f in sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip"))))
+    used = {k for c in sc.CASES for call in (c.victim,) + c.poisons for k, _ in call.opts} | {"att_hpb"}
+    assert used == set(sc.OPTION_DEFAULTS), used ^ set(sc.OPTION_DEFAULTS)
+    for key, dflt in sc.OPTION_DEFAULTS.items():
+        if key.startswith("gemm_bm_"):    # read through plan_layers' tile_height(key, ...): bm = mmiss_option(key, 0)
+            assert 'tile_height("%s"' % key in text
+            sites = re.findall(r'bm = mmiss_option\(key,\s*(-?\d+)\)', text)
+        else:
+            sites = re.findall(r'mmiss_option\("%s",\s*(-?\d+)\)' % re.escape(key), text)
+        assert sites and {int(v) for v in sites} == {dflt}, (key, dflt, sites)
+
+
+def test_every_poison_covers_the_rows_its_victim_can_read():
+    """A tile of height 128 / 160 / 192 / 256 reads rows below round_up(M, 256) + 192 at the most (ensure_tower_ws pads to that):
+    the poison call must have written every one of them, in one chunk."""
+    for c in sc.CASES:
+        M = sc.call_rows(c, c.victim)
+        assert c.victim.B <= c.max_batch, c.name
+        for p in c.poisons:
+            assert p.B <= c.max_batch, c.name
+            if p.covers:
+                assert sc.call_rows(c, p) >= sc.round_up(M, 256) + 192, (c.name, M, sc.call_rows(c, p))
+        assert any(p.covers for p in c.poisons) or c.name == "c-after-a-B77", c.name     # (that one: (c) over what (a) left)
+    for via, maxb, r in sc.CHUNK_CASES + sc.CHUNK_INT_CASES:
+        assert maxb * 5 >= sc.round_up(r * 5, 256) + 192
+
+
+def test_victim_row_counts_sit_on_the_tile_edges():
+    rows = {}
+    for c in sc.VISION_CASES:
+        e = dict(c.victim.expect)
+        for key in ("qkv_bm",):
+            if key in e:
+                rows.setdefault(e[key], set()).add(sc.call_rows(c, c.victim) % e[key])
+        if e.get("qkv") in ("Tile256", "P256", "P256Fp8", "P256Fp8Xt"):
+            rows.setdefault(256, set()).add(sc.call_rows(c, c.victim) % 256)
+        if c.plan == "b":
+            rows.setdefault("plain128", set()).add(sc.call_rows(c, c.victim) % 128)
+    assert rows[128] >= {1, 127, 0} and rows[192] >= {1, 191, 0} and rows[160] >= {1, 159, 0}, rows
+    assert rows[256] >= {1, 255, 0}, rows       # 1025, 1535 = 6 * 256 - 1, 1280
+    assert rows["plain128"] >= {1, 127, 0}, rows
+    skinny = {sc.call_rows(c, c.victim) for c in sc.CASES if dict(c.victim.expect).get("sfold") == 1}
+    assert skinny >= {5, 125, 128}, skinny
+
+
+def test_no_victim_prompt_holds_the_nan_token():
+    for c in sc.TEXT_CASES:
+        ids = sc.call_input(c, c.victim)
+        assert not (ids == sc.NAN_ID).any() and ids.min() >= 0 and ids.max() < sc.SHAPES[c.shape].t_vocab, c.name
+        for p in c.poisons:
+            if p.kind == "twin":
+                assert not (sc.call_input(c, p) == sc.NAN_ID).any()
+    for shape in sc.SHAPES:
+        tok = sc.weights(shape)["text_model.embeddings.token_embedding.weight"]
+        assert np.isnan(tok[sc.NAN_ID]).all() and np.isfinite(np.delete(tok, sc.NAN_ID, axis=0)).all()
+
+
+@pytest.mark.parametrize("shape,tower", [("tiny", "vision"), ("w512", "vision"), ("t257", "vision"), ("tiny", "text"), ("legacy", "text")])
+def test_nan_poison_reaches_every_output_row_of_the_oracle(shape, tower):
+    call = sc.Call("nan", 3, 7 if tower == "text" else 0)
+    out = _oracle(shape, tower, call)
+    assert out.shape[0] == 3 and np.isnan(out).all()
+
+
+def test_victims_are_finite_and_the_twin_is_another_input():
+    """Where the oracle is cheap (Case.oracle): finite unit rows for every victim, and no twin row within 1e-3 cosine of a victim
+    row of its case (a victim that came out as its twin would be told apart)."""
+    for c in sc.CASES:
+        if not c.oracle:
+            continue
+        v = _oracle(c.shape, c.tower, _plain(c.victim))
+        assert np.isfinite(v).all() and np.abs(np.linalg.norm(v, axis=1) - 1).max() < 1e-5, c.name
+        for p in c.poisons:
+            if p.kind == "twin":
+                t = _oracle(c.shape, c.tower, _plain(p))
+                assert np.isfinite(t).all() and (v @ t.T).max() < 1 - sc.COS_TOL, c.name
+
+
+def test_pooled_position_table_is_the_oracles():
+    for name, shape, ids, want in sc.pooled_position_cases():
+        s = sc.SHAPES[shape]
+        assert np.array_equal(co.eos_positions(ids, s.eos_token_id), want), name
+        assert not (ids == sc.NAN_ID).any() and ids.shape[1] == 16
+        pre = sc.pooled_position_prelude(shape, want)
+        got = co.eos_positions(pre, s.eos_token_id)
+        assert (got[: len(want)] != want).all() and pre.shape[0] >= len(want), name
+        assert np.isfinite(co.embed_texts(ids, sc.weights(shape), s)).all(), name
