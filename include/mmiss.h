@@ -311,7 +311,8 @@ int mmiss_index_guard_stats(mmiss_index* idx, int64_t out[4]);
  * exhaustive canonical pass instead (the canonical distance of every row, the k best by (distance, label)) — a plateau of
  * rows within the rounding bound of the k-th score, e.g. > 10^4 copies of one placeholder image; exact for any data, one
  * pass over the index and one host selection per such query. out[5] = rows the threshold passes collected and re-ranked.
- * out[6..7] are reserved (0).
+ * out[6] = queries served by the radius calls (below), out[7] = passes over the index those cost (1 per chunk on the score GEMM,
+ * one per 64 queries of a chunk on the streaming scan). Radius calls leave out[0..3] alone and add to out[4] and out[5].
  */
 int mmiss_index_guard_stats_ex(mmiss_index* idx, int64_t out[8]);
 
@@ -354,6 +355,44 @@ int mmiss_index_query_filtered(mmiss_index* idx, const float* queries, int32_t Q
 int mmiss_index_query_filtered_begin(mmiss_index* idx, const float* queries, int32_t Q, int32_t k,
                                      const uint64_t* require, const uint64_t* exclude,
                                      int64_t* out_labels, float* out_dist, int32_t* out_count);
+
+/* ---------------------------------------------------------------- radius queries --------------- */
+/*
+ * "Every row at least this similar", exactly. Row r is a MEMBER of query q iff the row has a direction, q admits it (require /
+ * exclude as for mmiss_index_query_filtered; null = 0) and d(q, r) <= max_dist[q], compared as floats, d being the canonical
+ * distance mmiss_index_query returns: (float)(1.0 - canon_dot(q^, row) [x (double)inv[row] for fp8 rows]). No special radii: a
+ * negative one is legal (a distance can be a few ulps below 0), one >= 2 admits every row; a NaN radius is MMISS_ERR_ARG.
+ *   out_total[q] (int64 [Q], may be null) = the exact number of members; out_count[q] (int32 [Q]) = min(cap, out_total[q]);
+ *   out_labels / out_dist ([Q, cap], 1 <= cap <= 4096) hold the out_count[q] nearest members in (distance, label) order, unused
+ *   slots label -1 / distance +inf. A query without a direction: count 0, total 0. An empty index: 0 everywhere.
+ * max_dist: float32 [Q], host or device, as the masks. Outputs all host or all device. The call locks the handle, runs on its
+ * current stream, returns with its work finished, and fails with MMISS_ERR_STATE while a _begin query is open; it has no
+ * _begin / _end form. Any Q: the work is done in chunks of at most 1024 queries.
+ * One pass over the index instead of a top-k query's one or two: the exactness guard's threshold pass with the threshold taken
+ * from the radius, thr_q = (1 - max_dist[q]) - eps_q (no member's approximate score lies below it), then the canonical re-rank
+ * of what it collected, cut at the radius. A query that collects more than 8192 rows goes through the exhaustive canonical pass
+ * (one pass over the index and one host selection per such query), as a plateau does under mmiss_index_query.
+ * replaces the caller-side "pick a k, hope it is large enough, cut the list": the UI's "All" = 1000
+ * (backend/app/main.py:757) and similarity = 1 - d / 2 (main.py:782); the reference's roadmap names the missing piece,
+ * "Adjustable similarity thresholds" (CHANGELOG.md:475).
+ */
+int mmiss_index_query_radius(mmiss_index* idx, const float* queries, int32_t Q, const float* max_dist, int32_t cap,
+                             const uint64_t* require, const uint64_t* exclude,
+                             int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_total);
+/*
+ * The same, the queries being the rows the index REPRESENTS under `labels` (host int64 [n]; one radius for all): the stored rows
+ * are widened to f32 on the device (fp8 rows x their inverse norm) and handed to the same core — nothing crosses PCIe — which
+ * gives exactly what mmiss_index_query_radius returns for the output of mmiss_index_get(labels). later_only != 0 admits only
+ * rows whose label is GREATER than the query's own: row order is label order, so the self match is dropped and every pair of a
+ * near-duplicate search over all labels is reported once, with the smaller label as the query. A label not in the index ->
+ * MMISS_ERR_ARG and nothing is written.
+ * replaces nothing the reference can do: its "Duplicate Detection" (README.md:21) is an exact perceptual hash
+ * (backend/app/main.py:628-640), so a re-encoded, resized or lightly cropped copy is stored again; its CLIP embedding sits at
+ * cosine 0.99 to the original's.
+ */
+int mmiss_index_query_radius_by_label(mmiss_index* idx, const int64_t* labels, int64_t n, float max_dist, int32_t cap,
+                                      int32_t later_only, int64_t* out_labels, float* out_dist, int32_t* out_count,
+                                      int64_t* out_total);
 
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*

@@ -224,6 +224,14 @@ int mmiss_dbg_resize_crop_variant(int64_t blob_bytes, int32_t max_ksx);
  *   widen pass:        [18] 1 = strip score GEMM, 0 = scan;  GEMM: [22] strip;  scan: [19] nqt  [20] slabs  [21] tiles_per_block */
 struct mmiss_index;
 int mmiss_dbg_index_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int32_t filtered, int32_t flagged, int32_t* out);
+/* The path a radius call (mmiss_index_query_radius*) of Q queries (filtered != 0: with masks) would take on the index as it
+ * stands: its chunks of at most 1024 queries and the threshold pass of the first and of the last chunk (every chunk but the last
+ * is a full one). Launches nothing, changes nothing, needs no device. out is a HOST int32 [16]; fields that do not apply are 0:
+ *   [0] chunks
+ *   first chunk: [1] queries   [2] 1 = strip score GEMM, 0 = scan;  GEMM: [3] strip;  scan: [4] nqt  [5] slabs  [6] tiles_per_block
+ *                [7] qtiles
+ *   last chunk:  [8] .. [14] the same seven fields */
+int mmiss_dbg_index_radius_plan(struct mmiss_index* ix, int32_t Q, int32_t filtered, int32_t* out);
 
 
 /* The path one chunk of an encode call would take on the handle as it stands and under the options as they stand: B items

@@ -98,6 +98,8 @@ SIGNATURES = {
     "mmiss_index_get_tags": (_I, [_P, _P, _I64, _P]),
     "mmiss_index_query_filtered": (_I, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "mmiss_index_query_filtered_begin": (_I, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "mmiss_index_query_radius": (_I, [_P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "mmiss_index_query_radius_by_label": (_I, [_P, _P, _I64, C.c_float, _I32, _I32, _P, _P, _P, _P]),
     "mmiss_blend": (_I, [_I, _P, _P, _P, C.c_double, _I32, _I32, _P]),
     "mmiss_merge_topk": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_prof_enable": (_I, [_I]),
@@ -146,6 +148,7 @@ SIGNATURES = {
     "mmiss_dbg_resize_coeffs": (_I, [_I, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_dbg_resize_crop_variant": (_I, [_I64, _I32]),
     "mmiss_dbg_index_plan": (_I, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
+    "mmiss_dbg_index_radius_plan": (_I, [_P, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
@@ -259,6 +262,19 @@ def index_plan(handle, Q: int, k: int, filtered: bool = False, flagged: int = 0)
     out = (_I32 * 24)()
     check(load().mmiss_dbg_index_plan(handle, int(Q), int(k), 1 if filtered else 0, int(flagged), out))
     return dict(zip(INDEX_PLAN_FIELDS, (int(v) for v in out)))
+
+
+RADIUS_PLAN_FIELDS = ("queries", "gemm", "strip", "nqt", "slabs", "tiles_per_block", "qtiles")
+
+
+def index_radius_plan(handle, Q: int, filtered: bool = False) -> dict:
+    """mmiss_dbg_index_radius_plan as a dict: {"chunks": n, "first": {...}, "last": {...}}, the threshold pass of the first and
+    of the last chunk (at most 1024 queries each) of a radius call of Q queries on the index `handle` as it stands. Nothing is
+    launched."""
+    out = (_I32 * 16)()
+    check(load().mmiss_dbg_index_radius_plan(handle, int(Q), 1 if filtered else 0, out))
+    v = [int(x) for x in out]
+    return {"chunks": v[0], "first": dict(zip(RADIUS_PLAN_FIELDS, v[1:8])), "last": dict(zip(RADIUS_PLAN_FIELDS, v[8:15]))}
 
 
 ENCODER_PLAN_FIELDS = ("fold", "fold_final", "fp8", "fold8", "out8", "resid16", "sfold", "prune", "embed", "qkv", "qkv_bm", "out", "out_bm",

@@ -74,6 +74,18 @@ def _prefilter(fields) -> bool:
     return str(_first(fields, "prefilter", "")).strip().lower() in ("1", "true")
 
 
+def _similarity_kw(fields, field: str, kw: str) -> dict:
+    """The optional form field `field`, a similarity in [0, 1], as the keyword argument `kw` of the search / ingest call; absent:
+    no argument at all (today's call). Anything else raises, and the route answers as it answers a bad `limit`."""
+    raw = _first(fields, field)
+    if raw is None:
+        return {}
+    s = float(raw)
+    if not 0.0 <= s <= 1.0:      # (NaN fails both comparisons)
+        raise ValueError(f"{field} must be a number in [0, 1], got {raw!r}")
+    return {kw: s}
+
+
 def apply_filters(results: List[dict], filters: Optional[List[str]]) -> List[dict]:
     """Keep r iff every selected filter answered "yes" in r["filter_results_json"] (main.py:202-222)."""
     if not filters:
@@ -153,7 +165,8 @@ def create_app():
             metadata = {"id": image_id, "filename": filename, "description": description or "",
                         "custom_metadata": custom_metadata or "", "url": f"/static/processed/{image_id}.png",
                         "thumbnail_url": f"/static/processed/{image_id}.png", "filter_results_json": "{}"}
-            metadata, success = search.process_image(image, image_id, metadata, document=description or "")
+            metadata, success = search.process_image(image, image_id, metadata, document=description or "",
+                                                     **_similarity_kw(fields, "near_duplicate_similarity", "near_duplicate_similarity"))
             if success:
                 return {"success": True, "metadata": metadata}
             return JSONResponse(status_code=409, content={
@@ -169,12 +182,13 @@ def create_app():
             fields, files = await _form(request)
             image = _open(files, convert_all=True)
             limit = int(_first(fields, "limit", 10))
+            sim = _similarity_kw(fields, "min_similarity", "min_similarity")
             model, processor = utils.load_clip_model()
             embedding_result = utils.generate_clip_embedding(image=image, model=model, processor=processor)
             if _prefilter(fields):
                 return {"results": search.search_similar(embedding=embedding_result["image"][0], limit=limit,
-                                                         filters=fields.get("filters"))}
-            results = search.search_similar(embedding=embedding_result["image"][0], limit=limit)
+                                                         filters=fields.get("filters"), **sim)}
+            results = search.search_similar(embedding=embedding_result["image"][0], limit=limit, **sim)
             return {"results": apply_filters(results, fields.get("filters"))}
         except Exception as e:
             logger.error(f"Error in image search: {e}")
@@ -188,6 +202,7 @@ def create_app():
                 return JSONResponse(status_code=422, content={"detail": "field 'query' is required"})
             query = fields["query"][0]
             limit = int(_first(fields, "limit", 10))
+            sim = _similarity_kw(fields, "min_similarity", "min_similarity")
             filters = fields.get("filters")
             if not query.strip() and filters:
                 # filter-only browse (main.py:245-249,1225-1242): every stored image, no vector search
@@ -195,9 +210,9 @@ def create_app():
                 n = 1000 if limit <= 0 else limit
                 results = [dict(m or {}) for m in got["metadatas"]][:n]
             elif _prefilter(fields):
-                return {"results": search.search_by_text(query_text=query, limit=limit, filters=filters)}
+                return {"results": search.search_by_text(query_text=query, limit=limit, filters=filters, **sim)}
             else:
-                results = search.search_by_text(query_text=query, limit=limit)
+                results = search.search_by_text(query_text=query, limit=limit, **sim)
             return {"results": apply_filters(results, filters)}
         except Exception as e:
             logger.error(f"Error in text search: {e}")
@@ -212,11 +227,12 @@ def create_app():
                 return JSONResponse(status_code=422, content={"detail": "field 'query' is required"})
             weight_image = float(_first(fields, "weight_image", 0.5))  # not clamped, as in the backend route
             limit = int(_first(fields, "limit", 10))
+            sim = _similarity_kw(fields, "min_similarity", "min_similarity")
             if _prefilter(fields):
                 return {"results": search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,
-                                                            limit=limit, filters=fields.get("filters"))}
+                                                            limit=limit, filters=fields.get("filters"), **sim)}
             results = search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,
-                                               limit=limit)
+                                               limit=limit, **sim)
             return {"results": apply_filters(results, fields.get("filters"))}
         except Exception as e:
             logger.error(f"Error in multimodal search: {e}")

@@ -338,8 +338,16 @@ class FlatCollection:
         self._index.set_tags(np.asarray(labs, dtype=np.int64), np.asarray(tags, dtype=np.uint64))
         self._tag_dirty.clear()
 
-    def _filtered_query(self, q: np.ndarray, k: int, filters: List[str]):
-        """Exact top-k among the rows answering "yes" to every filter -> (labels [Q,k], distances [Q,k], counts [Q])."""
+    def _index_query(self, q: np.ndarray, k: int, max_distance=None, **masks):
+        """The index's top-k query or, max_distance given, its radius query with k as the cap (FlatIndex.query_radius: only the
+        rows within max_distance, the k nearest of them) -> (labels [Q,k], distances [Q,k], counts [Q])."""
+        if max_distance is None:
+            return self._index.query(q, k, **masks)
+        return self._index.query_radius(q, max_distance, k, **masks)[:3]
+
+    def _filtered_query(self, q: np.ndarray, k: int, filters: List[str], max_distance=None):
+        """Exact top-k among the rows answering "yes" to every filter -> (labels [Q,k], distances [Q,k], counts [Q]);
+        max_distance: among those of them within that distance."""
         self._push_tags()
         Q = q.shape[0]
         if any(f not in self._filter_bits and f not in self._filter_overflow for f in filters):
@@ -351,12 +359,12 @@ class FlatCollection:
                 req |= 1 << self._filter_bits[f]
         over = [f for f in filters if f in self._filter_overflow]
         if not over:
-            return self._index.query(q, k, require=np.uint64(req))
+            return self._index_query(q, k, max_distance, require=np.uint64(req))
         # a name past the 64th bit: the mapped bits narrow the query, the rest is checked on the host. Exact as long as the rows
         # passing the mapped bits fit one call (MAX_N_RESULTS); beyond that it is the best MAX_N_RESULTS of them, post-filtered.
         ok = {lab for lab in self._labels if all(answers_yes(filter_answers(self._meta.get(lab)).get(f, "")) for f in filters)}
         wide = min(len(self._labels), MAX_N_RESULTS)
-        labs_w, dist_w, cnt_w = self._index.query(q, wide, require=np.uint64(req))
+        labs_w, dist_w, cnt_w = self._index_query(q, wide, max_distance, require=np.uint64(req))
         labs = np.full((Q, k), -1, np.int64)
         dist = np.full((Q, k), np.inf, np.float32)
         cnt = np.zeros((Q,), np.int32)
@@ -368,9 +376,13 @@ class FlatCollection:
         return labs, dist, cnt
 
     def query(self, query_embeddings=None, n_results: int = 10, include: Sequence[str] = ("metadatas", "documents", "distances"),
-              filters: Optional[Sequence[str]] = None, **_unused) -> dict:
+              filters: Optional[Sequence[str]] = None, max_distance: Optional[float] = None, **_unused) -> dict:
         """collection.query. filters: names of yes/no filters; when given, the result is the exact n_results nearest among the
-        rows whose filter_results_json answers "yes" to every one of them (pre-filtering; see the module docstring)."""
+        rows whose filter_results_json answers "yes" to every one of them (pre-filtering; see the module docstring).
+        max_distance: a radius query (FlatIndex.query_radius) — only the rows within that cosine distance are returned, exactly,
+        and n_results is the cap on how many (the nearest ones). It combines with filters: the members among the rows the filters
+        admit; past 64 filter names the host post-filter of the filtered query applies to the radius result (the best
+        MAX_N_RESULTS members passing the mapped bits, post-filtered)."""
         filters = list(dict.fromkeys(_as_list(filters))) if filters else []
         if query_embeddings is None:
             raise ValueError("FlatCollection.query needs query_embeddings (text embedding functions are out of scope)")
@@ -391,9 +403,9 @@ class FlatCollection:
                     logger.warning(f"n_results={n_results} clamped to {MAX_N_RESULTS}")
                     k = MAX_N_RESULTS
                 if filters:
-                    labs, dist, cnt = self._filtered_query(q, k, filters)
+                    labs, dist, cnt = self._filtered_query(q, k, filters, max_distance)
                 else:
-                    labs, dist, cnt = self._index.query(q, k)
+                    labs, dist, cnt = self._index_query(q, k, max_distance)
             label_to_id = dict(zip(self._labels, self._ids))
             out = {"ids": [], "distances": None, "metadatas": None, "documents": None, "embeddings": None,
                    "uris": None, "data": None, "included": include}
@@ -411,6 +423,17 @@ class FlatCollection:
             if "embeddings" in include:
                 out["embeddings"] = [self._index.get(np.asarray(ls, dtype=np.int64)) for ls in rows]
             return out
+
+    def near_duplicates(self, max_distance: float, cap_per_row: int = 64) -> List[tuple]:
+        """Every pair of stored rows within cosine distance max_distance, each once (FlatIndex.near_duplicates) ->
+        [(id_a, id_b, distance)], id_a the row added earlier, ordered by (id_a's position, distance, id_b's position); a row
+        with more than cap_per_row later partners reports its cap_per_row nearest."""
+        with self._lock:
+            if not self._ids or self._index is None:
+                return []
+            a, b, d = self._index.near_duplicates(max_distance, cap_per_row)[:3]
+            label_to_id = dict(zip(self._labels, self._ids))
+            return [(label_to_id[int(x)], label_to_id[int(y)], float(z)) for x, y, z in zip(a, b, d)]
 
     def get(self, ids=None, include: Sequence[str] = ("metadatas", "documents"), limit: Optional[int] = None,
             offset: Optional[int] = None, **_unused) -> dict:

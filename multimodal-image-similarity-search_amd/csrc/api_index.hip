@@ -54,6 +54,10 @@ struct mmiss_index {
     } pend;
     DevBuf dist_all;  // exhaustive fallback: one canonical distance per row
     PinBuf dist_pin;  // ... and the pinned host block they come back through
+    // radius queries (mmiss_index_query_radius*): a chunk's radii, its queries' own rows (later_only) and, when the caller
+    // passes no out_total, the totals; the queries served and the passes over the index they cost
+    DevBuf rad, row_min, rtotal;
+    int64_t stat_radius_queries = 0, stat_radius_pages = 0;
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -637,16 +641,39 @@ void guard_terms(const mmiss_index* ix, double* fixed, double* cnorm) {
     *cnorm = ix->dtype == MMISS_F32 ? 0.0 : cn * 1.003;
 }
 
-int launch_rerank(mmiss_index* ix, hipStream_t st, const RerankArgs& r, int blocks) {
+// radius: the radius form of the kernel (r.max_dist; mmiss_index_query_radius*)
+int launch_rerank(mmiss_index* ix, hipStream_t st, const RerankArgs& r, int blocks, bool radius = false) {
     int npow = 1;
     while (npow < r.ncand) npow <<= 1;
     const int lds = npow * 8 + 16;
     MM_PROF("rerank", st, 2.0 * blocks * r.ncand * r.D, (double)blocks * r.ncand * r.D * ix->elt);
     const int threads = r.ncand >= 16 ? 1024 : 256;  // one wave per candidate row: more waves hide the gather latency
-    void (*kern)(RerankArgs) = with_storage(ix->dtype, [](auto s) { return &rerank_kernel<typename decltype(s)::T>; });
+    void (*kern)(RerankArgs) = with_storage(ix->dtype, [radius](auto s) {
+        using T = typename decltype(s)::T;
+        return radius ? &rerank_kernel<T, true> : &rerank_kernel<T>;
+    });
     if (lds > 32768) MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds));
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, st, r);
     MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+// The canonical distance of every row to query q of the call's normalised queries (ix->qn), left in the pinned block
+// ix->dist_pin (float [N]; dist_all / dist_pin sized by the caller). Returns with the stream drained.
+int canonical_distances(mmiss_index* ix, hipStream_t st, int32_t q) {
+    const int64_t N = ix->count;
+    const int D = ix->dim;
+    {
+        MM_PROF("canonical_scan", st, 2.0 * N * D, (double)N * D * ix->elt);
+        const int grid = (int)std::min<int64_t>(8192, (N + 15) / 16);
+        with_storage(ix->dtype, [&](auto s) {   // (inv: the inverse norms of fp8 rows, null for the others)
+            hipLaunchKernelGGL(canonical_scan_kernel<typename decltype(s)::T>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
+                               ix->qn.as<float>() + (size_t)q * D, ix->dist_all.as<float>(), (const float*)ix->inv.as<float>());
+        });
+        MM_HIP(hipGetLastError());
+    }
+    MM_HIP(hipMemcpyAsync(ix->dist_pin.p, ix->dist_all.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    MM_HIP(hipStreamSynchronize(st));
     return MMISS_OK;
 }
 
@@ -668,17 +695,7 @@ int exhaustive_queries(mmiss_index* ix, hipStream_t st, const mmiss_index::Pendi
     typedef std::pair<float, int32_t> Ent;  // (distance, row); NaN distances never enter
     for (int i = 0; i < nq; ++i) {
         const int32_t q = which[i];
-        {
-            MM_PROF("canonical_scan", st, 2.0 * N * D, (double)N * D * ix->elt);
-            const int grid = (int)std::min<int64_t>(8192, (N + 15) / 16);
-            with_storage(ix->dtype, [&](auto s) {   // (inv: the inverse norms of fp8 rows, null for the others)
-                hipLaunchKernelGGL(canonical_scan_kernel<typename decltype(s)::T>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
-                                   ix->qn.as<float>() + (size_t)q * D, ix->dist_all.as<float>(), (const float*)ix->inv.as<float>());
-            });
-            MM_HIP(hipGetLastError());
-        }
-        MM_HIP(hipMemcpyAsync(ix->dist_pin.p, ix->dist_all.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-        MM_HIP(hipStreamSynchronize(st));
+        MM_TRY(canonical_distances(ix, st, q));
         std::priority_queue<Ent> heap;  // max-heap: top = the worst of the best kk so far, by (distance, row)
         // filtered query: rows it does not admit never enter (host mirror of the tags)
         const uint64_t rq = pd.filt ? pd.req[(size_t)q] : 0, rx = pd.filt ? pd.exc[(size_t)q] : 0;
@@ -757,6 +774,101 @@ bool sweep_uses_gemm(const mmiss_index* ix, bool filt, int Qf) {
     return !filt && strip_gemm_rows(ix) && strip_v3(ix) && Qf > mmiss_option("sweep_gemm_min_q", 64);
 }
 
+// ONE threshold pass over the index for Qf queries: every row whose approximate score reaches its query's threshold thr_sw[q]
+// is appended to the query's list ix->swp_list[q] (SWEEP_CAP entries; ix->swp_cnt[q] counts them and may run past that). The
+// strip score GEMM for an f16 / fp8 index once the queries fill a quarter of a 256-query tile (it costs about what 1.2 streaming
+// scans cost, and a scan serves 64 queries), the scan otherwise. fm_sw: the masks of filtered queries ([Qf] required, then [Qf]
+// excluded; null: unfiltered) — always the scan, whose FILT form collects admitted rows only; the score GEMM has no filtered
+// epilogue. qs_sw: [Qf rounded up to 256][D] scan operand, rows >= Qf zero; thr_sw likewise, +inf (or anything: m_valid masks
+// them) behind Qf. row_begin: no query wants a row below it (the GEMM starts at its column tile). *pages: the passes over the
+// index this cost. The widen pass of a top-k query and a radius query share it.
+int threshold_pass(mmiss_index* ix, hipStream_t st, int Qf, const void* qs_sw, const float* thr_sw, const uint64_t* fm_sw,
+                   int64_t row_begin, int* pages) {
+    const int D = ix->dim;
+    const int64_t N = ix->count;
+    const bool gemm = sweep_uses_gemm(ix, fm_sw != nullptr, Qf);
+    const int Qfp = (int)round_up(Qf, 256);
+    MM_TRY(ix->swp_cnt.ensure((size_t)Qfp * 4));
+    MM_TRY(ix->swp_list.ensure((size_t)Qf * SWEEP_CAP * 4));
+    MM_HIP(hipMemsetAsync(ix->swp_cnt.p, 0, (size_t)Qfp * 4, st));
+    *pages = 0;
+    if (N <= 0) return MMISS_OK;   // (an empty index: every list stays empty)
+    if (gemm) {
+        const int64_t Npad = round_up(N, 256), nbn = Npad / 256;
+        GemmEpi ep{};
+        ep.m_valid = Qf; ep.p0 = (int)N; ep.m_fast = 1;
+        ep.aux = ix->inv.as<float>();   // (fp8 rows: inverse norms; null otherwise)
+        StripFilter flt{};
+        flt.tau = thr_sw; flt.tau_stride = 1; flt.cnt = ix->swp_cnt.as<int32_t>();
+        flt.buf_s = nullptr; flt.buf_g = ix->swp_list.as<int32_t>(); flt.cap = SWEEP_CAP;
+        flt.bn_begin = (int)(std::min<int64_t>(std::max<int64_t>(row_begin, 0), N - 1) / 256);
+        const int strip = strip_length(Qfp, nbn, nbn - flt.bn_begin);
+        MM_PROF(ix->dtype == MMISS_F8 ? "sweep_gemm_f8" : "sweep_gemm_f16", st, 2.0 * Qf * (double)N * D, (double)N * D * ix->elt);
+        MM_TRY(launch_strip_gemm(ix, st, true, qs_sw, ep, Qfp, (int)Npad, strip, &flt));
+        *pages = 1;
+    } else {
+        const ScanPlan p = plan_sweep(D, ix->qelt(), Qf, N);
+        if (p.lds > SCAN_LDS_LIMIT)
+            MM_FAIL(MMISS_ERR_UNSUPPORTED, "widen pass: a 16-query block of dim %d does not fit the LDS (%d bytes)", D, p.lds);
+        ScanArgs a{};
+        a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>(); a.qs = qs_sw; a.Q = Qf;
+        a.thr = thr_sw; a.gcnt = ix->swp_cnt.as<int32_t>(); a.glist = ix->swp_list.as<int32_t>(); a.gcap = SWEEP_CAP;
+        if (fm_sw) { a.tags = ix->tags.as<uint64_t>(); a.req = fm_sw; a.exc = fm_sw + Qf; }
+        a.tiles_per_block = p.tiles_per_block;
+        MM_TRY(launch_scan(ix, st, a, p));
+        *pages = p.qtiles;
+    }
+    return MMISS_OK;
+}
+
+// The canonical re-rank of the lists a threshold pass collected, Qf blocks (block b: list b; its query r.qmap[b], null: b;
+// `which`: the same map on the host). `r` carries the queries, k, the outputs and, `radius`, the cut. The typical list is short
+// (tens to hundreds of rows), so the first launch sorts at most SWEEP_FAST rows per query WITHOUT waiting to learn the counts;
+// the counts come back with it (one wait), and only the queries that collected more get a second, larger launch. `over`: the
+// blocks whose list overflowed SWEEP_CAP — theirs is the exhaustive pass, the caller's. Returns with the stream drained of the
+// first launch; the second may still be queued.
+int rerank_swept(mmiss_index* ix, hipStream_t st, RerankArgs r, int Qf, const int32_t* which, bool radius, std::vector<int32_t>& over) {
+    const int SWEEP_FAST = 1024;
+    r.rows = ix->rows.p; r.D = ix->dim; r.inv = ix->inv.as<float>(); r.qn = ix->qn.as<float>(); r.cand = ix->swp_list.as<int32_t>();
+    r.cand_stride = SWEEP_CAP; r.ncand = SWEEP_FAST; r.cand_cnt = ix->swp_cnt.as<int32_t>();
+    r.group_mode = 0; r.nrows = ix->count;
+    r.labels = ix->labels_d.as<int64_t>();
+    // the list lengths come back with the re-rank itself: every block stores its list's raw length into a pinned block (a copy
+    // into pageable memory behind the kernel was a second operation and a staged host copy in front of the next query's first
+    // launch: part of the ~87 us the GPU idled per pipelined step, round 6)
+    MM_TRY(ix->swp_pin.ensure((size_t)Qf * 4, st, (size_t)(Qf < 1024 ? 1024 : 2 * Qf) * 4));
+    r.cnt_host = ix->swp_pin.as<int32_t>();
+    MM_TRY(launch_rerank(ix, st, r, Qf, radius));
+    r.cnt_host = nullptr;
+    MM_HIP(hipStreamSynchronize(st));
+    const int32_t* cnt = ix->swp_pin.as<int32_t>();
+    std::vector<int32_t> big_b;   // blocks that need the large re-rank
+    int maxc = 1;
+    over.clear();
+    for (int b = 0; b < Qf; ++b) {
+        if (cnt[b] > SWEEP_CAP) over.push_back(b);
+        else {
+            ix->stat_swept_rows += cnt[b];
+            if (cnt[b] > SWEEP_FAST) { big_b.push_back(b); maxc = std::max(maxc, cnt[b]); }
+        }
+    }
+    if (!big_b.empty()) {
+        // block j of this launch = block big_b[j] of the sweep: its list and count by bmap, its query by qmap
+        const int nb = (int)big_b.size();
+        std::vector<int32_t> qm((size_t)nb);
+        for (int j = 0; j < nb; ++j) qm[j] = which ? which[big_b[j]] : big_b[j];
+        MM_TRY(ix->cand2.ensure((size_t)nb * 8));
+        MM_HIP(hipMemcpyAsync(ix->cand2.p, big_b.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
+        MM_HIP(hipMemcpyAsync(ix->cand2.as<int32_t>() + nb, qm.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
+        MM_HIP(hipStreamSynchronize(st));
+        r.ncand = (int)round_up(maxc, 32);
+        r.bmap = ix->cand2.as<int32_t>();
+        r.qmap = ix->cand2.as<int32_t>() + nb;
+        MM_TRY(launch_rerank(ix, st, r, nb, radius));
+    }
+    return MMISS_OK;
+}
+
 // The widen pass for the queries of `pd` listed in `which` (original indices): ONE threshold pass over the index for all of
 // them (thr_q = c_k - eps_q, left in ix->thr by the first pass's re-rank), the canonical re-rank of the rows it collected, and
 // the exhaustive pass for the lists that overflowed. Results overwrite the queries' rows of pd's outputs. Returns with the
@@ -765,14 +877,7 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const mmiss_index::Pending& p
     const int Qf = (int)which.size(), D = ix->dim;
     const int64_t N = ix->count;
     if (Qf == 0 || N <= 0) return MMISS_OK;
-    // the score GEMM for an f16 index once the flagged queries fill a quarter of a 256-query tile (it costs about what 1.2
-    // streaming scans cost, and a scan serves 64 queries), the scan otherwise
-    // (filtered queries: always the scan, whose FILT form collects admitted rows only; the score GEMM has no filtered epilogue)
-    const bool gemm = sweep_uses_gemm(ix, pd.filt, Qf);
     const int Qfp = (int)round_up(Qf, 256);
-    MM_TRY(ix->swp_cnt.ensure((size_t)Qfp * 4));
-    MM_TRY(ix->swp_list.ensure((size_t)Qf * SWEEP_CAP * 4));
-    MM_HIP(hipMemsetAsync(ix->swp_cnt.p, 0, (size_t)Qfp * 4, st));
     // Every query of the call flagged (the encoder's own embeddings as the index: all of them, every call): the first pass's
     // operands are the sweep's operands — no gather, no map, nothing crosses PCIe. Otherwise the flagged queries are compacted.
     const bool all = Qf == pd.Q;
@@ -809,75 +914,18 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const mmiss_index::Pending& p
         MM_HIP(hipGetLastError());
         qs_sw = ix->qs2.p; thr_sw = ix->thr2.as<float>(); qmap_sw = ix->qmap.as<int32_t>();
     }
-    if (gemm) {
-        const int64_t Npad = round_up(N, 256), nbn = Npad / 256;
-        GemmEpi ep{};
-        ep.m_valid = Qf; ep.p0 = (int)N; ep.m_fast = 1;
-        ep.aux = ix->inv.as<float>();   // (fp8 rows: inverse norms; null otherwise)
-        StripFilter flt{};
-        flt.tau = thr_sw; flt.tau_stride = 1; flt.cnt = ix->swp_cnt.as<int32_t>();
-        flt.buf_s = nullptr; flt.buf_g = ix->swp_list.as<int32_t>(); flt.cap = SWEEP_CAP; flt.bn_begin = 0;
-        const int strip = strip_length(Qfp, nbn, nbn);
-        MM_PROF(ix->dtype == MMISS_F8 ? "sweep_gemm_f8" : "sweep_gemm_f16", st, 2.0 * Qf * (double)N * D, (double)N * D * ix->elt);
-        MM_TRY(launch_strip_gemm(ix, st, true, qs_sw, ep, Qfp, (int)Npad, strip, &flt));
-        ix->stat_pages += 1;
-    } else {
-        const ScanPlan p = plan_sweep(D, ix->qelt(), Qf, N);
-        if (p.lds > SCAN_LDS_LIMIT)
-            MM_FAIL(MMISS_ERR_UNSUPPORTED, "widen pass: a 16-query block of dim %d does not fit the LDS (%d bytes)", D, p.lds);
-        ScanArgs a{};
-        a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>(); a.qs = qs_sw; a.Q = Qf;
-        a.thr = thr_sw; a.gcnt = ix->swp_cnt.as<int32_t>(); a.glist = ix->swp_list.as<int32_t>(); a.gcap = SWEEP_CAP;
-        if (pd.filt) { a.tags = ix->tags.as<uint64_t>(); a.req = fm_sw; a.exc = fm_sw + Qf; }
-        a.tiles_per_block = p.tiles_per_block;
-        MM_TRY(launch_scan(ix, st, a, p));
-        ix->stat_pages += p.qtiles;
-    }
-    // Re-rank what was collected. The typical list is short (tens to hundreds of rows), so the first launch sorts at most
-    // SWEEP_FAST rows per query WITHOUT waiting to learn the counts; the counts come back with it (one small copy behind the
-    // kernels, one wait), and only the queries that collected more get a second, larger launch — or, past SWEEP_CAP, the
-    // exhaustive pass.
-    const int SWEEP_FAST = 1024;
+    int pages = 0;
+    MM_TRY(threshold_pass(ix, st, Qf, qs_sw, thr_sw, pd.filt ? fm_sw : nullptr, 0, &pages));
+    ix->stat_pages += pages;
+    // Re-rank what was collected; past SWEEP_CAP, the exhaustive pass.
     RerankArgs r{};
-    r.rows = ix->rows.p; r.D = D; r.inv = ix->inv.as<float>(); r.qn = ix->qn.as<float>(); r.cand = ix->swp_list.as<int32_t>();
-    r.cand_stride = SWEEP_CAP; r.ncand = SWEEP_FAST; r.cand_cnt = ix->swp_cnt.as<int32_t>();
-    r.group_mode = 0; r.nrows = N;
-    r.labels = ix->labels_d.as<int64_t>(); r.k = pd.k;
+    r.k = pd.k;
     r.out_labels = pd.d_lab; r.out_dist = pd.d_dist; r.out_count = pd.d_cnt;
     r.qmap = qmap_sw;
-    // the list lengths come back with the re-rank itself: every block stores its list's raw length into a pinned block (a copy
-    // into pageable memory behind the kernel was a second operation and a staged host copy in front of the next query's first
-    // launch: part of the ~87 us the GPU idled per pipelined step, round 6)
-    MM_TRY(ix->swp_pin.ensure((size_t)Qf * 4, st, (size_t)(Qf < 1024 ? 1024 : 2 * Qf) * 4));
-    r.cnt_host = ix->swp_pin.as<int32_t>();
-    MM_TRY(launch_rerank(ix, st, r, Qf));
-    r.cnt_host = nullptr;
-    MM_HIP(hipStreamSynchronize(st));
-    const int32_t* cnt = ix->swp_pin.as<int32_t>();
+    std::vector<int32_t> over, rest;   // blocks whose list overflowed / their original indices for the exhaustive pass
+    MM_TRY(rerank_swept(ix, st, r, Qf, which.data(), false, over));
     ix->stat_rounds += 1;
-    std::vector<int32_t> big_b, rest;   // blocks that need the large re-rank / original indices for the exhaustive pass
-    int maxc = 1;
-    for (int b = 0; b < Qf; ++b) {
-        if (cnt[b] > SWEEP_CAP) rest.push_back(which[b]);
-        else {
-            ix->stat_swept_rows += cnt[b];
-            if (cnt[b] > SWEEP_FAST) { big_b.push_back(b); maxc = std::max(maxc, cnt[b]); }
-        }
-    }
-    if (!big_b.empty()) {
-        // block j of this launch = block big_b[j] of the sweep: its list and count by bmap, its query by qmap
-        const int nb = (int)big_b.size();
-        std::vector<int32_t> qm((size_t)nb);
-        for (int j = 0; j < nb; ++j) qm[j] = which[big_b[j]];
-        MM_TRY(ix->cand2.ensure((size_t)nb * 8));
-        MM_HIP(hipMemcpyAsync(ix->cand2.p, big_b.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
-        MM_HIP(hipMemcpyAsync(ix->cand2.as<int32_t>() + nb, qm.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
-        MM_HIP(hipStreamSynchronize(st));
-        r.ncand = (int)round_up(maxc, 32);
-        r.bmap = ix->cand2.as<int32_t>();
-        r.qmap = ix->cand2.as<int32_t>() + nb;
-        MM_TRY(launch_rerank(ix, st, r, nb));
-    }
+    for (int32_t b : over) rest.push_back(which[b]);
     MM_TRY(exhaustive_queries(ix, st, pd, rest));
     MM_HIP(hipStreamSynchronize(st));
     return MMISS_OK;
@@ -1266,6 +1314,7 @@ extern "C" int mmiss_index_guard_stats_ex(mmiss_index* ix, int64_t out[8]) {
     for (int i = 0; i < 8; ++i) out[i] = 0;
     out[0] = ix->stat_queries; out[1] = ix->stat_flagged; out[2] = ix->stat_rounds; out[3] = ix->stat_pages;
     out[4] = ix->stat_exhaustive; out[5] = ix->stat_swept_rows;
+    out[6] = ix->stat_radius_queries; out[7] = ix->stat_radius_pages;
     return MMISS_OK;
 }
 
@@ -1273,6 +1322,267 @@ extern "C" int mmiss_index_guard_stats(mmiss_index* ix, int64_t out[4]) {
     if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_guard_stats: null argument");
     std::lock_guard<std::mutex> lk(ix->mu);
     out[0] = ix->stat_queries; out[1] = ix->stat_flagged; out[2] = ix->stat_rounds; out[3] = ix->stat_pages;
+    return MMISS_OK;
+}
+
+// ================================================================================================ radius queries
+// "Every row at least this similar": the members of query q are the rows with a direction that q admits and whose canonical
+// distance is <= max_dist[q] (float compare). It is the widen pass with the threshold taken from the caller's radius instead
+// of a top-k's k-th score: ONE threshold pass (threshold_pass: thr_q = (1 - R) - eps_q, radius_thr_kernel has the derivation),
+// the canonical re-rank with the cut (rerank_kernel<T, true>), and for a list of more than SWEEP_CAP rows the exhaustive
+// canonical pass with a host selection. No first pass, no guard decision: a call costs one pass over the index per chunk on the
+// score GEMM, one per 64 queries on the scan. Exact: ids and distance bits are the canonical arithmetic's.
+namespace {
+
+constexpr int RADIUS_CHUNK = 1024;   // queries per chunk: bounds the lists (SWEEP_CAP x 4 B each) and the pinned staging
+constexpr int RADIUS_MAX_CAP = 4096;
+
+// one radius call, as its chunks see it
+struct RadiusCall {
+    int cap = 0;
+    const float* rad = nullptr;         // [Q] HOST radii (no NaN)
+    const uint64_t* req = nullptr;      // [Q] masks as the caller passed them (host or device), null = 0
+    const uint64_t* exc = nullptr;
+    const int32_t* row_min = nullptr;   // [Q] HOST: later_only, the queries' own rows; null otherwise
+    bool out_dev = false;
+    int64_t* out_labels = nullptr; float* out_dist = nullptr; int32_t* out_count = nullptr; int64_t* out_total = nullptr;
+};
+
+// host copy of a (host or device) float array; device memory is read on the index's stream
+int fetch_f32(const float* p, int64_t n, std::vector<float>& out, hipStream_t st) {
+    out.resize((size_t)n);
+    if (n == 0) return MMISS_OK;
+    if (mmiss_is_device_ptr(p)) {
+        MM_HIP(hipMemcpyAsync(out.data(), p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        MM_HIP(hipStreamSynchronize(st));
+    } else {
+        memcpy(out.data(), p, (size_t)n * 4);
+    }
+    return MMISS_OK;
+}
+
+// The exhaustive pass of a radius query: chunk query qc (radius R, masks of ix->pend, later_only: rows above row_min) against
+// every row — the admitted rows with d <= R, all counted, the `cap` best by (distance, row) kept. `lab` / `dist`: [cap] host.
+int radius_exhaustive(mmiss_index* ix, hipStream_t st, int32_t qc, float R, int64_t row_min, int cap, int64_t* lab, float* dist,
+                      int32_t* count, int64_t* total) {
+    const int64_t N = ix->count;
+    const mmiss_index::Pending& pd = ix->pend;
+    MM_TRY(ix->dist_all.ensure((size_t)N * 4));
+    MM_TRY(ix->dist_pin.ensure((size_t)N * 4, st));
+    MM_TRY(canonical_distances(ix, st, qc));
+    const float* d_all = ix->dist_pin.as<float>();
+    typedef std::pair<float, int32_t> Ent;  // (distance, row); NaN distances are no members (d <= R is false)
+    std::vector<Ent> mem;
+    const uint64_t rq = pd.filt ? pd.req[(size_t)qc] : 0, rx = pd.filt ? pd.exc[(size_t)qc] : 0;
+    for (int64_t r = std::max<int64_t>(row_min + 1, 0); r < N; ++r) {
+        const float d = d_all[(size_t)r];
+        if (!(d <= R)) continue;
+        if (pd.filt && !tag_admits_h(ix->tags_h[(size_t)r], rq, rx)) continue;
+        mem.push_back(Ent(d, (int32_t)r));
+    }
+    const size_t keep = std::min<size_t>((size_t)cap, mem.size());
+    std::partial_sort(mem.begin(), mem.begin() + keep, mem.end());
+    for (int i = 0; i < cap; ++i) {
+        lab[i] = (size_t)i < keep ? ix->labels_h[(size_t)mem[i].second] : -1;
+        dist[i] = (size_t)i < keep ? mem[i].first : INFINITY;
+    }
+    *count = (int32_t)keep;
+    *total = (int64_t)mem.size();
+    ix->stat_exhaustive += 1;
+    return MMISS_OK;
+}
+
+// One chunk of a radius call: queries [q0, q0 + Qc) of the call, `queries` pointing at the chunk's first (host or device).
+// row_begin: no query of the chunk wants a row below it. Returns with the stream drained and the chunk's outputs delivered.
+int radius_chunk(mmiss_index* ix, hipStream_t st, const RadiusCall& c, const float* queries, int64_t q0, int Qc, int64_t row_begin) {
+    const int cap = c.cap;
+    const int Qpad = (int)round_up(Qc, 256);
+    MM_TRY(stage_filter(ix, st, Qc, c.req ? c.req + q0 : nullptr, c.exc ? c.exc + q0 : nullptr));
+    const mmiss_index::Pending& pd = ix->pend;   // (the chunk's masks; no query is open: MM_NO_PENDING at the entry)
+    // outputs: the caller's device buffers, or a pinned host block the re-rank writes straight into
+    int64_t* d_lab; float* d_dist; int32_t* d_cnt; int64_t* d_tot;
+    if (c.out_dev) {
+        d_lab = c.out_labels + q0 * cap; d_dist = c.out_dist + q0 * cap; d_cnt = c.out_count + q0;
+        d_tot = c.out_total ? c.out_total + q0 : nullptr;
+        if (!d_tot) { MM_TRY(ix->rtotal.ensure((size_t)RADIUS_CHUNK * 8)); d_tot = ix->rtotal.as<int64_t>(); }
+    } else {
+        const size_t o_tot = (size_t)Qc * cap * 8, o_dist = o_tot + (size_t)Qc * 8, o_cnt = o_dist + (size_t)Qc * cap * 4;
+        const size_t need = o_cnt + (size_t)Qc * 4;
+        size_t grow = 4096;
+        while (grow < need) grow *= 2;
+        MM_TRY(ix->pin.ensure(need, st, grow));
+        char* const pin = ix->pin.as<char>();
+        d_lab = reinterpret_cast<int64_t*>(pin); d_tot = reinterpret_cast<int64_t*>(pin + o_tot);
+        d_dist = reinterpret_cast<float*>(pin + o_dist); d_cnt = reinterpret_cast<int32_t*>(pin + o_cnt);
+    }
+    MM_TRY(upload_queries(ix, st, queries, Qc));   // qn, qs (pad rows zero), eps_q
+    MM_TRY(ix->rad.ensure((size_t)RADIUS_CHUNK * 4));
+    MM_HIP(hipMemcpyAsync(ix->rad.p, c.rad + q0, (size_t)Qc * 4, hipMemcpyHostToDevice, st));
+    if (c.row_min) {
+        MM_TRY(ix->row_min.ensure((size_t)RADIUS_CHUNK * 4));
+        MM_HIP(hipMemcpyAsync(ix->row_min.p, c.row_min + q0, (size_t)Qc * 4, hipMemcpyHostToDevice, st));
+    }
+    {
+        MM_PROF("radius_thr", st, 2.0 * Qc, (double)Qpad * 12);
+        hipLaunchKernelGGL(radius_thr_kernel, dim3((Qpad + 255) / 256), dim3(256), 0, st, ix->rad.as<float>(), ix->eps_q.as<float>(),
+                           ix->thr.as<float>(), Qc, Qpad);
+        MM_HIP(hipGetLastError());
+    }
+    int pages = 0;
+    MM_TRY(threshold_pass(ix, st, Qc, ix->qs.p, ix->thr.as<float>(), pd.filt ? pd.d_mask : nullptr, row_begin, &pages));
+    RerankArgs r{};
+    r.k = cap;
+    r.out_labels = d_lab; r.out_dist = d_dist; r.out_count = d_cnt; r.out_total = d_tot;
+    r.max_dist = ix->rad.as<float>();
+    r.row_min = c.row_min ? ix->row_min.as<int32_t>() : nullptr;
+    std::vector<int32_t> over;
+    MM_TRY(rerank_swept(ix, st, r, Qc, nullptr, true, over));
+    MM_HIP(hipStreamSynchronize(st));
+    ix->stat_radius_queries += Qc;
+    ix->stat_radius_pages += pages;
+    if (!over.empty()) {   // a list of more than SWEEP_CAP rows: one canonical pass and one host selection per such query
+        std::vector<int64_t> xl((size_t)cap);
+        std::vector<float> xd((size_t)cap);
+        for (int32_t qc : over) {
+            int32_t cnt = 0;
+            int64_t tot = 0;
+            MM_TRY(radius_exhaustive(ix, st, qc, c.rad[q0 + qc], c.row_min ? c.row_min[q0 + qc] : -1, cap, xl.data(), xd.data(), &cnt, &tot));
+            if (c.out_dev) {
+                MM_HIP(hipMemcpyAsync(d_lab + (size_t)qc * cap, xl.data(), (size_t)cap * 8, hipMemcpyHostToDevice, st));
+                MM_HIP(hipMemcpyAsync(d_dist + (size_t)qc * cap, xd.data(), (size_t)cap * 4, hipMemcpyHostToDevice, st));
+                MM_HIP(hipMemcpyAsync(d_cnt + qc, &cnt, 4, hipMemcpyHostToDevice, st));
+                MM_HIP(hipMemcpyAsync(d_tot + qc, &tot, 8, hipMemcpyHostToDevice, st));
+                MM_HIP(hipStreamSynchronize(st));   // (pageable sources, reused by the next query)
+            } else {
+                memcpy(d_lab + (size_t)qc * cap, xl.data(), (size_t)cap * 8);
+                memcpy(d_dist + (size_t)qc * cap, xd.data(), (size_t)cap * 4);
+                d_cnt[qc] = cnt;
+                d_tot[qc] = tot;
+            }
+        }
+    }
+    if (!c.out_dev) {
+        memcpy(c.out_labels + q0 * cap, d_lab, (size_t)Qc * cap * 8);
+        memcpy(c.out_dist + q0 * cap, d_dist, (size_t)Qc * cap * 4);
+        memcpy(c.out_count + q0, d_cnt, (size_t)Qc * 4);
+        if (c.out_total) memcpy(c.out_total + q0, d_tot, (size_t)Qc * 8);
+    }
+    return MMISS_OK;
+}
+
+// what the two entry points check alike; fills c's outputs and cap
+int radius_check(const char* who, int cap, int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_total, RadiusCall& c) {
+    if (!out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (cap < 1 || cap > RADIUS_MAX_CAP) MM_FAIL(MMISS_ERR_ARG, "%s: cap = %d (1 .. %d result slots per query)", who, cap, RADIUS_MAX_CAP);
+    c.out_dev = mmiss_is_device_ptr(out_labels);
+    if (c.out_dev != mmiss_is_device_ptr(out_dist) || c.out_dev != mmiss_is_device_ptr(out_count) ||
+        (out_total && c.out_dev != mmiss_is_device_ptr(out_total)))
+        MM_FAIL(MMISS_ERR_ARG, "%s: output pointers must be all host or all device", who);
+    c.cap = cap;
+    c.out_labels = out_labels; c.out_dist = out_dist; c.out_count = out_count; c.out_total = out_total;
+    return MMISS_OK;
+}
+
+}  // namespace
+
+extern "C" int mmiss_index_query_radius(mmiss_index* ix, const float* queries, int32_t Q, const float* max_dist, int32_t cap,
+                                        const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
+                                        int32_t* out_count, int64_t* out_total) {
+    const char* who = "mmiss_index_query_radius";
+    if (!ix || (Q > 0 && (!queries || !max_dist))) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 0) MM_FAIL(MMISS_ERR_ARG, "%s: Q = %d", who, Q);
+    if (Q == 0) return MMISS_OK;
+    RadiusCall c;
+    MM_TRY(radius_check(who, cap, out_labels, out_dist, out_count, out_total, c));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    std::vector<float> rad;
+    MM_TRY(fetch_f32(max_dist, Q, rad, st));
+    for (int q = 0; q < Q; ++q)
+        if (rad[(size_t)q] != rad[(size_t)q]) MM_FAIL(MMISS_ERR_ARG, "%s: max_dist[%d] is NaN", who, q);
+    c.rad = rad.data(); c.req = require; c.exc = exclude;
+    for (int64_t q0 = 0; q0 < Q; q0 += RADIUS_CHUNK) {
+        const int Qc = (int)std::min<int64_t>(RADIUS_CHUNK, Q - q0);
+        MM_TRY(radius_chunk(ix, st, c, queries + q0 * ix->dim, q0, Qc, 0));
+    }
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_query_radius_by_label(mmiss_index* ix, const int64_t* labels, int64_t n, float max_dist, int32_t cap,
+                                                 int32_t later_only, int64_t* out_labels, float* out_dist, int32_t* out_count,
+                                                 int64_t* out_total) {
+    const char* who = "mmiss_index_query_radius_by_label";
+    if (!ix || (n > 0 && !labels)) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (n < 0) MM_FAIL(MMISS_ERR_ARG, "%s: n = %lld", who, (long long)n);
+    if (max_dist != max_dist) MM_FAIL(MMISS_ERR_ARG, "%s: max_dist is NaN", who);
+    if (n == 0) return MMISS_OK;
+    RadiusCall c;
+    MM_TRY(radius_check(who, cap, out_labels, out_dist, out_count, out_total, c));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    std::vector<int64_t> rows((size_t)n);
+    std::vector<int32_t> rows32((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {   // every label first: a missing one writes nothing
+        rows[(size_t)i] = find_row(ix, labels[i]);
+        if (rows[(size_t)i] < 0) MM_FAIL(MMISS_ERR_ARG, "%s: label %lld not in the index", who, (long long)labels[i]);
+        rows32[(size_t)i] = (int32_t)rows[(size_t)i];
+    }
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    const std::vector<float> rad((size_t)n, max_dist);
+    c.rad = rad.data();
+    c.row_min = later_only ? rows32.data() : nullptr;
+    const int D = ix->dim;
+    for (int64_t q0 = 0; q0 < n; q0 += RADIUS_CHUNK) {
+        const int Qc = (int)std::min<int64_t>(RADIUS_CHUNK, n - q0);
+        // the chunk's queries: the rows the index represents, widened to f32 on the device (what mmiss_index_get returns)
+        MM_TRY(ix->map.ensure((size_t)RADIUS_CHUNK * 8));
+        MM_TRY(ix->stage.ensure((size_t)RADIUS_CHUNK * D * 4));
+        MM_HIP(hipMemcpyAsync(ix->map.p, rows.data() + q0, (size_t)Qc * 8, hipMemcpyHostToDevice, st));
+        {
+            MM_PROF("rows_as_queries", st, 0.0, (double)Qc * D * (4 + ix->elt));
+            const int grid = (int)std::min<int64_t>(4096, ((int64_t)Qc * D + 255) / 256);
+            with_storage(ix->dtype, [&](auto s) {
+                using T = typename decltype(s)::T;
+                hipLaunchKernelGGL(rows_as_queries_kernel<T>, dim3(grid), dim3(256), 0, st, ix->rows.as<T>(), (const float*)ix->inv.as<float>(),
+                                   ix->map.as<int64_t>(), ix->stage.as<float>(), (int64_t)Qc, D);
+            });
+            MM_HIP(hipGetLastError());
+        }
+        // later_only: a query wants rows above its own only, so the pass may start at the chunk's smallest row
+        int64_t row_begin = 0;
+        if (later_only) row_begin = *std::min_element(rows.begin() + q0, rows.begin() + q0 + Qc);
+        MM_TRY(radius_chunk(ix, st, c, ix->stage.as<float>(), q0, Qc, row_begin));
+    }
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: the path a radius call of Q queries would take on the index as it stands, chunk by chunk: the functions
+// radius_chunk itself calls, nothing launched, no state changed.
+extern "C" int mmiss_dbg_index_radius_plan(mmiss_index* ix, int32_t Q, int32_t filtered, int32_t* out) {
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_radius_plan: null argument");
+    if (Q <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_radius_plan: Q=%d", Q);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    const int64_t N = ix->count;
+    const int chunks = (Q + RADIUS_CHUNK - 1) / RADIUS_CHUNK;
+    out[0] = chunks;
+    const int Qc[2] = {std::min<int>(Q, RADIUS_CHUNK), Q - (chunks - 1) * RADIUS_CHUNK};   // the first chunk, the last
+    for (int i = 0; i < 2; ++i) {
+        int32_t* o = out + 1 + 7 * i;
+        o[0] = Qc[i];
+        if (N <= 0) continue;   // (an empty index: no pass at all)
+        if (sweep_uses_gemm(ix, filtered != 0, Qc[i])) {
+            const int64_t nbn = round_up(N, 256) / 256;
+            o[1] = 1;
+            o[2] = strip_length((int)round_up(Qc[i], 256), nbn, nbn);
+        } else {
+            const ScanPlan sp = plan_sweep(ix->dim, ix->qelt(), Qc[i], N);
+            o[3] = sp.nqt; o[4] = sp.slabs; o[5] = sp.tiles_per_block; o[6] = sp.qtiles;
+        }
+    }
     return MMISS_OK;
 }
 

@@ -844,18 +844,24 @@ struct RerankArgs {
     // exactness guard (see api_index.hip "exactness contract"): tau[b] = stage 1's bound on the approximate score of every
     // row that is NOT among the candidates (-inf: every row is a candidate). The result is proven exact when the k-th
     // canonical score clears tau by more than eps; otherwise flags[b] = 1 and *nflag (when given) counts it.
-    const float* tau;
+    // radius form (rerank_kernel<T, true>, mmiss_index_query_radius*): no guard — the three pointers the guard alone reads
+    // (tau, ovf_cnt, thr_out) carry the cut instead, under their own names; the struct, and with it every kernel-argument
+    // offset of the top-k instantiations, stays as it was. k is the caller's cap; the members of query q are the sorted
+    // entries with dist <= max_dist[q] (a float compare; NaN distances are no members): out_total[q] counts them all, the
+    // first min(k, total) are written. row_min (later_only, null otherwise): a candidate row <= row_min[q] is dropped before
+    // the sort. All three by the ORIGINAL query.
+    union { const float* tau; const float* max_dist; };
     double eps;
     int32_t* flags;
     int32_t* nflag;
     int force_flag;         // tests: flag every query whose candidate list was full
     // threshold-filtered selection: a query whose candidate list overflowed (ovf_cnt[q] > ovf_cap) lost candidates: flag it
-    const int32_t* ovf_cnt;
+    union { const int32_t* ovf_cnt; const int32_t* row_min; };
     int ovf_cap;
     const float* eps_q;     // per-query error bound (prep_queries_kernel), indexed by the ORIGINAL query; null: eps
     // out: the threshold of the widen pass, thr_out[q] = (k-th canonical score) - eps rounded down — every row that can
     // still belong to the top-k has an approximate score >= it (-inf when fewer than k candidates were valid)
-    float* thr_out;
+    union { float* thr_out; int64_t* out_total; };
     const int32_t* cand_cnt;  // per-block candidate count (widen pass: the appended rows), null: ncand for every block
     const int32_t* bmap;      // block b reads candidate list / count bmap[b] (null: b)
     const float* inv;         // fp8 rows: inverse norm per row (f8_row_inv_kernel): canonical score = canon_dot x (double)inv[row]
@@ -906,7 +912,7 @@ __device__ __forceinline__ void canon_partial_dots(const T* rv, bool live, const
     }
 }
 
-template <typename T>
+template <typename T, bool RADIUS = false>
 __global__ __launch_bounds__(1024) void rerank_kernel(RerankArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -928,6 +934,11 @@ __global__ __launch_bounds__(1024) void rerank_kernel(RerankArgs a) {
     const float* qv = a.qn + (size_t)q * a.D;
     const int nthreads = blockDim.x, nwaves = blockDim.x >> 6;
     for (int i = tid; i < npow; i += nthreads) { sd[i] = INFINITY; sr[i] = INT32_MAX; }
+    // (radius form: the member count, in the 16 spare bytes every launch provides behind the sort buffer)
+    int* const s_members = reinterpret_cast<int*>(smem + (size_t)npow * 8);
+    if constexpr (RADIUS) {
+        if (tid == 0) *s_members = 0;
+    }
     __syncthreads();
     // Canonical dot products, FOUR candidate rows per wave at a time: the 16 lanes p of a quarter wave stand for the 64
     // lanes of the canonical reduction, lane p holding the partial sums of canonical lanes 4p .. 4p+3 (elements
@@ -948,6 +959,9 @@ __global__ __launch_bounds__(1024) void rerank_kernel(RerankArgs a) {
                 }
             } else {
                 row = a.cand[(size_t)lb * a.cand_stride + c];
+            }
+            if constexpr (RADIUS) {   // later_only: rows up to the query's own never enter the sort
+                if (a.row_min && row <= (int64_t)a.row_min[q]) row = -1;
             }
         }
         const bool live = row >= 0;  // (no candidate, or an empty index: nothing is dereferenced)
@@ -987,6 +1001,27 @@ __global__ __launch_bounds__(1024) void rerank_kernel(RerankArgs a) {
             }
             __syncthreads();
         }
+    }
+    if constexpr (RADIUS) {
+        // The cut: members are the entries with dist <= max_dist[q] — a prefix of the sorted order (NaN distances and the
+        // padding sort last; the padding's +inf distance is told from a row's by its row id). Every member is counted, the
+        // first min(k, members) are the result.
+        const float rmax = a.max_dist[q];
+        int mine = 0;
+        for (int i = tid; i < npow; i += nthreads) mine += (sr[i] != INT32_MAX && sd[i] <= rmax) ? 1 : 0;
+        if (mine) atomicAdd(s_members, mine);
+        __syncthreads();
+        const int members = *s_members;
+        for (int i = tid; i < a.k; i += nthreads) {
+            const bool ok = i < members;
+            a.out_labels[(size_t)q * a.k + i] = ok ? a.labels[sr[i]] : -1;
+            a.out_dist[(size_t)q * a.k + i] = ok ? sd[i] : INFINITY;
+        }
+        if (tid == 0) {
+            a.out_count[q] = members < a.k ? members : a.k;
+            if (a.out_total) a.out_total[q] = members;
+        }
+        return;
     }
     for (int i = tid; i < a.k; i += nthreads) {
         const bool ok = i < npow && sr[i] != INT32_MAX;
@@ -1162,6 +1197,51 @@ __global__ __launch_bounds__(256) void shard_merge_kernel(const float* __restric
         const int lim = k < npow ? k : npow;
         for (int i = 0; i < lim; ++i) c += (sl[i] != INT64_MAX);
         out_count[q] = c;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Radius queries (mmiss_index_query_radius*, api_index.hip "radius queries"): the threshold of the ONE threshold pass.
+//   Row r is a member of query q iff d(q, r) = (float)(1 - c) <= R, c the canonical score, R = max_dist[q].
+//   The float rounding of 1 - c moves it by at most 2^-23 (|1 - c| <= 2), so a member has c >= (1 - R) - 2^-23; guard_terms'
+//   2^-21 term, part of eps_q, covers that rounding (and three more of its size).
+//   A row's approximate score s is within eps_q of c minus that term (prep_queries_kernel, guard_terms): s >= c - eps_q'.
+//   So every member has s >= (1 - R) - eps_q =: thr_q, evaluated in fp64 and rounded toward -inf, exactly as rerank_kernel
+//   rounds thr_out: no member scores below thr_q, and the threshold pass (s >= thr_q) collects every member.
+// A query without a direction (eps_q = +inf, prep_queries_kernel) gets +inf — it has no members and collects nothing — as do
+// the pad queries [Q, Qpad) of the score GEMM's 256-query tile. No special case for R: a negative R only raises the
+// threshold, R >= 2 puts it below every score, R = +inf gives -inf.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void radius_thr_kernel(const float* __restrict__ max_dist, const float* __restrict__ eps_q,
+                                                         float* __restrict__ thr, int Q, int Qpad) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= Qpad) return;
+    float t = INFINITY;
+    if (q < Q) {
+        const float e = eps_q[q];
+        if (e < INFINITY) {
+            const double lim = (1.0 - (double)max_dist[q]) - (double)e;
+            t = (float)lim;
+            if ((double)t > lim) t = nextafterf(t, -INFINITY);
+        }
+    }
+    thr[q] = t;
+}
+
+// The rows the index represents as f32 query vectors (mmiss_index_query_radius_by_label): dst[i] = the stored row map[i] widened
+// to f32, fp8 rows x their inverse norm (one f32 multiply) — element for element what mmiss_index_get returns. map holds rows
+// below the index's count (the host looked the labels up): nothing behind count is read.
+template <typename T>
+__global__ __launch_bounds__(256) void rows_as_queries_kernel(const T* __restrict__ src, const float* __restrict__ inv,
+                                                              const int64_t* __restrict__ map, float* __restrict__ dst, int64_t n, int D) {
+    const int64_t total = n * D;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / D;
+        const int d = (int)(i - r * D);
+        const int64_t row = map[r];
+        const float v = (float)src[row * D + d];
+        if constexpr (sizeof(T) == 1) dst[i] = v * inv[row];
+        else dst[i] = v;
     }
 }
 

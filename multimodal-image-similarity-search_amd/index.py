@@ -244,14 +244,99 @@ class FlatIndex:
                 return PendingQuery(self, q, (lab, dist, cnt), self._query_gen, masks)
         return (lab, dist, cnt)
 
+    # ------------------------------------------------------------------ radius queries
+    def _radius_outputs(self, Q: int, cap: int, like=None):
+        if like is not None:
+            import torch
+
+            dev = like.device
+            return (torch.empty((Q, cap), dtype=torch.int64, device=dev), torch.empty((Q, cap), dtype=torch.float32, device=dev),
+                    torch.empty((Q,), dtype=torch.int32, device=dev), torch.empty((Q,), dtype=torch.int64, device=dev))
+        # (filled here: a call of no queries writes nothing)
+        return (np.full((Q, cap), -1, dtype=np.int64), np.full((Q, cap), np.inf, dtype=np.float32),
+                np.zeros((Q,), dtype=np.int32), np.zeros((Q,), dtype=np.int64))
+
+    def query_radius(self, queries, max_dist, cap: int = 1000, require=None, exclude=None):
+        """Every row within cosine distance max_dist of each query, exactly (mmiss_index_query_radius) -> (labels int64 [Q, cap],
+        distances float32 [Q, cap], counts int32 [Q], totals int64 [Q]): row r is a member of query q iff it has a direction, q
+        admits it (require / exclude as in query()) and its distance — the bits query() returns — is <= max_dist[q] as floats.
+        totals = the members there are, counts = min(cap, totals), the slots the counts nearest members by (distance, label),
+        unused ones -1 / +inf. max_dist: a scalar (every query) or [Q], numpy or a CUDA tensor; NaN raises. cap: 1 .. 4096.
+        numpy in -> numpy out, CUDA tensor in -> CUDA tensors out."""
+        q = self._vecs(queries)
+        Q = int(q.shape[0])
+        cuda = _is_torch(q) and q.is_cuda
+        if _is_torch(q) and not cuda:
+            q = q.numpy()
+        if _is_torch(max_dist) and max_dist.is_cuda and cuda:
+            import torch
+
+            r = max_dist.to(torch.float32)
+            r = (r.reshape(1).expand(Q) if r.dim() == 0 else r).contiguous()
+        else:
+            if _is_torch(max_dist):
+                max_dist = max_dist.detach().cpu().numpy()
+            r = np.asarray(max_dist, dtype=np.float32)
+            r = np.ascontiguousarray(np.full(Q, r, dtype=np.float32) if r.ndim == 0 else r)
+        if r.ndim != 1 or int(r.shape[0]) != Q:
+            raise ValueError(f"max_dist: expected a scalar or [{Q}] radii, got shape {tuple(r.shape)}")
+        masks = self._masks(q, require, exclude) or (None, None)
+        lab, dist, cnt, tot = self._radius_outputs(Q, int(cap), q if cuda else None)
+        with self._call_lock:
+            self._sync_stream(q)
+            _lib.check(self._lib.mmiss_index_query_radius(self._h, _lib.ptr(q), Q, _lib.ptr(r), int(cap), _lib.ptr(masks[0]),
+                                                          _lib.ptr(masks[1]), _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt), _lib.ptr(tot)))
+        return lab, dist, cnt, tot
+
+    def query_radius_by_label(self, labels, max_dist: float, cap: int, later_only: bool = False, device=None):
+        """query_radius with the rows the index represents under `labels` as the queries (mmiss_index_query_radius_by_label):
+        exactly query_radius(self.get(labels), max_dist, cap), without the rows leaving the device. later_only: only rows whose
+        label is greater than the query's own are admitted (no self match; every pair once, the smaller label as the query). A
+        label that is not stored raises and writes nothing. device: a torch device for CUDA outputs; numpy outputs otherwise."""
+        lab_in = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        n = int(lab_in.shape[0])
+        like = None
+        if device is not None:
+            import torch
+
+            like = torch.empty(0, device=device)
+        lab, dist, cnt, tot = self._radius_outputs(n, int(cap), like)
+        with self._call_lock:
+            self._sync_stream(like)
+            _lib.check(self._lib.mmiss_index_query_radius_by_label(self._h, lab_in.ctypes.data, n, float(max_dist), int(cap),
+                                                                   1 if later_only else 0, _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt),
+                                                                   _lib.ptr(tot)))
+        return lab, dist, cnt, tot
+
+    def near_duplicates(self, max_dist: float, cap_per_row: int = 64):
+        """Every pair of stored rows within cosine distance max_dist, each once -> (a int64 [P], b int64 [P], dist float32 [P],
+        overflow): labels a < b, ordered by (a, dist, b); overflow = {label: total} for the rows with more than cap_per_row
+        later partners (of those the cap_per_row nearest are reported). Walks the labels in chunks of 1024 through
+        query_radius_by_label(later_only=True)."""
+        labels = self.labels()
+        pa, pb, pd, overflow = [], [], [], {}
+        for i0 in range(0, labels.shape[0], 1024):
+            chunk = labels[i0:i0 + 1024]
+            lab, dist, cnt, tot = self.query_radius_by_label(chunk, max_dist, cap_per_row, later_only=True)
+            keep = np.arange(lab.shape[1])[None, :] < cnt[:, None]
+            pa.append(np.repeat(chunk, cnt))
+            pb.append(lab[keep])
+            pd.append(dist[keep])
+            for j in np.nonzero(tot > cap_per_row)[0]:
+                overflow[int(chunk[j])] = int(tot[j])
+        if not pa:
+            return np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.float32), overflow
+        return np.concatenate(pa), np.concatenate(pb), np.concatenate(pd), overflow
+
     def guard_stats(self) -> dict:
         """Exactness accounting (mmiss_index_guard_stats_ex): queries served, queries whose first pass could not be proven
         exact and were widened, widen (threshold) passes run, extra passes over the index they cost, the queries that ended in
-        the exhaustive canonical pass (a tie plateau of more than 8192 rows), and the rows the threshold passes re-ranked."""
+        the exhaustive canonical pass (a tie plateau of more than 8192 rows), the rows the threshold passes re-ranked, and the
+        radius calls' own two: the queries they served and the passes over the index those cost."""
         out = (C.c_int64 * 8)()
         _lib.check(self._lib.mmiss_index_guard_stats_ex(self._h, out))
         return {"queries": out[0], "widened": out[1], "rounds": out[2], "pages": out[3], "exhaustive": out[4],
-                "swept_rows": out[5]}
+                "swept_rows": out[5], "radius_queries": out[6], "radius_pages": out[7]}
 
     # ------------------------------------------------------------------ persistence
     def save(self, path: str) -> None:

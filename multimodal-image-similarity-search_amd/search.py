@@ -62,16 +62,25 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
     return similar_images
 
 
-def _filter_kw(filters) -> dict:
-    return {"filters": list(filters)} if filters else {}
+def _filter_kw(filters, min_similarity=None) -> dict:
+    """the keyword arguments of FlatCollection.query for a search's filters and similarity threshold; min_similarity = s becomes
+    the radius utils.max_distance_for_similarity(s): on its results "similarity_score >= s" holds for exactly the members"""
+    kw = {"filters": list(filters)} if filters else {}
+    if min_similarity is not None:
+        kw["max_distance"] = float(utils.max_distance_for_similarity(min_similarity))
+    return kw
 
 
-def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None) -> List[Dict]:
-    """Search for similar images using an embedding (main.py:748-805)."""
+def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
+                   min_similarity: Optional[float] = None) -> List[Dict]:
+    """Search for similar images using an embedding (main.py:748-805). min_similarity: only the images whose similarity_score
+    reaches it, exactly (a radius query; `limit` caps how many) — the reference's roadmap item "Adjustable similarity
+    thresholds" (CHANGELOG.md:475)."""
     try:
         actual_limit = 1000 if limit <= 0 else limit  # "All" option (limit of 0), main.py:757
         results = _collection().query(query_embeddings=[np.asarray(embedding, dtype=np.float32).tolist()],
-                                      n_results=actual_limit, include=["metadatas", "distances"], **_filter_kw(filters))
+                                      n_results=actual_limit, include=["metadatas", "distances"],
+                                      **_filter_kw(filters, min_similarity))
         out = _results_from_query(results, 0)
         logger.info(f"Found {len(out)} similar images")
         return out
@@ -80,33 +89,35 @@ def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[
         return []
 
 
-def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None) -> List[List[Dict]]:
+def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
+                         min_similarity: Optional[float] = None) -> List[List[Dict]]:
     """[Q, D] embeddings -> one result list per query, one index pass for the whole batch."""
     try:
         actual_limit = 1000 if limit <= 0 else limit
         q = np.asarray(embeddings, dtype=np.float32)
         results = _collection().query(query_embeddings=q, n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters))
+                                      **_filter_kw(filters, min_similarity))
         return [_results_from_query(results, qi) for qi in range(q.shape[0])]
     except Exception as e:
         logger.error(f"Error searching for similar images: {e}")
         return []
 
 
-def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequence[str]] = None) -> List[Dict]:
+def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
+                   min_similarity: Optional[float] = None) -> List[Dict]:
     """Search for images using a text query (main.py:807-827)."""
     try:
         model, processor = utils.load_clip_model()
         embedding_result = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)
         text_embedding = embedding_result["text"][0]
-        return search_similar(embedding=text_embedding, limit=limit, filters=filters)
+        return search_similar(embedding=text_embedding, limit=limit, filters=filters, min_similarity=min_similarity)
     except Exception as e:
         logger.error(f"Error in text search: {e}")
         return []
 
 
 def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: int = 10, *,
-                      filters: Optional[Sequence[str]] = None) -> List[Dict]:
+                      filters: Optional[Sequence[str]] = None, min_similarity: Optional[float] = None) -> List[Dict]:
     """Search using both image and text with a weighted combination (main.py:829-867); weight_image is not
     clamped, as in the backend route."""
     try:
@@ -115,26 +126,55 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
         text_embedding = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)["text"][0]
         # normalise both, weighted sum, normalise again (main.py:852-860) — one GPU kernel
         combined_embedding = blend(image_embedding[None], text_embedding[None], weight_image)[0]
-        return search_similar(embedding=combined_embedding, limit=limit, filters=filters)
+        return search_similar(embedding=combined_embedding, limit=limit, filters=filters, min_similarity=min_similarity)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
 
 
 def search_multimodal_batch(image_embeddings: np.ndarray, text_embeddings: np.ndarray, weight_image: float = 0.5,
-                            limit: int = 10, *, filters: Optional[Sequence[str]] = None) -> List[List[Dict]]:
+                            limit: int = 10, *, filters: Optional[Sequence[str]] = None,
+                            min_similarity: Optional[float] = None) -> List[List[Dict]]:
     """BASELINE config 4: a batch of (image, text) embedding pairs, blended and searched in one pass."""
     try:
-        return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit, filters=filters)
+        return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit, filters=filters,
+                                    min_similarity=min_similarity)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
 
 
-def process_image(image, image_id: str, metadata: Optional[Dict[str, Any]] = None, document: str = ""):
+def find_near_duplicates(min_similarity: float = 0.95, limit: Optional[int] = None) -> List[tuple]:
+    """Every pair of stored images whose similarity (1 - d / 2) reaches min_similarity -> [(id_a, id_b, similarity_score)],
+    each pair once, id_a the earlier upload, ordered by (id_a's upload order, similarity descending). The reference's
+    "Duplicate Detection" (README.md:21) is an exact perceptual hash (main.py:628-640): a re-encoded or resized copy passes it.
+    limit: at most that many pairs. An image with more than 64 later partners reports its 64 nearest."""
+    try:
+        col = _collection()
+        pairs = col.near_duplicates(float(utils.max_distance_for_similarity(min_similarity)))
+        out = [(a, b, 1 - (float(d) / 2)) for a, b, d in pairs]
+        return out if limit is None else out[:max(int(limit), 0)]
+    except Exception as e:
+        logger.error(f"Error searching for near duplicates: {e}")
+        return []
+
+
+def _near_duplicate_of(col, embedding, near_duplicate_similarity):
+    """metadata of the nearest stored image within near_duplicate_similarity of `embedding`, or None"""
+    hit = col.query(query_embeddings=[embedding], n_results=1, include=["metadatas"],
+                    max_distance=float(utils.max_distance_for_similarity(near_duplicate_similarity)))
+    if hit["ids"] and hit["ids"][0]:
+        return hit["metadatas"][0][0] or {"id": hit["ids"][0][0]}
+    return None
+
+
+def process_image(image, image_id: str, metadata: Optional[Dict[str, Any]] = None, document: str = "",
+                  near_duplicate_similarity: Optional[float] = None):
     """The embedding + collection.add portion of process_image (main.py:631-640,685-687,733-744): returns
     (metadata, True) when stored, (existing_metadata, False) for a duplicate id (the caller answers 409).
-    Hashing, captioning, background removal and file writes are outside the hot path; the caller supplies the id."""
+    Hashing, captioning, background removal and file writes are outside the hot path; the caller supplies the id.
+    near_duplicate_similarity: an upload whose embedding has a stored image within that similarity is not stored either:
+    (that image's metadata, False) — the same 409 (a re-encoded, resized or lightly cropped copy gets a new hash id)."""
     col = _collection()
     existing = col.get(ids=[image_id], include=["metadatas"])
     if existing and existing["ids"]:
@@ -142,6 +182,10 @@ def process_image(image, image_id: str, metadata: Optional[Dict[str, Any]] = Non
     model, processor = utils.load_clip_model()
     embedding_result = utils.generate_clip_embedding(image, model=model, processor=processor)
     embedding = embedding_result["image"][0].tolist()
+    if near_duplicate_similarity is not None:
+        twin = _near_duplicate_of(col, embedding, near_duplicate_similarity)
+        if twin is not None:
+            return twin, False
     metadata = dict(metadata or {})
     metadata.setdefault("id", image_id)
     try:
@@ -155,14 +199,25 @@ def process_image(image, image_id: str, metadata: Optional[Dict[str, Any]] = Non
 
 
 def process_images(images: Sequence, image_ids: Sequence[str], metadatas: Optional[Sequence[dict]] = None,
-                   documents: Optional[Sequence[str]] = None) -> int:
-    """Batched ingest: one encoder pass for all new images, one collection.add."""
+                   documents: Optional[Sequence[str]] = None, near_duplicate_similarity: Optional[float] = None) -> int:
+    """Batched ingest: one encoder pass for all new images, one collection.add. near_duplicate_similarity: images with a stored
+    image within that similarity are skipped, as process_image skips them (checked against the collection as it stands before
+    the batch, and against the batch's earlier images)."""
     col = _collection()
     have = set(col.get(ids=list(image_ids), include=[])["ids"])
     todo = [i for i, iid in enumerate(image_ids) if iid not in have]
     if not todo:
         return 0
     emb = utils.generate_clip_embeddings(images=[images[i] for i in todo])["image"]
+    if near_duplicate_similarity is not None:
+        n = 0
+        for j, i in enumerate(todo):   # one by one: an image may be the near duplicate of an earlier one of the batch
+            if _near_duplicate_of(col, np.asarray(emb[j]).tolist(), near_duplicate_similarity) is None:
+                col.add(ids=[image_ids[i]], embeddings=[np.asarray(emb[j]).tolist()],
+                        metadatas=[dict((metadatas[i] if metadatas else None) or {"id": image_ids[i]})],
+                        documents=[(documents[i] if documents else "")])
+                n += 1
+        return n
     metas = [dict((metadatas[i] if metadatas else None) or {"id": image_ids[i]}) for i in todo]
     docs = [(documents[i] if documents else "") for i in todo]
     col.add(ids=[image_ids[i] for i in todo], embeddings=emb, metadatas=metas, documents=docs)

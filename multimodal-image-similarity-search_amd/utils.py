@@ -129,6 +129,35 @@ def generate_clip_embeddings(images: Optional[Sequence] = None, texts: Optional[
     return result
 
 
+def max_distance_for_similarity(s: float) -> np.float32:
+    """The radius that "similarity >= s" stands for. The reference reports similarity = 1 - d / 2 (main.py:782), evaluated in
+    Python floats on the float32 distance; this returns the largest float32 r with 1 - float(r) / 2 >= s, so that on the results
+    of a radius query at r (FlatIndex.query_radius: d <= r as floats) "similarity_score >= s" holds for exactly the members.
+    The inequality is monotone in r, so the answer is found by bisection over the float32 values in their order (near s = 1 the
+    rounding of 1 - r / 2 lets some 10^8 floats above 2 (1 - s) = 0 still satisfy it: stepping from there would take as many steps)."""
+    s = float(s)
+    if s != s:
+        raise ValueError("similarity is NaN")
+
+    def value(key):   # the float32 of rank `key` in the order of the floats (negative keys: negative floats)
+        bits = key if key >= 0 else (-key) | 0x80000000
+        return np.array([bits], np.uint32).view(np.float32)[0]
+
+    def holds(key):
+        return 1 - float(value(key)) / 2 >= s
+
+    lo, hi = -0x7F800000, 0x7F800000     # -inf (holds for every s) .. +inf
+    if holds(hi):
+        return value(hi)
+    while hi - lo > 1:                   # holds(lo), not holds(hi)
+        mid = (lo + hi) // 2
+        if holds(mid):
+            lo = mid
+        else:
+            hi = mid
+    return value(lo)
+
+
 def init_chromadb() -> FlatCollection:
     """Open (or create) the persistent cosine collection (utils.py:104-137)."""
     logger.info("Initializing flat index collection...")
