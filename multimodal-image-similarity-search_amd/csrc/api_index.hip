@@ -4,7 +4,9 @@
 #include <queue>
 #include "retrieval_kernels.h"
 #include "gemm_bf16_256.h"
-#include "gemm_bf16_p256.h"
+#include "gemm_bf16_p256.h"   // (unused here since the strip kernel has its own header; its eight gemm256p_kernel instantiations
+                              // are still emitted into this code object, and dropping them is a change of the product, not a refactor)
+#include "gemm_strip_p256.h"
 #include <algorithm>
 
 struct mmiss_index {
@@ -750,7 +752,7 @@ int strip_length(int Mq, int64_t nbn, int64_t ncol) {
     return strip;
 }
 
-// the strip score GEMM on the staggered loop of the persistent encoder GEMM (gemm_bf16_p256.h; round 3): D % 128 == 0
+// the strip score GEMM on the staggered loop of the persistent encoder GEMM (gemm_strip_p256.h; round 3): D % 128 == 0
 bool strip_v3(const mmiss_index* ix) { return mmiss_option("score_strip_v3", 1) != 0 && (ix->dim % 128) == 0 && ix->dim >= 256; }
 
 // the rows the strip score GEMM serves: f16, and fp8 unless score_f8_gemm = 0 (round 4: gemm256s_kernel<_Float16, .., W8>

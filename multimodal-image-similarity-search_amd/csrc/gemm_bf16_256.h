@@ -19,6 +19,7 @@
 
 #define G256_SLOT 16384
 #define G256_LDS (8 * G256_SLOT)
+#include "gemm_p256_stream.h"  // the fenced barrier (and, for the persistent kernels on these slots, the whole K-tile stream)
 
 template <typename IN, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(const IN* __restrict__ A, const IN* __restrict__ W, int M,
@@ -115,18 +116,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const IN* __restrict__ 
         if (full) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");      \
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            \
     }
-#define G256_BARRIER()                         \
-    {                                          \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    }
 
     // ---- prologue: K-tile 0 completely, K-tile 1 except its m1 slot (staged by phase 0 of K-tile 0)
     stage(0, 0, 0); stage(2, 0, 0); stage(3, 0, 0); stage(1, 0, 0);
     stage(0, 1, 1); stage(2, 1, 1); stage(3, 1, 1);
     G256_WAIT(nt >= 2);  // retires A m0 / W n0 of K-tile 0 (the 5 younger slot loads may still fly)
-    G256_BARRIER();
+    p256s_barrier();
 
     for (int t = 0; t < nt; ++t) {
         const int b = t & 1;
@@ -137,23 +132,23 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const IN* __restrict__ 
         stage(1, b ^ 1, t + 1);
         G256_MMA(0, 0);
         G256_WAIT(full);
-        G256_BARRIER();
+        p256s_barrier();
         // phase 1: quadrant (m0, n1)
         G256_READ_W(b, 1);
         stage(0, b, t + 2);
         G256_MMA(0, 1);
         G256_WAIT(full);
-        G256_BARRIER();
+        p256s_barrier();
         // phase 2: quadrant (m1, n1)
         G256_READ_A(b, 1);
         stage(2, b, t + 2);
         G256_MMA(1, 1);
-        G256_BARRIER();
+        p256s_barrier();
         // phase 3: quadrant (m1, n0) — operands already in registers
         stage(3, b, t + 2);
         G256_MMA(1, 0);
         G256_WAIT(full);
-        G256_BARRIER();
+        p256s_barrier();
     }
 
     if constexpr (EPI == MMISS_EPI_GROUPMAX_F32) {
@@ -284,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_strip_kernel(const IN* __restr
     stage(0, 0, 0, 0, true); stage(2, 0, 0, 0, true); stage(3, 0, 0, 0, true); stage(1, 0, 0, 0, true);
     stage(0, 1, tile1, kt1, T > 1); stage(2, 1, tile1, kt1, T > 1); stage(3, 1, tile1, kt1, T > 1);
     G256_WAIT(T >= 2);
-    G256_BARRIER();
+    p256s_barrier();
 
     int kt = 0, tile = 0;
     for (int t = 0; t < T; ++t) {
@@ -297,23 +292,23 @@ __global__ __launch_bounds__(512, 2) void gemm256_strip_kernel(const IN* __restr
         stage(1, b ^ 1, tile1, kt1, live1);
         G256_MMA(0, 0);
         G256_WAIT(full);
-        G256_BARRIER();
+        p256s_barrier();
         // phase 1: quadrant (m0, n1)
         G256_READ_W(b, 1);
         stage(0, b, tile2, kt2, full);
         G256_MMA(0, 1);
         G256_WAIT(full);
-        G256_BARRIER();
+        p256s_barrier();
         // phase 2: quadrant (m1, n1)
         G256_READ_A(b, 1);
         stage(2, b, tile2, kt2, full);
         G256_MMA(1, 1);
-        G256_BARRIER();
+        p256s_barrier();
         // phase 3: quadrant (m1, n0)
         stage(3, b, tile2, kt2, full);
         G256_MMA(1, 0);
         G256_WAIT(full);
-        G256_BARRIER();
+        p256s_barrier();
         if (++kt1 == nt) { kt1 = 0; ++tile1; }
         if (++kt2 == nt) { kt2 = 0; ++tile2; }
         if (++kt == nt) {
@@ -355,7 +350,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_strip_kernel(const IN* __restr
 #undef G256_READ_W
 #undef G256_MMA
 #undef G256_WAIT
-#undef G256_BARRIER
 
 template <typename IN>
 static int launch_gemm256_strip(hipStream_t st, const void* A, const void* W, const GemmEpi& ep, int M, int N, int K,

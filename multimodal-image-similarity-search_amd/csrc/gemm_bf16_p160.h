@@ -243,16 +243,8 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
                 acc[i][mf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[i], am[mf], acc[i][mf], 0, 0, 0);   \
         __builtin_amdgcn_s_setprio(0);                                                                      \
     }
-#define G160_BARRIER()                            \
-    {                                             \
-        __builtin_amdgcn_sched_barrier(0);        \
-        __builtin_amdgcn_s_barrier();             \
-        __builtin_amdgcn_sched_barrier(0);        \
-    }
-// The half that runs one barrier behind reads a buffer for the last time in the interval right before the other half restages
-// it: its reads must have completed before the barrier between the two.
-#define G160_LATE_READS_DONE() \
-    if (wm == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+// (p256s_barrier, p256s_late_reads_done: gemm_p256_stream.h. The half that runs one barrier behind reads a buffer for the last
+// time in the interval right before the other half restages it.)
 // K-tile t out of buffer B while K-tile t+2 (byte offset ko2) is staged into buffer B2 = (B + 2) % 3, which held K-tile t-1.
 // The two phases are the two K STEPS of the tile (32 columns each): every read part pulls 9 fragments (5 A + 4 W) and every
 // MFMA part is the full 5 x 4 block. A wave issues 7 LDS-DMA operations per K-tile (A A A in phase 0, W0 W0 W1 W1 in phase
@@ -263,18 +255,18 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     {                                                                                                       \
         G160_READ(B, 0);                                                                                    \
         G160_STAGE_A(B2, ko2);                                                                              \
-        G160_LATE_READS_DONE();                                                                             \
-        G160_BARRIER();                                                                                     \
+        p256s_late_reads_done(wm);                                                                             \
+        p256s_barrier();                                                                                     \
         G160_MMA();                                                                                         \
-        G160_BARRIER();                                                                                     \
+        p256s_barrier();                                                                                     \
         G160_READ(B, 1);                                                                                    \
         G160_STAGE_W(B2, 0, ko2);                                                                           \
         G160_STAGE_W(B2, 1, ko2);                                                                           \
-        G160_LATE_READS_DONE();                                                                             \
+        p256s_late_reads_done(wm);                                                                             \
         asm volatile("s_waitcnt vmcnt(7)" ::: "memory");                                                    \
-        G160_BARRIER();                                                                                     \
+        p256s_barrier();                                                                                     \
         G160_MMA();                                                                                         \
-        G160_BARRIER();                                                                                     \
+        p256s_barrier();                                                                                     \
         G160_NEXT_KTILE();                                                                                  \
     }
 
@@ -287,18 +279,18 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     {                                                                                                       \
         G160_READ(B, 0);                                                                                    \
         G160_PIX_LOAD(SET, k2);                                                                             \
-        G160_LATE_READS_DONE();                                                                             \
-        G160_BARRIER();                                                                                     \
+        p256s_late_reads_done(wm);                                                                             \
+        p256s_barrier();                                                                                     \
         G160_MMA();                                                                                         \
-        G160_BARRIER();                                                                                     \
+        p256s_barrier();                                                                                     \
         G160_READ(B, 1);                                                                                    \
         G160_PIX_WRITE((SET) ^ 1, B1, 10);                                                                  \
         G160_STAGE_W(B2, 0, ko2);                                                                           \
         G160_STAGE_W(B2, 1, ko2);                                                                           \
         asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");                                        \
-        G160_BARRIER();                                                                                     \
+        p256s_barrier();                                                                                     \
         G160_MMA();                                                                                         \
-        G160_BARRIER();                                                                                     \
+        p256s_barrier();                                                                                     \
         G160_NEXT_KTILE();                                                                                  \
     }
 
@@ -338,8 +330,8 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
 #pragma unroll
         for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(bias[i]));
     }
-    G160_BARRIER();
-    if (wm == 1) G160_BARRIER();  // the lower half runs one barrier behind from here on
+    p256s_barrier();
+    if (wm == 1) p256s_barrier();  // the lower half runs one barrier behind from here on
 
     if constexpr (PIX) {
 #pragma unroll 1   // three buffers x two register sets: nt % 6 == 0 (12 K-tiles at P = 16, 48 at P = 32)
@@ -359,9 +351,9 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
         if (t + 2 < nt) G160_KTILE(2, 1);
     }
     }
-    if (wm == 0) G160_BARRIER();   // (the upper half's last barrier: the lower half is still one behind)
+    if (wm == 0) p256s_barrier();   // (the upper half's last barrier: the lower half is still one behind)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last two stagings (old rows / wrap-around) have landed ...
-    G160_BARRIER();                // ... on every wave, and every wave has read its last fragments: the buffers are free
+    p256s_barrier();                // ... on every wave, and every wave has read its last fragments: the buffers are free
     // the epilogue's transpose patches: the residual GEMMs' old rows sit in buffers nt % 3 and (nt + 1) % 3 now, so their
     // patches lie over the third one, (nt - 1) % 3, the last one read; the patch-embedding GEMM keeps buffer 0
     const int free_buf = RESID ? ((nt + 2) % 3) * G160_BUF : 0;
@@ -482,8 +474,6 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
 #undef G160_STAGE_W
 #undef G160_READ
 #undef G160_MMA
-#undef G160_BARRIER
-#undef G160_LATE_READS_DONE
 #undef G160_KTILE
 #undef G160_KTILE_PIX
 #undef G160_PIX_LOAD

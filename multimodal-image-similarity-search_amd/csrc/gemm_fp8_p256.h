@@ -43,13 +43,16 @@
 //     tile. Everything else — the ring's parity per group, the epilogues, the ragged pass — is the K % 512 kernel's; the
 //     ODD = 0 instantiations are unchanged.
 // K >= 512, K % 256 == 0, M, N % 256 == 0.
+// The stream itself is gemm_p256_stream.h, the deal p256_deal.h; this file holds the kernel's hooks — fragment reads with the
+// scale byte, the block-scaled MFMAs, the waits that know the scale pieces, the scale cursor —, the ragged pass, the epilogues
+// and the launcher.
 #pragma once
 #include <type_traits>
 #include "gemm_fp8.h"
-#include "gemm_bf16_256.h"
+#include "gemm_bf16_256.h"   // G256_SLOT, and behind it gemm_p256_stream.h
 
 #define Q256_BC (8 * G256_SLOT)        // 2 x 2 KB: bias [256] f32 + wscale [256] f32 of the current / next tile
-#define Q256_TILES (Q256_BC + 4096)    // this workgroup's tile list: 64 x packed (bm, bn, half)
+#define Q256_TILES (Q256_BC + 4096)    // this workgroup's tile list: p256_table_entries packed tiles
 #define Q256_RING (Q256_TILES + 256)   // 2 x 4 KB: scale dwords [parity][A slot mq][slot row 128][k-block 4]
 #define Q256_PATCH (Q256_RING + 8192)  // 8 waves x 2 KB: the epilogue's transposes (XT = 1: a wave's 1 KB of raw row statistics lands here during the K stream)
 #define Q256_LDS (Q256_PATCH + 16384)
@@ -299,33 +302,10 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
         // waits never see them; the barrier above is what hands `red` to the staging slots)
     }
 
-    // ---- tile list (gemm256p_kernel: rounds of G tiles of a banded global order; a last round of at most G/2 tiles in halves)
-    const int T = nbm * nbn, G = gridDim.x;
-    const int pb = xcd_remap(blockIdx.x, G);
-    const int full_rounds = T / G, rem = T - full_rounds * G;
-    const bool halves = full_rounds >= 1 && rem > 0 && 2 * rem <= G;
-    const int nfull = full_rounds + ((!halves && pb < rem) ? 1 : 0);
-    const int nhalf = (halves && pb < 2 * rem) ? 1 : 0;
-    const int mine = nfull + nhalf;
-    if (tid < mine && tid < 64) {
-        const bool hf = tid >= nfull;
-        const int L = hf ? full_rounds * G + (pb >> 1) : tid * G + pb;
-        int bm_, bn_;
-        tile_order(L, nbm, nbn, g.m_fast, bm_, bn_);
-        reinterpret_cast<unsigned*>(smem + Q256_TILES)[tid] = (unsigned)bm_ | ((unsigned)bn_ << 16) | (hf ? (1u << 30) : 0u) |
-                                                             ((hf && (pb & 1)) ? (1u << 31) : 0u);
-    }
-    __syncthreads();
-    auto tile_of = [&](int i, int& bm, int& bn, int& half) {  // half: 0 whole tile, 1 / 2 = its m0 / m1 rows only
-        const unsigned pk = (unsigned)__builtin_amdgcn_readfirstlane(((const __attribute__((address_space(3))) int*)(smem + Q256_TILES))[i]);
-        bm = pk & 0xffff;
-        bn = (pk >> 16) & 0x3fff;
-        half = (pk >> 30) ? 1 + (int)(pk >> 31) : 0;
-    };
+    // ---- this workgroup's tile list (p256_deal.h)
+    P256S_BUILD_TILE_LIST(Q256_TILES, nbm, nbn, g.m_fast)
 
-    // ---- LDS-DMA sources, buffer form. Slot row r of an A slot is the activation row (r>>6)*128 + mq*64 + (r&63) of the tile,
-    // of a W slot the weight row (r>>5)*64 + nq*32 + (r&31); a wave stages slot rows 16*wave .. +15 as two 8-row pieces of
-    // 128-byte rows; XOR swizzle of the 16-byte chunk on the source side.
+    // ---- LDS-DMA sources, buffer form (slot map: gemm_p256_stream.h); XOR swizzle of the 16-byte chunk on the source side.
     // Everything the K loop derives from the lane id is recomputed (a few dozen vector instructions) behind every epilogue
     // from the hardware's lane count, not kept: held across the epilogue these ~10 registers were spilled and reloaded —
     // scratch loads behind an s_waitcnt vmcnt(0), i.e. a drain of the staging pipeline per tile.
@@ -348,7 +328,7 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             ab[s] = (wm * 64 + fr) * 128 + (((4 * s + fg) ^ (fr & 7)) << 4);
-            wb[s] = (8 * G256_SLOT / 2) + (wn * 32 + fr) * 128 + (((4 * s + fg) ^ (fr & 7)) << 4);
+            wb[s] = P256S_SLOT(2, 0) + (wn * 32 + fr) * 128 + (((4 * s + fg) ^ (fr & 7)) << 4);
         }
         // scale bytes: ring + parity * 4096 + mq * 2048 + (slot row wm*64 + mf*16 + fr) * 16 + fg * 4 + K-tile in group
         sc_lane = Q256_RING + (wm * 64 + fr) * 16 + fg * 4;
@@ -359,42 +339,18 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
     const __amdgpu_buffer_rsrc_t srdS = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(g.As), 0, 0x7fffffff, 0x00020000);
     const int row8 = 8 * K;  // bytes between a slot's two 8-row pieces
     const int stage_dst = wave * 2048;
-#define Q256_SLOT(which, b) (((which) * 2 + (b)) * G256_SLOT)
-#define Q256_BLDS(srd, vo, so, dst) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(dst), 16, vo, so, 0, 0)
-#define Q256_BLDS4(srd, vo, so, dst) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(dst), 4, vo, so, 0, 0)
-// LIVE = false: the slot is not read (the A m1 slot of a half tile): its pieces shrink to 4 bytes per lane, the COUNT stays
-#define Q256_STAGE(which, b, oA, oW, LIVE)                                                                   \
-    {                                                                                                       \
-        char* dst_ = smem + Q256_SLOT(which, b) + stage_dst;                                                \
-        if constexpr ((which) < 2) {                                                                        \
-            const int so_ = (oA);                                                                           \
-            if (LIVE) {                                                                                     \
-                Q256_BLDS(srdA, a_vo, so_, dst_);                                                           \
-                Q256_BLDS(srdA, a_vo, so_ + row8, dst_ + 1024);                                             \
-            } else {                                                                                        \
-                Q256_BLDS4(srdA, a_vo, so_, dst_);                                                          \
-                Q256_BLDS4(srdA, a_vo, so_ + row8, dst_ + 1024);                                            \
-            }                                                                                               \
-        } else {                                                                                            \
-            const int so_ = (oW) + ((which) & 1) * 4 * row8;                                                \
-            Q256_BLDS(srdW, w_vo, so_, dst_);                                                               \
-            Q256_BLDS(srdW, w_vo, so_ + row8, dst_ + 1024);                                                 \
-        }                                                                                                   \
-    }
     // bias / weight scales of tile (., bn): one 4-byte piece per wave
     const __amdgpu_buffer_rsrc_t srdX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wave >= 4 ? g.wscale : g.bias), 0, 0x7fffffff, 0x00020000);
     auto stage_x = [&](int bm, int bn, int par) {
         const int l = lane_now();        // (recomputed: no 64-bit lane address kept)
-        Q256_BLDS4(srdX, l * 4, (bn * 256 + (wave & 3) * 64) * 4, smem + Q256_BC + par * 2048 + wave * 256);
+        p256s_blds4(srdX, smem + Q256_BC + par * 2048 + wave * 256, l * 4, (bn * 256 + (wave & 3) * 64) * 4);
         if constexpr (FOLD) {
             // c [256] f16 = 512 B: two 4-byte pieces (waves of equal parity bring the same bytes); the tile rows' raw statistics:
             // 256 rows x 32 B, rows 32 wave .. + 31 into this wave's OWN patch (free until its next epilogue)
             const __amdgpu_buffer_rsrc_t srdC = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.c16), 0, 0x7fffffff, 0x00020000);
             const __amdgpu_buffer_rsrc_t srdT = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.ln_stats), 0, 0x7fffffff, 0x00020000);
-            Q256_BLDS4(srdC, l * 4, (bn * 256 + (wave & 1) * 128) * 2, smem + Q256_C16 + par * 512 + (wave & 1) * 256);
-            Q256_BLDS(srdT, l * 16, (bm * 256 + wave * 32) * 32, smem + Q256_PATCH + wave * 2048);
+            p256s_blds4(srdC, smem + Q256_C16 + par * 512 + (wave & 1) * 256, l * 4, (bn * 256 + (wave & 1) * 128) * 2);
+            p256s_blds16(srdT, smem + Q256_PATCH + wave * 2048, l * 16, (bm * 256 + wave * 32) * 32);
         }
     };
 
@@ -409,25 +365,26 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#define Q256_READ_A(b, mq)                                                                                   \
+// ---- this kernel's hooks of the K-tile stream (gemm_p256_stream.h)
+#define KT_READ_A(b, mq)                                                                                     \
     _Pragma("unroll") for (int mf = 0; mf < 4; ++mf) {                                                      \
-        const u32x4 lo_ = *reinterpret_cast<const u32x4*>(smem + ab[0] + Q256_SLOT(mq, b) + mf * 2048);     \
-        const u32x4 hi_ = *reinterpret_cast<const u32x4*>(smem + ab[1] + Q256_SLOT(mq, b) + mf * 2048);     \
+        const u32x4 lo_ = *reinterpret_cast<const u32x4*>(smem + ab[0] + P256S_SLOT(mq, b) + mf * 2048);    \
+        const u32x4 hi_ = *reinterpret_cast<const u32x4*>(smem + ab[1] + P256S_SLOT(mq, b) + mf * 2048);    \
         am[mf][0] = lo_[0]; am[mf][1] = lo_[1]; am[mf][2] = lo_[2]; am[mf][3] = lo_[3];                     \
         am[mf][4] = hi_[0]; am[mf][5] = hi_[1]; am[mf][6] = hi_[2]; am[mf][7] = hi_[3];                     \
         sc[mf] = (int)((lds_u8)smem)[sc_lane + sc_off + (mq) * 2048 + mf * 256];               \
     }
-#define Q256_READ_W(b, nq)                                                                                   \
+#define KT_READ_W(b, nq)                                                                                     \
     _Pragma("unroll") for (int nf = 0; nf < 2; ++nf) {                                                      \
-        const u32x4 lo_ = *reinterpret_cast<const u32x4*>(smem + wb[0] + Q256_SLOT(nq, b) + nf * 2048);     \
-        const u32x4 hi_ = *reinterpret_cast<const u32x4*>(smem + wb[1] + Q256_SLOT(nq, b) + nf * 2048);     \
+        const u32x4 lo_ = *reinterpret_cast<const u32x4*>(smem + wb[0] + P256S_SLOT(nq, b) + nf * 2048);    \
+        const u32x4 hi_ = *reinterpret_cast<const u32x4*>(smem + wb[1] + P256S_SLOT(nq, b) + nf * 2048);    \
         wq[nq][nf][0] = lo_[0]; wq[nq][nf][1] = lo_[1]; wq[nq][nf][2] = lo_[2]; wq[nq][nf][3] = lo_[3];     \
         wq[nq][nf][4] = hi_[0]; wq[nq][nf][5] = hi_[1]; wq[nq][nf][6] = hi_[2]; wq[nq][nf][7] = hi_[3];     \
     }
 // 8 block-scaled MFMAs: weights = A operand (unit block scales), activations = B operand (scale byte 0 of sc[mf])
 // (The phase's two LDS-DMA pieces issued from the middle of the MFMA part, between the two sched_barriers, instead of in the
 // read part: measured in round 5 with a build variant since removed, equal or 1-3 % slower; profiles/gemm_fp8_p256_r05.txt.)
-#define Q256_MMA(mq, nq)                                                                                     \
+#define KT_MMA(mq, nq)                                                                                  \
     {                                                                                                       \
         __builtin_amdgcn_s_setprio(1);                                                                      \
         _Pragma("unroll") for (int nf = 0; nf < 2; ++nf) {                                                  \
@@ -446,58 +403,21 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
                 asm volatile("" : Q256_PIN(acc[(nq) * 2 + nf][(mq) * 4 + mf]));                                \
         __builtin_amdgcn_s_setprio(0);                                                                      \
     }
-// counted wait: 10 younger slot pieces stay in flight; POST: + the previous tile's epilogue operations; XS: + the pair's scale piece
-// (ODD: two scale pieces per pair)
-#define Q256_WAIT(POST, XS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(10 + ((POST) ? EX : 0) + ((XS) ? 1 + ODD : 0)) : "memory")
-#define Q256_BARRIER()                       \
-    {                                        \
-        __builtin_amdgcn_sched_barrier(0);   \
-        __builtin_amdgcn_s_barrier();        \
-        __builtin_amdgcn_sched_barrier(0);   \
-    }
-#define Q256_LATE_READS_DONE() \
-    if (wm == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-// One K-tile out of buffer B (gemm256p_kernel's P256_KTILE): four phases [reads + one slot's staging + wait] B [8 MFMAs] B.
-// P0 / P1 / P3: POST form of the three waits; X0 / X1 / X3: the pair's scale piece is younger than the slot the wait retires.
-#define Q256_KTILE(B, P0, P1, P3, X0, X1, X3, HALF)                                                          \
-    {                                                                                                       \
-        Q256_READ_A(B, 0);                                                                                  \
-        Q256_READ_W(B, 0);                                                                                  \
-        Q256_STAGE(1, (B) ^ 1, oA1 + mA1, oW1, mA1 != 0); /* A m1 of K-tile t+1 */                          \
-        Q256_LATE_READS_DONE();                                                                             \
-        Q256_WAIT(P0, X0);                /* retires W n1 of this K-tile */                                 \
-        Q256_BARRIER();                                                                                     \
-        Q256_MMA(0, 0);                                                                                     \
-        Q256_BARRIER();                                                                                     \
-        Q256_READ_W(B, 1);                                                                                  \
-        Q256_STAGE(0, B, oA2, oW2, true);          /* A m0 of K-tile t+2 */                                 \
-        Q256_LATE_READS_DONE();                                                                             \
-        Q256_WAIT(P1, X1);                /* retires A m1 of this K-tile */                                 \
-        Q256_BARRIER();                                                                                     \
-        Q256_MMA(0, 1);                                                                                     \
-        Q256_BARRIER();                                                                                     \
-        if constexpr (!(HALF)) { Q256_READ_A(B, 1); }                                                       \
-        Q256_STAGE(2, B, oA2, oW2, true);          /* W n0 of K-tile t+2; nothing new is read in the next phase: no wait */ \
-        Q256_LATE_READS_DONE();                                                                             \
-        Q256_BARRIER();                                                                                     \
-        if constexpr (!(HALF)) { Q256_MMA(1, 1); }                                                          \
-        Q256_BARRIER();                                                                                     \
-        Q256_STAGE(3, B, oA2, oW2, true);          /* W n1 of K-tile t+2 */                                 \
-        Q256_WAIT(P3, X3);                /* retires A m0 / W n0 of the next K-tile */                      \
-        Q256_BARRIER();                                                                                     \
-        if constexpr (!(HALF)) { Q256_MMA(1, 0); }                                                          \
-        Q256_BARRIER();                                                                                     \
-        Q256_ADVANCE();                                                                                     \
-    }
+#define KT_STAGE_W(dst, which, b, oW) P256S_STAGE_W(dst, which, oW, row8)
+// counted wait: 10 younger slot pieces stay in flight; POST: + the previous tile's epilogue operations; the pair's scale piece
+// (ODD: two) is younger than the slots its first four waits retire — all of buffer 0's, the first of buffer 1's
+#define KT_WAIT(POST, b, which) \
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(10 + ((POST) ? EX : 0) + (((b) == 0 || (which) == 0) ? 1 + ODD : 0)) : "memory")
+#define KT_PHASE3(FIN)
 // position t+1 becomes the old t+2; t+2 moves on one K-tile (into the next tile, or wraps in the last one); the scale byte
 // offset moves on one K-tile: + 1 inside a group, other parity at a group's end
-#define Q256_ADVANCE()                                                                                       \
+#define KT_ADVANCE()                                                                                         \
     oA1 = oA2; oW1 = oW2; mA1 = mA2;                                                                        \
     if (++k2 == nt) {                                                                                       \
         k2 = 0;                                                                                             \
         if (o2 + 1 < mine) ++o2;                                                                            \
         int bm_, bn_, hf_;                                                                                  \
-        tile_of(o2, bm_, bn_, hf_);                                                                         \
+        p256s_tile_of(smem + Q256_TILES, o2, bm_, bn_, hf_);                                                \
         oA2 = bm_ * 256 * K + (hf_ == 2 ? 8 * row8 : 0);                                                    \
         oW2 = bn_ * 256 * K;                                                                                \
         mA2 = hf_ ? 0 : 8 * row8;                                                                           \
@@ -512,7 +432,7 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
 // rows come from the tile list; past the last tile it re-reads the last one)
 #define Q256_SCALE_PIECE()                                                                                   \
     {                                                                                                       \
-        Q256_BLDS4(srdS, s_vo, pc_so, smem + Q256_RING + pc_par + pc_mq * 2048 + wave * 256);               \
+        p256s_blds4(srdS, smem + Q256_RING + pc_par + pc_mq * 2048 + wave * 256, s_vo, pc_so);               \
         if (pc_mq == 0) { pc_mq = 1; pc_so += 64 * g.ld_as; }                                               \
         else {                                                                                              \
             pc_mq = 0; pc_par ^= 4096;                                                                      \
@@ -520,7 +440,7 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
                 pc_g = 0;                                                                                   \
                 if (pc_o + 1 < mine) ++pc_o;                                                                \
                 int bm_, bn_, hf_;                                                                          \
-                tile_of(pc_o, bm_, bn_, hf_);                                                               \
+                p256s_tile_of(smem + Q256_TILES, pc_o, bm_, bn_, hf_);                                                      \
                 pc_so = (bm_ * 256 + (hf_ == 2 ? 64 : 0)) * g.ld_as;                                        \
             } else {                                                                                        \
                 pc_so += 16 - 64 * g.ld_as;                                                                 \
@@ -532,27 +452,28 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
 // behind the half group's only pair (kp = this pair's index in its tile)
 #define Q256_SCALE_PIECE2(kp)                                                                                \
     {                                                                                                       \
-        Q256_BLDS4(srdS, s_vo, pc_so, smem + Q256_RING + pc_par + wave * 256);                              \
-        Q256_BLDS4(srdS, s_vo, pc_so + 64 * g.ld_as, smem + Q256_RING + pc_par + 2048 + wave * 256);        \
+        p256s_blds4(srdS, smem + Q256_RING + pc_par + wave * 256, s_vo, pc_so);                              \
+        p256s_blds4(srdS, smem + Q256_RING + pc_par + 2048 + wave * 256, s_vo, pc_so + 64 * g.ld_as);        \
         if (((kp) & 1) || (kp) == npair - 1) {                                                              \
             pc_par ^= 4096;                                                                                 \
             if (++pc_g == ngrp) {                                                                           \
                 pc_g = 0;                                                                                   \
                 if (pc_o + 1 < mine) ++pc_o;                                                                \
                 int bm_, bn_, hf_;                                                                          \
-                tile_of(pc_o, bm_, bn_, hf_);                                                               \
+                p256s_tile_of(smem + Q256_TILES, pc_o, bm_, bn_, hf_);                                                      \
                 pc_so = (bm_ * 256 + (hf_ == 2 ? 64 : 0)) * g.ld_as;                                        \
             } else {                                                                                        \
                 pc_so += 16;                                                                                \
             }                                                                                               \
         }                                                                                                   \
     }
-#define Q256_PAIR_PIECES(kp) \
+#define KT_PAIR_HEAD(kp) \
     if constexpr (ODD) { Q256_SCALE_PIECE2(kp); } else { Q256_SCALE_PIECE(); }
+#define KT_AFTER_EPILOGUE() lane_consts()
 
     // ---- stream state
-    int cbm, cbn, chalf;
-    tile_of(0, cbm, cbn, chalf);
+    int cbm, cbn, chalf;   // the tile being computed; chalf: 0 whole tile, 1 / 2 = its m0 / m1 rows only
+    p256s_tile_of(smem + Q256_TILES, 0, cbm, cbn, chalf);
     int oA1 = cbm * 256 * K + (chalf == 2 ? 8 * row8 : 0), oW1 = cbn * 256 * K;  // K-tile 0 of tile 0, then position t+1
     int oA2 = oA1 + 128, oW2 = oW1 + 128;
     int mA1 = chalf ? 0 : 8 * row8, mA2 = mA1;   // where a position's A m1 slot comes from (a half tile has none: m0 again)
@@ -564,29 +485,11 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
     int pc_o = 0, pc_g = 0, pc_mq = 0, pc_par = 0;
     int pc_so = (cbm * 256 + (chalf == 2 ? 64 : 0)) * g.ld_as;
 
-    // prologue: the first group's scale dwords, the first tile's bias / weight scales, K-tile 0 completely, K-tile 1 except its
-    // A m1 slot (staged by phase 0 of K-tile 0)
+    // prologue: the first group's scale dwords and the first tile's bias / weight scales in front of the slots
     Q256_SCALE_PIECE();
     Q256_SCALE_PIECE();
     stage_x(cbm, cbn, 0);
-    {
-        char* d0 = smem + stage_dst;
-        Q256_BLDS(srdA, a_vo, oA1, d0 + Q256_SLOT(0, 0)); Q256_BLDS(srdA, a_vo, oA1 + row8, d0 + Q256_SLOT(0, 0) + 1024);
-        Q256_BLDS(srdW, w_vo, oW1, d0 + Q256_SLOT(2, 0)); Q256_BLDS(srdW, w_vo, oW1 + row8, d0 + Q256_SLOT(2, 0) + 1024);
-        Q256_BLDS(srdW, w_vo, oW1 + 4 * row8, d0 + Q256_SLOT(3, 0)); Q256_BLDS(srdW, w_vo, oW1 + 5 * row8, d0 + Q256_SLOT(3, 0) + 1024);
-        if (mA1 != 0) { Q256_BLDS(srdA, a_vo, oA1 + mA1, d0 + Q256_SLOT(1, 0)); Q256_BLDS(srdA, a_vo, oA1 + mA1 + row8, d0 + Q256_SLOT(1, 0) + 1024); }
-        else { Q256_BLDS4(srdA, a_vo, oA1, d0 + Q256_SLOT(1, 0)); Q256_BLDS4(srdA, a_vo, oA1 + row8, d0 + Q256_SLOT(1, 0) + 1024); }
-        Q256_BLDS(srdA, a_vo, oA2, d0 + Q256_SLOT(0, 1)); Q256_BLDS(srdA, a_vo, oA2 + row8, d0 + Q256_SLOT(0, 1) + 1024);
-        Q256_BLDS(srdW, w_vo, oW2, d0 + Q256_SLOT(2, 1)); Q256_BLDS(srdW, w_vo, oW2 + row8, d0 + Q256_SLOT(2, 1) + 1024);
-        Q256_BLDS(srdW, w_vo, oW2 + 4 * row8, d0 + Q256_SLOT(3, 1)); Q256_BLDS(srdW, w_vo, oW2 + 5 * row8, d0 + Q256_SLOT(3, 1) + 1024);
-    }
-    // position t+1 = K-tile 1 (its A m1 slot is still to come), t+2 = K-tile 2
-    oA1 = oA2; oW1 = oW2;
-    oA2 += 128; oW2 += 128;
-    k2 = 2;
-    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");  // all but the five youngest slot loads: A m0 / W n0 of K-tile 0, the pieces in front of them
-    Q256_BARRIER();
-    if (wm == 1) Q256_BARRIER();  // the lower half runs one barrier behind from here on
+    P256S_PROLOGUE(mA1 != 0, 128, 128, 10);
 
     // ---- epilogue of the tile (cbm, cbn) out of the accumulators: JN = 8 (whole tile) or 4 (half tile: 64 rows per wave, hrow = 0 / 64)
     // 16-row sub-tiles per wave. acc[i][j][r] = C[m = wm*128 + hrow + j*16 + fr][n = wn*64 + i*16 + 4*fg + r].
@@ -623,7 +526,7 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
             if (lane_e < 32)
                 *reinterpret_cast<u32x2*>(smem + Q256_TABLE + (wave * 32 + lane_e) * 8) =
                     u32x2{__float_as_uint(mean), __float_as_uint(1.0f / sqrtf(var + g.ln_eps))};
-            Q256_BARRIER();
+            p256s_barrier();
         }
         if constexpr (EPI == MMISS_EPI8_BIAS_BF16 || EPI == MMISS_EPI8_BIAS_RESID_BF16) {
             // 16 rows x 64 bf16 columns through the patch: 8-byte slot s of row r at slot s ^ 2 (r & 7); whole 128-byte rows per store
@@ -746,7 +649,7 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
                         *reinterpret_cast<u32x2*>(patch + (rchunk * 16 + 8 + rrow) * 8) = u32x2{__float_as_uint(k[2]), __float_as_uint(k[3])};
                     }
                 }
-                Q256_BARRIER();
+                p256s_barrier();
                 const int R = wave * 32 + (lane_e & 31);          // tile row
                 const char* src = smem + Q256_PATCH + (R >> 7) * 4 * 2048 + (R & 127) * 8;
                 float t1 = 0.f, t2 = 0.f;
@@ -815,79 +718,39 @@ __global__ __launch_bounds__(512, 2) void gemm256p8_kernel(Gemm8Args g) {
         }
     };
 
-    // ---- whole tiles. Pair kp of a tile: scale piece, K-tile 2 kp out of buffer 0, K-tile 2 kp + 1 out of buffer 1.
-    for (int ti = 0; ti < nfull; ++ti) {
-        for (int kp = 0; kp < npair; ++kp) {
-            Q256_PAIR_PIECES(kp);
-            if (kp == 0 && ti > 0) {
-                Q256_KTILE(0, true, true, true, true, true, true, false);
-                Q256_KTILE(1, true, false, false, true, false, false, false);
-            } else {
-                Q256_KTILE(0, false, false, false, true, true, true, false);
-                Q256_KTILE(1, false, false, false, true, false, false, false);
-            }
-        }
-        // The tile is complete. The upper half waits one barrier for the lower half's last MFMAs, both run the epilogue side
-        // by side, then the lower half falls one barrier behind again.
-        if (wm == 0) Q256_BARRIER();
-        epilogue(std::integral_constant<int, 8>{}, 0, ti & 1);
-        lane_consts();
-        if (ti + 1 < mine) {
-            tile_of(ti + 1, cbm, cbn, chalf);
-            stage_x(cbm, cbn, (ti + 1) & 1);
-            if (wm == 1) Q256_BARRIER();
-        }
-    }
-    // ---- the half tile of the last round, if this workgroup has one (always behind at least one whole tile: POST waits)
-    if (nhalf) {
-        for (int kp = 0; kp < npair; ++kp) {
-            Q256_PAIR_PIECES(kp);
-            if (kp == 0) {
-                Q256_KTILE(0, true, true, true, true, true, true, true);
-                Q256_KTILE(1, true, false, false, true, false, false, true);
-            } else {
-                Q256_KTILE(0, false, false, false, true, true, true, true);
-                Q256_KTILE(1, false, false, false, true, false, false, true);
-            }
-        }
-        if (wm == 0) Q256_BARRIER();
-        epilogue(std::integral_constant<int, 4>{}, chalf == 2 ? 64 : 0, nfull & 1);
-    }
-    // the unconditional staging of the last K-tiles is still in flight: LDS must not be handed on with DMA writes pending
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // ---- whole tiles, then the half tile of the last round. Pair kp of a tile: scale piece, K-tile 2 kp out of buffer 0,
+    // K-tile 2 kp + 1 out of buffer 1; behind every epilogue the lane's constants are recomputed (lane_consts).
+    P256S_RUN_TILES(Q256_TILES)
 }
-#undef Q256_SLOT
 #undef Q256_PIN
 #undef Q256_BIAS
 #undef Q256_SW
 #undef Q256_C
-#undef Q256_BLDS
-#undef Q256_BLDS4
-#undef Q256_STAGE
-#undef Q256_READ_A
-#undef Q256_READ_W
-#undef Q256_MMA
-#undef Q256_WAIT
-#undef Q256_BARRIER
-#undef Q256_LATE_READS_DONE
-#undef Q256_KTILE
-#undef Q256_ADVANCE
+#undef KT_READ_A
+#undef KT_READ_W
+#undef KT_MMA
+#undef KT_STAGE_W
+#undef KT_WAIT
+#undef KT_PHASE3
+#undef KT_ADVANCE
 #undef Q256_SCALE_PIECE
 #undef Q256_SCALE_PIECE2
-#undef Q256_PAIR_PIECES
+#undef KT_PAIR_HEAD
+#undef KT_AFTER_EPILOGUE
 
 // can this GEMM run on the persistent fp8 kernel?
 static inline bool gemm256p8_ok(int epi, int M, int N, int K) {
     if (M <= 0 || (M % 256) || N <= 0 || (N % 256) || K < 512 || (K % 256)) return false;
-    if ((int64_t)(M / 256) * (N / 256) > 48 * 256 || M / 256 > 0xffff) return false;  // (tile table: 64 entries per workgroup)
+    if ((int64_t)(M / 256) * (N / 256) > p256_max_tiles || M / 256 > 0xffff) return false;  // (the tile table and its entries: p256_deal.h)
     if ((int64_t)M * N * 2 >= (1LL << 31) || (int64_t)M * K >= (1LL << 31) || (int64_t)N * K >= (1LL << 31)) return false;  // (32-bit buffer offsets)
     return epi == MMISS_EPI8_BIAS_BF16 || epi == MMISS_EPI8_QGELU_MXFP8 || epi == MMISS_EPI8_BIAS_RESID_BF16;
 }
 
+static inline int gemm256p8_tiles(const Gemm8Args& g) { return (g.M / 256 - (g.ragged > 0 ? 1 : 0)) * (g.N / 256); }   // (a ragged last row block is not a tile)
+
 template <int EPI, int XT, int ODD = 0>
 static int launch_gemm256p8_inst(hipStream_t st, const Gemm8Args& g) {
-    const int T = (g.M / 256 - (g.ragged > 0 ? 1 : 0)) * (g.N / 256);
-    const int grid = T >= 256 ? 256 : T;
+    const int grid = p256_grid(gemm256p8_tiles(g));
     constexpr int LDS = XT == 1 ? Q256_LDS_FOLD : Q256_LDS;
     MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&gemm256p8_kernel<EPI, XT, ODD>), LDS));
     hipLaunchKernelGGL((gemm256p8_kernel<EPI, XT, ODD>), dim3(grid), dim3(512), LDS, st, g);
@@ -905,9 +768,7 @@ static inline bool gemm256p8_xt_ok(int epi, int xt, const Gemm8Args& g) {
     if (xt != 2 || epi != MMISS_EPI8_BIAS_RESID_BF16 || g.N != 1024 || !g.q_out || !g.q_scale || !g.stats_out ||
         g.ld_qs < mx_scale_row_bytes(g.N) || (int64_t)g.M * g.ld_qs >= (1LL << 31))
         return false;
-    const int T = (g.M / 256 - (g.ragged > 0 ? 1 : 0)) * (g.N / 256), G = T >= 256 ? 256 : T;
-    const int rem = T % G;
-    return !(T / G >= 1 && rem > 0 && 2 * rem <= G);
+    return !p256_last_round_in_halves(gemm256p8_tiles(g));
 }
 
 // g.M = rows padded to 256 (A8, As, out and out_scale must hold g.M rows); rows >= g.m_valid are computed and land in row M - 1.
