@@ -151,7 +151,7 @@ int mmiss_encoder_set_tower_precision(mmiss_encoder* enc, int32_t tower, int32_t
  * like the ones to be encoded; 16-64 are enough (the statistics are over B * T rows).
  * The stored calibration: cleared by mmiss_encoder_calibration_clear, by any mmiss_encoder_set_weight of a vision-tower tensor
  * and by mmiss_encoder_finalize; no effect on the text tower, on the bf16 settings, or on calls below the fp8 row threshold
- * (they run the bf16 kernels); NOT used under option fp8_ln_fold = 1 (gamma folded into the fp8 weights: that GEMM has no beta).
+ * (they run the bf16 kernels).
  * Errors (MMISS_ERR_ARG, with a message): a call before finalize, B outside 1 .. max_batch_image, a null pointer, a table of
  * the wrong length.
  *   _info   out[0] = sites (2 * v_layers; 0 when uncalibrated), out[1] = v_hidden, out[2] = centred channels over all sites,

@@ -169,22 +169,6 @@ int mmiss_dbg_attention_mx(int device, void* hip_stream, const void* qkv, void* 
 /* epi: 0 out bf16 = acc * wscale[n] + bias[n]; 1 out e4m3 + out_scale = mx(quick_gelu(.)); 2 out f32 += . ; bm = 128 | 160 | 192 */
 int mmiss_dbg_gemm8(int device, void* hip_stream, int epi, int bm, const void* A8, const void* As, const void* W8,
                     const float* wscale, const float* bias, void* out, void* out_scale, int32_t M, int32_t N, int32_t K);
-/* the persistent fp8 GEMM's extensions of round 5 (gemm_fp8_p256.h; M % 256 == 0, rows >= m_valid are padding):
- * xt = 1 (epi 0 / 1, K = 1024): LayerNorm folded in — A8 / As = the RAW bf16 rows x16 [M, K] as MXFP8, W8 the gamma-folded weights,
- *        bias = b', c16 = f16 [N] row sums of the dequantised W8, ln_stats = f32 [M][4][2] (sum, sumsq) per 256-column quarter of
- *        the rows of x16: out = rstd (acc wscale - mean c) + b' (then QuickGELU -> MXFP8 for epi 1);
- * xt = 2 (epi 3, N = 1024): out bf16 += ..., and the new rows also as MXFP8 (q_out e4m3 [M, N], q_scale permuted E8M0) with
- *        stats_out f32 [M][N/256][2] of the tile rows (the rows of a ragged last block get none). */
-int mmiss_dbg_gemm8_xt(int device, void* hip_stream, int epi, int xt, const void* A8, const void* As, const void* W8,
-                       const float* wscale, const float* bias, void* out, void* out_scale, int32_t M, int32_t N, int32_t K,
-                       int32_t m_valid, const void* c16, const float* ln_stats, const void* x16, float ln_eps, void* q_out,
-                       void* q_scale, float* stats_out);
-/* bf16 rows [M, 1024] -> MXFP8 (raw) + (sum, sumsq) per 256-column quarter, f32 [M][4][2]: the entry of the folded fp8 mode */
-int mmiss_dbg_quant16_mxfp8_stats(int device, void* hip_stream, const void* x_bf16, void* out8, void* out_scale, float* stats,
-                                  int32_t M, int32_t d);
-/* e4m3 codes + per-channel scales of bf16 weights [N, K] and c16 = f16 row sums of the dequantised codes */
-int mmiss_dbg_quantize_weights_fp8_csum(int device, void* hip_stream, const void* w_bf16, void* w8, float* scale, void* c16,
-                                        int32_t N, int32_t K);
 int mmiss_dbg_gemm8_time(int device, int epi, int bm, const void* A8, const void* As, const void* W8, const float* wscale,
                          const float* bias, void* out, void* out_scale, int32_t M, int32_t N, int32_t K, int32_t iters,
                          float* ms_per_launch);
@@ -238,18 +222,17 @@ int mmiss_dbg_index_radius_plan(struct mmiss_index* ix, int32_t Q, int32_t filte
  * (1 .. the tower's max_batch) on `tower` (MMISS_TOWER_*), T tokens per item for the text tower (the vision tower's is fixed: pass 0).
  * The encoder's own planning functions, evaluated on the host; no kernel is launched. Like an encode call it allocates the tower's
  * workspaces (zero-filled) if they do not exist yet, because the plan depends on which of them there are. out is a HOST int32 [32]:
- *   [0] fold   [1] fold_final   [2] fp8   [3] fold8   [4] out8   [5] resid16   [6] sfold   [7] prune
- *   [8] embed: 0 nothing, 1 xb + 64-column statistics, 2 xb + 16-column statistics (one request)
- *   [9],[10] kernel and tile height of the QKV GEMM   [11],[12] out-projection   [13],[14] FC1   [15],[16] FC2
+ *   [0] fold   [1] fold_final   [2] fp8   [3] out8   [4] resid16   [5] sfold   [6] prune
+ *   [7] embed: 0 nothing, 1 xb + 64-column statistics, 2 xb + 16-column statistics (one request)
+ *   [8],[9] kernel and tile height of the QKV GEMM   [10],[11] out-projection   [12],[13] FC1   [14],[15] FC2
  *        kernel: 0 BM x 128 tile (the launcher takes the skinny kernel for few rows), 1 256 x 256 tile, 2 persistent 256 x 256,
- *        3 160 x 256 residual, 4 skinny with the LayerNorm folded in, 5 fp8 BM x 128 tile, 6 persistent fp8, 7 persistent fp8 with
- *        the LayerNorm folded in
- *   [17] the pruned last layer runs the pooled-query tail   [18] FC2 is a split-K candidate   [19] M = B * T
- *   vision only: [20] lean pre-LayerNorm   [21],[22] kernel and tile height of the patch GEMM   [23] it is a split-K candidate
+ *        3 160 x 256 residual, 4 skinny with the LayerNorm folded in, 5 fp8 BM x 128 tile, 6 persistent fp8
+ *   [16] the pruned last layer runs the pooled-query tail   [17] FC2 is a split-K candidate   [18] M = B * T
+ *   vision only: [19] lean pre-LayerNorm   [20],[21] kernel and tile height of the patch GEMM   [22] it is a split-K candidate
  *   the attention kernel (the token count picks the family: up to 128 one pass, up to 288 long, above it key chunks):
- *   [24] heads per workgroup of the one-pass kernels (attention_pick_hpb; it applies up to 128 tokens)
- *   [25] the shape may run on the streaming kernel (attention_stream_ok; option attention_stream = 0 keeps the long kernel)
- *   [26..31] 0 */
+ *   [23] heads per workgroup of the one-pass kernels (attention_pick_hpb; it applies up to 128 tokens)
+ *   [24] the shape may run on the streaming kernel (attention_stream_ok; option attention_stream = 0 keeps the long kernel)
+ *   [25..31] 0 */
 int mmiss_dbg_encoder_plan(struct mmiss_encoder* enc, int32_t tower, int32_t B, int32_t T, int32_t* out);
 
 #ifdef __cplusplus

@@ -139,9 +139,6 @@ SIGNATURES = {
     "mmiss_dbg_layernorm16_mxfp8": (_I, [_I, _P, _P, _P, _P, _P, _P, _I32, _I32, C.c_float]),
     "mmiss_dbg_attention_mx": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _I32]),
     "mmiss_dbg_gemm8": (_I, [_I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32]),
-    "mmiss_dbg_gemm8_xt": (_I, [_I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, C.c_float, _P, _P, _P]),
-    "mmiss_dbg_quant16_mxfp8_stats": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32]),
-    "mmiss_dbg_quantize_weights_fp8_csum": (_I, [_I, _P, _P, _P, _P, _P, _I32, _I32]),
     "mmiss_dbg_gemm8_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
     "mmiss_dbg_ln_colstats": (_I, [_I, _P, _P, _I32, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P]),
     "mmiss_dbg_bias_fold": (_I, [_I, _P, _P, _P, _P, _I32, _I32, _P]),
@@ -277,10 +274,10 @@ def index_radius_plan(handle, Q: int, filtered: bool = False) -> dict:
     return {"chunks": v[0], "first": dict(zip(RADIUS_PLAN_FIELDS, v[1:8])), "last": dict(zip(RADIUS_PLAN_FIELDS, v[8:15]))}
 
 
-ENCODER_PLAN_FIELDS = ("fold", "fold_final", "fp8", "fold8", "out8", "resid16", "sfold", "prune", "embed", "qkv", "qkv_bm", "out", "out_bm",
+ENCODER_PLAN_FIELDS = ("fold", "fold_final", "fp8", "out8", "resid16", "sfold", "prune", "embed", "qkv", "qkv_bm", "out", "out_bm",
                        "fc1", "fc1_bm", "fc2", "fc2_bm", "pooled_tail", "fc2_splitk", "M", "lean_pre", "patch", "patch_bm", "patch_splitk",
                        "att_hpb", "att_stream")
-GEMM_KINDS = ("Tile", "Tile256", "P256", "P160", "Skinny", "Fp8Tile", "P256Fp8", "P256Fp8Xt")
+GEMM_KINDS = ("Tile", "Tile256", "P256", "P160", "Skinny", "Fp8Tile", "P256Fp8")
 EMBED_OUTS = ("Nothing", "Stats64", "Stats16")
 
 

@@ -21,7 +21,6 @@ struct LayerW {
     DevBuf wqkv_f, cqkv, bqkv_f, w1_f, c1, b1_f;  // LayerNorm folded into the QKV / FC1 weights (finalize)
     DevBuf wqkv8, sqkv, w1_8, s1, w2_8, s2;       // fp8 path: e4m3 weights + per-output-channel f32 scales
     DevBuf wo8, so;                               // ... of the out-projection (used when the attention output is MXFP8)
-    DevBuf wqkv8f, sqkvf, cqkv16, w1_8f, s1f, c1_16;  // fp8 path with the LayerNorm folded in (hidden 1024): e4m3 of the gamma-folded weights, scales, f16 row sums
     DevBuf ln1b_c, bqkv_c, ln2b_c, b1_c;          // calibrated fp8 path: beta' = beta - mu, b' = b + W mu of LN1 -> QKV and LN2 -> FC1 (calibrate_kernels.h)
 };
 
@@ -232,10 +231,10 @@ int ensure_tower_ws(mmiss_encoder* e, Tower& tw, int max_batch, int proj_dim) {
 // Which kernel runs one GEMM role of the layer loop (plan_layers picks it, run_wide / run_resid launch it): the BM x 128 tile
 // (launch_gemm, _fold, _resid16), the 256 x 256 tile (gemm_bf16_256.h), the persistent 256 x 256 (gemm_bf16_p256.h), the 160 x 256
 // residual GEMM (gemm_bf16_p160.h), the skinny GEMM with the LayerNorm folded in (gemm_skinny.h), the BM x 128 fp8 tile
-// (gemm_fp8.h), the persistent fp8 256 x 256 (gemm_fp8_p256.h) and its folded-LayerNorm form (fold8: xt 1 for QKV / FC1, 2 after)
-enum class GemmKind { Tile, Tile256, P256, P160, Skinny, Fp8Tile, P256Fp8, P256Fp8Xt };
+// (gemm_fp8.h), the persistent fp8 256 x 256 (gemm_fp8_p256.h)
+enum class GemmKind { Tile, Tile256, P256, P160, Skinny, Fp8Tile, P256Fp8 };
 struct GemmPick { GemmKind kind; int bm; };   // bm: tile height of Tile / Fp8Tile, M is padded to it
-static bool is_fp8(GemmKind k) { return k == GemmKind::Fp8Tile || k == GemmKind::P256Fp8 || k == GemmKind::P256Fp8Xt; }
+static bool is_fp8(GemmKind k) { return k == GemmKind::Fp8Tile || k == GemmKind::P256Fp8; }
 
 // What the vision embedding stage leaves for the first layer besides x: nothing (in-place pre-LayerNorm; the text tower),
 // xb + 64-column row statistics (layernorm_stats_kernel), xb + the 16-column statistics of one request (prelayernorm_skinny_kernel)
@@ -247,7 +246,6 @@ struct LayerPlan {
     bool causal = false;    // the text tower
     bool fold = false, fold_final = false;  // LayerNorm folded into QKV / FC1 (mode 2; else kernels), on FINISHED (mean, rstd) (d > 768)
     bool fp8 = false;       // QKV / FC1 / FC2 on the block-scaled fp8 GEMMs
-    bool fold8 = false;     // fp8 with the LayerNorm folded into QKV / FC1 (hidden 1024)
     bool out8 = false;      // the attention output leaves as MXFP8 and the out-projection runs on fp8 (not the pruned last layer)
     bool resid16 = false;   // the residual stream is the bf16 rows xb (no f32 stream)
     bool sfold = false;     // one request: skinny GEMMs with the LayerNorm folded in (16-column statistics)
@@ -299,14 +297,11 @@ int plan_layers(const mmiss_encoder* e, const Tower& tw, int B, bool causal, Lay
     // n > 1 = minimum tile count. The N = 768 GEMMs of ViT-B/32 at 12 800 rows (FC2, out-projection) are 150 tiles of 256 x 256
     // — one round on 150 of the 256 CUs — and measure SLOWER there than on the BM x 128 tile kernel, whose 600+ smaller tiles
     // fill the chip (tools/b32_kernel_table.py, profiles/b32_fp8_r06.txt: 34.1 vs 30.7 us per launch on average, the encode
-    // 113.4 vs 117.7 k images/s): they stay on gemm8_kernel. Option gemm_p256_fp8_narrow = the minimum tile count from which
-    // such one-round grids take the persistent kernel anyway (0 = never, the default).
+    // 113.4 vs 117.7 k images/s): they stay on gemm8_kernel.
     const int p8_min = mmiss_option("gemm_p256_fp8", 1);
-    const int p8_narrow = mmiss_option("gemm_p256_fp8_narrow", 0);
     auto p8 = [&](int epi, int N, int K) {
         if (p8_min == 0 || !gemm256p8_ok(epi, (int)round_up(M, 256), N, K)) return false;
         const int64_t tiles = (int64_t)(round_up(M, 256) / 256) * (N / 256);
-        if (p8_min == 1 && p8_narrow > 0 && tiles < 256 && tiles >= p8_narrow && M >= 6000) return true;   // (measured at 12 800 rows only)
         return tiles >= (p8_min > 1 ? p8_min : 256);
     };
     auto pick8 = [&](int epi, int N, int K) -> GemmPick {
@@ -390,31 +385,14 @@ int plan_layers(const mmiss_encoder* e, const Tower& tw, int B, bool causal, Lay
     // GEMM on gathered rows).
     const bool fp8_outproj = mmiss_option("fp8_outproj", 1) != 0;
     P.out8 = P.fp8 && !causal && P.resid16 && tw.L[0].wo8.p && tw.ctx8.p && attention_mx_ok(tw.T, tw.heads) && fp8_outproj;
-    // fp8 tower with the LayerNorm FOLDED into the QKV / FC1 GEMMs (round 5; hidden 1024 on the persistent fp8 kernel): the residual
-    // GEMMs' epilogue leaves the new bf16 rows as MXFP8 — raw — with their 256-column statistics, the QKV / FC1 epilogue applies
-    // (mean, rstd): 46 of the 47 LayerNorm launches of a ViT-L/14 encode disappear (tools/fp8_fold_sim.py: the same 1 - cos as
-    // LayerNorm-then-quantise). OFF by default (option fp8_ln_fold = 1 turns it on): measured inside the bs-128 encode the 1.03 ms
-    // of LayerNorm kernels (HBM-bound, 4.5 TB/s) come back as 1.3 ms of epilogue time in the GEMMs — +12 us per residual GEMM
-    // (half again as many bytes stored in the epilogue burst of 256 workgroups in step), +12 / +20 us per QKV / FC1 (two more packed
-    // operations per value and a workgroup barrier per tile), with the matrix pipes idle meanwhile: 9.19 k against 9.40 k images/s
-    // (tools/l14_fp8_ab.py, tools/l14_kernel_table.py).
-    if (P.fp8 && P.resid16 && !causal && d == 1024 && tw.layers >= 1 && tw.L[0].wqkv8f.p && tw.ctx8.p && attention_mx_ok(tw.T, tw.heads) &&
-        fp8_outproj && mmiss_option("fp8_ln_fold", 0) != 0 && p8(MMISS_EPI8_BIAS_BF16, 3 * d, d) &&
-        p8(MMISS_EPI8_QGELU_MXFP8, tw.mlp, d) && p8(MMISS_EPI8_BIAS_RESID_BF16, d, d) && p8(MMISS_EPI8_BIAS_RESID_BF16, d, tw.mlp)) {
-        Gemm8Args t{};   // (the residual form must not end in a round of half tiles)
-        t.M = (int)round_up(M, 256); t.N = d; t.K = d; t.m_valid = M;
-        t.ragged = (t.M >= 512 && M > t.M - 256 && M <= t.M - 128 && mmiss_option("gemm_p256_ragged", 1) != 0) ? M - (t.M - 256) : 0;
-        t.q_out = tw.h8.as<uint8_t>(); t.q_scale = tw.hs.as<uint8_t>(); t.stats_out = tw.stats.as<float>(); t.ld_qs = mx_scale_row_bytes(d);
-        P.fold8 = gemm256p8_xt_ok(MMISS_EPI8_BIAS_RESID_BF16, 2, t);
-    }
 
-    const GemmPick xt{GemmKind::P256Fp8Xt, 256}, skinny{GemmKind::Skinny, 0};
-    P.qkv = P.fold8 ? xt : P.fp8 ? pick8(MMISS_EPI8_BIAS_BF16, 3 * d, d)
+    const GemmPick skinny{GemmKind::Skinny, 0};
+    P.qkv = P.fp8 ? pick8(MMISS_EPI8_BIAS_BF16, 3 * d, d)
           : P.sfold ? skinny : wide(MMISS_EPI_BIAS_BF16, MMISS_EPI_LNFOLD_BF16, 3 * d, bm_qkv, true);
-    P.fc1 = P.fold8 ? xt : P.fp8 ? pick8(MMISS_EPI8_QGELU_MXFP8, tw.mlp, d)
+    P.fc1 = P.fp8 ? pick8(MMISS_EPI8_QGELU_MXFP8, tw.mlp, d)
           : P.sfold ? skinny : wide(MMISS_EPI_BIAS_QGELU_BF16, MMISS_EPI_LNFOLD_QGELU_BF16, tw.mlp, bm_mlp, fold256_mlp);
-    P.out = P.out8 ? (P.fold8 ? xt : pick8(MMISS_EPI8_BIAS_RESID_BF16, d, d)) : resid(d);
-    P.fc2 = P.fp8 ? (P.fold8 ? xt : pick8(P.resid16 ? MMISS_EPI8_BIAS_RESID_BF16 : MMISS_EPI8_BIAS_RESID_F32, d, tw.mlp)) : resid(tw.mlp);
+    P.out = P.out8 ? pick8(MMISS_EPI8_BIAS_RESID_BF16, d, d) : resid(d);
+    P.fc2 = P.fp8 ? pick8(P.resid16 ? MMISS_EPI8_BIAS_RESID_BF16 : MMISS_EPI8_BIAS_RESID_F32, d, tw.mlp) : resid(tw.mlp);
 
     // the vision embedding stage's pre-LayerNorm: one request at a time (the layers run in the skinny folded mode) CLS rows,
     // pre_layrnorm and the mode's entry statistics are ONE launch behind the patch GEMM (option embed_fused = 0: off); when
@@ -461,11 +439,11 @@ static PatchPlan plan_patch(const mmiss_encoder* e, int B) {
     return pp;
 }
 
-// an fp8 GEMM on the planned kernel, M rows padded to its tile height (xt: the folded-LayerNorm form of P256Fp8Xt)
-static int launch_gemm8_pick(hipStream_t st, GemmPick k, int epi, Gemm8Args g, int M, int xt) {
+// an fp8 GEMM on the planned kernel, M rows padded to its tile height
+static int launch_gemm8_pick(hipStream_t st, GemmPick k, int epi, Gemm8Args g, int M) {
     if (k.kind == GemmKind::Fp8Tile) { g.M = (int)round_up(M, k.bm); return launch_gemm8(st, epi, k.bm, g); }
     g.M = (int)round_up(M, 256);
-    return launch_gemm256p8(st, epi, g, k.kind == GemmKind::P256Fp8Xt ? xt : 0);
+    return launch_gemm256p8(st, epi, g);
 }
 
 // QKV / FC1: LayerNorm(x; g, beta) W^T + bias (+ QuickGELU for FC1), with the LayerNorm as the plan places it
@@ -476,7 +454,6 @@ struct WideRole {
     const DevBuf *W, *b;              // bf16 weights [N, d], bias
     const DevBuf *Wf, *bf, *c;        // the LayerNorm folded in: gamma-folded weights, bias b', row sums c (fold, sfold)
     const DevBuf *W8, *s8;            // fp8 weights, per-channel scales
-    const DevBuf *W8f, *s8f, *c16;    // fp8 of the folded weights, scales, f16 row sums (fold8)
     const DevBuf *beta_c, *b_c;       // the calibrated fp8 path's beta' and b'
     int site;                         // 2 * layer (QKV) / 2 * layer + 1 (FC1): the row of the calibration table
     void *out, *out8;                 // bf16 [M, N]; on the fp8 path bf16 (QKV) or e4m3 + MXFP8 scales (FC1)
@@ -491,24 +468,18 @@ int run_wide(hipStream_t st, Tower& tw, const LayerPlan& P, GemmPick k, const Wi
                                   nullptr, nullptr));
     if (is_fp8(k.kind)) {
         Gemm8Args g{};
-        if (k.kind == GemmKind::P256Fp8Xt) {   // A = the raw rows as MXFP8 + statistics, the bf16 rows for a ragged block
-            g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
-            g.ln_stats = tw.stats.as<float>(); g.x16 = tw.xb.as<uint16_t>(); g.ln_eps = eps;
-            g.W = r.W8f->as<uint8_t>(); g.wscale = r.s8f->as<float>(); g.bias = r.bf->as<float>(); g.c16 = r.c16->as<uint16_t>();
-        } else {
-            // calibrated: the same two kernels on beta' = beta - mu and b' = b + W mu (the constant part of the LayerNorm output
-            // goes round the fp8 operands; no launch more, none changed)
-            const DevBuf* beta = tw.calibrated ? r.beta_c : r.beta;
-            const DevBuf* bias = tw.calibrated ? r.b_c : r.b;
-            MM_TRY(launch_layernorm_mxfp8(st, P.resid16 ? tw.xb.p : tw.x.p, P.resid16, r.g->as<float>(), beta->as<float>(),
-                                          tw.h8.as<uint8_t>(), tw.hs.as<uint8_t>(), M, d, eps));
-            g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
-            g.W = r.W8->as<uint8_t>(); g.wscale = r.s8->as<float>(); g.bias = bias->as<float>();
-        }
+        // calibrated: the same two kernels on beta' = beta - mu and b' = b + W mu (the constant part of the LayerNorm output
+        // goes round the fp8 operands; no launch more, none changed)
+        const DevBuf* beta = tw.calibrated ? r.beta_c : r.beta;
+        const DevBuf* bias = tw.calibrated ? r.b_c : r.b;
+        MM_TRY(launch_layernorm_mxfp8(st, P.resid16 ? tw.xb.p : tw.x.p, P.resid16, r.g->as<float>(), beta->as<float>(),
+                                      tw.h8.as<uint8_t>(), tw.hs.as<uint8_t>(), M, d, eps));
+        g.A = tw.h8.as<uint8_t>(); g.As = tw.hs.as<uint8_t>(); g.ld_as = mx_scale_row_bytes(d);
+        g.W = r.W8->as<uint8_t>(); g.wscale = r.s8->as<float>(); g.bias = bias->as<float>();
         g.out = r.out8;
         if (r.out8_scale) { g.out_scale = r.out8_scale; g.ld_os = mx_scale_row_bytes(N); }
         g.ldo = N; g.N = N; g.K = d; g.m_valid = M;
-        return launch_gemm8_pick(st, k, r.gelu ? MMISS_EPI8_QGELU_MXFP8 : MMISS_EPI8_BIAS_BF16, g, M, 1);
+        return launch_gemm8_pick(st, k, r.gelu ? MMISS_EPI8_QGELU_MXFP8 : MMISS_EPI8_BIAS_BF16, g, M);
     }
     GemmEpi ep{};
     ep.out = r.out; ep.bias = r.b->as<float>(); ep.ldo = N; ep.m_valid = M;
@@ -560,10 +531,7 @@ int run_resid(hipStream_t st, Tower& tw, const LayerPlan& P, GemmPick k, const R
         g.A = r.A8; g.As = r.As; g.ld_as = mx_scale_row_bytes(r.K);
         g.W = r.W8->as<uint8_t>(); g.wscale = r.s8->as<float>(); g.bias = r.b->as<float>();
         g.out = P.resid16 ? tw.xb.p : tw.x.p; g.ldo = d; g.N = d; g.K = r.K; g.m_valid = M;
-        if (k.kind == GemmKind::P256Fp8Xt) {   // fold8: the new rows also leave as MXFP8 + statistics for the next QKV / FC1
-            g.q_out = tw.h8.as<uint8_t>(); g.q_scale = tw.hs.as<uint8_t>(); g.ld_qs = mx_scale_row_bytes(d); g.stats_out = tw.stats.as<float>();
-        }
-        return launch_gemm8_pick(st, k, P.resid16 ? MMISS_EPI8_BIAS_RESID_BF16 : MMISS_EPI8_BIAS_RESID_F32, g, M, 2);
+        return launch_gemm8_pick(st, k, P.resid16 ? MMISS_EPI8_BIAS_RESID_BF16 : MMISS_EPI8_BIAS_RESID_F32, g, M);
     }
     GemmEpi ep{};
     ep.out = tw.x.p; ep.bias = r.b->as<float>(); ep.ldo = d; ep.m_valid = M;
@@ -597,13 +565,11 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
         MM_TRY(launch_row_stats16(st, tw.x.as<float>(), tw.stats.as<float>(), tw.xb.as<uint16_t>(), M, d));
     if ((P.fold || P.resid16) && P.embed != EmbedOut::Stats64)  // (separate-LayerNorm mode with a bf16 stream: only the bf16 copy is used)
         MM_TRY(launch_row_stats(st, tw.x.as<float>(), tw.stats.as<float>(), tw.xb.as<uint16_t>(), M, d, d / 64, P.fold));
-    if (P.fold8)
-        MM_TRY(launch_quant16_mxfp8_stats(st, tw.xb.as<uint16_t>(), tw.h8.as<uint8_t>(), tw.hs.as<uint8_t>(), tw.stats.as<float>(), M, d));
     for (int l = 0; l < tw.layers; ++l) {
         LayerW& L = tw.L[l];
         WideRole qkv{};
         qkv.N = 3 * d; qkv.g = &L.ln1g; qkv.beta = &L.ln1b; qkv.W = &L.wqkv; qkv.b = &L.bqkv; qkv.Wf = &L.wqkv_f; qkv.bf = &L.bqkv_f;
-        qkv.c = &L.cqkv; qkv.W8 = &L.wqkv8; qkv.s8 = &L.sqkv; qkv.W8f = &L.wqkv8f; qkv.s8f = &L.sqkvf; qkv.c16 = &L.cqkv16; qkv.out = qkv.out8 = tw.qkv.p;
+        qkv.c = &L.cqkv; qkv.W8 = &L.wqkv8; qkv.s8 = &L.sqkv; qkv.out = qkv.out8 = tw.qkv.p;
         qkv.beta_c = &L.ln1b_c; qkv.b_c = &L.bqkv_c; qkv.site = 2 * l;
         MM_TRY(run_wide(st, tw, P, P.qkv, qkv, eps));
         const bool last_pruned = P.prune && l == tw.layers - 1;
@@ -649,7 +615,7 @@ int run_layers(mmiss_encoder* e, Tower& tw, const LayerPlan& P, hipStream_t st) 
         MM_TRY(run_resid(st, tw, P, P.out, out));
         WideRole fc1{};
         fc1.N = tw.mlp; fc1.gelu = true; fc1.g = &L.ln2g; fc1.beta = &L.ln2b; fc1.W = &L.w1; fc1.b = &L.b1; fc1.Wf = &L.w1_f; fc1.bf = &L.b1_f;
-        fc1.c = &L.c1; fc1.W8 = &L.w1_8; fc1.s8 = &L.s1; fc1.W8f = &L.w1_8f; fc1.s8f = &L.s1f; fc1.c16 = &L.c1_16;
+        fc1.c = &L.c1; fc1.W8 = &L.w1_8; fc1.s8 = &L.s1;
         fc1.out = tw.u.p; fc1.out8 = tw.u8.p; fc1.out8_scale = tw.us.as<uint8_t>();
         fc1.beta_c = &L.ln2b_c; fc1.b_c = &L.b1_c; fc1.site = 2 * l + 1;
         MM_TRY(run_wide(st, tw, P, P.fc1, fc1, eps));
@@ -1046,21 +1012,11 @@ static int build_fp8_weights(mmiss_encoder* enc) {
             MM_TRY(sc.alloc((size_t)N * 4));
             return launch_quantize_weights_fp8(st, wb.as<uint16_t>(), w8.as<uint8_t>(), sc.as<float>(), N, K);
         };
-        auto quant_fold = [&](DevBuf& wf, DevBuf& w8, DevBuf& sc, DevBuf& c16, int N, int K) -> int {
-            MM_TRY(w8.alloc((size_t)N * K));
-            MM_TRY(sc.alloc((size_t)N * 4));
-            MM_TRY(c16.alloc((size_t)N * 2));
-            return launch_quantize_weights_fp8_csum(st, wf.as<uint16_t>(), w8.as<uint8_t>(), sc.as<float>(), c16.as<uint16_t>(), N, K);
-        };
         for (LayerW& L : tw->L) {
             MM_TRY(quant(L.wqkv, L.wqkv8, L.sqkv, 3 * d, d));
             MM_TRY(quant(L.w1, L.w1_8, L.s1, mlp, d));
             MM_TRY(quant(L.w2, L.w2_8, L.s2, d, mlp));
             MM_TRY(quant(L.wo, L.wo8, L.so, d, d));
-            if (d == 1024 && L.wqkv_f.p && L.w1_f.p) {   // the folded form (run_layers: fold8)
-                MM_TRY(quant_fold(L.wqkv_f, L.wqkv8f, L.sqkvf, L.cqkv16, 3 * d, d));
-                MM_TRY(quant_fold(L.w1_f, L.w1_8f, L.s1f, L.c1_16, mlp, d));
-            }
         }
         tw->fp8_ready = true;
     }

@@ -462,38 +462,6 @@ extern "C" int mmiss_dbg_gemm8(int device, void* hip_stream, int epi, int bm, co
     return launch_gemm8(reinterpret_cast<hipStream_t>(hip_stream), epi, bm, g);
 }
 
-extern "C" int mmiss_dbg_gemm8_xt(int device, void* hip_stream, int epi, int xt, const void* A8, const void* As, const void* W8,
-                                  const float* wscale, const float* bias, void* out, void* out_scale, int32_t M, int32_t N, int32_t K,
-                                  int32_t m_valid, const void* c16, const float* ln_stats, const void* x16, float ln_eps,
-                                  void* q_out, void* q_scale, float* stats_out) {
-    MM_TRY(mmiss_use_device(device));
-    Gemm8Args g{};
-    g.A = reinterpret_cast<const uint8_t*>(A8); g.As = reinterpret_cast<const uint8_t*>(As); g.ld_as = mx_scale_row_bytes(K);
-    g.W = reinterpret_cast<const uint8_t*>(W8); g.wscale = wscale; g.bias = bias; g.out = out;
-    g.out_scale = reinterpret_cast<uint8_t*>(out_scale); g.ld_os = mx_scale_row_bytes(N);
-    g.M = M; g.N = N; g.K = K; g.ldo = N; g.m_valid = m_valid > 0 && m_valid < M ? m_valid : M;
-    g.c16 = reinterpret_cast<const uint16_t*>(c16); g.ln_stats = ln_stats; g.x16 = reinterpret_cast<const uint16_t*>(x16); g.ln_eps = ln_eps;
-    g.q_out = reinterpret_cast<uint8_t*>(q_out); g.q_scale = reinterpret_cast<uint8_t*>(q_scale); g.ld_qs = mx_scale_row_bytes(N);
-    g.stats_out = stats_out;
-    return launch_gemm256p8(reinterpret_cast<hipStream_t>(hip_stream), epi, g, xt);
-}
-
-extern "C" int mmiss_dbg_quant16_mxfp8_stats(int device, void* hip_stream, const void* x_bf16, void* out8, void* out_scale,
-                                             float* stats, int32_t M, int32_t d) {
-    if (!x_bf16 || !out8 || !out_scale || !stats) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_quant16_mxfp8_stats: bad argument");
-    MM_TRY(mmiss_use_device(device));
-    return launch_quant16_mxfp8_stats(reinterpret_cast<hipStream_t>(hip_stream), reinterpret_cast<const uint16_t*>(x_bf16),
-                                      reinterpret_cast<uint8_t*>(out8), reinterpret_cast<uint8_t*>(out_scale), stats, M, d);
-}
-
-extern "C" int mmiss_dbg_quantize_weights_fp8_csum(int device, void* hip_stream, const void* w_bf16, void* w8, float* scale, void* c16,
-                                                   int32_t N, int32_t K) {
-    if (!w_bf16 || !w8 || !scale || !c16) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_quantize_weights_fp8_csum: bad argument");
-    MM_TRY(mmiss_use_device(device));
-    return launch_quantize_weights_fp8_csum(reinterpret_cast<hipStream_t>(hip_stream), reinterpret_cast<const uint16_t*>(w_bf16),
-                                            reinterpret_cast<uint8_t*>(w8), scale, reinterpret_cast<uint16_t*>(c16), N, K);
-}
-
 extern "C" int mmiss_dbg_gemm8_time(int device, int epi, int bm, const void* A8, const void* As, const void* W8,
                                     const float* wscale, const float* bias, void* out, void* out_scale, int32_t M, int32_t N,
                                     int32_t K, int32_t iters, float* ms_per_launch) {
@@ -525,21 +493,21 @@ extern "C" int mmiss_dbg_encoder_plan(mmiss_encoder* enc, int32_t tower, int32_t
     LayerPlan P;
     const int rc = plan_layers(enc, tw, B, text, P);
     if (rc == MMISS_OK) {
-        out[0] = P.fold; out[1] = P.fold_final; out[2] = P.fp8; out[3] = P.fold8; out[4] = P.out8; out[5] = P.resid16;
-        out[6] = P.sfold; out[7] = P.prune; out[8] = (int)P.embed;
+        out[0] = P.fold; out[1] = P.fold_final; out[2] = P.fp8; out[3] = P.out8; out[4] = P.resid16;
+        out[5] = P.sfold; out[6] = P.prune; out[7] = (int)P.embed;
         const GemmPick picks[4] = {P.qkv, P.out, P.fc1, P.fc2};
-        for (int i = 0; i < 4; ++i) { out[9 + 2 * i] = (int)picks[i].kind; out[10 + 2 * i] = picks[i].bm; }
-        out[17] = pooled_tail_planned(tw, P);
-        out[18] = fc2_splitk_planned(tw, P.M);
-        out[19] = P.M;
-        out[24] = attention_pick_hpb(B, tw.heads);
-        out[25] = attention_stream_ok(B, tw.T, tw.heads, text);
+        for (int i = 0; i < 4; ++i) { out[8 + 2 * i] = (int)picks[i].kind; out[9 + 2 * i] = picks[i].bm; }
+        out[16] = pooled_tail_planned(tw, P);
+        out[17] = fc2_splitk_planned(tw, P.M);
+        out[18] = P.M;
+        out[23] = attention_pick_hpb(B, tw.heads);
+        out[24] = attention_stream_ok(B, tw.T, tw.heads, text);
         if (!text) {
             const PatchPlan pp = plan_patch(enc, B);
-            out[20] = lean_prelayernorm_planned(P);
-            out[21] = (int)(pp.p160 ? GemmKind::P160 : GemmKind::Tile);
-            out[22] = pp.p160 ? 160 : pp.bm;
-            out[23] = pp.splitk;
+            out[19] = lean_prelayernorm_planned(P);
+            out[20] = (int)(pp.p160 ? GemmKind::P160 : GemmKind::Tile);
+            out[21] = pp.p160 ? 160 : pp.bm;
+            out[22] = pp.splitk;
         }
     }
     tw.T = savedT;

@@ -4,8 +4,6 @@
 #include <queue>
 #include "retrieval_kernels.h"
 #include "gemm_bf16_256.h"
-#include "gemm_bf16_p256.h"   // (unused here since the strip kernel has its own header; its eight gemm256p_kernel instantiations
-                              // are still emitted into this code object, and dropping them is a change of the product, not a refactor)
 #include "gemm_strip_p256.h"
 #include <algorithm>
 

@@ -49,21 +49,11 @@ struct Gemm8Args {
     // gemm256p8_kernel only: the last 256-row block holds `ragged` <= 128 valid rows (0: none). They are computed by a
     // register-streamed pass of all workgroups in front of the tile stream; the tiles then cover M - 256 rows.
     int ragged;
-    // gemm256p8_kernel<EPI, XT> only (gemm_fp8_p256.h). XT = 1, LayerNorm FOLDED into the BIAS_BF16 / QGELU_MXFP8 GEMMs (K = 1024):
-    // A8 / As are the RAW residual rows as MXFP8, W8 the gamma-folded weights, bias = b', c16 = f16 [N] row sums of the
-    // dequantised folded weights, ln_stats = [M][4][2] f32 (sum, sumsq) of every 256-column quarter of the bf16 residual row;
-    // y = rstd (acc sw - mean c) + b'. x16 = those bf16 rows [M, K] (the ragged pass takes its rows' statistics from them).
-    const uint16_t* c16;
-    const float* ln_stats;
-    const uint16_t* x16;
-    float ln_eps;
-    // XT = 2, BIAS_RESID_BF16 that ALSO leaves the new bf16 rows as MXFP8 (q_out e4m3 [M, N], q_scale E8M0 [M, ld_qs] permuted)
-    // and their statistics stats_out [M][N/256][2] (tile rows only: a ragged block's rows get theirs in the consumer)
-    uint8_t* q_out;
-    uint8_t* q_scale;
-    float* stats_out;
-    int ld_qs;
+    // 64 unused bytes behind the last field: the kernels' implicit arguments (gridDim, which the ragged pass reads) follow the
+    // struct in the argument segment, and they stay at byte 160, where the compiled gemm256p8_kernel instantiations load them from
+    uint64_t reserved_[8];
 };
+static_assert(sizeof(Gemm8Args) == 160, "the implicit kernel arguments of gemm256p8_kernel move with this size");
 
 // bytes per row of a permuted scale array for K columns
 static inline int mx_scale_row_bytes(int K) { return 16 * ((K + 511) / 512); }
@@ -396,93 +386,6 @@ __global__ __launch_bounds__(256) void quantize_weights_fp8_kernel(const uint16_
     if (lane == 0) scale[n] = sc;
 }
 
-// The same for weights that carry a folded LayerNorm gamma (W' = bf16(W gamma), fold_ln_weights_kernel): e4m3 codes + per-channel
-// scale + c16[n] = f16(sum_k of the DEQUANTISED codes) — the row sum the folded fp8 GEMM's epilogue multiplies the row mean by
-// (gemm_fp8_p256.h, XT = 1): of the quantised weights, because those are what the matrix cores multiply.
-__global__ __launch_bounds__(256) void quantize_weights_fp8_csum_kernel(const uint16_t* __restrict__ Wb, uint8_t* __restrict__ W8,
-                                                                        float* __restrict__ scale, uint16_t* __restrict__ c16, int N, int K) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const uint16_t* w = Wb + (size_t)n * K;
-    float amax = 0.f;
-    for (int k = lane * 4; k < K; k += 256) {
-        const u32x2 v = *reinterpret_cast<const u32x2*>(w + k);
-        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(bf16_bits_to_f32(v[0] & 0xffff)), fabsf(bf16_bits_to_f32(v[0] >> 16))),
-                                 fmaxf(fabsf(bf16_bits_to_f32(v[1] & 0xffff)), fabsf(bf16_bits_to_f32(v[1] >> 16)))));
-    }
-    amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
-    const float inv = 1.0f / sc;
-    float csum = 0.f;
-    for (int k = lane * 4; k < K; k += 256) {
-        const u32x2 v = *reinterpret_cast<const u32x2*>(w + k);
-        const float a = fminf(fmaxf(bf16_bits_to_f32(v[0] & 0xffff) * inv, -448.f), 448.f);
-        const float b = fminf(fmaxf(bf16_bits_to_f32(v[0] >> 16) * inv, -448.f), 448.f);
-        const float c = fminf(fmaxf(bf16_bits_to_f32(v[1] & 0xffff) * inv, -448.f), 448.f);
-        const float d = fminf(fmaxf(bf16_bits_to_f32(v[1] >> 16) * inv, -448.f), 448.f);
-        const uint32_t q = pack_fp8x4(a, b, c, d);
-        *reinterpret_cast<uint32_t*>(W8 + (size_t)n * K + k) = q;
-        // the codes' values, exactly (e4m3 -> f32): sums of at most a few thousand multiples of 2^-9 below 2^9 are exact in f32
-        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, true);
-        csum += (lo[0] + lo[1]) + (hi[0] + hi[1]);
-    }
-    csum = wave_sum(csum);
-    if (lane == 0) {
-        scale[n] = sc;
-        const _Float16 h = (_Float16)(csum * sc);
-        c16[n] = __builtin_bit_cast(uint16_t, h);
-    }
-}
-
-// Entry of the folded fp8 mode (hidden 1024): the bf16 residual rows as MXFP8 — RAW, no LayerNorm — and (sum, sumsq) of each
-// 256-column quarter of every row, [M][4][2] f32: what the residual GEMMs' XT = 2 epilogue leaves behind from then on.
-// One wave per row, lane l holds columns 16 l .. + 15 (two lanes = one 32-column block, 16 lanes = one quarter).
-__global__ __launch_bounds__(256) void quant16_mxfp8_stats_1024_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ out,
-                                                                       uint8_t* __restrict__ out_scale, float* __restrict__ stats, int M,
-                                                                       int ld_os) {
-    constexpr int D = 1024;
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= M) return;
-    const int c = lane * 16;
-    const u32x4 r0 = *reinterpret_cast<const u32x4*>(x + (size_t)r * D + c), r1 = *reinterpret_cast<const u32x4*>(x + (size_t)r * D + c + 8);
-    float v[16];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        v[2 * w] = __uint_as_float(r0[w] << 16);
-        v[2 * w + 1] = __uint_as_float(r0[w] & 0xFFFF0000u);
-        v[8 + 2 * w] = __uint_as_float(r1[w] << 16);
-        v[8 + 2 * w + 1] = __uint_as_float(r1[w] & 0xFFFF0000u);
-    }
-    float s1 = 0.f, s2 = 0.f, amax = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        s1 += v[e];
-        s2 += v[e] * v[e];
-        amax = fmaxf(amax, fabsf(v[e]));
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {   // the 16 lanes of a quarter, fixed order
-        s1 += __shfl_xor(s1, o);
-        s2 += __shfl_xor(s2, o);
-    }
-    amax = fmaxf(amax, __shfl_xor(amax, 1));
-    int e8;
-    float inv;
-    mx_scale_of(amax, e8, inv);
-    u32x4 pk;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pk[i] = pack_fp8x4(v[4 * i] * inv, v[4 * i + 1] * inv, v[4 * i + 2] * inv, v[4 * i + 3] * inv);
-    *reinterpret_cast<u32x4*>(out + (size_t)r * D + c) = pk;
-    if ((lane & 1) == 0) out_scale[(size_t)r * ld_os + mx_scale_offset(c >> 5)] = (uint8_t)e8;
-    if ((lane & 15) == 0) {
-        float* so = stats + ((size_t)r * 4 + (lane >> 4)) * 2;
-        so[0] = s1;
-        so[1] = s2;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // LayerNorm with MXFP8 output (K2 in front of the fp8 QKV / FC1 GEMMs): same statistics as layernorm_kernel
 // (encoder_kernels.h; HF:modeling_clip.py:358-360), the normalised row quantised per 32 columns. One wave per row held in
@@ -551,7 +454,7 @@ __global__ __launch_bounds__(256) void layernorm_mxfp8_kernel(const void* __rest
     }
 }
 
-// The same arithmetic for a bf16 residual stream with d = NS * 512 (ViT-L/14: 1024), wide accesses (round 4): a lane holds EIGHT
+// The same arithmetic for a bf16 residual stream with d = NS * 512 (512; 1024 has its own kernel below), wide accesses (round 4): a lane holds EIGHT
 // consecutive columns per 512-column step (one 16-byte load, one 8-byte store; the first form moves 8 / 4 bytes per lane and
 // re-reads gamma and beta — twice the row's own bytes — for every row), a wave walks four rows with gamma and beta in
 // registers, all four rows' loads issued before the first is used. A 32-column block = 4 lanes: two xor-shuffles.
@@ -644,13 +547,11 @@ __global__ __launch_bounds__(256) void layernorm16_mxfp8_wide_kernel(const uint1
 
 // d = 1024 (ViT-L/14): SIXTEEN consecutive columns per lane — two 16-byte loads, ONE 16-byte store per row and lane (the
 // 8-column form stores 8 bytes: half-width store instructions), a 32-column block = 2 lanes: one xor-shuffle.
-// PACKS (A/B of round 5, option ln_mxfp8_wide = 5): the row's 32 scale bytes leave as eight dwords from eight lanes (four
-// lane gathers per row) instead of 32 single-byte stores from 32 lanes
-template <int RW, bool PACKS = false>   // RW: rows per wave, all of them loaded before the first is used (4: round 4; 8: A/B of round 5, option ln_mxfp8_wide = 3)
 __global__ __launch_bounds__(256) void layernorm16_mxfp8_1024_kernel(const uint16_t* __restrict__ x, const float* __restrict__ gamma,
                                                                      const float* __restrict__ beta, uint8_t* __restrict__ out,
                                                                      uint8_t* __restrict__ out_scale, int M, int ld_os, float eps) {
     constexpr int D = 1024;
+    constexpr int RW = 4;   // rows per wave, all of them loaded before the first is used
     const int lane = threadIdx.x & 63;
     const int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RW;
     if (r0 >= M) return;
@@ -707,18 +608,7 @@ __global__ __launch_bounds__(256) void layernorm16_mxfp8_1024_kernel(const uint1
 #pragma unroll
             for (int i = 0; i < 4; ++i) pk[i] = pack_fp8x4(y[4 * i] * inv, y[4 * i + 1] * inv, y[4 * i + 2] * inv, y[4 * i + 3] * inv);
             *reinterpret_cast<u32x4*>(out + (size_t)r * D + c) = pk;
-            if constexpr (!PACKS) {
-                if ((lane & 1) == 0) out_scale[(size_t)r * ld_os + mx_scale_offset(c >> 5)] = (uint8_t)e8;
-            }
-        }
-        if constexpr (PACKS) {
-            // dword t = (group G = t >> 2, k-block c = t & 3) of the permuted row: bytes t' = 0..3 are the scales of column blocks
-            // 16 G + 4 t' + c, held by lanes 2 (16 G + 4 t' + c) — gathered by lane t (wave-uniform control flow: every lane shuffles)
-            const int t = lane & 7, srcl = 32 * (t >> 2) + 2 * (t & 3);
-            uint32_t dw = 0;
-#pragma unroll
-            for (int tp = 0; tp < 4; ++tp) dw |= (uint32_t)(__shfl(e8, srcl + 8 * tp) & 0xff) << (8 * tp);
-            if (r < M && lane < 8) *reinterpret_cast<uint32_t*>(out_scale + (size_t)r * ld_os + 4 * lane) = dw;
+            if ((lane & 1) == 0) out_scale[(size_t)r * ld_os + mx_scale_offset(c >> 5)] = (uint8_t)e8;
         }
     }
 }
@@ -727,19 +617,10 @@ static int launch_layernorm_mxfp8(hipStream_t st, const void* x, bool x_bf16, co
                                   uint8_t* out_scale, int M, int d, float eps) {
     if (d > 1024 || (d % 32)) MM_FAIL(MMISS_ERR_UNSUPPORTED, "layernorm_mxfp8: d=%d (need d <= 1024, d %% 32 == 0)", d);
     MM_PROF(x_bf16 ? "layernorm16_mxfp8" : "layernorm_mxfp8", st, 8.0 * M * d, (double)M * d * (x_bf16 ? 3 : 5));
-    if (x_bf16 && (d == 512 || d == 768 || d == 1024) && mmiss_option("ln_mxfp8_wide", 1) != 0) {
+    if (x_bf16 && (d == 512 || d == 768 || d == 1024)) {
         const int grid = (M + 15) / 16;
-        if (d == 1024 && mmiss_option("ln_mxfp8_wide", 1) == 1)
-            hipLaunchKernelGGL(layernorm16_mxfp8_1024_kernel<4>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(x), gamma,
-                               beta, out, out_scale, M, mx_scale_row_bytes(d), eps);
-        else if (d == 1024 && mmiss_option("ln_mxfp8_wide", 1) == 5)
-            hipLaunchKernelGGL((layernorm16_mxfp8_1024_kernel<4, true>), dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(x), gamma,
-                               beta, out, out_scale, M, mx_scale_row_bytes(d), eps);
-        else if (d == 1024 && mmiss_option("ln_mxfp8_wide", 1) == 3)
-            hipLaunchKernelGGL(layernorm16_mxfp8_1024_kernel<8>, dim3((M + 31) / 32), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(x), gamma,
-                               beta, out, out_scale, M, mx_scale_row_bytes(d), eps);
-        else if (d == 1024)   // (option ln_mxfp8_wide = 2: the 8-columns-per-lane form, A/B)
-            hipLaunchKernelGGL(layernorm16_mxfp8_wide_kernel<2>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(x), gamma,
+        if (d == 1024)
+            hipLaunchKernelGGL(layernorm16_mxfp8_1024_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(x), gamma,
                                beta, out, out_scale, M, mx_scale_row_bytes(d), eps);
         else if (d == 768)
             hipLaunchKernelGGL((layernorm16_mxfp8_wide_kernel<2, 768>), dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(x), gamma,
@@ -760,25 +641,10 @@ static int launch_layernorm_mxfp8(hipStream_t st, const void* x, bool x_bf16, co
     return MMISS_OK;
 }
 
-// (the weight quantisers read a row as 8-byte groups of four: K % 4 == 0)
+// (the weight quantiser reads a row as 8-byte groups of four: K % 4 == 0)
 static int launch_quantize_weights_fp8(hipStream_t st, const uint16_t* w, uint8_t* w8, float* scale, int N, int K) {
     if (N <= 0 || K <= 0 || (K % 4)) MM_FAIL(MMISS_ERR_ARG, "quantize_weights_fp8: bad argument (N=%d K=%d, K %% 4 == 0)", N, K);
     hipLaunchKernelGGL(quantize_weights_fp8_kernel, dim3((N + 3) / 4), dim3(256), 0, st, w, w8, scale, N, K);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-static int launch_quantize_weights_fp8_csum(hipStream_t st, const uint16_t* w, uint8_t* w8, float* scale, uint16_t* c16, int N, int K) {
-    if (N <= 0 || K <= 0 || (K % 4)) MM_FAIL(MMISS_ERR_ARG, "quantize_weights_fp8_csum: bad argument (N=%d K=%d, K %% 4 == 0)", N, K);
-    hipLaunchKernelGGL(quantize_weights_fp8_csum_kernel, dim3((N + 3) / 4), dim3(256), 0, st, w, w8, scale, c16, N, K);
-    MM_HIP(hipGetLastError());
-    return MMISS_OK;
-}
-
-static int launch_quant16_mxfp8_stats(hipStream_t st, const uint16_t* x16, uint8_t* out8, uint8_t* out_scale, float* stats, int M, int d) {
-    if (M <= 0 || d != 1024) MM_FAIL(MMISS_ERR_ARG, "quant16_mxfp8_stats: bad argument (M=%d d=%d; d must be 1024)", M, d);
-    MM_PROF("quant16_mxfp8_stats", st, 3.0 * M * d, 3.0 * M * d);
-    hipLaunchKernelGGL(quant16_mxfp8_stats_1024_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x16, out8, out_scale, stats, M, mx_scale_row_bytes(d));
     MM_HIP(hipGetLastError());
     return MMISS_OK;
 }

@@ -48,7 +48,7 @@ NAN_ID = 997     # reserved: its token-embedding row is NaN; no victim prompt ho
 OPTION_DEFAULTS = {
     "ln_fold_min_rows": 6000, "fp8_min_rows": 1024, "embed_fused": 1, "pooled_tail": 1, "skinny_fold": 1, "att_hpb": 0,
     "gemm_bm_qkv": 0, "gemm_bm_d": 0, "gemm_bm_mlp": 0, "prelayernorm_lean": 1, "resid16": -1, "gemm_256_fold": -1,
-    "gemm_256_fold_mlp": 0, "gemm_p256": 1, "gemm_p256_fp8": 1, "fp8_ln_fold": 0, "attention_stream_min_pairs": 256,
+    "gemm_256_fold_mlp": 0, "gemm_p256": 1, "gemm_p256_fp8": 1, "attention_stream_min_pairs": 256,
     "gemm_splitk_target": 384,
 }
 
@@ -268,12 +268,12 @@ def _vision_cases():
             max_batch=384, precision="fp8")
     add("h-p256fp8-calibrated-B205", "h", 205, h8, _o(fp8=1, qkv="P256Fp8"), shape="w512", max_batch=384, precision="fp8", calibrated=True)
 
-    # (i) fp8 with the folded LayerNorm (d = 1024): a ragged last block, M in (Mpad - 256, Mpad - 128], and one without
-    i8 = _o(fp8_min_rows=129, ln_fold_min_rows=129, gemm_p256_fp8=2, fp8_ln_fold=1)
+    # (i) the same kernel at d = 1024 (two scale groups per tile at K = 1024): a ragged last block, M in (Mpad - 256, Mpad - 128], and one without
+    i8 = _o(fp8_min_rows=129, ln_fold_min_rows=129, gemm_p256_fp8=2)
     for B in (180, 205, 307, 256):                                    # 900 (not ragged: above Mpad - 128), 1025, 1535, 1280
-        add(f"i-fold8-B{B}", "i", B, i8, _o(fp8=1, fold8=1, qkv="P256Fp8Xt", out="P256Fp8Xt", fc1="P256Fp8Xt", fc2="P256Fp8Xt"), shape="w1024",
+        add(f"i-p256fp8-w1024-B{B}", "i", B, i8, _o(fp8=1, out8=1, qkv="P256Fp8", out="P256Fp8", fc1="P256Fp8", fc2="P256Fp8"), shape="w1024",
             max_batch=384, precision="fp8")
-    add("i-fold8-ragged-B170", "i", 170, i8, _o(fp8=1, fold8=1, qkv="P256Fp8Xt"), shape="w1024", max_batch=384, precision="fp8")  # 850 in (768, 896]
+    add("i-p256fp8-w1024-ragged-B170", "i", 170, i8, _o(fp8=1, out8=1, qkv="P256Fp8"), shape="w1024", max_batch=384, precision="fp8")  # 850 in (768, 896]
 
     # (k) the attention kernel by token count, inside an encode (T <= 128: every case above; one head per workgroup unless att_hpb)
     add("k-heads-B77", "k", 77, _o(att_hpb=2), _o(sfold=0, pooled_tail=1, att_hpb=2), max_batch=big)

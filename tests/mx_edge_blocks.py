@@ -102,36 +102,6 @@ def layout_rows(blocks, d):
     return np.ascontiguousarray(stack[idx].reshape(C, d))
 
 
-# ------------------------------------------------------------------------------------------------ e4m3-valued blocks
-def e4m3_catalogue():
-    """[(name, float32 [32])] of blocks whose values are e4m3 codes (the W8 columns of the one-hot GEMM cases): the position
-    sweep with 240 against 1 .. 1.75, both signs of it, zeros, +-448, an amax of 224 (amax / 448 a power of two: scale 126, the
-    maximum lands ON 448), 208 (one code below), 256, and a block of subnormals (amax 7 * 2^-9)."""
-    rng = np.random.default_rng(77)
-    out = []
-    small = lambda: ((1.0 + rng.integers(0, 7, 32) / 8.0) * rng.choice([-1.0, 1.0], 32)).astype(np.float32)
-    sweep = []
-    for p in range(32):
-        v = small()
-        v[p] = 240.0
-        sweep.append(v)
-        out.append(("w_maxpos%02d" % p, v))
-    out += [("w_maxpos%02d-" % p, -sweep[p]) for p in range(32)]
-    out += [("w_zeros+", np.zeros(32, np.float32)), ("w_zeros-", -np.zeros(32, np.float32)),
-            ("w_zeros+-", np.where(np.arange(32) % 2 == 0, 0.0, -0.0).astype(np.float32))]
-    v = small()
-    v[9], v[31] = 448.0, -448.0
-    out.append(("w_+448-448", v))
-    for i, a in enumerate((224.0, 208.0, 256.0)):
-        v = small() * np.float32(0.125)
-        v[(11 * i + 4) % 32] = -a if i == 1 else a
-        out.append(("w_amax%d" % int(a), v))
-    v = (rng.integers(0, 7, 32) * 2.0 ** -9 * rng.choice([-1.0, 1.0], 32)).astype(np.float32)
-    v[17] = 7 * 2.0 ** -9
-    out.append(("w_subnormals", v))
-    return out
-
-
 # ------------------------------------------------------------------------------------------------ QuickGELU -> MXFP8 cases
 QGELU_BAND = 2.0 ** -16     # relative distance of the exact scaled value to a code midpoint inside which one code step passes
 QGELU_CAP = 0.01            # largest share of elements the band may take

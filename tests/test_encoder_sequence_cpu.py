@@ -72,7 +72,7 @@ def test_victim_row_counts_sit_on_the_tile_edges():
         for key in ("qkv_bm",):
             if key in e:
                 rows.setdefault(e[key], set()).add(sc.call_rows(c, c.victim) % e[key])
-        if e.get("qkv") in ("Tile256", "P256", "P256Fp8", "P256Fp8Xt"):
+        if e.get("qkv") in ("Tile256", "P256", "P256Fp8"):
             rows.setdefault(256, set()).add(sc.call_rows(c, c.victim) % 256)
         if c.plan == "b":
             rows.setdefault("plain128", set()).add(sc.call_rows(c, c.victim) % 128)

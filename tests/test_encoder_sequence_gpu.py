@@ -86,10 +86,9 @@ def _expected_kernels(plan, s, tower, rows):
     must, never = set(), set()
     must.add({"Skinny": "gemm_skinny_lnfold_bias", "P256": "gemm_bf16_lnfold_bias_p256" if fold else "gemm_bf16_bias_p256",
               "Tile256": "gemm_bf16_lnfold_bias" if fold else "gemm_bf16_bias", "Fp8Tile": "gemm_fp8_bias", "P256Fp8": "gemm_fp8_bias_p256",
-              "P256Fp8Xt": "gemm_fp8_lnfold_bias_p256",
               "Tile": "gemm_bf16_lnfold_bias" if fold else ("gemm_bf16_bias" if rows > skinny_rows else "gemm_skinny_bias")}[plan["qkv"]])
     fc2 = {"P160": f"gemm_bf16_bias_resid16_p160_k{mlp}", "Fp8Tile": "gemm_fp8_bias_resid16" if r16 else "gemm_fp8_bias_resid",
-           "P256Fp8": "gemm_fp8_bias_resid16_p256", "P256Fp8Xt": "gemm_fp8_bias_resid16_mxq_p256",
+           "P256Fp8": "gemm_fp8_bias_resid16_p256",
            "Tile": f"gemm_bf16_bias_resid16_k{mlp}" if r16 else None}[plan["fc2"]]
     if fc2:
         must.add(fc2)
@@ -100,7 +99,7 @@ def _expected_kernels(plan, s, tower, rows):
     for name in ("gemm_skinny_lnfold_bias", "gemm_skinny_lnfold_qgelu"):
         (must if plan["sfold"] else never).add(name)
     if not plan["fp8"]:
-        never.update(("gemm_fp8_bias", "gemm_fp8_bias_p256", "gemm_fp8_lnfold_bias_p256", "layernorm_mxfp8", "layernorm16_mxfp8"))
+        never.update(("gemm_fp8_bias", "gemm_fp8_bias_p256", "layernorm_mxfp8", "layernorm16_mxfp8"))
     if not fold:
         never.update(("gemm_bf16_lnfold_bias", "gemm_bf16_lnfold_bias_p256"))
     if tower == "vision":

@@ -481,161 +481,3 @@ def test_longclip_l14_full_depth_vision_bf16_and_fp8(env):
     print("   out-projection bf16 (fp8_outproj = 0): fp8 bs 128 (first 8) %.2e" % d8_b.max())
     assert kern_b.get("gemm_fp8_bias_resid16_p256", 0) == 23 and kern_b.get("attention_mx", 0) == 0, kern_b
     assert d8_b.max() < COS_TOL
-
-
-def _rows_sample(mv, M):
-    """every 37th row, the rows around the tile boundaries and the (ragged) last row block"""
-    idx = set(range(0, mv, 37)) | set(range(max(0, M - 256 - 3), min(mv, M - 256 + 3))) | set(range(max(0, mv - 130), mv)) | {255, 256, 257}
-    return np.array(sorted(i for i in idx if i < mv))
-
-
-@pytest.mark.parametrize("K", [1024, 4096])
-def test_residual_fp8_gemm_leaves_the_rows_as_mxfp8_with_statistics(env, K):
-    """gemm256p8_kernel<BIAS_RESID_BF16, 2> (round 5, the producer side of the folded LayerNorm): the bf16 rows it writes are the
-    plain kernel's, byte for byte; their MXFP8 copy (one E8M0 scale per 32 columns of the NEW bf16 values, e4m3 codes) equals
-    the numpy quantisation of those very rows; stats_out holds (sum, sumsq) of every 256-column quarter of every TILE row
-    (the ragged last block's rows get theirs in the consumer). ViT-L/14 at batch 128: 32 896 valid of 33 024 rows."""
-    torch, _lib, lib, fo = env
-    M, mv, N = 33024, 32896, 1024
-    g = torch.Generator(device="cuda").manual_seed(31 + K)
-    tab = fo.e4m3_table()
-    ok = torch.from_numpy(np.nonzero(~np.isnan(tab) & (np.abs(tab) <= 16))[0].astype(np.uint8)).cuda()
-    A8 = ok[torch.randint(0, ok.numel(), (M, K), device="cuda", generator=g)]
-    W8 = ok[torch.randint(0, ok.numel(), (N, K), device="cuda", generator=g)]
-    e = torch.randint(121, 131, (M, K // 32), device="cuda", generator=g, dtype=torch.int32).to(torch.uint8)
-    As = torch.from_numpy(fo.permute_scales(e.cpu().numpy())).cuda()
-    ws = (torch.rand(N, device="cuda", generator=g) + 1.0) * 2.0 ** -7
-    bias = torch.randn(N, device="cuda", generator=g)
-    x0 = (torch.randn((M, N), device="cuda", generator=g) * 3).to(torch.bfloat16)
-    x0[:, 77] += 200.0                      # an outlier channel: its 32-column block takes a scale of its own
-    dummy = torch.zeros((M, fo.scale_row_bytes(N)), dtype=torch.uint8, device="cuda")
-    plain = x0.clone()
-    _lib.check(lib.mmiss_dbg_gemm8(0, None, 3, 256 + mv, A8.data_ptr(), As.data_ptr(), W8.data_ptr(), ws.data_ptr(), bias.data_ptr(),
-                                   plain.data_ptr(), dummy.data_ptr(), M, N, K))
-    out = x0.clone()
-    q8 = torch.zeros((M, N), dtype=torch.uint8, device="cuda")
-    qs = torch.full((M, fo.scale_row_bytes(N)), 127, dtype=torch.uint8, device="cuda")
-    st = torch.full((M, 4, 2), float("nan"), device="cuda")
-    _lib.check(lib.mmiss_dbg_gemm8_xt(0, None, 3, 2, A8.data_ptr(), As.data_ptr(), W8.data_ptr(), ws.data_ptr(), bias.data_ptr(),
-                                      out.data_ptr(), dummy.data_ptr(), M, N, K, mv, None, None, None, 0.0, q8.data_ptr(), qs.data_ptr(),
-                                      st.data_ptr()))
-    torch.cuda.synchronize()
-    assert torch.equal(out[:mv].view(torch.uint8), plain[:mv].view(torch.uint8))
-    rows = _rows_sample(mv, M)
-    x = out[rows].float().cpu().numpy()
-    q_ref, e_ref = fo.mx_quantize(x)
-    assert (fo.unpermute_scales(qs[rows].cpu().numpy(), N) == e_ref).all()
-    assert (q8[rows].cpu().numpy() == q_ref).all()
-    tile_rows = rows[rows < M - 256]
-    xt = out[tile_rows].double().cpu().numpy().reshape(len(tile_rows), 4, 256)
-    got = st[tile_rows].cpu().numpy().astype(np.float64)
-    assert np.isfinite(got).all()
-    assert (np.abs(got[:, :, 0] - xt.sum(axis=2)) <= 1e-5 * np.abs(xt).sum(axis=2) + 1e-6).all()
-    assert (np.abs(got[:, :, 1] - (xt * xt).sum(axis=2)) <= 1e-5 * (xt * xt).sum(axis=2) + 1e-6).all()
-
-
-@pytest.mark.parametrize("epi,M,mv,N", [(0, 33024, 32896, 3072), (1, 33024, 32896, 4096), (0, 2048, 2000, 512), (1, 4096, 3970, 512)])
-def test_fp8_gemm_with_the_layernorm_folded_in(env, epi, M, mv, N):
-    """gemm256p8_kernel<., 1> (round 5, the consumer side): A = the RAW bf16 residual rows as MXFP8 (quant16_mxfp8_stats_1024_kernel,
-    itself held to the numpy quantisation here), W = gamma-folded weights as e4m3 (quantize_weights_fp8_csum_kernel: codes,
-    scales, f16 row sums of the dequantised codes), the epilogue applies rstd (acc sw - mean c) + b' from the 256-column
-    statistics — against the float64 evaluation of the same formula on the dequantised operands, tile rows and the ragged last
-    block (whose statistics the kernel takes from the bf16 rows themselves); QuickGELU -> MXFP8 for epi 1."""
-    torch, _lib, lib, fo = env
-    K, eps = 1024, 1e-5
-    g = torch.Generator(device="cuda").manual_seed(900 + 10 * epi + N)
-    x16 = (torch.randn((M, K), device="cuda", generator=g) * (0.5 + 2.5 * torch.rand((M, 1), device="cuda", generator=g)) +
-           2.0 * torch.randn((M, 1), device="cuda", generator=g))
-    x16[:, 31] += 60.0
-    x16[:, 700] -= 35.0
-    x16 = x16.to(torch.bfloat16)
-    A8 = torch.zeros((M, K), dtype=torch.uint8, device="cuda")
-    As = torch.full((M, fo.scale_row_bytes(K)), 127, dtype=torch.uint8, device="cuda")
-    st = torch.zeros((M, 4, 2), device="cuda")
-    _lib.check(lib.mmiss_dbg_quant16_mxfp8_stats(0, None, x16.data_ptr(), A8.data_ptr(), As.data_ptr(), st.data_ptr(), M, K))
-    wf = (torch.randn((N, K), device="cuda", generator=g) * 0.03 * (1.0 + 0.1 * torch.randn((1, K), device="cuda", generator=g))).to(torch.bfloat16)
-    W8 = torch.zeros((N, K), dtype=torch.uint8, device="cuda")
-    ws = torch.zeros(N, device="cuda")
-    c16 = torch.zeros(N, dtype=torch.float16, device="cuda")
-    _lib.check(lib.mmiss_dbg_quantize_weights_fp8_csum(0, None, wf.data_ptr(), W8.data_ptr(), ws.data_ptr(), c16.data_ptr(), N, K))
-    bias = torch.randn(N, device="cuda", generator=g)
-    osc = torch.zeros((M, fo.scale_row_bytes(N)), dtype=torch.uint8, device="cuda")
-    out = torch.zeros((M, N), dtype=torch.bfloat16 if epi == 0 else torch.uint8, device="cuda")
-    _lib.check(lib.mmiss_dbg_gemm8_xt(0, None, epi, 1, A8.data_ptr(), As.data_ptr(), W8.data_ptr(), ws.data_ptr(), bias.data_ptr(),
-                                      out.data_ptr(), osc.data_ptr(), M, N, K, mv, c16.data_ptr(), st.data_ptr(), x16.data_ptr(), eps,
-                                      None, None, None))
-    torch.cuda.synchronize()
-    rows = _rows_sample(mv, M)
-    xs = x16[rows].float().cpu().numpy()
-    # the entry kernel: codes and scales of the raw rows, and their quarter sums
-    q_ref, e_ref = fo.mx_quantize(xs)
-    assert (A8[rows].cpu().numpy() == q_ref).all() and (fo.unpermute_scales(As[rows].cpu().numpy(), K) == e_ref).all()
-    xq = xs.astype(np.float64).reshape(len(rows), 4, 256)
-    sg = st[rows].cpu().numpy().astype(np.float64)
-    assert (np.abs(sg[:, :, 0] - xq.sum(axis=2)) <= 1e-5 * np.abs(xq).sum(axis=2) + 1e-6).all()
-    assert (np.abs(sg[:, :, 1] - (xq * xq).sum(axis=2)) <= 1e-5 * (xq * xq).sum(axis=2) + 1e-6).all()
-    # the weights: codes / scales as the plain quantiser's, c16 = f16 of the dequantised row sums
-    w_np = wf.float().cpu().numpy()
-    wq_ref, ws_ref = fo.quantize_weights(w_np)
-    assert (W8.cpu().numpy() == wq_ref).all() and np.array_equal(ws.cpu().numpy(), ws_ref)
-    Wd = fo.e4m3_decode(wq_ref).astype(np.float64) * ws_ref[None, :].T.astype(np.float64)
-    c_ref = Wd.sum(axis=1)
-    c_got = c16.float().cpu().numpy().astype(np.float64)
-    assert (np.abs(c_got - c_ref) <= np.abs(c_ref) * 2.0 ** -10 + 1e-6).all()
-    # the GEMM
-    A = fo.mx_dequantize(q_ref, e_ref)
-    acc = A @ Wd.T
-    absacc = np.abs(A) @ np.abs(Wd).T
-    mean = xs.astype(np.float64).mean(axis=1, keepdims=True)
-    rstd = 1.0 / np.sqrt(xs.astype(np.float64).var(axis=1, keepdims=True) + eps)
-    ref = rstd * (acc - mean * c_got[None, :]) + bias.cpu().numpy()[None, :].astype(np.float64)
-    # tolerance: the MFMA's in-instruction alignment (2^-11 of sum |terms|), f32 statistics (1e-5 relative on mean / rstd)
-    tol = rstd * (absacc * 2.0 ** -11 + 2e-5 * (np.abs(acc) + np.abs(mean * c_got[None, :]))) + 1e-5
-    if epi == 0:
-        got = out[rows].float().cpu().numpy()
-        bad = np.abs(got - ref) > tol + np.abs(ref) * 2.0 ** -8
-        assert not bad.any(), (int(bad.sum()), np.abs(got - ref).max())
-    else:
-        y = ref * (1.0 / (1.0 + np.exp(-1.702 * ref)))
-        got_e = fo.unpermute_scales(osc[rows].cpu().numpy(), N)
-        back = fo.mx_dequantize(out[rows].cpu().numpy(), got_e)
-        g64 = np.abs(y).reshape(len(rows), -1, 64).max(axis=2)
-        e_r, _ = fo.e8m0_for(g64.astype(np.float32))
-        assert (got_e[:, ::2] == got_e[:, 1::2]).all()
-        assert (np.abs(got_e[:, ::2].astype(int) - e_r.astype(int)) <= 1).all() and (got_e[:, ::2] == e_r).mean() > 0.98
-        gmax = g64.repeat(64, axis=1)
-        assert (np.abs(back - y) <= gmax * 2.0 ** -4 * 1.02 + tol * 2 + 1e-6).all()
-
-
-def test_folded_layernorm_fp8_tower_holds_the_bar_end_to_end():
-    """Option fp8_ln_fold = 1 (off by default: it measured slower): the ViT-L/14 vision tower with its LayerNorms
-    folded into the fp8 QKV / FC1 GEMMs and the residual GEMMs leaving the rows as MXFP8 — 24 layers at the config's batch of 128
-    against the fp32 oracle at the 1e-3 bar, the kernels that ran, and no LayerNorm -> MXFP8 launch but the entry quantisation."""
-    import dataclasses
-    import mmiss_amd  # noqa: F401
-    from mmiss_amd import _lib
-    from mmiss_amd.encoder import ClipEncoder, ClipShape
-    from oracle import clip_oracle as co
-
-    s = dataclasses.replace(co.LONGCLIP_L14, t_layers=1, t_vocab=1000, eos_token_id=999)
-    W = co.init_weights(s, seed=3)
-    rng = np.random.Generator(np.random.Philox(8))
-    px = rng.standard_normal((128, 3, 224, 224), dtype=np.float32)
-    ref = co.embed_images(px[:3], W, s)
-    enc = ClipEncoder(ClipShape.from_any(s), max_batch_image=128, max_batch_text=2, precision="fp8")
-    enc.load_state_dict(W)
-    try:
-        _lib.set_option("fp8_ln_fold", 1)
-        out, kern = _with_kernels(lambda: enc.encode_image(px))
-        _lib.set_option("fp8_ln_fold", 0)
-        plain = enc.encode_image(px)
-    finally:
-        _lib.set_option("fp8_ln_fold", 0)
-        enc.close()
-    d_fold = float((1 - (out[:3] * ref).sum(axis=1)).max())
-    d_plain = float((1 - (plain[:3] * ref).sum(axis=1)).max())
-    print("ViT-L/14 fp8, 24 layers at 128 per call: 1 - cos vs oracle with the LayerNorm folded %.2e, with LayerNorm kernels %.2e" % (d_fold, d_plain))
-    assert d_fold < 1e-3 and d_plain < 1e-3, (d_fold, d_plain)
-    assert kern.get("gemm_fp8_lnfold_bias_p256", 0) == 24 and kern.get("gemm_fp8_lnfold_qgelu_mx_p256", 0) == 23, kern
-    assert kern.get("gemm_fp8_bias_resid16_mxq_p256", 0) == 46 and kern.get("quant16_mxfp8_stats", 0) == 1, kern
-    assert kern.get("layernorm16_mxfp8", 0) == 0, kern

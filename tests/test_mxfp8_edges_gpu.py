@@ -13,25 +13,21 @@ and scale bytes no block owns keep their fill.
   producer                                   test                                       shapes                  how the launch takes it
   layernorm_mxfp8_kernel<false>              test_layernorm_f32_rows                    d 96 768 1024, M 19     dedicated entry point (f32 rows)
   layernorm_mxfp8_kernel<true>               test_layernorm_bf16_rows[96]               d 96, M 19              shape rule: d not in {512, 768, 1024}
-  layernorm16_mxfp8_wide_kernel<1>           test_layernorm_bf16_rows[512]              d 512, M 19             shape rule at the default ln_mxfp8_wide
+  layernorm16_mxfp8_wide_kernel<1>           test_layernorm_bf16_rows[512]              d 512, M 19             shape rule
   layernorm16_mxfp8_wide_kernel<2, 768>      test_layernorm_bf16_rows[768]              d 768, M 19             shape rule
-  layernorm16_mxfp8_1024_kernel<4>           test_layernorm_bf16_rows[1024]             d 1024, M 19            shape rule at the default ln_mxfp8_wide = 1
-  quant16_mxfp8_stats_1024_kernel            test_quant16_rows_and_statistics           d 1024, M 101           dedicated entry point
+  layernorm16_mxfp8_1024_kernel              test_layernorm_bf16_rows[1024]             d 1024, M 19            shape rule
   attention_kernel<NKP, false, true>         test_attention_one_head_kernel             T 1 17 50 77 128, B 2, H 2   shape rule, proved: the pooled form is refused
   attention_heads_kernel<NKP, false, 2, true> test_attention_heads_kernel               the same                option att_hpb = 2, proved: the pooled form is accepted
   attention_long_kernel<NKP, false, true>    test_attention_long_kernel                 T 130 257 288, B 2, H 2 shape rule: 128 < T <= 288, B H = 4 < 256 pairs
   attention_stream_kernel<true>              test_attention_stream_kernel               T 257, B 3, H 2         option attention_stream_min_pairs = 1 (attention_stream_ok)
   attention_tiled_kernel<false, true>        test_attention_tiled_kernel                T 289 577, B 2, H 2     dedicated entry point
-  gemm256p8_kernel<RESID_BF16, 2> tile rows  test_requantising_residual_epilogue        M 256 (200 valid), 512 (300), N 1024, K 512   dedicated entry point, xt = 2
-  ... its ragged pass (MXQ)                  the same, M 512 / 300 valid                rows 256 .. 299         shape rule: M - 256 < m_valid <= M - 128
   gemm8_kernel<BM, QGELU_MXFP8>              test_qgelu_epilogue_tile_kernel            M bm and 2 bm, N 256, K 512   bm argument 128 / 160 / 192
-  gemm256p8_kernel<QGELU_MXFP8, 0> + ragged  test_qgelu_epilogue_persistent_kernel[0]   M 512 (300 valid), N 512, K 512   bm argument 256 + m_valid
-  gemm256p8_kernel<QGELU_MXFP8, 1> + ragged  test_qgelu_epilogue_persistent_kernel[1]   the same, K 1024        dedicated entry point, xt = 1
+  gemm256p8_kernel<QGELU_MXFP8> + ragged     test_qgelu_epilogue_persistent_kernel[512]   M 512 (300 valid), N 512, K 512   bm argument 256 + m_valid
+  ... two scale groups of four K-tiles       test_qgelu_epilogue_persistent_kernel[1024]  the same, K 1024        bm argument 256 + m_valid
   operand decode, gemm8_kernel               test_operand_edges_tile_kernel             M 640 / 640 / 576, N 256, K 512   bm argument
   operand decode, gemm256p8_kernel           test_operand_edges_persistent_kernel       M 768 (768 and 556 valid)        bm argument 256 + m_valid
 
-Shapes the issue names that an entry point does not admit: none. (xt = 2 admits M = 256 as its smallest; the second case adds a
-ragged last block because that pass is a separate epilogue with its own block maxima.)
+Shapes the issue names that an entry point does not admit: none.
 """
 import contextlib
 
@@ -42,7 +38,6 @@ import mx_edge_blocks as mxb
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
 FILL = 0x5A
 
 
@@ -98,25 +93,6 @@ def _assert_mx_bytes(fo, got_q, got_e, y, what, name_of=None):
                                                                                             "\n".join(lines)))
 
 
-def _assert_sums(got, y64, n, what):
-    """got f32 [..., 2] = (sum, sumsq) against the f64 sums over the last axis of y64 (n terms each). An f32 sum of n terms in ANY order
-    is within (n - 1) u sum|x_i| of the exact sum, a sum of n rounded products within n u sum x_i^2 (u = 2^-24): n u for both, as
-    tests/test_layernorm_chain_gpu.py. That holds while nothing overflows or underflows; for the squares, which do both here:
-      * a square under the normal range loses at most 2^-126 (flushed to zero or rounded as a subnormal): + n 2^-126, absolute;
-      * where one square alone reaches 2^128 the exact answer of f32 arithmetic is +inf in any order: sumsq must BE +inf."""
-    s, a, q = y64.sum(-1), np.abs(y64).sum(-1), (y64 * y64).sum(-1)
-    got = got.astype(np.float64)
-    es, eq = np.abs(got[..., 0] - s), np.abs(got[..., 1] - q)
-    print(what, "sum err / bound max", float((es / np.maximum(n * U * a, 1e-300)).max()))
-    assert (es <= n * U * a).all(), (what, "sum", np.argwhere(es > n * U * a)[:4].tolist())
-    over = (np.abs(y64) >= 2.0 ** 64).any(-1)
-    assert q[~over].max() < 2.0 ** 100                 # (nothing in between: the finite sums are far from the f32 range)
-    assert (got[..., 1][over] == np.inf).all(), (what, "sumsq of a quarter whose squares overflow", got[..., 1][over][:4].tolist())
-    bound = n * U * q + n * 2.0 ** -126
-    assert (eq <= bound)[~over].all(), (what, "sumsq", np.argwhere((eq > bound) & ~over)[:4].tolist())
-    return int(over.sum())
-
-
 # ================================================================================================ LayerNorm -> MXFP8, gamma = 0
 def _layernorm_case(env, cat, bf16_rows, d):
     """gamma = 0, beta = one row of the catalogue layout: y = (x - mean) rstd 0 + beta = beta exactly for every finite x (a zero of
@@ -157,32 +133,9 @@ def test_layernorm_f32_rows(env, cat, d):
 
 @pytest.mark.parametrize("d", [96, 512, 768, 1024])
 def test_layernorm_bf16_rows(env, cat, d):
-    """At the default ln_mxfp8_wide (launch_layernorm_mxfp8): d = 96 the first form on bf16 rows, 512 / 768 the eight-columns form
+    """launch_layernorm_mxfp8 picks by shape: d = 96 the first form on bf16 rows, 512 / 768 the eight-columns form
     (four lanes per block; at 768 half of the second step's lanes idle), 1024 the sixteen-columns form (two lanes per block)."""
     _layernorm_case(env, cat, True, d)
-
-
-# ================================================================================================ quant16_mxfp8_stats
-def test_quant16_rows_and_statistics(env, cat):
-    """quant16_mxfp8_stats_1024_kernel on the catalogue layout itself (101 rows, four to a workgroup): bytes and scales exact;
-    (sum, sumsq) of every 256-column quarter under the any-order f32 bound (_assert_sums), no quarter left out: the 32 quarters
-    that hold the 3e38 block must report sumsq = +inf, the ones that hold the blocks under the clamp get the underflow term."""
-    torch, _lib, lib, fo = env
-    names, blocks = cat
-    rows = mxb.layout_rows(blocks, 1024)
-    M, PAD = rows.shape[0], 3
-    xb = _dev(torch, rows).to(torch.bfloat16)
-    assert np.array_equal(xb.float().cpu().numpy().view(np.uint32), rows.view(np.uint32))
-    out = torch.full((M + PAD, 1024), FILL, dtype=torch.uint8, device="cuda")
-    osc = torch.full((M + PAD, 32), FILL, dtype=torch.uint8, device="cuda")
-    st = torch.full((M + PAD, 4, 2), float("nan"), device="cuda")
-    _lib.check(lib.mmiss_dbg_quant16_mxfp8_stats(0, None, xb.data_ptr(), out.data_ptr(), osc.data_ptr(), st.data_ptr(), M, 1024))
-    torch.cuda.synchronize()
-    assert (out[M:] == FILL).all() and (osc[M:] == FILL).all() and torch.isnan(st[M:]).all()
-    _assert_mx_bytes(fo, out[:M].cpu().numpy(), fo.unpermute_scales(osc[:M].cpu().numpy(), 1024), rows, "quant16",
-                     lambda r, j: names[(r + j) % M])
-    yq = rows.astype(np.float64).reshape(M, 4, 256)
-    assert _assert_sums(st[:M].cpu().numpy(), yq, 256, "quant16 quarters") == 32
 
 
 # ================================================================================================ attention, one-hot softmax
@@ -314,58 +267,6 @@ def test_attention_tiled_kernel(env, cat, T):
 
 
 # ================================================================================================ one-hot fp8 GEMMs
-ONE = 0x38   # e4m3 code of 1.0
-
-
-def _one_hot_rows(M, K, k_of_m):
-    A8 = np.zeros((M, K), np.uint8)
-    A8[np.arange(M), k_of_m] = ONE
-    return A8
-
-
-@pytest.mark.parametrize("M,mv", [(256, 200), (512, 300)])
-def test_requantising_residual_epilogue(env, M, mv):
-    """gemm256p8_kernel<BIAS_RESID_BF16, 2> (mmiss_dbg_gemm8_xt, epi 3, xt = 2, N = 1024, K = 512: the smallest it admits). A rows
-    are one-hot (code 1.0 at column k_m = (5 m + 3) % K, every scale byte 127), wscale = 1, bias = 0, old rows = 0: the new bf16 row
-    m is column k_m of W8 decoded, exactly. The columns of W8 are blocks of e4m3 values (mx_edge_blocks.e4m3_catalogue), column k
-    holding block (k + j) % E at n-block j. M = 256 with 200 valid rows: one row of tiles whose rows >= 200 are dumped into row
-    255; M = 512 with 300: rows 256 .. 299 go through the ragged pass, which quantises with its own lane-group maxima.
-    Rows >= m_valid (include/mmiss_debug.h: padding; the dump row M - 1 excepted) keep their fill in all four outputs; the ragged
-    block's rows get no statistics."""
-    torch, _lib, lib, fo = env
-    N, K = 1024, 512
-    eb = mxb.e4m3_catalogue()
-    E = len(eb)
-    Wf = mxb.layout_rows([v for _, v in eb] * -(-K // E), N)[:K].T.copy()           # [N, K]: column k = layout row k
-    W8 = fo.e4m3_encode(Wf)
-    assert np.array_equal(fo.e4m3_decode(W8).view(np.uint32), Wf.view(np.uint32))
-    km = (5 * np.arange(M) + 3) % K
-    y = np.ascontiguousarray(Wf.T[km])                                              # [M, N]
-    A8 = _one_hot_rows(M, K, km)
-    As = fo.permute_scales(np.full((M, K // 32), 127, np.uint8))
-    out = torch.full((M, N), -7.0, dtype=torch.bfloat16, device="cuda")
-    out[:mv] = 0
-    q8 = torch.full((M, N), FILL, dtype=torch.uint8, device="cuda")
-    qs = torch.full((M, fo.scale_row_bytes(N)), FILL, dtype=torch.uint8, device="cuda")
-    st = torch.full((M, 4, 2), float("nan"), device="cuda")
-    dummy = torch.zeros((M, fo.scale_row_bytes(N)), dtype=torch.uint8, device="cuda")
-    A8d, Asd, W8d = _dev(torch, A8), _dev(torch, As), _dev(torch, W8)
-    ws, bias = torch.ones(N, device="cuda"), torch.zeros(N, device="cuda")
-    _lib.check(lib.mmiss_dbg_gemm8_xt(0, None, 3, 2, A8d.data_ptr(), Asd.data_ptr(), W8d.data_ptr(), ws.data_ptr(), bias.data_ptr(),
-                                      out.data_ptr(), dummy.data_ptr(), M, N, K, mv, None, None, None, 0.0, q8.data_ptr(), qs.data_ptr(),
-                                      st.data_ptr()))
-    torch.cuda.synchronize()
-    got = out.float().cpu().numpy()
-    bad = got[:mv] != y[:mv]
-    assert not bad.any(), ("out is not the decoded column", np.argwhere(bad)[:6].tolist())
-    name_of = lambda r, j: eb[(km[r] + j) % E][0]
-    _assert_mx_bytes(fo, q8[:mv].cpu().numpy(), fo.unpermute_scales(qs[:mv].cpu().numpy(), N), y[:mv], "xt = 2", name_of)
-    tile_rows = min(mv, M - 256) if M > 256 else mv
-    _assert_sums(st[:tile_rows].cpu().numpy(), y[:tile_rows].astype(np.float64).reshape(tile_rows, 4, 256), 256, "xt = 2 quarters")
-    assert torch.isnan(st[tile_rows:M - 1]).all(), "statistics of ragged or padding rows were written"
-    assert (out[mv:M - 1] == -7.0).all() and (q8[mv:M - 1] == FILL).all() and (qs[mv:M - 1] == FILL).all(), "padding rows were written"
-
-
 # ------------------------------------------------------------------------------------------------ QuickGELU -> MXFP8 (64-column scales)
 def _assert_qgelu_bytes(fo, got_q, got_e, pre, what):
     """The banded rule. Reference: float64 QuickGELU of the exactly known pre-activation, then mx_quantize(., 64). Scale bytes equal
@@ -410,38 +311,28 @@ def test_qgelu_epilogue_tile_kernel(env, bm, blocks_m):
     _assert_qgelu_bytes(fo, out[:M].cpu().numpy(), gs[:M][:, used], pre, "gemm8 bm=%d M=%d" % (bm, M))
 
 
-@pytest.mark.parametrize("xt", [0, 1])
-def test_qgelu_epilogue_persistent_kernel(env, xt):
-    """gemm256p8_kernel<QGELU_MXFP8, xt>, M = 512 with 300 valid rows, N = 512: rows 0 .. 255 leave through the tile epilogue, rows
+@pytest.mark.parametrize("K", [512, 1024])
+def test_qgelu_epilogue_persistent_kernel(env, K):
+    """gemm256p8_kernel<QGELU_MXFP8>, M = 512 with 300 valid rows, N = 512: rows 0 .. 255 leave through the tile epilogue, rows
     256 .. 299 through the ragged pass (its own maxima over lane groups), rows 300 .. 510 are padding and keep their fill (row
-    M - 1 is the dump row). xt = 0: K = 512. xt = 1 (K = 1024, the LayerNorm folded in): the statistics are (0, 256) per quarter
-    and x16 alternates +1 / -1 (the ragged pass takes its rows' statistics from x16), eps = 0: mean = 0 and rstd = 1 / sqrt(1) = 1,
-    so y = (acc - 0 c) 1 + b' is the same exactly known value, whatever c16 holds."""
+    M - 1 is the dump row). K = 512 is one scale group of four K-tiles, K = 1024 two: the scale ring changes parity inside the
+    tile, and the ragged pass reads a second scale dword per row."""
     torch, _lib, lib, fo = env
-    M, mv, N, K = 512, 300, 512, 1024 if xt else 512
+    M, mv, N = 512, 300, 512
     A8, As, W8, bias, pre = mxb.qgelu_case(M, N, K)
     srb = fo.scale_row_bytes(N)
     out = torch.full((M, N), FILL, dtype=torch.uint8, device="cuda")
     osc = torch.full((M, srb), FILL, dtype=torch.uint8, device="cuda")
     A8d, Asd, W8d, bd = _dev(torch, A8), _dev(torch, fo.permute_scales(As)), _dev(torch, W8), _dev(torch, bias)
     ws = torch.ones(N, device="cuda")
-    if xt:
-        g = torch.Generator(device="cuda").manual_seed(5)
-        c16 = torch.randn(N, device="cuda", generator=g).to(torch.float16)
-        stats = torch.tensor([0.0, 256.0], device="cuda").repeat(M, 4, 1).contiguous()
-        x16 = torch.tensor([1.0, -1.0], device="cuda").repeat(M, K // 2).to(torch.bfloat16).contiguous()
-        _lib.check(lib.mmiss_dbg_gemm8_xt(0, None, 1, 1, A8d.data_ptr(), Asd.data_ptr(), W8d.data_ptr(), ws.data_ptr(), bd.data_ptr(),
-                                          out.data_ptr(), osc.data_ptr(), M, N, K, mv, c16.data_ptr(), stats.data_ptr(), x16.data_ptr(), 0.0,
-                                          None, None, None))
-    else:
-        _lib.check(lib.mmiss_dbg_gemm8(0, None, 1, 256 + mv, A8d.data_ptr(), Asd.data_ptr(), W8d.data_ptr(), ws.data_ptr(), bd.data_ptr(),
-                                       out.data_ptr(), osc.data_ptr(), M, N, K))
+    _lib.check(lib.mmiss_dbg_gemm8(0, None, 1, 256 + mv, A8d.data_ptr(), Asd.data_ptr(), W8d.data_ptr(), ws.data_ptr(), bd.data_ptr(),
+                                   out.data_ptr(), osc.data_ptr(), M, N, K))
     torch.cuda.synchronize()
     assert (out[mv:M - 1] == FILL).all() and (osc[mv:M - 1] == FILL).all(), "padding rows were written"
     used = fo.scale_offset(np.arange(N // 32))
     assert srb == used.size                                                     # (N = 512: every scale byte of a row is owned)
     for lo, hi, part in ((0, 256, "tile rows"), (256, mv, "ragged rows")):
-        _assert_qgelu_bytes(fo, out[lo:hi].cpu().numpy(), osc[lo:hi].cpu().numpy()[:, used], pre[lo:hi], "gemm256p8 xt=%d %s" % (xt, part))
+        _assert_qgelu_bytes(fo, out[lo:hi].cpu().numpy(), osc[lo:hi].cpu().numpy()[:, used], pre[lo:hi], "gemm256p8 K=%d %s" % (K, part))
 
 
 # ------------------------------------------------------------------------------------------------ operand edges, exact

@@ -6,7 +6,9 @@ compiler's resource figures (csrc/*.resources.txt) of an OLD and a NEW build.
     usage: python tools/codeobj_diff.py OLD/csrc NEW/csrc      (both built by `make -C .../csrc`; no GPU needed)
 
 Kernels are matched by demangled name through RENAMES (old -> new, for kernels whose template or argument lists changed);
-the match must be a bijection over all kernels of an object. ONE normalisation: the 32-bit literal of the s_add_u32 behind
+the match must be a bijection over all kernels of an object. Padding behind a kernel's last instruction (zeros, or s_nop behind
+an s_endpgm / s_branch) is not part of it. Kernels of the OLD build whose demangled name matches a pattern of
+REMOVED are reported as "removed, expected" and not counted (for a refactor that retires kernels). ONE normalisation: the 32-bit literal of the s_add_u32 behind
 an s_getpc_b64 is a PC-relative distance to read-only data and moves when anything earlier in the code object changes size;
 kernels that needed it are listed. For a kernel whose instructions differ, the opcodes whose counts differ follow
 (before -> after): equal counts say the same instructions in another order or with other registers. Exit status 0 = identical."""
@@ -22,6 +24,13 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # (pattern on the OLD demangled name, replacement): for a refactor that changes kernels' template or argument lists. Empty
 # between such refactors: a stale rule maps kernels that kept their names onto names that do not exist.
 RENAMES = []
+
+# patterns (re.search on the OLD demangled name) of kernels a refactor retires on purpose. Empty between such refactors, like RENAMES.
+REMOVED = []
+
+
+def removed(name):
+    return any(re.search(pat, name) for pat in REMOVED)
 
 
 def rename(name):
@@ -49,6 +58,12 @@ def disassembly(csrc, obj):
             cur = kernels.setdefault(m.group(1), [])
         elif cur is not None and line.startswith("\t") and line.strip() != "...":   # ("...": zero padding behind a kernel's end)
             cur.append(line.split("//")[0].strip())
+    for ins in kernels.values():   # alignment padding behind a kernel's end comes as s_nop as well: it moves with the kernel's place in the object
+        n = len(ins)
+        while n and ins[n - 1].startswith("s_nop"):
+            n -= 1
+        if n and ins[n - 1].split()[0] in ("s_endpgm", "s_branch"):
+            del ins[n:]
     return kernels, names
 
 
@@ -87,7 +102,10 @@ def main():
         (old, old_names), (new, new_names) = disassembly(old_dir, obj), disassembly(new_dir, obj)
         old_res, new_res = resources(old_dir, obj, old_names), resources(new_dir, obj, new_names)
         mapped = {}
+        gone = sorted(k for k in old if removed(k) and rename(k) not in new)
         for k in old:
+            if k in gone:
+                continue
             assert rename(k) not in mapped, ("two old kernels map to one name", k)
             mapped[rename(k)] = k
         only_old = sorted(set(mapped) - set(new))
@@ -110,6 +128,8 @@ def main():
               f"{nres} with resource figures")
         for k in masked:
             print(f"  identical after masking PC-relative literals: {k}")
+        for k in gone:
+            print(f"  removed, expected: {k}")
         for k in only_old:
             print(f"  ONLY BEFORE: {mapped[k]}")
         for k in only_new:
