@@ -216,6 +216,18 @@ int mmiss_dbg_index_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int32_t f
  *                [7] qtiles
  *   last chunk:  [8] .. [14] the same seven fields */
 int mmiss_dbg_index_radius_plan(struct mmiss_index* ix, int32_t Q, int32_t filtered, int32_t* out);
+/* The index's row store as it lies on the device: rows [row0, row0 + n) with 0 <= row0, row0 + n <= capacity (rows behind count
+ * included; a range past the capacity is refused with MMISS_ERR_ARG). All outputs are HOST buffers and any may be NULL:
+ * rows_out n * dim * (4 | 2 | 1) bytes, the raw f32 / f16 / e4m3 elements; inv_out f32 [n], the inverse norms of fp8 rows (left
+ * untouched for f32 / f16 rows); labels_out int64 [n] and tags_out uint64 [n], the DEVICE copies of labels and tags. Reads
+ * only: refuses an open query like every other entry, waits for the handle's stream first and returns drained. */
+int mmiss_dbg_index_read_rows(struct mmiss_index* ix, int64_t row0, int64_t n, void* rows_out, float* inv_out, int64_t* labels_out,
+                              uint64_t* tags_out);
+/* The query preparation of a query call, alone: queries f32 [Q, dim] (host or device) go through the call's own upload and
+ * prep_queries_kernel launch, and the handle's scratch comes back to HOST buffers (any may be NULL): qn_out f32 [Q, dim] the
+ * normalised queries, qs_out [round_up(Q, 256), dim] the first pass's operand (f32 for f32 rows, f16 for f16 / fp8 rows; pad rows
+ * included), eps_out f32 [Q] the guard's bound per query. Refuses an open query; returns drained. */
+int mmiss_dbg_index_prep_queries(struct mmiss_index* ix, const float* queries, int32_t Q, float* qn_out, void* qs_out, float* eps_out);
 
 
 /* The path one chunk of an encode call would take on the handle as it stands and under the options as they stand: B items

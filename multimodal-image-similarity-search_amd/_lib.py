@@ -146,6 +146,8 @@ SIGNATURES = {
     "mmiss_dbg_resize_crop_variant": (_I, [_I64, _I32]),
     "mmiss_dbg_index_plan": (_I, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_radius_plan": (_I, [_P, _I32, _I32, C.POINTER(_I32)]),
+    "mmiss_dbg_index_read_rows": (_I, [_P, _I64, _I64, _P, _P, _P, _P]),
+    "mmiss_dbg_index_prep_queries": (_I, [_P, _P, _I32, _P, _P, _P]),
     "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
@@ -272,6 +274,38 @@ def index_radius_plan(handle, Q: int, filtered: bool = False) -> dict:
     check(load().mmiss_dbg_index_radius_plan(handle, int(Q), 1 if filtered else 0, out))
     v = [int(x) for x in out]
     return {"chunks": v[0], "first": dict(zip(RADIUS_PLAN_FIELDS, v[1:8])), "last": dict(zip(RADIUS_PLAN_FIELDS, v[8:15]))}
+
+
+_INDEX_ELT = {MMISS_F32: "float32", MMISS_F16: "float16", MMISS_F8: "uint8"}
+
+
+def index_read_rows(handle, dim: int, dtype: int, row0: int, n: int) -> dict:
+    """mmiss_dbg_index_read_rows as numpy arrays: {"rows": [n, dim] float32 / float16 / uint8 (e4m3 codes), "inv": float32 [n] (fp8
+    rows; None otherwise), "labels": int64 [n], "tags": uint64 [n]}, the device buffers of rows [row0, row0 + n) as they stand
+    (row0 + n <= capacity; rows behind count included)."""
+    import numpy as np
+
+    rows = np.empty((n, dim), dtype=_INDEX_ELT[dtype])
+    inv = np.empty(n, dtype=np.float32) if dtype == MMISS_F8 else None
+    labels = np.empty(n, dtype=np.int64)
+    tags = np.empty(n, dtype=np.uint64)
+    check(load().mmiss_dbg_index_read_rows(handle, int(row0), int(n), rows.ctypes.data, None if inv is None else inv.ctypes.data,
+                                           labels.ctypes.data, tags.ctypes.data))
+    return {"rows": rows, "inv": inv, "labels": labels, "tags": tags}
+
+
+def index_prep_queries(handle, dim: int, dtype: int, queries) -> tuple:
+    """mmiss_dbg_index_prep_queries -> (qn float32 [Q, dim], qs [round_up(Q, 256), dim] float32 for f32 rows / float16 otherwise,
+    eps_q float32 [Q]): what the query preparation of a query call with these queries (numpy, or a CUDA tensor on the handle's
+    current stream) leaves in the handle's scratch."""
+    import numpy as np
+
+    Q = int(queries.shape[0])
+    qn = np.empty((Q, dim), dtype=np.float32)
+    qs = np.empty(((Q + 255) // 256 * 256, dim), dtype=np.float32 if dtype == MMISS_F32 else np.float16)
+    eps = np.empty(Q, dtype=np.float32)
+    check(load().mmiss_dbg_index_prep_queries(handle, ptr(queries), Q, qn.ctypes.data, qs.ctypes.data, eps.ctypes.data))
+    return qn, qs, eps
 
 
 ENCODER_PLAN_FIELDS = ("fold", "fold_final", "fp8", "out8", "resid16", "sfold", "prune", "embed", "qkv", "qkv_bm", "out", "out_bm",

@@ -1625,6 +1625,43 @@ extern "C" int mmiss_dbg_index_plan(mmiss_index* ix, int32_t Q, int32_t k, int32
     return MMISS_OK;
 }
 
+// mmiss_debug.h: the row store as it lies on the device (rows behind count included), to host buffers. Reads only.
+extern "C" int mmiss_dbg_index_read_rows(mmiss_index* ix, int64_t row0, int64_t n, void* rows_out, float* inv_out, int64_t* labels_out,
+                                         uint64_t* tags_out) {
+    if (!ix) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_read_rows: null index");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, "mmiss_dbg_index_read_rows");
+    if (row0 < 0 || n < 0 || row0 > ix->capacity || n > ix->capacity - row0)
+        MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_read_rows: rows [%lld, %lld + %lld) of a capacity of %lld", (long long)row0,
+                (long long)row0, (long long)n, (long long)ix->capacity);
+    if (n == 0) return MMISS_OK;
+    MM_TRY(mmiss_use_device(ix->device));
+    MM_HIP(hipStreamSynchronize(ix->stream()));   // (what an earlier call left queued on a caller's stream)
+    const size_t row_bytes = (size_t)ix->dim * ix->elt;
+    if (rows_out) MM_HIP(hipMemcpy(rows_out, ix->rows.as<char>() + (size_t)row0 * row_bytes, (size_t)n * row_bytes, hipMemcpyDeviceToHost));
+    if (inv_out && ix->dtype == MMISS_F8) MM_HIP(hipMemcpy(inv_out, ix->inv.as<float>() + row0, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (labels_out) MM_HIP(hipMemcpy(labels_out, ix->labels_d.as<int64_t>() + row0, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (tags_out) MM_HIP(hipMemcpy(tags_out, ix->tags.as<uint64_t>() + row0, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: upload_queries as a query call runs it, and what it left in qn / qs / eps_q, to host buffers.
+extern "C" int mmiss_dbg_index_prep_queries(mmiss_index* ix, const float* queries, int32_t Q, float* qn_out, void* qs_out, float* eps_out) {
+    if (!ix || !queries) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_prep_queries: null argument");
+    if (Q <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_prep_queries: Q=%d", Q);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, "mmiss_dbg_index_prep_queries");
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    MM_TRY(upload_queries(ix, st, queries, Q));
+    MM_HIP(hipStreamSynchronize(st));
+    const size_t D = (size_t)ix->dim, Qpad = (size_t)round_up(Q, 256);
+    if (qn_out) MM_HIP(hipMemcpy(qn_out, ix->qn.p, (size_t)Q * D * 4, hipMemcpyDeviceToHost));
+    if (qs_out) MM_HIP(hipMemcpy(qs_out, ix->qs.p, Qpad * D * ix->qelt(), hipMemcpyDeviceToHost));
+    if (eps_out) MM_HIP(hipMemcpy(eps_out, ix->eps_q.p, (size_t)Q * 4, hipMemcpyDeviceToHost));
+    return MMISS_OK;
+}
+
 // ================================================================================================ persistence
 namespace {
 struct IdxHeader {
@@ -1694,6 +1731,9 @@ extern "C" int mmiss_index_load(mmiss_index* ix, const char* path) {
     MM_NO_PENDING(ix, "mmiss_index_load");
     MM_TRY(mmiss_use_device(ix->device));
     hipStream_t st = ix->stream();
+    // the rows are overwritten by blocking copies that do not run on `st`: a query with device outputs may still be queued on a
+    // caller's stream (async_pending) and reads them
+    MM_HIP(hipStreamSynchronize(st));
     FILE* f = fopen(path, "rb");
     if (!f) MM_FAIL(MMISS_ERR_IO, "cannot open %s", path);
     IdxHeader h{};
