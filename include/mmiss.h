@@ -313,6 +313,8 @@ int mmiss_index_guard_stats(mmiss_index* idx, int64_t out[4]);
  * pass over the index and one host selection per such query. out[5] = rows the threshold passes collected and re-ranked.
  * out[6] = queries served by the radius calls (below), out[7] = passes over the index those cost (1 per chunk on the score GEMM,
  * one per 64 queries of a chunk on the streaming scan). Radius calls leave out[0..3] alone and add to out[4] and out[5].
+ * The membership / tagging calls (below) count like radius calls: out[6] += their probes, out[7] += their passes over the index,
+ * out[5] += the (row, probe) pairs they resolved canonically, out[4] += the probes that took the per-probe canonical route.
  */
 int mmiss_index_guard_stats_ex(mmiss_index* idx, int64_t out[8]);
 
@@ -393,6 +395,46 @@ int mmiss_index_query_radius(mmiss_index* idx, const float* queries, int32_t Q, 
 int mmiss_index_query_radius_by_label(mmiss_index* idx, const int64_t* labels, int64_t n, float max_dist, int32_t cap,
                                       int32_t later_only, int64_t* out_labels, float* out_dist, int32_t* out_count,
                                       int64_t* out_total);
+
+/* ---------------------------------------------------------------- membership / tagging --------- */
+/*
+ * The DENSE form of the radius question: for P probes (1 <= P <= 64; probe p = query vector queries[p] and radius max_dist[p])
+ * the exact membership of EVERY row, one bit per (row, probe), in one streaming pass over the index per 16 / 32 / 64 probes
+ * (as many as fit the LDS at the index's dim and dtype). Row r is a member of probe p iff the row has a direction, the probe's
+ * query has a direction, and d(q_p, r) <= max_dist[p] compared as floats — the member definition of mmiss_index_query_radius
+ * (no masks), so for any cap large enough the member set IS the label set that call reports. No special radii: a negative one
+ * is legal, one >= 2 admits every row that has a direction; a NaN radius is MMISS_ERR_ARG. There is no cap on the members: the
+ * answer is a bit per row, not a list.
+ * queries: float32 [P, dim]; max_dist: float32 [P]; out_members: int64 [P], may be null, the exact member count per probe. Each
+ * of them host or device memory, independently.
+ * Exact: approximate matrix-core scores decide the pairs whose score clears (1 - R_p) + eps_p (member) or stays below
+ * (1 - R_p) - eps_p (no member), eps_p being the exactness guard's bound; the borderline pairs in between are re-scored in the
+ * canonical arithmetic; a probe with more than 8192 borderline rows (mass duplicates at exactly its radius) gets the canonical
+ * distance of every row, on the device.
+ * Both calls lock the handle, run on its current stream, return with their work finished, fail with MMISS_ERR_STATE while a
+ * _begin query is open, check every argument before they write anything, and on an empty index write nothing but zeros to
+ * out_members. Accounting (mmiss_index_guard_stats_ex): out[6] += P, out[7] += passes over the index, out[5] += the (row,
+ * probe) pairs resolved canonically (every row of a probe that took the per-probe canonical route), out[4] += the probes that
+ * took that route; out[0..3] stay untouched, as for radius calls.
+ * replaces the reference's filter pass over the whole collection — add_filter -> process_filter_on_all_images
+ * (backend/app/main.py:939-1056) asks a yes/no model about every stored image and stores the answers the searches filter on
+ * (main.py:202-222) — for the question CLIP itself answers: "is this image within distance R of this text / image embedding".
+ *
+ * mmiss_index_membership: out_words uint64 [count] (host or device) in row order — the order of mmiss_index_labels —, bit p of
+ * out_words[r] = row r is a member of probe p, bits >= P zero. cap_rows = the rows out_words has room for; cap_rows < count is
+ * MMISS_ERR_ARG. Read-only on the index.
+ */
+int mmiss_index_membership(mmiss_index* idx, const float* queries, int32_t P, const float* max_dist, uint64_t* out_words,
+                           int64_t cap_rows, int64_t* out_members);
+/*
+ * mmiss_index_tag_by_radius: the memberships written straight into the rows' tag words. bits: HOST int32 [P], distinct, each in
+ * 0 .. 63 (otherwise MMISS_ERR_ARG); with M = the OR of 1 << bits[p], every row's tag becomes
+ *     tags[r] = (tags[r] & ~M) | sum over p of member(r, p) << bits[p]
+ * — the named bits are overwritten (set or cleared), every other bit keeps its value. The host copy of the tags that
+ * mmiss_index_get_tags, mmiss_index_remove and the exhaustive passes read is up to date when the call returns.
+ */
+int mmiss_index_tag_by_radius(mmiss_index* idx, const float* queries, int32_t P, const float* max_dist, const int32_t* bits,
+                              int64_t* out_members);
 
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*

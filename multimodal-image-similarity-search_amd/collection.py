@@ -424,6 +424,40 @@ class FlatCollection:
                 out["embeddings"] = [self._index.get(np.asarray(ls, dtype=np.int64)) for ls in rows]
             return out
 
+    def add_similarity_filter(self, name: str, embedding, max_distance: float) -> int:
+        """A yes/no filter answered by the embedding arithmetic itself: every stored row gets "yes" under `name` in its
+        filter_results_json when it lies within cosine distance max_distance of `embedding` (exactly: the member definition of
+        FlatIndex.query_radius), "no" otherwise -> the number of "yes" rows. The CLIP form of the reference's add_filter ->
+        process_filter_on_all_images (backend/app/main.py:939-1056), which asks a yes/no model about every image and stores
+        the answers the searches filter on (main.py:202-222).
+        ONE FlatIndex.membership call decides all rows (the only GPU work); writing the answers is a walk over the metadata of
+        every row on the host, proportional to count(), through this collection's own update(): journaled, and the rows' tag
+        words are re-derived from the metadata at the next filtered query — the metadata stays the source of truth for them, so
+        query(filters=[name]), api.apply_filters, persistence and more than 64 filter names work as for any other answer.
+        Answers other filters left in filter_results_json are kept. Rows added later have no answer under `name` (as the
+        reference's filters until it processes them); running the filter again refreshes every row."""
+        name = str(name)
+        q = self._embeddings_array(embedding)
+        if q.shape[0] != 1:
+            raise ValueError("add_similarity_filter takes one embedding")
+        with self._lock:
+            if not self._ids or self._index is None:
+                return 0
+            if q.shape[1] != self._dim:
+                raise ValueError(f"embedding dimension {q.shape[1]} does not match the collection's {self._dim}")
+            words, members = self._index.membership(q, float(max_distance))
+            words = np.asarray(words.cpu() if hasattr(words, "cpu") else words)
+            if words.shape[0] != len(self._labels):
+                raise RuntimeError("index and collection differ in row count")
+            yes = (words.astype(np.uint64) & np.uint64(1)).astype(bool)   # row order == label order == self._labels
+            metas = []
+            for lab, y in zip(self._labels, yes.tolist()):
+                answers = dict(filter_answers(self._meta.get(lab)))
+                answers[name] = "yes" if y else "no"
+                metas.append({"filter_results_json": json.dumps(answers)})
+            self.update(ids=list(self._ids), metadatas=metas)
+            return int(yes.sum())
+
     def near_duplicates(self, max_distance: float, cap_per_row: int = 64) -> List[tuple]:
         """Every pair of stored rows within cosine distance max_distance, each once (FlatIndex.near_duplicates) ->
         [(id_a, id_b, distance)], id_a the row added earlier, ordered by (id_a's position, distance, id_b's position); a row

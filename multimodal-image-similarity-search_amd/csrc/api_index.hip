@@ -3,6 +3,7 @@
 #include "common.h"
 #include <queue>
 #include "retrieval_kernels.h"
+#include "membership_kernels.h"
 #include "gemm_bf16_256.h"
 #include "gemm_strip_p256.h"
 #include <algorithm>
@@ -58,6 +59,9 @@ struct mmiss_index {
     // passes no out_total, the totals; the queries served and the passes over the index they cost
     DevBuf rad, row_min, rtotal;
     int64_t stat_radius_queries = 0, stat_radius_pages = 0;
+    // membership / tagging (mmiss_index_membership, mmiss_index_tag_by_radius): the words when the caller's are host memory or
+    // the call merges them into the tags; radii, the two thresholds per probe and the tag form's bits ([64] each); the counts
+    DevBuf mem_words, mem_thr, mem_cnt;
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -1556,6 +1560,231 @@ extern "C" int mmiss_index_query_radius_by_label(mmiss_index* ix, const int64_t*
         if (later_only) row_begin = *std::min_element(rows.begin() + q0, rows.begin() + q0 + Qc);
         MM_TRY(radius_chunk(ix, st, c, ix->stage.as<float>(), q0, Qc, row_begin));
     }
+    return MMISS_OK;
+}
+
+// ================================================================================================ membership / tagging
+// The DENSE form of the radius question: for P <= 64 probes (a query vector and a radius each) the exact membership of every row,
+// one bit per (row, probe) — the member definition of mmiss_index_query_radius, with no cap on the members, because the answer
+// is a bit per row and not a list. membership_kernels.h has the kernels and the two-sided bound; the three routes:
+//   scan      member_scan_kernel decides every pair whose approximate score clears hi_p = (1 - R_p) + eps_p (member) or stays
+//             below lo_p = (1 - R_p) - eps_p (no member); one pass over the index per 16 * nqt probes;
+//   resolve   the borderline pairs in between, listed per probe (ix->swp_cnt / ix->swp_list, SWEEP_CAP rows per probe), get their
+//             canonical distance (member_resolve_kernel);
+//   overflow  a probe with more than SWEEP_CAP borderline rows: canonical_scan_kernel + member_from_dist_kernel, on the device
+//             (radius_exhaustive's host selection has nothing to select here).
+namespace {
+
+struct MemberPlan { int nqt, lds, slabs, tiles_per_block, passes; };
+
+// The probe tile of a membership pass: the narrowest of 16 / 32 / 64 probes that holds all P (a wider one would only multiply the
+// MFMA work of a pass that is bound by reading the rows), halved while its staged operands do not fit the LDS budget: 64 probes
+// fit at dim 512 / 768 / 1024 in f16 or fp8 and at dim 512 in f32, 16 at dim 3968 (and f32 at 1920); more probes than the tile
+// holds make several passes.
+MemberPlan plan_membership(int D, int qelt, int P, int64_t N) {
+    MemberPlan p{};
+    p.nqt = P > 32 ? 4 : P > 16 ? 2 : 1;
+    while (p.nqt > 1 && sweep_scan_lds(D, qelt, p.nqt) > SCAN_LDS_LIMIT) p.nqt >>= 1;
+    p.lds = sweep_scan_lds(D, qelt, p.nqt);
+    p.passes = (P + 16 * p.nqt - 1) / (16 * p.nqt);
+    const int64_t ntiles = (N + 15) / 16;
+    const int per_cu = std::max(1, std::min(8, SCAN_LDS_LIMIT / p.lds));
+    const int64_t target = (int64_t)256 * per_cu;
+    const int64_t tpb = std::max<int64_t>(4, (((ntiles + target - 1) / target) + 3) / 4 * 4);
+    p.tiles_per_block = (int)tpb;
+    p.slabs = (int)((ntiles + tpb - 1) / tpb);
+    return p;
+}
+
+typedef void (*MemberKernel)(MemberScanArgs);
+
+// Bit p of d_words[r] (device, [count]) = row r is a member of probe p, bits >= P zero. rad: [P] HOST radii (no NaN), left on
+// the device in ix->mem_thr ([64] floats). count > 0. Waits once, for the lists' lengths (launching the resolve blind, with a
+// fixed grid, and delivering before the lengths are known saved nothing measurable: profiles/membership.txt); what it queues
+// behind that wait is left to the caller's final synchronisation.
+int membership_core(mmiss_index* ix, hipStream_t st, const float* queries, int P, const float* rad, uint64_t* d_words) {
+    const int D = ix->dim;
+    const int64_t N = ix->count;
+    MM_TRY(upload_queries(ix, st, queries, P));   // qn, qs (rows behind P zero, 256 of them at least), eps_q
+    MM_TRY(ix->mem_thr.ensure((size_t)4 * 64 * 4));
+    float* const d_rad = ix->mem_thr.as<float>();
+    float* const d_lo = d_rad + 64;
+    float* const d_hi = d_rad + 128;
+    MM_HIP(hipMemcpyAsync(d_rad, rad, (size_t)P * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(member_thr_kernel, dim3(1), dim3(64), 0, st, (const float*)d_rad, (const float*)ix->eps_q.as<float>(), d_lo, d_hi, P, 64);
+    MM_HIP(hipGetLastError());
+    const size_t cnt_bytes = (size_t)64 * MEMBER_CNT_STRIDE * 4;   // one counter per probe, 256 bytes apart
+    MM_TRY(ix->swp_cnt.ensure(cnt_bytes));
+    MM_TRY(ix->swp_list.ensure((size_t)64 * SWEEP_CAP * 4));
+    MM_TRY(ix->swp_pin.ensure(cnt_bytes, st));
+    MM_HIP(hipMemsetAsync(ix->swp_cnt.p, 0, cnt_bytes, st));
+    const MemberPlan mp = plan_membership(D, ix->qelt(), P, N);
+    if (mp.lds > SCAN_LDS_LIMIT)
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "membership: a 16-probe block of dim %d does not fit the LDS (%d bytes)", D, mp.lds);
+    const MemberKernel kern = with_storage(ix->dtype, [&](auto s) -> MemberKernel {
+        using T = typename decltype(s)::T;
+        if (mp.nqt == 4) return &member_scan_kernel<T, 4>;
+        if (mp.nqt == 2) return &member_scan_kernel<T, 2>;
+        return &member_scan_kernel<T, 1>;
+    });
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), mp.lds));
+    const int NQ = 16 * mp.nqt;
+    for (int j = 0; j < mp.passes; ++j) {
+        MemberScanArgs a{};
+        a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>();
+        a.qs = ix->qs.as<char>() + (size_t)j * NQ * D * ix->qelt();
+        a.lo = d_lo + j * NQ; a.hi = d_hi + j * NQ;
+        a.tiles_per_block = mp.tiles_per_block;
+        a.words = d_words; a.bit0 = j * NQ; a.first = j == 0;
+        a.bcnt = ix->swp_cnt.as<int32_t>() + (size_t)j * NQ * MEMBER_CNT_STRIDE;
+        a.blist = ix->swp_list.as<int32_t>() + (size_t)j * NQ * SWEEP_CAP;
+        a.bcap = SWEEP_CAP;
+        const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
+        MM_PROF(f16 ? "member_scan_f16" : f8 ? "member_scan_f8" : "member_scan_f32", st, 2.0 * NQ * (double)N * D, (double)N * (D * ix->elt + 8));
+        hipLaunchKernelGGL(kern, dim3(mp.slabs), dim3(256), mp.lds, st, a);
+        MM_HIP(hipGetLastError());
+    }
+    // the lists' lengths decide the rest
+    MM_HIP(hipMemcpyAsync(ix->swp_pin.p, ix->swp_cnt.p, cnt_bytes, hipMemcpyDeviceToHost, st));
+    MM_HIP(hipStreamSynchronize(st));
+    const int32_t* cnt = ix->swp_pin.as<int32_t>();   // (one per probe, MEMBER_CNT_STRIDE apart)
+    std::vector<int> over;
+    int64_t resolved = 0;
+    int maxc = 0;
+    for (int p = 0; p < P; ++p) {
+        const int32_t c = cnt[p * MEMBER_CNT_STRIDE];
+        if (c > SWEEP_CAP) over.push_back(p);
+        else { resolved += c; maxc = std::max(maxc, (int)c); }
+    }
+    if (maxc > 0) {
+        MM_PROF("member_resolve", st, 2.0 * resolved * D, (double)resolved * D * ix->elt);
+        const int grid = std::min(512, (maxc + 15) / 16);
+        with_storage(ix->dtype, [&](auto s) {
+            using T = typename decltype(s)::T;
+            hipLaunchKernelGGL(member_resolve_kernel<T>, dim3(grid, P), dim3(256), 0, st, (const void*)ix->rows.p, D, (const float*)ix->qn.as<float>(),
+                               (const float*)ix->inv.as<float>(), (const float*)d_rad, (const int32_t*)ix->swp_cnt.as<int32_t>(),
+                               (const int32_t*)ix->swp_list.as<int32_t>(), SWEEP_CAP, d_words);
+        });
+        MM_HIP(hipGetLastError());
+    }
+    for (int p : over) {   // more than SWEEP_CAP rows within eps of the probe's threshold: every row's canonical distance decides
+        MM_TRY(ix->dist_all.ensure((size_t)N * 4));
+        MM_PROF("canonical_scan", st, 2.0 * N * D, (double)N * D * ix->elt);
+        const int grid = (int)std::min<int64_t>(8192, (N + 15) / 16);
+        with_storage(ix->dtype, [&](auto s) {
+            hipLaunchKernelGGL(canonical_scan_kernel<typename decltype(s)::T>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
+                               ix->qn.as<float>() + (size_t)p * D, ix->dist_all.as<float>(), (const float*)ix->inv.as<float>());
+        });
+        MM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(member_from_dist_kernel, dim3((int)std::min<int64_t>(4096, (N + 255) / 256)), dim3(256), 0, st,
+                           (const float*)ix->dist_all.as<float>(), N, (const float*)d_rad, p, d_words);
+        MM_HIP(hipGetLastError());
+    }
+    ix->stat_radius_queries += P;
+    ix->stat_radius_pages += mp.passes;
+    ix->stat_swept_rows += resolved + (int64_t)over.size() * N;
+    ix->stat_exhaustive += (int64_t)over.size();
+    return MMISS_OK;
+}
+
+// the members of every probe, counted from the words into ix->mem_cnt ([64] u64)
+int membership_counts(mmiss_index* ix, hipStream_t st, const uint64_t* d_words) {
+    MM_TRY(ix->mem_cnt.ensure((size_t)64 * 8));
+    MM_HIP(hipMemsetAsync(ix->mem_cnt.p, 0, (size_t)64 * 8, st));
+    hipLaunchKernelGGL(member_count_kernel, dim3((int)std::min<int64_t>(1024, (ix->count + 255) / 256)), dim3(256), 0, st, d_words, ix->count,
+                       ix->mem_cnt.as<unsigned long long>());
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+// out_members (host or device, may be null) <- the first P counts of ix->mem_cnt, or zeros (an empty index)
+int deliver_members(mmiss_index* ix, hipStream_t st, int P, int64_t* out_members, bool zeros) {
+    if (!out_members) return MMISS_OK;
+    const bool dev = mmiss_is_device_ptr(out_members);
+    if (zeros) {
+        if (dev) { MM_HIP(hipMemsetAsync(out_members, 0, (size_t)P * 8, st)); MM_HIP(hipStreamSynchronize(st)); }
+        else memset(out_members, 0, (size_t)P * 8);
+        return MMISS_OK;
+    }
+    MM_HIP(hipMemcpyAsync(out_members, ix->mem_cnt.p, (size_t)P * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    return MMISS_OK;
+}
+
+// what both entry points check before they touch anything; on success `rad` holds the P radii on the host
+int membership_check(mmiss_index* ix, const char* who, int32_t P, const float* max_dist, hipStream_t* st, std::vector<float>& rad) {
+    MM_NO_PENDING(ix, who);
+    MM_TRY(mmiss_use_device(ix->device));
+    *st = ix->stream();
+    MM_TRY(fetch_f32(max_dist, P, rad, *st));
+    for (int p = 0; p < P; ++p)
+        if (rad[(size_t)p] != rad[(size_t)p]) MM_FAIL(MMISS_ERR_ARG, "%s: max_dist[%d] is NaN", who, p);
+    return MMISS_OK;
+}
+
+}  // namespace
+
+extern "C" int mmiss_index_membership(mmiss_index* ix, const float* queries, int32_t P, const float* max_dist, uint64_t* out_words,
+                                      int64_t cap_rows, int64_t* out_members) {
+    const char* who = "mmiss_index_membership";
+    if (!ix) MM_FAIL(MMISS_ERR_ARG, "%s: null index", who);
+    if (P < 1 || P > 64) MM_FAIL(MMISS_ERR_ARG, "%s: P = %d (1 .. 64 probes per call)", who, P);
+    if (!queries || !max_dist) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (cap_rows < ix->count) MM_FAIL(MMISS_ERR_ARG, "%s: cap_rows = %lld for %lld rows", who, (long long)cap_rows, (long long)ix->count);
+    if (ix->count > 0 && !out_words) MM_FAIL(MMISS_ERR_ARG, "%s: null out_words", who);
+    hipStream_t st = nullptr;
+    std::vector<float> rad;
+    MM_TRY(membership_check(ix, who, P, max_dist, &st, rad));
+    const int64_t N = ix->count;
+    if (N == 0) {   // nothing to write but the counts
+        ix->stat_radius_queries += P;
+        return deliver_members(ix, st, P, out_members, true);
+    }
+    const bool out_dev = mmiss_is_device_ptr(out_words);
+    uint64_t* d_words = out_words;
+    if (!out_dev) { MM_TRY(ix->mem_words.ensure((size_t)N * 8)); d_words = ix->mem_words.as<uint64_t>(); }
+    MM_TRY(membership_core(ix, st, queries, P, rad.data(), d_words));
+    if (out_members) MM_TRY(membership_counts(ix, st, d_words));
+    if (!out_dev) MM_HIP(hipMemcpyAsync(out_words, d_words, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+    MM_TRY(deliver_members(ix, st, P, out_members, false));
+    MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_tag_by_radius(mmiss_index* ix, const float* queries, int32_t P, const float* max_dist, const int32_t* bits,
+                                         int64_t* out_members) {
+    const char* who = "mmiss_index_tag_by_radius";
+    if (!ix) MM_FAIL(MMISS_ERR_ARG, "%s: null index", who);
+    if (P < 1 || P > 64) MM_FAIL(MMISS_ERR_ARG, "%s: P = %d (1 .. 64 probes per call)", who, P);
+    if (!queries || !max_dist || !bits) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    uint64_t mask = 0;
+    for (int p = 0; p < P; ++p) {
+        if (bits[p] < 0 || bits[p] > 63) MM_FAIL(MMISS_ERR_ARG, "%s: bits[%d] = %d (0 .. 63)", who, p, bits[p]);
+        if (mask & (1ull << bits[p])) MM_FAIL(MMISS_ERR_ARG, "%s: bit %d is named twice", who, bits[p]);
+        mask |= 1ull << bits[p];
+    }
+    std::lock_guard<std::mutex> lk(ix->mu);
+    hipStream_t st = nullptr;
+    std::vector<float> rad;
+    MM_TRY(membership_check(ix, who, P, max_dist, &st, rad));
+    const int64_t N = ix->count;
+    if (N == 0) {
+        ix->stat_radius_queries += P;
+        return deliver_members(ix, st, P, out_members, true);
+    }
+    MM_TRY(ix->mem_words.ensure((size_t)N * 8));
+    uint64_t* const d_words = ix->mem_words.as<uint64_t>();
+    MM_TRY(membership_core(ix, st, queries, P, rad.data(), d_words));
+    if (out_members) MM_TRY(membership_counts(ix, st, d_words));
+    // the merge under the named bits, then the host mirror (get_tags, remove and the exhaustive passes read it)
+    int32_t* const d_bits = reinterpret_cast<int32_t*>(ix->mem_thr.as<float>() + 192);
+    MM_HIP(hipMemcpyAsync(d_bits, bits, (size_t)P * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(member_merge_tags_kernel, dim3((int)std::min<int64_t>(4096, (N + 255) / 256)), dim3(256), 0, st, ix->tags.as<uint64_t>(),
+                       (const uint64_t*)d_words, N, (const int32_t*)d_bits, P, mask);
+    MM_HIP(hipGetLastError());
+    MM_HIP(hipMemcpyAsync(ix->tags_h.data(), ix->tags.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+    MM_TRY(deliver_members(ix, st, P, out_members, false));
+    MM_HIP(hipStreamSynchronize(st));
     return MMISS_OK;
 }
 

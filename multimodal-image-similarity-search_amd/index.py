@@ -328,11 +328,82 @@ class FlatIndex:
             return np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.float32), overflow
         return np.concatenate(pa), np.concatenate(pb), np.concatenate(pd), overflow
 
+    # ------------------------------------------------------------------ membership / tagging
+    def _probes(self, queries, max_dist):
+        """(queries [P, dim], radii [P], cuda) in the form the membership calls take: numpy arrays, or CUDA tensors for CUDA
+        queries. max_dist: a scalar (every probe) or [P], as in query_radius."""
+        q = self._vecs(queries)
+        P = int(q.shape[0])
+        cuda = _is_torch(q) and q.is_cuda
+        if _is_torch(q) and not cuda:
+            q = q.numpy()
+        if _is_torch(max_dist) and max_dist.is_cuda and cuda:
+            import torch
+
+            r = max_dist.to(torch.float32)
+            r = (r.reshape(1).expand(P) if r.dim() == 0 else r).contiguous()
+        else:
+            if _is_torch(max_dist):
+                max_dist = max_dist.detach().cpu().numpy()
+            r = np.asarray(max_dist, dtype=np.float32)
+            r = np.ascontiguousarray(np.full(P, r, dtype=np.float32) if r.ndim == 0 else r)
+        if r.ndim != 1 or int(r.shape[0]) != P:
+            raise ValueError(f"max_dist: expected a scalar or [{P}] radii, got shape {tuple(r.shape)}")
+        return q, r, cuda
+
+    def membership(self, queries, max_dist):
+        """The exact membership of EVERY row in up to 64 radii, one pass (mmiss_index_membership) -> (words, members): bit p of
+        words[r] = row r (the order of labels()) lies within cosine distance max_dist[p] of queries[p] — the member definition of
+        query_radius, with no cap on the members —, bits >= P zero; members[p] = how many rows. queries [P, dim], 1 <= P <= 64;
+        max_dist a scalar or [P]; NaN raises. numpy in -> uint64 [count] and int64 [P]; CUDA tensors in -> a CUDA int64 tensor of
+        the same bit patterns and a CUDA int64 tensor."""
+        q, r, cuda = self._probes(queries, max_dist)
+        P = int(q.shape[0])
+        with self._call_lock:
+            n = self.count()
+            if cuda:
+                import torch
+
+                words = torch.zeros((n,), dtype=torch.int64, device=q.device)
+                members = torch.zeros((P,), dtype=torch.int64, device=q.device)
+            else:
+                words = np.zeros(n, dtype=np.uint64)
+                members = np.zeros(P, dtype=np.int64)
+            self._sync_stream(q)
+            _lib.check(self._lib.mmiss_index_membership(self._h, _lib.ptr(q), P, _lib.ptr(r), _lib.ptr(words), n, _lib.ptr(members)))
+        return words, members
+
+    def tag_by_radius(self, queries, max_dist, bits):
+        """membership() written straight into the rows' tag words (mmiss_index_tag_by_radius): bit bits[p] of every row's tag
+        becomes "row is a member of probe p" (set or cleared), every other bit keeps its value -> members (int64 [P], numpy or
+        CUDA as the queries). bits: [P] distinct integers in 0 .. 63."""
+        q, r, cuda = self._probes(queries, max_dist)
+        P = int(q.shape[0])
+        b = np.asarray(bits)
+        if b.dtype.kind not in "ui" or isinstance(bits, (bool, np.bool_)):
+            raise TypeError(f"bits must be integers, got {b.dtype}")
+        b = np.ascontiguousarray(b.reshape(-1).astype(np.int64))
+        if b.shape[0] != P:
+            raise ValueError(f"{P} probes but {b.shape[0]} bits")
+        b = np.ascontiguousarray(np.clip(b, -1, 64).astype(np.int32))   # (out of range stays out of range: the call refuses it)
+        if cuda:
+            import torch
+
+            members = torch.zeros((P,), dtype=torch.int64, device=q.device)
+        else:
+            members = np.zeros(P, dtype=np.int64)
+        with self._call_lock:
+            self._sync_stream(q)
+            _lib.check(self._lib.mmiss_index_tag_by_radius(self._h, _lib.ptr(q), P, _lib.ptr(r), b.ctypes.data, _lib.ptr(members)))
+        return members
+
     def guard_stats(self) -> dict:
         """Exactness accounting (mmiss_index_guard_stats_ex): queries served, queries whose first pass could not be proven
         exact and were widened, widen (threshold) passes run, extra passes over the index they cost, the queries that ended in
         the exhaustive canonical pass (a tie plateau of more than 8192 rows), the rows the threshold passes re-ranked, and the
-        radius calls' own two: the queries they served and the passes over the index those cost."""
+        radius calls' own two: the queries they served and the passes over the index those cost. membership() / tag_by_radius()
+        count like radius calls: their probes and passes, the (row, probe) pairs they resolved canonically under swept_rows, the
+        probes that took the per-probe canonical route under exhaustive."""
         out = (C.c_int64 * 8)()
         _lib.check(self._lib.mmiss_index_guard_stats_ex(self._h, out))
         return {"queries": out[0], "widened": out[1], "rounds": out[2], "pages": out[3], "exhaustive": out[4],

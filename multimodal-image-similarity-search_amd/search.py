@@ -5,6 +5,8 @@ backend/app/main.py (same names, argument meaning, return layout and error behav
   search_by_text(query_text, limit)                            main.py:807-827
   search_multimodal(image, query_text, weight_image, limit)    main.py:829-867
   process_image(...) — the embedding + collection.add portion  main.py:685-687,733-744
+  apply_text_filter(filter_query, min_similarity) /            main.py:939-1056 (add_filter -> process_filter_on_all_images),
+  apply_image_filter(image, name, min_similarity)              answered by CLIP similarity instead of a yes/no model
 
 plus batched forms (the reference is batch-1 everywhere; BASELINE configs 2-4 are batched).
 Like the reference, the wrappers catch every exception, log it and return [].
@@ -157,6 +159,28 @@ def find_near_duplicates(min_similarity: float = 0.95, limit: Optional[int] = No
     except Exception as e:
         logger.error(f"Error searching for near duplicates: {e}")
         return []
+
+
+def apply_text_filter(filter_query: str, min_similarity: float) -> int:
+    """A filter named `filter_query` answered by CLIP itself: every stored image whose similarity (1 - d / 2) to the text's
+    embedding reaches min_similarity gets "yes", every other "no" -> the number of "yes" images. The CLIP stand-in for the
+    reference's add_filter -> process_filter_on_all_images (main.py:939-1056), whose answers come from a yes/no vision model;
+    the searches' `filters=[filter_query]` then work on it as on any stored answer. One pass over the index
+    (FlatCollection.add_similarity_filter). Raises what the encoder or the collection raise (a filter half applied is not
+    an empty result)."""
+    model, processor = utils.load_clip_model()
+    embedding = utils.generate_clip_embedding(text=filter_query, model=model, processor=processor)["text"][0]
+    return _collection().add_similarity_filter(filter_query, np.asarray(embedding, dtype=np.float32),
+                                               float(utils.max_distance_for_similarity(min_similarity)))
+
+
+def apply_image_filter(image, name: str, min_similarity: float) -> int:
+    """apply_text_filter with an example image as the probe: "yes" under `name` for every stored image at least min_similarity
+    similar to `image` -> the number of "yes" images."""
+    model, processor = utils.load_clip_model()
+    embedding = utils.generate_clip_embedding(image=image, model=model, processor=processor)["image"][0]
+    return _collection().add_similarity_filter(name, np.asarray(embedding, dtype=np.float32),
+                                               float(utils.max_distance_for_similarity(min_similarity)))
 
 
 def _near_duplicate_of(col, embedding, near_duplicate_similarity):
