@@ -282,6 +282,12 @@ int mmiss_index_query(mmiss_index* idx, const float* queries, int32_t Q, int32_t
  * encode between the two calls, bench.py does). _begin queues the first pass on the index's stream and returns without
  * waiting; _end waits for exactly that work (an event, not the stream: whatever the caller queued behind it keeps running),
  * runs the guard's widen pass for the queries that need it, and fills host outputs. mmiss_index_query = _begin + _end.
+ * Streams: the first pass is ordered on the index's stream; the widen pass that _end decides on runs on a second stream of
+ * the handle's, so it may run BESIDE the work the caller queued on the index's stream between the two calls (the first pass is
+ * ahead of that work, by stream order). `queries` may be overwritten by work queued there behind _begin. The results — host
+ * or device outputs — are complete when _end returns, for work on any stream queued after that; until then the output buffers
+ * hold nothing defined. _end waits for the query's own work only: it does not wait for the caller's stream, and the caller's
+ * stream never waits for the widen pass.
  * Between the two calls `queries` and the output buffers must stay valid, and every other call on this index except
  * count / labels / guard_stats fails with MMISS_ERR_STATE (the scratch buffers belong to the open query); _end without
  * _begin -> MMISS_ERR_STATE. No reference analogue: collection.query is synchronous (backend/app/main.py:761-765).

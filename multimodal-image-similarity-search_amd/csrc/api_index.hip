@@ -17,6 +17,10 @@ struct mmiss_index {
     // switching streams waits for exactly that work, not for whatever else the caller has put on the stream since
     hipEvent_t done_ev = nullptr;
     bool async_pending = false;
+    // The handle's second stream: every widen pass runs here, beside whatever the caller has queued on stream() since
+    // mmiss_index_query_begin (see query_end_locked). No event ties it to stream() in either direction: the host has seen the
+    // first pass finish before it queues anything here, and drains it before query_end returns.
+    hipStream_t side_stream = nullptr;
     std::mutex mu;
     int64_t count = 0, capacity = 0;
     DevBuf rows, labels_d;
@@ -305,6 +309,14 @@ int launch_merge(mmiss_index* ix, hipStream_t st, MergeArgs m) {
     return MMISS_OK;
 }
 
+// the handle's streams and its event (those that exist), then the handle: destroy, and every failure path of create
+void release_handle(mmiss_index* ix) {
+    if (ix->own_stream) (void)hipStreamDestroy(ix->own_stream);
+    if (ix->side_stream) (void)hipStreamDestroy(ix->side_stream);
+    if (ix->done_ev) (void)hipEventDestroy(ix->done_ev);
+    delete ix;
+}
+
 }  // namespace
 
 // ================================================================================================ lifecycle
@@ -325,19 +337,28 @@ extern "C" int mmiss_index_create(int32_t dim, int32_t storage_dtype, int device
     if (!ix) MM_FAIL(MMISS_ERR_NOMEM, "out of host memory");
     ix->dim = dim; ix->dtype = storage_dtype; ix->device = device; ix->elt = storage_dtype == MMISS_F16 ? 2 : storage_dtype == MMISS_F8 ? 1 : 4;
     if (hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking) != hipSuccess) {
-        delete ix;
+        release_handle(ix);
+        MM_FAIL(MMISS_ERR_HIP, "hipStreamCreate failed");
+    }
+    // The LOWEST stream priority, and not for the scheduling: the pipelined step measures the same at either priority
+    // (profiles/query_side_stream.txt). The runtime deals a process's streams onto a few hardware queues PER PRIORITY (4 by
+    // default); a normal-priority side stream shared its queue with one caller's stream in four, and packets of one queue are
+    // taken in order, so query_end then waited for everything the caller had queued behind query_begin after all. Callers'
+    // streams are normal priority as a rule (torch's default and pool streams are), so this one never shares with them.
+    int prio_lo = 0, prio_hi = 0;
+    if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = 0;
+    if (hipStreamCreateWithPriority(&ix->side_stream, hipStreamNonBlocking, prio_lo) != hipSuccess) {
+        release_handle(ix);
         MM_FAIL(MMISS_ERR_HIP, "hipStreamCreate failed");
     }
     if (hipEventCreateWithFlags(&ix->done_ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipStreamDestroy(ix->own_stream);
-        delete ix;
+        release_handle(ix);
         MM_FAIL(MMISS_ERR_HIP, "hipEventCreate failed");
     }
     if (capacity_hint > 0) {
         int rc = index_reserve(ix, capacity_hint, ix->own_stream);
         if (rc != MMISS_OK) {
-            (void)hipStreamDestroy(ix->own_stream); (void)hipEventDestroy(ix->done_ev);
-            delete ix;
+            release_handle(ix);
             return rc;
         }
     }
@@ -349,9 +370,7 @@ extern "C" int mmiss_index_destroy(mmiss_index* ix) {
     if (!ix) return MMISS_OK;
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
-    if (ix->own_stream) (void)hipStreamDestroy(ix->own_stream);
-    if (ix->done_ev) (void)hipEventDestroy(ix->done_ev);
-    delete ix;
+    release_handle(ix);
     return MMISS_OK;
 }
 
@@ -1193,6 +1212,10 @@ int rerank_first(mmiss_index* ix, hipStream_t st, const QueryPlan& p) {
     return launch_rerank(ix, st, r, pd.Q);
 }
 
+// Where a guarded query's widen pass goes (option query_side_stream, a diagnostic: the results are the same bits either way):
+// 1 side_stream, 0 the handle's stream.
+int side_stream_mode() { return mmiss_option("query_side_stream", 1); }
+
 // first pass of a query: everything up to and including the rerank is QUEUED on the stream; ix->pend describes it
 // req / exc: a filtered query's [Q] masks (host or device, null = 0; both null: unfiltered)
 int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const uint64_t* req, const uint64_t* exc,
@@ -1226,7 +1249,11 @@ int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t
 }
 
 // second half: wait for the first pass (its event, NOT the stream: the caller may have queued the next batch's encode behind
-// it), widen what the guard could not prove, hand host outputs over
+// it), widen what the guard could not prove, hand host outputs over.
+// The widen pass runs on side_stream and needs NO edge: the host has seen done_ev, so everything it reads — qs, qn, thr, eps_q,
+// the masks, the output rows the first re-rank wrote — is complete, and everything it writes is complete before this returns
+// (sweep_queries drains the stream it is given), so whatever the caller queues afterwards sees it. On the caller's stream it
+// would sit behind the work queued there since query_begin (the next batch's encode), and its waits would wait for that too.
 int query_end_locked(mmiss_index* ix) {
     const mmiss_index::Pending& pd = ix->pend;   // (unchanged until the next query begins)
     ix->pend.active = false;
@@ -1243,7 +1270,13 @@ int query_end_locked(mmiss_index* ix) {
             if (pd.h_flags[q]) which.push_back(q);
         if (!which.empty()) {
             ix->stat_flagged += (int64_t)which.size();
-            MM_TRY(sweep_queries(ix, st, pd, which));  // returns with the stream drained
+            hipStream_t ws = side_stream_mode() != 0 ? ix->side_stream : st;
+            const int rc = sweep_queries(ix, ws, pd, which);  // returns with `ws` drained
+            if (rc != MMISS_OK) {
+                // (the scratch buffers are the next call's, written by stream order on st: nothing may be left running beside it)
+                if (ws != st) (void)hipStreamSynchronize(ws);
+                return rc;
+            }
         }
     }
     if (!pd.out_dev) {
@@ -1301,7 +1334,7 @@ extern "C" int mmiss_index_query_end(mmiss_index* ix) {
 
 // Drop a query opened with mmiss_index_query_begin without taking its results: waits for the first pass that is queued (its
 // kernels write the caller's output buffers and the handle's scratch), then frees the handle for other calls. A no-op when
-// no query is open.
+// no query is open. Nothing can be in flight on side_stream then: a widen pass is queued only by query_end, which drains it.
 extern "C" int mmiss_index_query_abort(mmiss_index* ix) {
     if (!ix) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_query_abort: null index");
     std::lock_guard<std::mutex> lk(ix->mu);

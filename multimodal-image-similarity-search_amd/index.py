@@ -187,7 +187,9 @@ class FlatIndex:
         Python has to do for the NEW query (layout checks, output buffers) happens BEFORE the pending one is ended, so between the
         last operation of its widen pass and the first kernel of the new first pass lie two C calls and nothing else. In a serving
         loop that keeps one query batch open per step (bench.py) the GPU idled ~87 us per step there (rocprofv3 kernel trace of
-        round 6: the gap between the widen pass's count readback and prep_queries_kernel)."""
+        round 6: the gap between the widen pass's count readback and prep_queries_kernel). Since the library runs the widen pass
+        on the handle's side stream, the 39 us that were left of it no longer idle the GPU either: the next batch's encode,
+        already queued on the caller's stream, runs through them (6 us in front of prep_queries_kernel in the same kind of trace)."""
         q, outs = self._prepare(queries, k)
         masks = self._masks(q, require, exclude)
         prev = pending.result()
