@@ -321,6 +321,8 @@ int mmiss_index_guard_stats(mmiss_index* idx, int64_t out[4]);
  * one per 64 queries of a chunk on the streaming scan). Radius calls leave out[0..3] alone and add to out[4] and out[5].
  * The membership / tagging calls (below) count like radius calls: out[6] += their probes, out[7] += their passes over the index,
  * out[5] += the (row, probe) pairs they resolved canonically, out[4] += the probes that took the per-probe canonical route.
+ * mmiss_index_assign counts the same way: out[6] += its centres, out[7] += its passes, out[5] += borderline rows x centres with
+ * a direction (the one distance per decided row is not counted); out[0..4] stay untouched.
  */
 int mmiss_index_guard_stats_ex(mmiss_index* idx, int64_t out[8]);
 
@@ -441,6 +443,40 @@ int mmiss_index_membership(mmiss_index* idx, const float* queries, int32_t P, co
  */
 int mmiss_index_tag_by_radius(mmiss_index* idx, const float* queries, int32_t P, const float* max_dist, const int32_t* bits,
                               int64_t* out_members);
+
+/* ---------------------------------------------------------------- assignment / clustering ------ */
+/*
+ * The TRANSPOSED question of a query: for EVERY stored row, which of C given vectors is nearest? — zero-shot classification of
+ * the collection against C prompt embeddings, and the assignment step of spherical k-means.
+ * centres: float32 [C, dim], 1 <= C <= 1024, any norm (normalised as queries are). out_assign: int32 [count] in row order — the
+ * order of mmiss_index_labels —; out_dist: float32 [count], may be null; out_sizes: int64 [C], may be null. Each of them host or
+ * device memory, independently. cap_rows = the rows out_assign (and out_dist) have room for; cap_rows < count is MMISS_ERR_ARG.
+ * With Dm[c][r] = the canonical distance of centre c and row r (the bits mmiss_index_query returns for query c and row r):
+ *   out_assign[r] = the c that minimises (Dm[c][r], c) over the c whose Dm[c][r] is not NaN — ties in the float distance go to
+ *   the smaller centre index —, out_dist[r] = that distance; a row without a direction gets -1 / +inf, as does every row when
+ *   no centre has a direction; a centre without a direction is never chosen. out_sizes[c] = the rows assigned to c.
+ * Exact: one streaming pass over the index per 16 / 32 / 64 centres (the membership call's tile choice) keeps the two largest
+ * approximate matrix-core scores of every row; a row whose best score leads the second by more than twice the exactness
+ * guard's bound is decided (its one canonical distance is computed only when out_dist is asked for), every other row gets the
+ * canonical distance to every centre. On well-separated centres the second kind is rare; with duplicate centres it is every row.
+ * Locks the handle, runs on its current stream, returns with its work finished, fails with MMISS_ERR_STATE while a _begin
+ * query is open, checks every argument before it writes anything, and on an empty index writes nothing but zeros to
+ * out_sizes. Read-only on the index. Accounting (mmiss_index_guard_stats_ex): out[6] += C, out[7] += passes over the index,
+ * out[5] += borderline rows x centres with a direction; out[0..4] stay untouched.
+ * (The reference has no counterpart: its collection can only be queried, one embedding at a time — backend/app/main.py:760-867.)
+ */
+int mmiss_index_assign(mmiss_index* idx, const float* centres, int32_t C, int32_t* out_assign, float* out_dist, int64_t cap_rows,
+                       int64_t* out_sizes);
+/*
+ * The reduction a k-means update needs: per cluster, the sum of its rows — in a fixed-point form that has exactly one value,
+ * whatever order the hardware adds in. assign: int32 [n] (host or device), n == count (otherwise MMISS_ERR_ARG), entries outside
+ * 0 .. C-1 (mmiss_index_assign's -1) are skipped; 1 <= C <= 1024; out_sums: int64 [C, dim]; out_sizes: int64 [C], may be null,
+ * the rows per cluster (host or device each). With x = the float32 value mmiss_index_get returns for an element,
+ *   out_sums[c][j] = sum over the rows r with assign[r] == c of (int64) rint((double) x[r][j] * 2^32)
+ * (round to nearest even; the product is exact); a cluster's mean direction is (double) out_sums[c] * 2^-32, up to its norm.
+ * One pass over the rows. Same locking, stream and state rules as mmiss_index_assign; read-only on the index; no accounting.
+ */
+int mmiss_index_cluster_sums(mmiss_index* idx, const int32_t* assign, int64_t n, int32_t C, int64_t* out_sums, int64_t* out_sizes);
 
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*

@@ -102,6 +102,8 @@ SIGNATURES = {
     "mmiss_index_query_radius_by_label": (_I, [_P, _P, _I64, C.c_float, _I32, _I32, _P, _P, _P, _P]),
     "mmiss_index_membership": (_I, [_P, _P, _I32, _P, _P, _I64, _P]),
     "mmiss_index_tag_by_radius": (_I, [_P, _P, _I32, _P, _P, _P]),
+    "mmiss_index_assign": (_I, [_P, _P, _I32, _P, _P, _I64, _P]),
+    "mmiss_index_cluster_sums": (_I, [_P, _P, _I64, _I32, _P, _P]),
     "mmiss_blend": (_I, [_I, _P, _P, _P, C.c_double, _I32, _I32, _P]),
     "mmiss_merge_topk": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_prof_enable": (_I, [_I]),

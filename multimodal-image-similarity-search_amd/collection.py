@@ -458,6 +458,41 @@ class FlatCollection:
             self.update(ids=list(self._ids), metadatas=metas)
             return int(yes.sum())
 
+    def assign(self, embeddings) -> tuple:
+        """For EVERY stored row, the nearest of the given embeddings (FlatIndex.assign: smallest cosine distance, ties to the
+        smaller index) -> (ids, assign int32 [count], dist float32 [count], sizes int64 [C]): ids[r] is the id of row r, assign[r]
+        the index of its embedding (-1 and +inf for a row without a direction), sizes[c] the rows that chose embedding c. One
+        call on the index; nothing is written, neither metadata nor journal. embeddings: [C, dim], 1 <= C <= 1024."""
+        c = self._embeddings_array(embeddings)
+        with self._lock:
+            if c.shape[0] < 1:
+                raise ValueError("assign takes at least one embedding")
+            if not self._ids or self._index is None:
+                return [], np.zeros(0, np.int32), np.zeros(0, np.float32), np.zeros(c.shape[0], np.int64)
+            if c.shape[1] != self._dim:
+                raise ValueError(f"embedding dimension {c.shape[1]} does not match the collection's {self._dim}")
+            a, d, sizes = self._index.assign(c)
+            if int(np.asarray(a).shape[0]) != len(self._labels):
+                raise RuntimeError("index and collection differ in row count")
+            return list(self._ids), np.asarray(a), np.asarray(d), np.asarray(sizes)    # (row order == label order == self._ids)
+
+    def cluster(self, n_clusters: int, iters: int = 10, init_ids=None) -> dict:
+        """Spherical k-means over the stored rows (FlatIndex.kmeans, deterministic) -> its dict plus "ids": ids[r] is the id of
+        row r of "assign" / "dist". init_ids: the ids of the n_clusters rows to start from (None: rows spread evenly over the
+        collection). Nothing is written."""
+        with self._lock:
+            if not self._ids or self._index is None:
+                raise ValueError("cluster on an empty collection")
+            init = None
+            if init_ids is not None:
+                id_to_label = dict(zip(self._ids, self._labels))
+                init = np.asarray([id_to_label[i] for i in init_ids], dtype=np.int64)
+            out = dict(self._index.kmeans(int(n_clusters), iters=int(iters), init=init))
+            if int(np.asarray(out["assign"]).shape[0]) != len(self._labels):
+                raise RuntimeError("index and collection differ in row count")
+            out["ids"] = list(self._ids)
+            return out
+
     def near_duplicates(self, max_distance: float, cap_per_row: int = 64) -> List[tuple]:
         """Every pair of stored rows within cosine distance max_distance, each once (FlatIndex.near_duplicates) ->
         [(id_a, id_b, distance)], id_a the row added earlier, ordered by (id_a's position, distance, id_b's position); a row

@@ -4,6 +4,7 @@
 #include <queue>
 #include "retrieval_kernels.h"
 #include "membership_kernels.h"
+#include "assign_kernels.h"
 #include "gemm_bf16_256.h"
 #include "gemm_strip_p256.h"
 #include <algorithm>
@@ -66,6 +67,10 @@ struct mmiss_index {
     // membership / tagging (mmiss_index_membership, mmiss_index_tag_by_radius): the words when the caller's are host memory or
     // the call merges them into the tags; radii, the two thresholds per probe and the tag form's bits ([64] each); the counts
     DevBuf mem_words, mem_thr, mem_cnt;
+    // assignment / clustering (mmiss_index_assign, mmiss_index_cluster_sums): the scan's per-row state (s1, i1, s2: [count] each),
+    // the borderline rows, the assignment and distances when the caller's are host memory (and a host assignment of
+    // cluster_sums), the sums when the caller's are host memory, and the small block: E, live centres, borderline rows, sizes
+    DevBuf asg_state, asg_list, asg_out, asg_sums, asg_meta;
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -1817,6 +1822,189 @@ extern "C" int mmiss_index_tag_by_radius(mmiss_index* ix, const float* queries, 
     MM_HIP(hipGetLastError());
     MM_HIP(hipMemcpyAsync(ix->tags_h.data(), ix->tags.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
     MM_TRY(deliver_members(ix, st, P, out_members, false));
+    MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+// ================================================================================================ assignment / clustering
+// The transposed question of a query: for EVERY row, which of C <= 1024 centres is nearest (canonical distance, ties to the
+// smaller centre index) — zero-shot classification of the collection, the assignment step of spherical k-means — and the
+// reduction its update step needs: the sums of the rows of every cluster, in a fixed-point form that has one value whatever
+// order the hardware adds in. assign_kernels.h has the kernels and the proof of the sure / borderline split.
+namespace {
+
+constexpr int ASSIGN_MAX_CENTRES = 1024;
+constexpr size_t ASSIGN_META_SIZES = 64;   // byte offset of the [1024] u64 sizes in asg_meta; in front: float E, int live, int borderline
+
+// n zeros to a (host or device, may be null) int64 array
+int deliver_zeros_i64(hipStream_t st, int64_t* out, int64_t n) {
+    if (!out || n <= 0) return MMISS_OK;
+    if (mmiss_is_device_ptr(out)) { MM_HIP(hipMemsetAsync(out, 0, (size_t)n * 8, st)); MM_HIP(hipStreamSynchronize(st)); }
+    else memset(out, 0, (size_t)n * 8);
+    return MMISS_OK;
+}
+
+// sizes of clusters [0, C) of d_assign (device, [count]) -> out_sizes (host or device); queued, not waited for
+int assign_sizes(mmiss_index* ix, hipStream_t st, const int32_t* d_assign, int C, int64_t* out_sizes) {
+    unsigned long long* const d_sizes = reinterpret_cast<unsigned long long*>(ix->asg_meta.as<char>() + ASSIGN_META_SIZES);
+    MM_HIP(hipMemsetAsync(d_sizes, 0, (size_t)C * 8, st));
+    hipLaunchKernelGGL(assign_sizes_kernel, dim3((int)std::min<int64_t>(1024, (ix->count + 255) / 256)), dim3(256), 0, st, d_assign, ix->count, C, d_sizes);
+    MM_HIP(hipGetLastError());
+    MM_HIP(hipMemcpyAsync(out_sizes, d_sizes, (size_t)C * 8, mmiss_is_device_ptr(out_sizes) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    return MMISS_OK;
+}
+
+typedef void (*AssignKernel)(AssignScanArgs);
+
+}  // namespace
+
+extern "C" int mmiss_index_assign(mmiss_index* ix, const float* centres, int32_t C, int32_t* out_assign, float* out_dist, int64_t cap_rows,
+                                  int64_t* out_sizes) {
+    const char* who = "mmiss_index_assign";
+    if (!ix) MM_FAIL(MMISS_ERR_ARG, "%s: null index", who);
+    if (C < 1 || C > ASSIGN_MAX_CENTRES) MM_FAIL(MMISS_ERR_ARG, "%s: C = %d (1 .. %d centres per call)", who, C, ASSIGN_MAX_CENTRES);
+    if (!centres) MM_FAIL(MMISS_ERR_ARG, "%s: null centres", who);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (cap_rows < ix->count) MM_FAIL(MMISS_ERR_ARG, "%s: cap_rows = %lld for %lld rows", who, (long long)cap_rows, (long long)ix->count);
+    if (ix->count > 0 && !out_assign) MM_FAIL(MMISS_ERR_ARG, "%s: null out_assign", who);
+    MM_NO_PENDING(ix, who);
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    const int64_t N = ix->count;
+    const int D = ix->dim;
+    if (N == 0) {   // nothing to write but the sizes
+        ix->stat_radius_queries += C;
+        return deliver_zeros_i64(st, out_sizes, C);
+    }
+    const MemberPlan mp = plan_membership(D, ix->qelt(), C, N);   // the centre tile and the slabs: §4c's choice
+    if (mp.lds > SCAN_LDS_LIMIT)
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: a 16-centre block of dim %d does not fit the LDS (%d bytes)", who, D, mp.lds);
+    const bool asg_dev = mmiss_is_device_ptr(out_assign), dist_dev = out_dist && mmiss_is_device_ptr(out_dist);
+    MM_TRY(ix->asg_out.ensure((size_t)N * 8));
+    MM_TRY(ix->asg_state.ensure((size_t)N * 12));
+    MM_TRY(ix->asg_list.ensure((size_t)N * 4));
+    MM_TRY(ix->asg_meta.ensure(ASSIGN_META_SIZES + (size_t)ASSIGN_MAX_CENTRES * 8));
+    MM_TRY(ix->swp_pin.ensure(16, st));
+    int32_t* const d_assign = asg_dev ? out_assign : ix->asg_out.as<int32_t>();
+    float* const d_dist = !out_dist ? nullptr : dist_dev ? out_dist : ix->asg_out.as<float>() + N;
+    float* const st_s1 = ix->asg_state.as<float>();
+    int32_t* const st_i1 = reinterpret_cast<int32_t*>(st_s1 + N);
+    float* const st_s2 = st_s1 + 2 * N;
+    float* const d_E = ix->asg_meta.as<float>();
+    int32_t* const d_live = ix->asg_meta.as<int32_t>() + 1;
+    int32_t* const d_bcnt = ix->asg_meta.as<int32_t>() + 2;
+    MM_TRY(upload_queries(ix, st, centres, C));   // qn, qs (rows behind C zero, 256 of them at least), eps_q
+    const float* const eps = ix->eps_q.as<float>();
+    MM_HIP(hipMemsetAsync(d_bcnt, 0, 4, st));
+    hipLaunchKernelGGL(assign_bound_kernel, dim3(1), dim3(64), 0, st, eps, (int)C, d_E, d_live);
+    MM_HIP(hipGetLastError());
+    const AssignKernel kern = with_storage(ix->dtype, [&](auto s) -> AssignKernel {
+        using T = typename decltype(s)::T;
+        if (mp.nqt == 4) return &assign_scan_kernel<T, 4>;
+        if (mp.nqt == 2) return &assign_scan_kernel<T, 2>;
+        return &assign_scan_kernel<T, 1>;
+    });
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), mp.lds));
+    const int NQ = 16 * mp.nqt;
+    const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
+    for (int j = 0; j < mp.passes; ++j) {
+        AssignScanArgs a{};
+        a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>();
+        a.qs = ix->qs.as<char>() + (size_t)j * NQ * D * ix->qelt();
+        a.eps_q = eps;
+        a.tiles_per_block = mp.tiles_per_block;
+        a.c0 = j * NQ; a.C = C; a.first = j == 0;
+        a.st_s1 = st_s1; a.st_i1 = st_i1; a.st_s2 = st_s2;
+        MM_PROF(f16 ? "assign_scan_f16" : f8 ? "assign_scan_f8" : "assign_scan_f32", st, 2.0 * NQ * (double)N * D, (double)N * (D * ix->elt + 12));
+        hipLaunchKernelGGL(kern, dim3(mp.slabs), dim3(256), mp.lds, st, a);
+        MM_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(assign_decide_kernel, dim3((int)std::min<int64_t>(2048, (N + 255) / 256)), dim3(256), 0, st, (const float*)st_s1,
+                       (const int32_t*)st_i1, (const float*)st_s2, N, (const float*)d_E, d_assign, d_dist, ix->asg_list.as<int32_t>(), d_bcnt);
+    MM_HIP(hipGetLastError());
+    // the resolve kernels are launched blind: the list's length stays on the device
+    const int rgrid = (int)std::min<int64_t>(4096, (N + 15) / 16);
+    with_storage(ix->dtype, [&](auto s) {
+        using T = typename decltype(s)::T;
+        if (d_dist) {   // the sure rows' one distance
+            MM_PROF("assign_dist", st, 2.0 * N * D, (double)N * D * ix->elt);
+            hipLaunchKernelGGL(assign_resolve_kernel<T>, dim3(rgrid), dim3(256), 0, st, (const void*)ix->rows.p, D, (const float*)ix->qn.as<float>(),
+                               (const float*)ix->inv.as<float>(), eps, (int)C, (const int32_t*)nullptr, (const int32_t*)nullptr, N, d_assign, d_dist);
+        }
+        MM_PROF("assign_resolve", st, 0.0, 0.0);
+        hipLaunchKernelGGL(assign_resolve_kernel<T>, dim3(rgrid), dim3(256), 0, st, (const void*)ix->rows.p, D, (const float*)ix->qn.as<float>(),
+                           (const float*)ix->inv.as<float>(), eps, (int)C, (const int32_t*)ix->asg_list.as<int32_t>(), (const int32_t*)d_bcnt, N,
+                           d_assign, d_dist);
+    });
+    MM_HIP(hipGetLastError());
+    if (out_sizes) MM_TRY(assign_sizes(ix, st, d_assign, C, out_sizes));
+    if (!asg_dev) MM_HIP(hipMemcpyAsync(out_assign, d_assign, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    if (out_dist && !dist_dev) MM_HIP(hipMemcpyAsync(out_dist, d_dist, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    MM_HIP(hipMemcpyAsync(ix->swp_pin.p, ix->asg_meta.p, 12, hipMemcpyDeviceToHost, st));
+    MM_HIP(hipStreamSynchronize(st));
+    const int32_t* meta = ix->swp_pin.as<int32_t>();   // (E, live centres, borderline rows)
+    ix->stat_radius_queries += C;
+    ix->stat_radius_pages += mp.passes;
+    ix->stat_swept_rows += (int64_t)meta[2] * meta[1];
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_cluster_sums(mmiss_index* ix, const int32_t* assign, int64_t n, int32_t C, int64_t* out_sums, int64_t* out_sizes) {
+    const char* who = "mmiss_index_cluster_sums";
+    if (!ix) MM_FAIL(MMISS_ERR_ARG, "%s: null index", who);
+    if (C < 1 || C > ASSIGN_MAX_CENTRES) MM_FAIL(MMISS_ERR_ARG, "%s: C = %d (1 .. %d clusters per call)", who, C, ASSIGN_MAX_CENTRES);
+    if (!out_sums || (n > 0 && !assign)) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (n != ix->count) MM_FAIL(MMISS_ERR_ARG, "%s: %lld assignments for %lld rows", who, (long long)n, (long long)ix->count);
+    MM_NO_PENDING(ix, who);
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    const int64_t N = ix->count;
+    const int D = ix->dim;
+    const bool sums_dev = mmiss_is_device_ptr(out_sums);
+    const size_t sum_bytes = (size_t)C * D * 8;
+    if (N == 0) {
+        if (sums_dev) MM_HIP(hipMemsetAsync(out_sums, 0, sum_bytes, st)); else memset(out_sums, 0, sum_bytes);
+        MM_TRY(deliver_zeros_i64(st, out_sizes, C));
+        MM_HIP(hipStreamSynchronize(st));
+        return MMISS_OK;
+    }
+    MM_TRY(ix->asg_meta.ensure(ASSIGN_META_SIZES + (size_t)ASSIGN_MAX_CENTRES * 8));
+    const int32_t* d_assign = assign;
+    if (!mmiss_is_device_ptr(assign)) {
+        MM_TRY(ix->asg_out.ensure((size_t)N * 4));
+        MM_HIP(hipMemcpyAsync(ix->asg_out.p, assign, (size_t)N * 4, hipMemcpyHostToDevice, st));
+        d_assign = ix->asg_out.as<int32_t>();
+    }
+    unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(out_sums);
+    if (!sums_dev) { MM_TRY(ix->asg_sums.ensure(sum_bytes)); d_sums = ix->asg_sums.as<unsigned long long>(); }
+    MM_HIP(hipMemsetAsync(d_sums, 0, sum_bytes, st));
+    // the widest column chunk (a divisor of dim, a multiple of 16) whose [C][cols] table of 64-bit sums fits 128 KiB of LDS:
+    // all of dim 512 up to 32 clusters, 16 columns at 1024 clusters
+    constexpr int TABLE_LDS = 128 * 1024;
+    ClusterSumsArgs a{};
+    a.cols = 16;
+    for (int k = 1; k <= D / 16; ++k)
+        if (D % k == 0 && (D / k) % 16 == 0 && (size_t)C * (D / k) * 8 <= (size_t)TABLE_LDS) { a.cols = D / k; break; }
+    const int chunks = D / a.cols;
+    const int64_t slab_target = std::max<int64_t>(1, 2048 / chunks);
+    a.rows_per_block = (int)std::max<int64_t>(64, (N + slab_target - 1) / slab_target);
+    const int slabs = (int)((N + a.rows_per_block - 1) / a.rows_per_block);
+    a.rows = ix->rows.p; a.inv = ix->inv.as<float>(); a.assign = d_assign; a.N = N; a.D = D; a.C = C; a.sums = d_sums;
+    const int lds = C * a.cols * 8;
+    {
+        MM_PROF("cluster_sums", st, (double)N * D, (double)N * (D * ix->elt + 4));
+        int rc = MMISS_OK;
+        with_storage(ix->dtype, [&](auto s) {
+            using T = typename decltype(s)::T;
+            rc = mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&cluster_sums_kernel<T>), lds);
+            if (rc == MMISS_OK) hipLaunchKernelGGL(cluster_sums_kernel<T>, dim3(slabs, chunks), dim3(1024), lds, st, a);
+        });
+        MM_TRY(rc);
+        MM_HIP(hipGetLastError());
+    }
+    if (out_sizes) MM_TRY(assign_sizes(ix, st, d_assign, C, out_sizes));
+    if (!sums_dev) MM_HIP(hipMemcpyAsync(out_sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, st));
     MM_HIP(hipStreamSynchronize(st));
     return MMISS_OK;
 }

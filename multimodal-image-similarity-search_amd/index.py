@@ -399,13 +399,127 @@ class FlatIndex:
             _lib.check(self._lib.mmiss_index_tag_by_radius(self._h, _lib.ptr(q), P, _lib.ptr(r), b.ctypes.data, _lib.ptr(members)))
         return members
 
+    # ------------------------------------------------------------------ assignment / clustering
+    MAX_CENTRES = 1024
+
+    def _centres(self, centres):
+        """(centres [C, dim], cuda) in the form the assign call takes; C outside 1 .. MAX_CENTRES raises"""
+        c = self._vecs(centres)
+        cuda = _is_torch(c) and c.is_cuda
+        if _is_torch(c) and not cuda:
+            c = c.numpy()
+        if not 1 <= int(c.shape[0]) <= self.MAX_CENTRES:
+            raise ValueError(f"centres: 1 .. {self.MAX_CENTRES} vectors per call, got {int(c.shape[0])}")
+        return c, cuda
+
+    def assign(self, centres, want_dist: bool = True):
+        """For EVERY row, the nearest of the C centres (mmiss_index_assign) -> (assign, dist | None, sizes): assign[r] (int32, the
+        order of labels()) = the centre of smallest cosine distance to row r — exactly: the c that minimises (d(centre c, row r), c)
+        with d the distance query() reports, so ties go to the smaller index —, dist[r] that distance (float32; None unless
+        want_dist), sizes[c] (int64) the rows assigned to c. A row without a direction gets -1 / +inf, a centre without one is
+        never chosen. centres [C, dim], 1 <= C <= 1024, any norm. numpy in -> numpy out, CUDA tensors in -> CUDA tensors out."""
+        c, cuda = self._centres(centres)
+        Cn = int(c.shape[0])
+        with self._call_lock:
+            n = self.count()
+            if cuda:
+                import torch
+
+                asg = torch.full((n,), -1, dtype=torch.int32, device=c.device)
+                dist = torch.full((n,), float("inf"), dtype=torch.float32, device=c.device) if want_dist else None
+                sizes = torch.zeros((Cn,), dtype=torch.int64, device=c.device)
+            else:
+                asg = np.full(n, -1, dtype=np.int32)
+                dist = np.full(n, np.inf, dtype=np.float32) if want_dist else None
+                sizes = np.zeros(Cn, dtype=np.int64)
+            self._sync_stream(c)
+            _lib.check(self._lib.mmiss_index_assign(self._h, _lib.ptr(c), Cn, _lib.ptr(asg), _lib.ptr(dist) if want_dist else None, n,
+                                                    _lib.ptr(sizes)))
+        return asg, dist, sizes
+
+    def cluster_sums(self, assign, n_clusters: int):
+        """Per cluster, the sum of its rows in 2^-32 fixed point (mmiss_index_cluster_sums) -> (sums int64 [C, dim], sizes int64
+        [C]): sums[c][j] = the sum over the rows r with assign[r] == c of rint(float64(x[r][j]) * 2^32), x = what get() returns —
+        one value whatever order the GPU adds in. assign: int32 [count] (numpy or a CUDA tensor; entries outside 0 .. C-1 are
+        skipped). numpy in -> numpy out, CUDA in -> CUDA out."""
+        Cn = int(n_clusters)
+        if not 1 <= Cn <= self.MAX_CENTRES:
+            raise ValueError(f"n_clusters: 1 .. {self.MAX_CENTRES}, got {Cn}")
+        cuda = _is_torch(assign) and assign.is_cuda
+        if cuda:
+            import torch
+
+            if assign.dtype.is_floating_point or assign.dtype == torch.bool:
+                raise TypeError(f"assign must be integers, got {assign.dtype}")
+            a = assign.to(torch.int32).contiguous()
+        else:
+            a = np.asarray(assign.numpy() if _is_torch(assign) else assign)
+            if a.dtype.kind not in "ui":
+                raise TypeError(f"assign must be integers, got {a.dtype}")
+            a = np.ascontiguousarray(a.astype(np.int32))
+        if a.ndim != 1:
+            raise ValueError(f"assign: expected one entry per row, got shape {tuple(a.shape)}")
+        with self._call_lock:
+            n = self.count()
+            if int(a.shape[0]) != n:
+                raise ValueError(f"assign: {int(a.shape[0])} entries for {n} rows")
+            if cuda:
+                sums = torch.zeros((Cn, self.dim), dtype=torch.int64, device=a.device)
+                sizes = torch.zeros((Cn,), dtype=torch.int64, device=a.device)
+            else:
+                sums = np.zeros((Cn, self.dim), dtype=np.int64)
+                sizes = np.zeros(Cn, dtype=np.int64)
+            self._sync_stream(a)
+            _lib.check(self._lib.mmiss_index_cluster_sums(self._h, _lib.ptr(a), n, Cn, _lib.ptr(sums), _lib.ptr(sizes)))
+        return sums, sizes
+
+    def kmeans(self, n_clusters: int, iters: int = 10, init=None) -> dict:
+        """Spherical k-means over the stored rows, deterministic by construction -> dict(centres float32 [C, dim], assign int32
+        [count], dist float32 [count], sizes int64 [C], iterations).
+        Initial centres: get() of the rows under `init` (labels, length C); None: the rows at positions floor(i * count / C).
+        Up to `iters` times: assign (no distances); stop when the assignment equals the previous one; otherwise
+        centres[c] = float32(float64(sums[c]) * 2^-32) from cluster_sums — a cluster that is empty, or whose sum is all zero,
+        keeps its centre; no re-normalisation, assign() normalises. `iterations` counts the centre updates. One more assign with
+        distances follows the loop: the returned assignment always belongs to the returned centres."""
+        Cn, iters = int(n_clusters), int(iters)
+        if not 1 <= Cn <= self.MAX_CENTRES:
+            raise ValueError(f"n_clusters: 1 .. {self.MAX_CENTRES}, got {Cn}")
+        if iters < 0:
+            raise ValueError(f"iters: {iters}")
+        with self._call_lock:
+            labels = self.labels()
+            n = int(labels.shape[0])
+            if init is None:
+                if n < 1:
+                    raise ValueError("kmeans on an empty index")
+                init = labels[(np.arange(Cn, dtype=np.int64) * n) // Cn]
+            init = np.ascontiguousarray(init, dtype=np.int64).reshape(-1)
+            if init.shape[0] != Cn:
+                raise ValueError(f"init: {init.shape[0]} labels for {Cn} clusters")
+            centres = np.ascontiguousarray(self.get(init), dtype=np.float32)
+            prev, done = None, 0
+            for _ in range(iters):
+                asg, _d, _s = self.assign(centres, want_dist=False)
+                if prev is not None and np.array_equal(asg, prev):
+                    break
+                prev = asg
+                sums, sizes = self.cluster_sums(asg, Cn)
+                new = (sums.astype(np.float64) * 2.0 ** -32).astype(np.float32)
+                keep = (sizes == 0) | ~sums.any(axis=1)
+                new[keep] = centres[keep]
+                centres = new
+                done += 1
+            asg, dist, sizes = self.assign(centres, want_dist=True)
+        return {"centres": centres, "assign": asg, "dist": dist, "sizes": sizes, "iterations": done}
+
     def guard_stats(self) -> dict:
         """Exactness accounting (mmiss_index_guard_stats_ex): queries served, queries whose first pass could not be proven
         exact and were widened, widen (threshold) passes run, extra passes over the index they cost, the queries that ended in
         the exhaustive canonical pass (a tie plateau of more than 8192 rows), the rows the threshold passes re-ranked, and the
         radius calls' own two: the queries they served and the passes over the index those cost. membership() / tag_by_radius()
         count like radius calls: their probes and passes, the (row, probe) pairs they resolved canonically under swept_rows, the
-        probes that took the per-probe canonical route under exhaustive."""
+        probes that took the per-probe canonical route under exhaustive. assign() counts its centres and passes there too, and
+        borderline rows x centres with a direction under swept_rows."""
         out = (C.c_int64 * 8)()
         _lib.check(self._lib.mmiss_index_guard_stats_ex(self._h, out))
         return {"queries": out[0], "widened": out[1], "rounds": out[2], "pages": out[3], "exhaustive": out[4],

@@ -7,6 +7,8 @@ backend/app/main.py (same names, argument meaning, return layout and error behav
   process_image(...) — the embedding + collection.add portion  main.py:685-687,733-744
   apply_text_filter(filter_query, min_similarity) /            main.py:939-1056 (add_filter -> process_filter_on_all_images),
   apply_image_filter(image, name, min_similarity)              answered by CLIP similarity instead of a yes/no model
+  classify_collection(prompts) / cluster_collection(n)         no counterpart: CLIP's zero-shot classification of every stored
+                                                               image, and k-means albums, in the index's own arithmetic
 
 plus batched forms (the reference is batch-1 everywhere; BASELINE configs 2-4 are batched).
 Like the reference, the wrappers catch every exception, log it and return [].
@@ -246,3 +248,26 @@ def process_images(images: Sequence, image_ids: Sequence[str], metadatas: Option
     docs = [(documents[i] if documents else "") for i in todo]
     col.add(ids=[image_ids[i] for i in todo], embeddings=emb, metadatas=metas, documents=docs)
     return len(todo)
+
+
+def classify_collection(prompts: Sequence[str]) -> List[tuple]:
+    """Zero-shot classification of the whole collection: which of the text prompts does each stored image match best? ->
+    [(image_id, prompt_index, similarity_score)] in upload order, similarity = 1 - d / 2 as everywhere here; an image without a
+    direction gets prompt index -1 and similarity None. The prompts are encoded with the text tower and ONE assign call decides
+    every image (FlatCollection.assign; ties go to the earlier prompt). Raises what the encoder or the collection raise."""
+    prompts = list(prompts)
+    if not prompts:
+        raise ValueError("classify_collection takes at least one prompt")
+    model, processor = utils.load_clip_model()
+    emb = np.stack([np.asarray(utils.generate_clip_embedding(text=p, model=model, processor=processor)["text"][0], dtype=np.float32)
+                    for p in prompts])
+    ids, assign, dist, _sizes = _collection().assign(emb)
+    return [(i, int(a), (1 - (float(d) / 2)) if a >= 0 else None) for i, a, d in zip(ids, assign.tolist(), dist.tolist())]
+
+
+def cluster_collection(n_clusters: int, iters: int = 10) -> tuple:
+    """Group the stored images into n_clusters by spherical k-means on their embeddings ("albums", browse by cluster) ->
+    ({image_id: cluster}, sizes): cluster -1 for an image without a direction, sizes[c] the images of cluster c. Deterministic
+    (FlatIndex.kmeans)."""
+    out = _collection().cluster(int(n_clusters), iters=int(iters))
+    return dict(zip(out["ids"], (int(a) for a in np.asarray(out["assign"]).tolist()))), [int(v) for v in np.asarray(out["sizes"]).tolist()]
