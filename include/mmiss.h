@@ -478,6 +478,61 @@ int mmiss_index_assign(mmiss_index* idx, const float* centres, int32_t C, int32_
  */
 int mmiss_index_cluster_sums(mmiss_index* idx, const int32_t* assign, int64_t n, int32_t C, int64_t* out_sums, int64_t* out_sizes);
 
+/* ---------------------------------------------------------------- partitioned search ----------- */
+/*
+ * An inverted-file search over the centres and cells the assignment calls produce: a query reads only the rows of the few cells
+ * whose centres are nearest to it instead of every row. The approximation is ONLY in which rows are looked at, and that set is
+ * defined exactly; within it the answer is the exact top-k — the distance bits and the (distance, label) order of
+ * mmiss_index_query — so probing every cell returns mmiss_index_query's bits. The reference's own store answers above 100 rows
+ * from an approximate HNSW graph (chromadb: backend/app/utils.py:127-130 create, backend/app/main.py:761-765 query).
+ *
+ * A PARTITION is C centres (1 <= C <= 1024, float32 [C, dim], any norm) and one cell number per row for the B rows the index held
+ * when it was set (int32; an entry outside 0 .. C-1, e.g. mmiss_index_assign's -1, puts the row in no cell). Rows added since
+ * (r >= B) are the TAIL. For a query q and nprobe >= 1:
+ *   dc[c]   = the canonical distance of the normalised query to the normalised centre c treated as an f32 row (the bits
+ *             mmiss_index_query reports for q against an f32 row holding the centre);
+ *   P(q)    = the min(nprobe, live centres) centres smallest by (dc[c], c) among the c whose dc[c] is not NaN — ties to the
+ *             smaller index; a centre without a direction is never probed;
+ *   cand(q) = { r < B : cells[r] in P(q) } and every tail row.
+ * The result is the exact top-k by (distance, label) over the rows of cand(q) that the masks admit (require / exclude as
+ * mmiss_index_query_filtered, null = 0) and that have a distance; out_count = min(k, those rows), unused slots -1 / +inf; a
+ * query without a direction gives count 0. out_scanned[q] = the sizes of the cells of P(q) + the tail rows, independent of the
+ * masks, 0 for a query without a direction. A row in an unprobed cell is NOT returned however near it is.
+ * mmiss_index_add keeps the partition (new rows are tail, candidates of every query); mmiss_index_update, _remove, _clear and
+ * _load drop it (rows move or change: a stale cell would silently lose results); mmiss_index_save does not persist it.
+ *
+ * All five calls lock the handle, run on its current stream, return with their work finished, fail with MMISS_ERR_STATE while
+ * a _begin query is open, check every argument before they write anything, and leave the eight guard counters alone.
+ *
+ * mmiss_index_partition_set: centres and cells each host or device memory; n must equal the row count. n != count, C outside
+ * 1 .. 1024, a null pointer or no centre with a direction -> MMISS_ERR_ARG, and the previous partition is kept. Stores the
+ * canonically normalised centres, the cells, the row numbers grouped by cell (a counting sort on the device; the order inside a
+ * cell is unspecified and no result depends on it), the cell offsets and the sizes.
+ */
+int mmiss_index_partition_set(mmiss_index* idx, const float* centres, int32_t C, const int32_t* cells, int64_t n);
+/* Forget the partition; none set: MMISS_OK, nothing happens. */
+int mmiss_index_partition_clear(mmiss_index* idx);
+/*
+ * out = { C (0 = no partition, and then every other entry is 0), B, tail rows, rows in cells, largest cell, empty cells,
+ *         probed queries served since the partition was set, rows scanned since (the sum of their out_scanned) }.
+ */
+int mmiss_index_partition_info(mmiss_index* idx, int64_t out[8]);
+/*
+ * The partition as stored: the NORMALISED centres float32 [C, dim], cells int32 [B], sizes int64 [C]; each may be null, each host
+ * or device memory. cap_rows = the entries `cells` has room for; cap_rows < B -> MMISS_ERR_ARG. No partition -> MMISS_ERR_STATE.
+ */
+int mmiss_index_partition_get(mmiss_index* idx, float* centres, int32_t* cells, int64_t cap_rows, int64_t* sizes);
+/*
+ * The probed query defined above. queries float32 [Q, dim] (host or device), Q >= 1; 1 <= k <= 2040 (above: MMISS_ERR_UNSUPPORTED,
+ * the flat query's own limit); nprobe >= 1, values above C are legal (every live centre is probed); require / exclude uint64 [Q],
+ * host or device, each may be null; out_labels int64 [Q, k], out_dist float32 [Q, k], out_count int32 [Q], out_scanned int64 [Q]
+ * (may be null): all host or all device. No partition -> MMISS_ERR_STATE. On an empty index with a partition: counts 0.
+ * Every candidate gets its canonical distance directly (no approximate pass, no guard); the scratch of a call is bounded by the
+ * tail and the nprobe largest cells per query, and the queries are taken in chunks that keep it under 512 MB.
+ */
+int mmiss_index_query_probed(mmiss_index* idx, const float* queries, int32_t Q, int32_t k, int32_t nprobe, const uint64_t* require,
+                             const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_scanned);
+
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*
  * out[q] = normalize(w * normalize(img[q]) + (1-w) * normalize(txt[q])), float32 [Q,dim].

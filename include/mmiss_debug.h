@@ -228,6 +228,14 @@ int mmiss_dbg_index_read_rows(struct mmiss_index* ix, int64_t row0, int64_t n, v
  * normalised queries, qs_out [round_up(Q, 256), dim] the first pass's operand (f32 for f32 rows, f16 for f16 / fp8 rows; pad rows
  * included), eps_out f32 [Q] the guard's bound per query. Refuses an open query; returns drained. */
 int mmiss_dbg_index_prep_queries(struct mmiss_index* ix, const float* queries, int32_t Q, float* qn_out, void* qs_out, float* eps_out);
+/* How a probed call (mmiss_index_query_probed) of Q queries, this k (1 .. 2040) and this nprobe would run on the index's partition
+ * as it stands and under the options as they stand (probe_scratch_kb: the scratch budget in KB, default 512 * 1024): the call's own
+ * planning function, evaluated on the host. Launches nothing, changes nothing. No partition -> MMISS_ERR_STATE. out is a HOST int32 [8]:
+ *   [0] splits: workgroups per list of the scan   [1] segment size of the selection (keys)   [2] levels: segment_topk launches
+ *   per chunk, the last (the one that writes the results) included   [3] queries per chunk   [4] the bound on one query's
+ *   candidates (the tail and the min(nprobe, C) largest cells)   [5] share: rows of a list per scan workgroup   [6] probe slots
+ *   min(nprobe, C)   [7] chunks */
+int mmiss_dbg_index_probe_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int32_t nprobe, int32_t* out);
 
 
 /* The path one chunk of an encode call would take on the handle as it stands and under the options as they stand: B items

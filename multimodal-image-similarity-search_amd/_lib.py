@@ -104,6 +104,11 @@ SIGNATURES = {
     "mmiss_index_tag_by_radius": (_I, [_P, _P, _I32, _P, _P, _P]),
     "mmiss_index_assign": (_I, [_P, _P, _I32, _P, _P, _I64, _P]),
     "mmiss_index_cluster_sums": (_I, [_P, _P, _I64, _I32, _P, _P]),
+    "mmiss_index_partition_set": (_I, [_P, _P, _I32, _P, _I64]),
+    "mmiss_index_partition_clear": (_I, [_P]),
+    "mmiss_index_partition_info": (_I, [_P, C.POINTER(_I64)]),
+    "mmiss_index_partition_get": (_I, [_P, _P, _P, _I64, _P]),
+    "mmiss_index_query_probed": (_I, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "mmiss_blend": (_I, [_I, _P, _P, _P, C.c_double, _I32, _I32, _P]),
     "mmiss_merge_topk": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_prof_enable": (_I, [_I]),
@@ -152,6 +157,7 @@ SIGNATURES = {
     "mmiss_dbg_index_radius_plan": (_I, [_P, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_read_rows": (_I, [_P, _I64, _I64, _P, _P, _P, _P]),
     "mmiss_dbg_index_prep_queries": (_I, [_P, _P, _I32, _P, _P, _P]),
+    "mmiss_dbg_index_probe_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
@@ -278,6 +284,17 @@ def index_radius_plan(handle, Q: int, filtered: bool = False) -> dict:
     check(load().mmiss_dbg_index_radius_plan(handle, int(Q), 1 if filtered else 0, out))
     v = [int(x) for x in out]
     return {"chunks": v[0], "first": dict(zip(RADIUS_PLAN_FIELDS, v[1:8])), "last": dict(zip(RADIUS_PLAN_FIELDS, v[8:15]))}
+
+
+PROBE_PLAN_FIELDS = ("splits", "segment", "levels", "queries_per_chunk", "bound", "share", "slots", "chunks")
+
+
+def index_probe_plan(handle, Q: int, k: int, nprobe: int) -> dict:
+    """mmiss_dbg_index_probe_plan as a dict: how a probed call of this shape would run on the partition of the index `handle` as it
+    stands (and under the option probe_scratch_kb as it stands). Nothing is launched."""
+    out = (_I32 * 8)()
+    check(load().mmiss_dbg_index_probe_plan(handle, int(Q), int(k), int(nprobe), out))
+    return dict(zip(PROBE_PLAN_FIELDS, (int(v) for v in out)))
 
 
 _INDEX_ELT = {MMISS_F32: "float32", MMISS_F16: "float16", MMISS_F8: "uint8"}

@@ -338,14 +338,17 @@ class FlatCollection:
         self._index.set_tags(np.asarray(labs, dtype=np.int64), np.asarray(tags, dtype=np.uint64))
         self._tag_dirty.clear()
 
-    def _index_query(self, q: np.ndarray, k: int, max_distance=None, **masks):
+    def _index_query(self, q: np.ndarray, k: int, max_distance=None, n_probe=None, **masks):
         """The index's top-k query or, max_distance given, its radius query with k as the cap (FlatIndex.query_radius: only the
-        rows within max_distance, the k nearest of them) -> (labels [Q,k], distances [Q,k], counts [Q])."""
+        rows within max_distance, the k nearest of them) -> (labels [Q,k], distances [Q,k], counts [Q]). n_probe given, no
+        max_distance and a partition present: the probed query (FlatIndex.query_probed) instead of the flat one."""
         if max_distance is None:
+            if n_probe is not None and self._index.partition_info()["cells"] > 0:
+                return self._index.query_probed(q, k, int(n_probe), **masks)[:3]
             return self._index.query(q, k, **masks)
         return self._index.query_radius(q, max_distance, k, **masks)[:3]
 
-    def _filtered_query(self, q: np.ndarray, k: int, filters: List[str], max_distance=None):
+    def _filtered_query(self, q: np.ndarray, k: int, filters: List[str], max_distance=None, n_probe=None):
         """Exact top-k among the rows answering "yes" to every filter -> (labels [Q,k], distances [Q,k], counts [Q]);
         max_distance: among those of them within that distance."""
         self._push_tags()
@@ -359,7 +362,7 @@ class FlatCollection:
                 req |= 1 << self._filter_bits[f]
         over = [f for f in filters if f in self._filter_overflow]
         if not over:
-            return self._index_query(q, k, max_distance, require=np.uint64(req))
+            return self._index_query(q, k, max_distance, n_probe, require=np.uint64(req))
         # a name past the 64th bit: the mapped bits narrow the query, the rest is checked on the host. Exact as long as the rows
         # passing the mapped bits fit one call (MAX_N_RESULTS); beyond that it is the best MAX_N_RESULTS of them, post-filtered.
         ok = {lab for lab in self._labels if all(answers_yes(filter_answers(self._meta.get(lab)).get(f, "")) for f in filters)}
@@ -376,13 +379,20 @@ class FlatCollection:
         return labs, dist, cnt
 
     def query(self, query_embeddings=None, n_results: int = 10, include: Sequence[str] = ("metadatas", "documents", "distances"),
-              filters: Optional[Sequence[str]] = None, max_distance: Optional[float] = None, **_unused) -> dict:
+              filters: Optional[Sequence[str]] = None, max_distance: Optional[float] = None, n_probe: Optional[int] = None,
+              **_unused) -> dict:
         """collection.query. filters: names of yes/no filters; when given, the result is the exact n_results nearest among the
         rows whose filter_results_json answers "yes" to every one of them (pre-filtering; see the module docstring).
         max_distance: a radius query (FlatIndex.query_radius) — only the rows within that cosine distance are returned, exactly,
         and n_results is the cap on how many (the nearest ones). It combines with filters: the members among the rows the filters
         admit; past 64 filter names the host post-filter of the filtered query applies to the radius result (the best
-        MAX_N_RESULTS members passing the mapped bits, post-filtered)."""
+        MAX_N_RESULTS members passing the mapped bits, post-filtered).
+        n_probe: with a partition present (build_partition), search only the n_probe cells nearest to each query and the rows
+        added since (FlatIndex.query_probed): the exact n_results nearest among those rows, filters included (up to 64 filter
+        names). Without a partition, with max_distance, or with more than 64 filter names it is ignored: the exact answer, never
+        an error. Nothing is written, neither metadata nor journal."""
+        if n_probe is not None and int(n_probe) < 1:
+            raise ValueError(f"n_probe: at least 1, got {n_probe}")
         filters = list(dict.fromkeys(_as_list(filters))) if filters else []
         if query_embeddings is None:
             raise ValueError("FlatCollection.query needs query_embeddings (text embedding functions are out of scope)")
@@ -403,9 +413,9 @@ class FlatCollection:
                     logger.warning(f"n_results={n_results} clamped to {MAX_N_RESULTS}")
                     k = MAX_N_RESULTS
                 if filters:
-                    labs, dist, cnt = self._filtered_query(q, k, filters, max_distance)
+                    labs, dist, cnt = self._filtered_query(q, k, filters, max_distance, n_probe)
                 else:
-                    labs, dist, cnt = self._index_query(q, k, max_distance)
+                    labs, dist, cnt = self._index_query(q, k, max_distance, n_probe)
             label_to_id = dict(zip(self._labels, self._ids))
             out = {"ids": [], "distances": None, "metadatas": None, "documents": None, "embeddings": None,
                    "uris": None, "data": None, "included": include}
@@ -492,6 +502,22 @@ class FlatCollection:
                 raise RuntimeError("index and collection differ in row count")
             out["ids"] = list(self._ids)
             return out
+
+    def build_partition(self, n_cells: int, iters: int = 10) -> dict:
+        """Partition the stored rows into n_cells k-means cells for query(..., n_probe=) (FlatIndex.build_partition) -> its info
+        dict. Rows added afterwards are searched by every probed query; update and delete drop the partition (queries then run
+        flat until it is built again), and it is not persisted. Nothing is written."""
+        with self._lock:
+            if not self._ids or self._index is None:
+                raise ValueError("build_partition on an empty collection")
+            return self._index.build_partition(int(n_cells), iters=int(iters))
+
+    def partition_info(self) -> dict:
+        """FlatIndex.partition_info of the collection's index; "cells" = 0 when there is no partition (or no index yet)."""
+        with self._lock:
+            if self._index is None:
+                return {"cells": 0, "rows": 0, "tail": 0, "rows_in_cells": 0, "largest_cell": 0, "empty_cells": 0, "queries": 0, "scanned": 0}
+            return self._index.partition_info()
 
     def near_duplicates(self, max_distance: float, cap_per_row: int = 64) -> List[tuple]:
         """Every pair of stored rows within cosine distance max_distance, each once (FlatIndex.near_duplicates) ->

@@ -5,6 +5,7 @@
 #include "retrieval_kernels.h"
 #include "membership_kernels.h"
 #include "assign_kernels.h"
+#include "partition_kernels.h"
 #include "gemm_bf16_256.h"
 #include "gemm_strip_p256.h"
 #include <algorithm>
@@ -71,6 +72,20 @@ struct mmiss_index {
     // the borderline rows, the assignment and distances when the caller's are host memory (and a host assignment of
     // cluster_sums), the sums when the caller's are host memory, and the small block: E, live centres, borderline rows, sizes
     DevBuf asg_state, asg_list, asg_out, asg_sums, asg_meta;
+    // partitioned search (mmiss_index_partition_set, mmiss_index_query_probed): the partition — C = 0: none — with the normalised
+    // centres, the cell of each of the first B rows, the rows grouped by cell, the cell offsets, the host mirror of the sizes and
+    // top_prefix[j] = the sum of the j largest of them (the bound on a query's candidates); the queries served and rows scanned
+    // since it was set. Dropped by whatever moves or changes rows (drop_partition).
+    struct Partition {
+        int C = 0;
+        int64_t B = 0, in_cells = 0, largest = 0, empty = 0;
+        DevBuf cn, cells, order, off;
+        std::vector<int64_t> sizes, top_prefix;
+        int64_t queries = 0, scanned = 0;
+    } part;
+    // ... and a probed call's scratch: the probed cells, their key offsets and the totals per query of a chunk, the masks when
+    // the caller's are host memory, the two key areas of the selection, and set's small block (live centres, sizes, cursors)
+    DevBuf prb_cell, prb_base, prb_total, prb_mask, prb_keys_a, prb_keys_b, prb_meta;
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -111,8 +126,18 @@ struct RowStore {
 // the index's row buffers and `s` trade places (the old ones leave with `s`)
 void swap_rows(mmiss_index* ix, RowStore& s) { ix->rows.swap(s.rows); ix->labels_d.swap(s.labels); ix->inv.swap(s.inv); ix->tags.swap(s.tags); }
 
+// Forget the partition of a partitioned search (update, remove, clear, load: rows move or change, and a stale cell would silently
+// lose results). Every partition call returns with its work finished, so nothing queued reads these buffers.
+void drop_partition(mmiss_index* ix) {
+    mmiss_index::Partition& p = ix->part;
+    p.C = 0; p.B = p.in_cells = p.largest = p.empty = p.queries = p.scanned = 0;
+    p.cn.release(); p.cells.release(); p.order.release(); p.off.release();
+    p.sizes.clear(); p.top_prefix.clear();
+}
+
 // Empty the index: no rows, and inverse norms and tags zero up to capacity (the invariant behind `count`); returns drained.
 int reset_rows(mmiss_index* ix, hipStream_t st) {
+    drop_partition(ix);
     ix->count = 0;
     ix->labels_h.clear();
     ix->tags_h.clear();
@@ -469,6 +494,7 @@ extern "C" int mmiss_index_update(mmiss_index* ix, const int64_t* labels, const 
         rows[i] = find_row(ix, lab[i]);
         if (rows[i] < 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_update: label %lld not in the index", (long long)lab[i]);
     }
+    drop_partition(ix);   // (rows change)
     const int D = ix->dim;
     const float* src = vecs;
     if (!mmiss_is_device_ptr(vecs)) {
@@ -500,6 +526,7 @@ extern "C" int mmiss_index_remove(mmiss_index* ix, const int64_t* labels, int64_
     }
     if (removed) *removed = ndrop;
     if (ndrop == 0) return MMISS_OK;
+    drop_partition(ix);   // (rows move)
     const int64_t keep = ix->count - ndrop;
     if (keep == 0) return reset_rows(ix, st);   // every row removed
     std::vector<int64_t> map((size_t)keep), nl((size_t)keep);
@@ -2009,6 +2036,310 @@ extern "C" int mmiss_index_cluster_sums(mmiss_index* ix, const int32_t* assign, 
     return MMISS_OK;
 }
 
+// ================================================================================================ partitioned search
+// An inverted-file search on the centres and cells the assignment calls produce: a query reads only the rows of the nprobe cells
+// whose centres are nearest to it, and the rows added since the partition was set. The approximation is in WHICH rows are looked
+// at — that set is defined exactly (partition_kernels.h) —; within it the answer is the exact top-k with mmiss_index_query's
+// distance bits and order, so probing every cell returns mmiss_index_query's bits. No first pass, no guard: every candidate gets
+// its canonical distance, and the eight guard counters stay as they are.
+namespace {
+
+constexpr int PROBE_MAX_K = 2040;   // the flat query's own limit
+
+// How a probed call of Q queries runs on the partition as it stands. bound: the most keys one query can have (the tail and the
+// NP largest cells, from the host mirror): it sizes the candidate areas and fixes the selection's levels, so nothing has to come
+// back from the device inside a call.
+struct ProbePlan {
+    int NP = 0;                 // probe slots: min(nprobe, C)
+    int splits = 1, share = 64; // workgroups per list of the scan, rows of a list per workgroup
+    int levels = 1;             // segment_topk launches, the FINAL one included
+    int qchunk = 1;             // queries per chunk (the scratch budget)
+    int64_t bound = 0, stride0 = 1, stride1 = 0;   // keys per query of the two key areas
+};
+
+ProbePlan plan_probed(const mmiss_index* ix, int Q, int k, int nprobe) {
+    const mmiss_index::Partition& pt = ix->part;
+    ProbePlan p;
+    p.NP = std::min(nprobe, pt.C);
+    const int64_t tail = ix->count - pt.B;
+    p.bound = tail + pt.top_prefix[(size_t)p.NP];
+    p.stride0 = std::max<int64_t>(p.bound, 1);
+    for (int64_t n = p.bound; n > PROBE_SEG; n = (n + PROBE_SEG - 1) / PROBE_SEG * k) {
+        if (p.levels == 1) p.stride1 = (n + PROBE_SEG - 1) / PROBE_SEG * k;
+        ++p.levels;
+    }
+    // chunks: the key areas of a chunk's queries stay under the budget (one query always runs, whatever it needs)
+    const int64_t budget = (int64_t)mmiss_option("probe_scratch_kb", 512 * 1024) * 1024;
+    const int64_t per_query = (p.stride0 + p.stride1) * 8;
+    p.qchunk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(Q, 32768), budget / per_query));
+    // the scan: about eight workgroups per CU over (lists x queries of a chunk), 64 rows per workgroup at the least, so that a
+    // single query with few probes still fills the chip
+    const int64_t maxlist = std::max(tail, pt.largest);
+    const int64_t lists = (int64_t)p.qchunk * (p.NP + 1);
+    const int64_t want = std::max<int64_t>(1, (2048 + lists - 1) / lists);
+    p.share = (int)std::max<int64_t>(64, round_up((maxlist + want - 1) / want, 16));
+    p.splits = (int)std::max<int64_t>(1, (maxlist + p.share - 1) / p.share);
+    return p;
+}
+
+// what the partition calls check alike
+#define MM_NEED_PARTITION(ix, who) \
+    do { if ((ix)->part.C == 0) MM_FAIL(MMISS_ERR_STATE, "%s: the index has no partition (mmiss_index_partition_set)", who); } while (0)
+
+// n bytes from src (host or device) to dst (host or device), queued on st
+int copy_any(void* dst, const void* src, size_t n, hipStream_t st) {
+    if (n == 0) return MMISS_OK;
+    const bool sd = mmiss_is_device_ptr(src), dd = mmiss_is_device_ptr(dst);
+    if (!sd && !dd) { memcpy(dst, src, n); return MMISS_OK; }
+    MM_HIP(hipMemcpyAsync(dst, src, n, sd ? (dd ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost) : hipMemcpyHostToDevice, st));
+    return MMISS_OK;
+}
+
+}  // namespace
+
+extern "C" int mmiss_index_partition_set(mmiss_index* ix, const float* centres, int32_t C, const int32_t* cells, int64_t n) {
+    const char* who = "mmiss_index_partition_set";
+    if (!ix) MM_FAIL(MMISS_ERR_ARG, "%s: null index", who);
+    if (C < 1 || C > PROBE_MAX_CENTRES) MM_FAIL(MMISS_ERR_ARG, "%s: C = %d (1 .. %d centres)", who, C, PROBE_MAX_CENTRES);
+    if (!centres || n < 0 || (n > 0 && !cells)) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    if (n != ix->count) MM_FAIL(MMISS_ERR_ARG, "%s: %lld cells for %lld rows", who, (long long)n, (long long)ix->count);
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    const int D = ix->dim;
+    // everything is built into fresh buffers and swapped in at the end: a refused call keeps the previous partition
+    mmiss_index::Partition fresh;
+    MM_TRY(fresh.cn.alloc((size_t)C * D * 4));
+    MM_TRY(fresh.cells.alloc((size_t)std::max<int64_t>(n, 1) * 4));
+    MM_TRY(fresh.off.alloc((size_t)(C + 1) * 4));
+    // the small block: live [1024] int32, sizes [1024] u64, cursors [1024] int32
+    MM_TRY(ix->prb_meta.ensure((size_t)PROBE_MAX_CENTRES * 16));
+    int32_t* const d_live = ix->prb_meta.as<int32_t>();
+    unsigned long long* const d_sizes = reinterpret_cast<unsigned long long*>(ix->prb_meta.as<char>() + (size_t)PROBE_MAX_CENTRES * 4);
+    int32_t* const d_cursor = reinterpret_cast<int32_t*>(ix->prb_meta.as<char>() + (size_t)PROBE_MAX_CENTRES * 12);
+    const float* src = centres;
+    if (!mmiss_is_device_ptr(centres)) {
+        MM_TRY(ix->stage.ensure((size_t)C * D * 4));
+        MM_HIP(hipMemcpyAsync(ix->stage.p, centres, (size_t)C * D * 4, hipMemcpyHostToDevice, st));
+        src = ix->stage.as<float>();
+    }
+    {   // the canonical normalisation of an f32 row: what oracle normalize_rows(centres, "f32") restates
+        MM_PROF("normalize_rows", st, 4.0 * C * D, 8.0 * C * D);
+        hipLaunchKernelGGL(normalize_rows_kernel<float>, dim3((C + 3) / 4), dim3(256), 0, st, src, fresh.cn.as<float>(), (int64_t)C, D);
+        MM_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(partition_live_kernel, dim3((C + 3) / 4), dim3(256), 0, st, (const float*)fresh.cn.as<float>(), (int)C, D, d_live);
+    MM_HIP(hipGetLastError());
+    MM_TRY(copy_any(fresh.cells.p, cells, (size_t)n * 4, st));
+    MM_HIP(hipMemsetAsync(d_sizes, 0, (size_t)C * 8, st));
+    if (n > 0) {
+        hipLaunchKernelGGL(assign_sizes_kernel, dim3((int)std::min<int64_t>(1024, (n + 255) / 256)), dim3(256), 0, st,
+                           (const int32_t*)fresh.cells.as<int32_t>(), n, (int)C, d_sizes);
+        MM_HIP(hipGetLastError());
+    }
+    std::vector<int32_t> live((size_t)C);
+    std::vector<unsigned long long> sizes((size_t)C);
+    MM_HIP(hipMemcpyAsync(live.data(), d_live, (size_t)C * 4, hipMemcpyDeviceToHost, st));
+    MM_HIP(hipMemcpyAsync(sizes.data(), d_sizes, (size_t)C * 8, hipMemcpyDeviceToHost, st));
+    MM_HIP(hipStreamSynchronize(st));
+    if (std::find(live.begin(), live.end(), 1) == live.end())
+        MM_FAIL(MMISS_ERR_ARG, "%s: none of the %d centres has a direction; the previous partition is kept", who, C);
+    // the counting sort: offsets = the prefix of the sizes, then the scatter
+    std::vector<int32_t> off((size_t)C + 1, 0);
+    fresh.C = C; fresh.B = n;
+    fresh.sizes.resize((size_t)C);
+    for (int c = 0; c < C; ++c) {
+        const int64_t sz = (int64_t)sizes[(size_t)c];
+        fresh.sizes[(size_t)c] = sz;
+        off[(size_t)c + 1] = off[(size_t)c] + (int32_t)sz;
+        fresh.largest = std::max(fresh.largest, sz);
+        fresh.empty += sz == 0;
+    }
+    fresh.in_cells = off[(size_t)C];
+    std::vector<int64_t> desc(fresh.sizes);
+    std::sort(desc.begin(), desc.end(), std::greater<int64_t>());
+    fresh.top_prefix.assign((size_t)C + 1, 0);
+    for (int c = 0; c < C; ++c) fresh.top_prefix[(size_t)c + 1] = fresh.top_prefix[(size_t)c] + desc[(size_t)c];
+    MM_TRY(fresh.order.alloc((size_t)std::max<int64_t>(fresh.in_cells, 1) * 4));
+    MM_HIP(hipMemcpyAsync(fresh.off.p, off.data(), (size_t)(C + 1) * 4, hipMemcpyHostToDevice, st));
+    MM_HIP(hipMemcpyAsync(d_cursor, off.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
+    if (n > 0) {
+        MM_PROF("partition_fill", st, 0.0, 8.0 * n);
+        hipLaunchKernelGGL(partition_fill_kernel, dim3((int)((n + PART_FILL_ROWS - 1) / PART_FILL_ROWS)), dim3(256), 0, st,
+                           (const int32_t*)fresh.cells.as<int32_t>(), n, (int)C, d_cursor, fresh.order.as<int32_t>());
+        MM_HIP(hipGetLastError());
+    }
+    MM_HIP(hipStreamSynchronize(st));
+    mmiss_index::Partition& pt = ix->part;
+    pt.C = fresh.C; pt.B = fresh.B; pt.in_cells = fresh.in_cells; pt.largest = fresh.largest; pt.empty = fresh.empty;
+    pt.cn.swap(fresh.cn); pt.cells.swap(fresh.cells); pt.order.swap(fresh.order); pt.off.swap(fresh.off);
+    pt.sizes.swap(fresh.sizes); pt.top_prefix.swap(fresh.top_prefix);
+    pt.queries = 0; pt.scanned = 0;
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_partition_clear(mmiss_index* ix) {
+    if (!ix) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_partition_clear: null index");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, "mmiss_index_partition_clear");
+    drop_partition(ix);
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_partition_info(mmiss_index* ix, int64_t out[8]) {
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_partition_info: null argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, "mmiss_index_partition_info");
+    const mmiss_index::Partition& pt = ix->part;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (pt.C == 0) return MMISS_OK;
+    out[0] = pt.C; out[1] = pt.B; out[2] = ix->count - pt.B; out[3] = pt.in_cells; out[4] = pt.largest; out[5] = pt.empty;
+    out[6] = pt.queries; out[7] = pt.scanned;
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_partition_get(mmiss_index* ix, float* centres, int32_t* cells, int64_t cap_rows, int64_t* sizes) {
+    const char* who = "mmiss_index_partition_get";
+    if (!ix) MM_FAIL(MMISS_ERR_ARG, "%s: null index", who);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    MM_NEED_PARTITION(ix, who);
+    const mmiss_index::Partition& pt = ix->part;
+    if (cells && cap_rows < pt.B) MM_FAIL(MMISS_ERR_ARG, "%s: cap_rows = %lld for %lld cells", who, (long long)cap_rows, (long long)pt.B);
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    if (centres) MM_TRY(copy_any(centres, pt.cn.p, (size_t)pt.C * ix->dim * 4, st));
+    if (cells) MM_TRY(copy_any(cells, pt.cells.p, (size_t)pt.B * 4, st));
+    if (sizes) MM_TRY(copy_any(sizes, pt.sizes.data(), (size_t)pt.C * 8, st));
+    MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_query_probed(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int32_t nprobe, const uint64_t* require,
+                                        const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_scanned) {
+    const char* who = "mmiss_index_query_probed";
+    if (!ix || !queries || !out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || nprobe < 1) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d nprobe=%d", who, Q, k, nprobe);
+    if (k > PROBE_MAX_K) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: k = %d too large (max %d)", who, k, PROBE_MAX_K);
+    const bool out_dev = mmiss_is_device_ptr(out_labels);
+    if (out_dev != mmiss_is_device_ptr(out_dist) || out_dev != mmiss_is_device_ptr(out_count) ||
+        (out_scanned && out_dev != mmiss_is_device_ptr(out_scanned)))
+        MM_FAIL(MMISS_ERR_ARG, "%s: output pointers must be all host or all device", who);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    MM_NEED_PARTITION(ix, who);
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    mmiss_index::Partition& pt = ix->part;
+    const int D = ix->dim;
+    const int tail = (int)(ix->count - pt.B);
+    const ProbePlan p = plan_probed(ix, Q, k, nprobe);
+    // outputs: the caller's device buffers, or a pinned host block the last kernel writes straight into; the scanned rows always
+    // go to a pinned block (the partition's counter adds them up) and from there to the caller
+    int64_t* d_lab = out_labels; float* d_dist = out_dist; int32_t* d_cnt = out_count;
+    if (!out_dev) {
+        const size_t o_dist = (size_t)Q * k * 8, o_cnt = o_dist + (size_t)Q * k * 4;
+        const size_t need = o_cnt + (size_t)Q * 4;
+        size_t grow = 4096;
+        while (grow < need) grow *= 2;
+        MM_TRY(ix->pin.ensure(need, st, grow));
+        char* const pin = ix->pin.as<char>();
+        d_lab = reinterpret_cast<int64_t*>(pin); d_dist = reinterpret_cast<float*>(pin + o_dist); d_cnt = reinterpret_cast<int32_t*>(pin + o_cnt);
+    }
+    MM_TRY(ix->swp_pin.ensure((size_t)Q * 8, st, (size_t)std::max(Q, 512) * 8));
+    int64_t* const h_scn = ix->swp_pin.as<int64_t>();
+    MM_TRY(upload_queries(ix, st, queries, Q));   // qn of every query of the call
+    const uint64_t* d_req = require; const uint64_t* d_exc = exclude;
+    if ((require && !mmiss_is_device_ptr(require)) || (exclude && !mmiss_is_device_ptr(exclude))) {
+        MM_TRY(ix->prb_mask.ensure((size_t)Q * 16));
+        if (require && !mmiss_is_device_ptr(require)) {
+            MM_HIP(hipMemcpyAsync(ix->prb_mask.p, require, (size_t)Q * 8, hipMemcpyHostToDevice, st));
+            d_req = ix->prb_mask.as<uint64_t>();
+        }
+        if (exclude && !mmiss_is_device_ptr(exclude)) {
+            MM_HIP(hipMemcpyAsync(ix->prb_mask.as<uint64_t>() + Q, exclude, (size_t)Q * 8, hipMemcpyHostToDevice, st));
+            d_exc = ix->prb_mask.as<uint64_t>() + Q;
+        }
+    }
+    MM_TRY(ix->prb_cell.ensure((size_t)p.qchunk * std::max(p.NP, 1) * 4));
+    MM_TRY(ix->prb_base.ensure((size_t)p.qchunk * (p.NP + 1) * 4));
+    MM_TRY(ix->prb_total.ensure((size_t)p.qchunk * 4));
+    MM_TRY(ix->prb_keys_a.ensure((size_t)p.qchunk * p.stride0 * 8));
+    if (p.stride1) MM_TRY(ix->prb_keys_b.ensure((size_t)p.qchunk * p.stride1 * 8));
+    const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
+    for (int q0 = 0; q0 < Q; q0 += p.qchunk) {
+        const int Qc = std::min(p.qchunk, Q - q0);
+        const float* qn = ix->qn.as<float>() + (size_t)q0 * D;
+        {
+            ProbeSelectArgs a{};
+            a.qn = qn; a.cn = pt.cn.as<float>(); a.off = pt.off.as<int32_t>(); a.C = pt.C; a.D = D; a.NP = p.NP; a.tail = tail;
+            a.probe_cell = ix->prb_cell.as<int32_t>(); a.probe_base = ix->prb_base.as<int32_t>(); a.total = ix->prb_total.as<int32_t>();
+            MM_PROF("probe_select", st, 2.0 * Qc * pt.C * D, 4.0 * pt.C * D);
+            hipLaunchKernelGGL(probe_select_kernel, dim3(Qc), dim3(1024), 0, st, a);
+            MM_HIP(hipGetLastError());
+        }
+        {
+            ListScanArgs a{};
+            a.rows = ix->rows.p; a.inv = ix->inv.as<float>(); a.tags = ix->tags.as<uint64_t>(); a.qn = qn;
+            a.req = d_req ? d_req + q0 : nullptr; a.exc = d_exc ? d_exc + q0 : nullptr;
+            a.order = pt.order.as<int32_t>(); a.off = pt.off.as<int32_t>();
+            a.probe_cell = ix->prb_cell.as<int32_t>(); a.probe_base = ix->prb_base.as<int32_t>(); a.total = ix->prb_total.as<int32_t>();
+            a.D = D; a.NP = p.NP; a.share = p.share; a.B = pt.B; a.tail = tail;
+            a.keys = ix->prb_keys_a.as<unsigned long long>(); a.stride = p.stride0;
+            MM_PROF(f16 ? "list_scan_f16" : f8 ? "list_scan_f8" : "list_scan_f32", st, 2.0 * Qc * (double)p.bound * D,
+                    (double)Qc * p.bound * (D * ix->elt + 12));
+            with_storage(ix->dtype, [&](auto s) {
+                hipLaunchKernelGGL(list_scan_kernel<typename decltype(s)::T>, dim3(p.splits, p.NP + 1, Qc), dim3(256), 0, st, a);
+            });
+            MM_HIP(hipGetLastError());
+        }
+        int64_t nb = p.bound;   // the most keys a query has at this level
+        for (int l = 0; l < p.levels; ++l) {
+            const bool last = l == p.levels - 1;
+            const bool from_a = (l & 1) == 0;
+            const int nseg = last ? 1 : (int)((nb + PROBE_SEG - 1) / PROBE_SEG);
+            SegmentTopkArgs a{};
+            a.in = from_a ? ix->prb_keys_a.as<unsigned long long>() : ix->prb_keys_b.as<unsigned long long>();
+            a.out = from_a ? ix->prb_keys_b.as<unsigned long long>() : ix->prb_keys_a.as<unsigned long long>();
+            a.in_stride = from_a ? p.stride0 : p.stride1; a.out_stride = from_a ? p.stride1 : p.stride0;
+            a.total = ix->prb_total.as<int32_t>(); a.level = l; a.k = k;
+            a.labels = ix->labels_d.as<int64_t>();
+            a.out_labels = d_lab + (size_t)q0 * k; a.out_dist = d_dist + (size_t)q0 * k; a.out_count = d_cnt + q0; a.out_scanned = h_scn + q0;
+            MM_PROF("segment_topk", st, 0.0, (double)Qc * nb * 8);
+            if (last) hipLaunchKernelGGL(segment_topk_kernel<true>, dim3(1, Qc), dim3(1024), 0, st, a);
+            else hipLaunchKernelGGL(segment_topk_kernel<false>, dim3(nseg, Qc), dim3(1024), 0, st, a);
+            MM_HIP(hipGetLastError());
+            nb = (int64_t)nseg * k;
+        }
+    }
+    if (out_dev && out_scanned) MM_HIP(hipMemcpyAsync(out_scanned, h_scn, (size_t)Q * 8, hipMemcpyHostToDevice, st));
+    MM_HIP(hipStreamSynchronize(st));
+    if (!out_dev) {
+        memcpy(out_labels, d_lab, (size_t)Q * k * 8);
+        memcpy(out_dist, d_dist, (size_t)Q * k * 4);
+        memcpy(out_count, d_cnt, (size_t)Q * 4);
+        if (out_scanned) memcpy(out_scanned, h_scn, (size_t)Q * 8);
+    }
+    pt.queries += Q;
+    for (int q = 0; q < Q; ++q) pt.scanned += h_scn[q];
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: how a probed call of this shape would run on the partition as it stands (plan_probed, nothing launched).
+extern "C" int mmiss_dbg_index_probe_plan(mmiss_index* ix, int32_t Q, int32_t k, int32_t nprobe, int32_t* out) {
+    const char* who = "mmiss_dbg_index_probe_plan";
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || k > PROBE_MAX_K || nprobe < 1) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d nprobe=%d", who, Q, k, nprobe);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NEED_PARTITION(ix, who);
+    const ProbePlan p = plan_probed(ix, Q, k, nprobe);
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = p.splits; out[1] = PROBE_SEG; out[2] = p.levels; out[3] = p.qchunk;
+    out[4] = (int32_t)std::min<int64_t>(p.bound, INT32_MAX); out[5] = p.share; out[6] = p.NP; out[7] = (Q + p.qchunk - 1) / p.qchunk;
+    return MMISS_OK;
+}
+
 // mmiss_debug.h: the path a radius call of Q queries would take on the index as it stands, chunk by chunk: the functions
 // radius_chunk itself calls, nothing launched, no state changed.
 extern "C" int mmiss_dbg_index_radius_plan(mmiss_index* ix, int32_t Q, int32_t filtered, int32_t* out) {
@@ -2214,6 +2545,7 @@ extern "C" int mmiss_index_load(mmiss_index* ix, const char* path) {
     if (!ok) { fclose(f); MM_FAIL(MMISS_ERR_IO, "%s: labels unreadable or not strictly increasing; the index is unchanged", path); }
     int rc = index_reserve(ix, h.count, st);
     if (rc != MMISS_OK) { fclose(f); return rc; }
+    drop_partition(ix);   // (the rows are replaced; the file holds no partition)
     rc = load_rows(ix, f, path, h.count, lab, st);
     fclose(f);
     if (rc != MMISS_OK) {

@@ -512,6 +512,99 @@ class FlatIndex:
             asg, dist, sizes = self.assign(centres, want_dist=True)
         return {"centres": centres, "assign": asg, "dist": dist, "sizes": sizes, "iterations": done}
 
+    # ------------------------------------------------------------------ partitioned search
+    MAX_K = 2040
+    PARTITION_INFO_FIELDS = ("cells", "rows", "tail", "rows_in_cells", "largest_cell", "empty_cells", "queries", "scanned")
+
+    def set_partition(self, centres, cells) -> None:
+        """Give the index a partition (mmiss_index_partition_set): centres [C, dim] (1 <= C <= 1024, any norm) and cells int32
+        [count], the cell of every row in the order of labels() (an entry outside 0 .. C-1, assign()'s -1, puts the row in no
+        cell) — what assign() / kmeans() return. numpy arrays or CUDA tensors, each. Rows added later are the tail: candidates
+        of every probed query. update / remove / clear / load drop the partition; save does not persist it."""
+        c, _cuda = self._centres(centres)
+        cuda_cells = _is_torch(cells) and cells.is_cuda
+        if cuda_cells:
+            import torch
+
+            if cells.dtype.is_floating_point or cells.dtype == torch.bool:
+                raise TypeError(f"cells must be integers, got {cells.dtype}")
+            a = cells.to(torch.int32).contiguous()
+        else:
+            a = np.asarray(cells.numpy() if _is_torch(cells) else cells)
+            if a.dtype.kind not in "ui":
+                raise TypeError(f"cells must be integers, got {a.dtype}")
+            a = np.ascontiguousarray(a.astype(np.int32))
+        if a.ndim != 1:
+            raise ValueError(f"cells: expected one entry per row, got shape {tuple(a.shape)}")
+        with self._call_lock:
+            self._sync_stream(c if _cuda else (a if cuda_cells else None))
+            _lib.check(self._lib.mmiss_index_partition_set(self._h, _lib.ptr(c), int(c.shape[0]), _lib.ptr(a) if a.shape[0] else None,
+                                                           int(a.shape[0])))
+
+    def clear_partition(self) -> None:
+        with self._call_lock:
+            _lib.check(self._lib.mmiss_index_partition_clear(self._h))
+
+    def partition_info(self) -> dict:
+        """mmiss_index_partition_info as a dict: cells (C; 0 = no partition), rows (B, the rows it was set on), tail (rows added
+        since), rows_in_cells, largest_cell, empty_cells, queries (probed queries served since it was set), scanned (rows they
+        looked at)."""
+        out = (C.c_int64 * 8)()
+        with self._call_lock:
+            _lib.check(self._lib.mmiss_index_partition_info(self._h, out))
+        return dict(zip(self.PARTITION_INFO_FIELDS, (int(v) for v in out)))
+
+    def partition(self):
+        """The partition as stored (mmiss_index_partition_get) -> (centres float32 [C, dim], NORMALISED; cells int32 [B]; sizes
+        int64 [C]), numpy. No partition raises."""
+        with self._call_lock:
+            info = self.partition_info()
+            if info["cells"] == 0:
+                _lib.check(self._lib.mmiss_index_partition_get(self._h, None, None, 0, None))   # (raises: no partition)
+            centres = np.empty((info["cells"], self.dim), dtype=np.float32)
+            cells = np.empty(info["rows"], dtype=np.int32)
+            sizes = np.empty(info["cells"], dtype=np.int64)
+            _lib.check(self._lib.mmiss_index_partition_get(self._h, centres.ctypes.data, cells.ctypes.data if cells.size else None,
+                                                           int(cells.shape[0]), sizes.ctypes.data))
+        return centres, cells, sizes
+
+    def build_partition(self, n_cells: int, iters: int = 10, init=None) -> dict:
+        """kmeans(n_cells, iters, init) followed by set_partition(its centres, its assignment), as one unit on this handle ->
+        partition_info()."""
+        with self._call_lock:
+            out = self.kmeans(n_cells, iters=iters, init=init)
+            self.set_partition(out["centres"], out["assign"])
+            return self.partition_info()
+
+    def query_probed(self, queries, k: int, nprobe: int, require=None, exclude=None):
+        """The exact top-k among the rows of the nprobe cells whose centres are nearest to each query, and the tail
+        (mmiss_index_query_probed) -> (labels int64 [Q,k], distances float32 [Q,k], counts int32 [Q], scanned int64 [Q]): the
+        distance bits and the order of query(); with every cell probed, query()'s result. A row in an unprobed cell is not
+        returned however near it is. scanned[q] = the rows looked at for query q. require / exclude as in query(). 1 <= k <=
+        2040, nprobe >= 1 (above the cell count: every cell). numpy in -> numpy out, CUDA tensor in -> CUDA tensors out. No
+        partition raises."""
+        k, nprobe = int(k), int(nprobe)
+        if not 1 <= k <= self.MAX_K:
+            raise ValueError(f"k: 1 .. {self.MAX_K}, got {k}")
+        if nprobe < 1:
+            raise ValueError(f"nprobe: at least 1, got {nprobe}")
+        q, (lab, dist, cnt) = self._prepare(queries, k)
+        Q = int(q.shape[0])
+        if Q < 1:
+            raise ValueError("query_probed takes at least one query")
+        masks = self._masks(q, require, exclude) or (None, None)
+        if _is_torch(q) and q.is_cuda:
+            import torch
+
+            scanned = torch.empty((Q,), dtype=torch.int64, device=q.device)
+        else:
+            scanned = np.empty((Q,), dtype=np.int64)
+        with self._call_lock:
+            self._sync_stream(q)
+            _lib.check(self._lib.mmiss_index_query_probed(self._h, _lib.ptr(q), Q, k, nprobe, _lib.ptr(masks[0]), _lib.ptr(masks[1]),
+                                                          _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt), _lib.ptr(scanned)))
+        return lab, dist, cnt, scanned
+
     def guard_stats(self) -> dict:
         """Exactness accounting (mmiss_index_guard_stats_ex): queries served, queries whose first pass could not be proven
         exact and were widened, widen (threshold) passes run, extra passes over the index they cost, the queries that ended in

@@ -66,25 +66,28 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
     return similar_images
 
 
-def _filter_kw(filters, min_similarity=None) -> dict:
-    """the keyword arguments of FlatCollection.query for a search's filters and similarity threshold; min_similarity = s becomes
-    the radius utils.max_distance_for_similarity(s): on its results "similarity_score >= s" holds for exactly the members"""
+def _filter_kw(filters, min_similarity=None, n_probe=None) -> dict:
+    """the keyword arguments of FlatCollection.query for a search's filters, similarity threshold and probe count; min_similarity =
+    s becomes the radius utils.max_distance_for_similarity(s): on its results "similarity_score >= s" holds for exactly the members"""
     kw = {"filters": list(filters)} if filters else {}
     if min_similarity is not None:
         kw["max_distance"] = float(utils.max_distance_for_similarity(min_similarity))
+    if n_probe is not None:
+        kw["n_probe"] = int(n_probe)
     return kw
 
 
 def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
-                   min_similarity: Optional[float] = None) -> List[Dict]:
+                   min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[Dict]:
     """Search for similar images using an embedding (main.py:748-805). min_similarity: only the images whose similarity_score
     reaches it, exactly (a radius query; `limit` caps how many) — the reference's roadmap item "Adjustable similarity
-    thresholds" (CHANGELOG.md:475)."""
+    thresholds" (CHANGELOG.md:475). n_probe: search only the n_probe k-means cells nearest to the embedding, and what was added
+    since (build_search_partition; FlatCollection.query(n_probe=)); without a partition the search is the exact one."""
     try:
         actual_limit = 1000 if limit <= 0 else limit  # "All" option (limit of 0), main.py:757
         results = _collection().query(query_embeddings=[np.asarray(embedding, dtype=np.float32).tolist()],
                                       n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity))
+                                      **_filter_kw(filters, min_similarity, n_probe))
         out = _results_from_query(results, 0)
         logger.info(f"Found {len(out)} similar images")
         return out
@@ -94,13 +97,13 @@ def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[
 
 
 def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
-                         min_similarity: Optional[float] = None) -> List[List[Dict]]:
+                         min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[List[Dict]]:
     """[Q, D] embeddings -> one result list per query, one index pass for the whole batch."""
     try:
         actual_limit = 1000 if limit <= 0 else limit
         q = np.asarray(embeddings, dtype=np.float32)
         results = _collection().query(query_embeddings=q, n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity))
+                                      **_filter_kw(filters, min_similarity, n_probe))
         return [_results_from_query(results, qi) for qi in range(q.shape[0])]
     except Exception as e:
         logger.error(f"Error searching for similar images: {e}")
@@ -108,20 +111,20 @@ def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Op
 
 
 def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
-                   min_similarity: Optional[float] = None) -> List[Dict]:
+                   min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[Dict]:
     """Search for images using a text query (main.py:807-827)."""
     try:
         model, processor = utils.load_clip_model()
         embedding_result = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)
         text_embedding = embedding_result["text"][0]
-        return search_similar(embedding=text_embedding, limit=limit, filters=filters, min_similarity=min_similarity)
+        return search_similar(embedding=text_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe)
     except Exception as e:
         logger.error(f"Error in text search: {e}")
         return []
 
 
 def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: int = 10, *,
-                      filters: Optional[Sequence[str]] = None, min_similarity: Optional[float] = None) -> List[Dict]:
+                      filters: Optional[Sequence[str]] = None, min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[Dict]:
     """Search using both image and text with a weighted combination (main.py:829-867); weight_image is not
     clamped, as in the backend route."""
     try:
@@ -130,7 +133,7 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
         text_embedding = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)["text"][0]
         # normalise both, weighted sum, normalise again (main.py:852-860) — one GPU kernel
         combined_embedding = blend(image_embedding[None], text_embedding[None], weight_image)[0]
-        return search_similar(embedding=combined_embedding, limit=limit, filters=filters, min_similarity=min_similarity)
+        return search_similar(embedding=combined_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
@@ -138,11 +141,11 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
 
 def search_multimodal_batch(image_embeddings: np.ndarray, text_embeddings: np.ndarray, weight_image: float = 0.5,
                             limit: int = 10, *, filters: Optional[Sequence[str]] = None,
-                            min_similarity: Optional[float] = None) -> List[List[Dict]]:
+                            min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[List[Dict]]:
     """BASELINE config 4: a batch of (image, text) embedding pairs, blended and searched in one pass."""
     try:
         return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit, filters=filters,
-                                    min_similarity=min_similarity)
+                                    min_similarity=min_similarity, n_probe=n_probe)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
@@ -183,6 +186,12 @@ def apply_image_filter(image, name: str, min_similarity: float) -> int:
     embedding = utils.generate_clip_embedding(image=image, model=model, processor=processor)["image"][0]
     return _collection().add_similarity_filter(name, np.asarray(embedding, dtype=np.float32),
                                                float(utils.max_distance_for_similarity(min_similarity)))
+
+
+def build_search_partition(n_cells: int, iters: int = 10) -> dict:
+    """Partition the collection into n_cells k-means cells so that the searches' n_probe has something to probe
+    (FlatCollection.build_partition) -> its info dict. Raises what the collection raises."""
+    return _collection().build_partition(int(n_cells), iters=int(iters))
 
 
 def _near_duplicate_of(col, embedding, near_duplicate_similarity):
