@@ -198,8 +198,9 @@ int mmiss_dbg_resize_coeffs(int device, void* hip_stream, int32_t H, int32_t W, 
 int mmiss_dbg_resize_crop_variant(int64_t blob_bytes, int32_t max_ksx);
 
 /* The plan a query call of Q queries and this k (filtered != 0: a filtered one) would follow on the index as it stands, and the
- * plan of the widen pass if `flagged` (0 .. Q) of its queries were flagged: the query path's own planning functions, evaluated
- * on the host. Launches nothing, changes nothing, needs no device. out is a HOST int32 [24]; fields that do not apply are 0:
+ * plan of the widen pass if `flagged` (0 .. Q) of its queries were flagged: the query path's own planning functions (plan_query,
+ * and from csrc/index_plans.h plan_scan, plan_dense, strip_length, select_splits, merge_two_level), evaluated on the host.
+ * Launches nothing, changes nothing, needs no device. out is a HOST int32 [24]; fields that do not apply are 0:
  *   [0] dense   [1] dense8   [2] big   [3] strip_v3   [4] sample   [5] kp (k')   [6] pages
  *   dense first pass:  [7] Mq   [8] Npad   [9] ns_tiles (the sample, when [4])   [10] strip (when [2])   [16] splits of select_topk
  *                      [23] groups per split
@@ -210,7 +211,8 @@ struct mmiss_index;
 int mmiss_dbg_index_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int32_t filtered, int32_t flagged, int32_t* out);
 /* The path a radius call (mmiss_index_query_radius*) of Q queries (filtered != 0: with masks) would take on the index as it
  * stands: its chunks of at most 1024 queries and the threshold pass of the first and of the last chunk (every chunk but the last
- * is a full one). Launches nothing, changes nothing, needs no device. out is a HOST int32 [16]; fields that do not apply are 0:
+ * is a full one; strip_length and plan_dense of csrc/index_plans.h). Launches nothing, changes nothing, needs no device. out is a
+ * HOST int32 [16]; fields that do not apply are 0:
  *   [0] chunks
  *   first chunk: [1] queries   [2] 1 = strip score GEMM, 0 = scan;  GEMM: [3] strip;  scan: [4] nqt  [5] slabs  [6] tiles_per_block
  *                [7] qtiles
@@ -230,7 +232,7 @@ int mmiss_dbg_index_read_rows(struct mmiss_index* ix, int64_t row0, int64_t n, v
 int mmiss_dbg_index_prep_queries(struct mmiss_index* ix, const float* queries, int32_t Q, float* qn_out, void* qs_out, float* eps_out);
 /* How a probed call (mmiss_index_query_probed) of Q queries, this k (1 .. 2040) and this nprobe would run on the index's partition
  * as it stands and under the options as they stand (probe_scratch_kb: the scratch budget in KB, default 512 * 1024): the call's own
- * planning function, evaluated on the host. Launches nothing, changes nothing. No partition -> MMISS_ERR_STATE. out is a HOST int32 [8]:
+ * planning function (plan_probed, csrc/index_plans.h), evaluated on the host. Launches nothing, changes nothing. No partition -> MMISS_ERR_STATE. out is a HOST int32 [8]:
  *   [0] splits: workgroups per list of the scan   [1] segment size of the selection (keys)   [2] levels: segment_topk launches
  *   per chunk, the last (the one that writes the results) included   [3] queries per chunk   [4] the bound on one query's
  *   candidates (the tail and the min(nprobe, C) largest cells)   [5] share: rows of a list per scan workgroup   [6] probe slots

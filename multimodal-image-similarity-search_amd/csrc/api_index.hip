@@ -9,6 +9,46 @@
 #include "gemm_bf16_256.h"
 #include "gemm_strip_p256.h"
 #include <algorithm>
+#include "index_plans.h"
+
+static_assert(PLAN_SELECT_UNIT == SELECT_UNIT && PLAN_PROBE_SEG == PROBE_SEG, "index_plans.h repeats what the kernel headers fix");
+
+// The results of a query-like call of Q queries: `slots` labels and distances and a count per query, for some calls a total and
+// a flag per query. lab / tot / dist / cnt are where the kernels write them: the caller's device buffers, or a pinned host block
+// the last kernel writes straight into — the call then ends with ONE stream synchronisation and no copy-engine operation (round
+// 3: four small device-to-host copies used to sit there, ~25 us) — and deliver() hands over. Flags are the host's own and always
+// lie in the pinned block. The block's layout and grow rule: result_layout (index_plans.h).
+struct ResultBlock {
+    int64_t* lab = nullptr; int64_t* tot = nullptr; float* dist = nullptr; int32_t* cnt = nullptr; int32_t* flags = nullptr;
+    bool dev = false;
+    int64_t Q = 0, slots = 0;
+    int64_t* out_lab = nullptr; int64_t* out_tot = nullptr; float* out_dist = nullptr; int32_t* out_cnt = nullptr;   // the caller's
+    // out_cnt_ / out_tot_ may be null: device outputs then leave cnt / tot null for the caller to point at scratch of its own
+    int stage(PinBuf& pin, hipStream_t st, int64_t Q_, int64_t slots_, bool dev_, bool totals, bool with_flags, int64_t* out_lab_,
+              float* out_dist_, int32_t* out_cnt_, int64_t* out_tot_) {
+        Q = Q_; slots = slots_; dev = dev_;
+        lab = out_lab = out_lab_; dist = out_dist = out_dist_; cnt = out_cnt = out_cnt_; tot = out_tot = out_tot_;
+        flags = nullptr;
+        if (dev && !with_flags) return MMISS_OK;
+        const ResultLayout l = result_layout(Q, slots, totals, with_flags);
+        MM_TRY(pin.ensure(l.need, st, l.grow));
+        char* const b = pin.as<char>();
+        if (with_flags) flags = reinterpret_cast<int32_t*>(b + l.flags);
+        if (!dev) {
+            lab = reinterpret_cast<int64_t*>(b); tot = totals ? reinterpret_cast<int64_t*>(b + l.tot) : nullptr;
+            dist = reinterpret_cast<float*>(b + l.dist); cnt = reinterpret_cast<int32_t*>(b + l.cnt);
+        }
+        return MMISS_OK;
+    }
+    // host outputs, once the stream has drained
+    void deliver() const {
+        if (dev) return;
+        memcpy(out_lab, lab, (size_t)Q * slots * 8);
+        memcpy(out_dist, dist, (size_t)Q * slots * 4);
+        if (out_cnt) memcpy(out_cnt, cnt, (size_t)Q * 4);
+        if (out_tot) memcpy(out_tot, tot, (size_t)Q * 8);
+    }
+};
 
 struct mmiss_index {
     int dim = 0, dtype = MMISS_F32, device = 0, elt = 4;
@@ -41,18 +81,14 @@ struct mmiss_index {
     DevBuf qmap, qmap64, qs2, cand2;
     DevBuf eps_q, thr, thr2, swp_cnt, swp_list;   // per-query error bound, sweep thresholds (all / flagged queries), appended rows
     DevBuf seed_s, seed_r, fcnt, fbuf_s, fbuf_g;  // threshold-filtered selection (Q > 128)
-    // Pinned, device-visible host block a query's LAST kernel (the rerank) writes straight into: the guard's per-query flags
-    // always, and labels / distances / counts when the caller's outputs are host buffers. The call then ends with ONE stream
-    // synchronisation and no copy-engine operation (round 3: four small device-to-host copies used to sit there, ~25 us).
-    PinBuf pin;
+    PinBuf pin;       // the pinned block of a call's ResultBlock: the guard's per-query flags always, host outputs on their way out
     PinBuf swp_pin;   // the widen pass's list lengths, written by the re-rank kernel itself (RerankArgs::cnt_host)
     int64_t stat_queries = 0, stat_flagged = 0, stat_rounds = 0, stat_pages = 0, stat_exhaustive = 0, stat_swept_rows = 0;
     // a query between mmiss_index_query_begin and mmiss_index_query_end: its first pass is queued, `done_ev` marks its end
     struct Pending {
-        bool active = false, out_dev = false, guard = false;
+        bool active = false, guard = false;
         int Q = 0, k = 0;
-        int64_t* d_lab = nullptr; float* d_dist = nullptr; int32_t* d_cnt = nullptr; int32_t* h_flags = nullptr;
-        int64_t* out_labels = nullptr; float* out_dist = nullptr; int32_t* out_count = nullptr;
+        ResultBlock out;   // k slots per query, and the guard's flags
         // the predicate of a filtered query (mmiss_index_query_filtered*; filt = false for an unfiltered one): [Q] required and
         // [Q] excluded masks on the host (the widen pass's compaction and the exhaustive pass read them) and on the device
         bool filt = false;
@@ -187,28 +223,75 @@ int launch_normalize(mmiss_index* ix, const float* src_dev, void* dst, int64_t n
     return launch_f8_inv(ix, row0, n, st);   // (fp8 rows only)
 }
 
-// host copy of a (host or device) int64 array
-int fetch_i64(const int64_t* p, int64_t n, std::vector<int64_t>& out) {
-    out.resize((size_t)n);
+// ---- the movers of host-or-device arrays
+// n bytes from src (host or device) to dst (host or device), queued on st
+int copy_any(void* dst, const void* src, size_t n, hipStream_t st) {
     if (n == 0) return MMISS_OK;
-    if (mmiss_is_device_ptr(p))
-        MM_HIP(hipMemcpy(out.data(), p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    else
-        memcpy(out.data(), p, (size_t)n * 8);
+    const bool sd = mmiss_is_device_ptr(src), dd = mmiss_is_device_ptr(dst);
+    if (!sd && !dd) { memcpy(dst, src, n); return MMISS_OK; }
+    MM_HIP(hipMemcpyAsync(dst, src, n, sd ? (dd ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost) : hipMemcpyHostToDevice, st));
     return MMISS_OK;
 }
 
-// host copy of a (host or device) uint64 array; device memory is read on the index's stream
-int fetch_u64(const uint64_t* p, int64_t n, std::vector<uint64_t>& out, hipStream_t st) {
+// n zero bytes to dst (host or device, may be null); device memory on st and, `wait`, waited for
+int zero_any(void* dst, size_t n, hipStream_t st, bool wait) {
+    if (!dst || n == 0) return MMISS_OK;
+    if (!mmiss_is_device_ptr(dst)) { memset(dst, 0, n); return MMISS_OK; }
+    MM_HIP(hipMemsetAsync(dst, 0, n, st));
+    if (wait) MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+// host copy of a (host or device) array of n V. Device memory is read on *st and waited for; st == nullptr: by a blocking copy
+// on the default stream (the labels of the mutating calls)
+template <typename V> int fetch_host(const V* p, int64_t n, std::vector<V>& out, const hipStream_t* st = nullptr) {
     out.resize((size_t)n);
     if (n == 0) return MMISS_OK;
-    if (mmiss_is_device_ptr(p)) {
-        MM_HIP(hipMemcpyAsync(out.data(), p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        MM_HIP(hipStreamSynchronize(st));
+    if (!mmiss_is_device_ptr(p)) {
+        memcpy(out.data(), p, (size_t)n * sizeof(V));
+    } else if (!st) {
+        MM_HIP(hipMemcpy(out.data(), p, (size_t)n * sizeof(V), hipMemcpyDeviceToHost));
     } else {
-        memcpy(out.data(), p, (size_t)n * 8);
+        MM_HIP(hipMemcpyAsync(out.data(), p, (size_t)n * sizeof(V), hipMemcpyDeviceToHost, *st));
+        MM_HIP(hipStreamSynchronize(*st));
     }
     return MMISS_OK;
+}
+
+// *p as the kernels can read it: itself when it is null or device memory, else its n elements copied into `buf` at byte `at`
+// (queued on st); `buf` holds `total` bytes by then
+template <typename V> int device_view(const V** p, size_t n, DevBuf& buf, size_t at, size_t total, hipStream_t st) {
+    if (!*p || mmiss_is_device_ptr(*p)) return MMISS_OK;
+    MM_TRY(buf.ensure(total));
+    V* const d = reinterpret_cast<V*>(buf.as<char>() + at);
+    MM_HIP(hipMemcpyAsync(d, *p, n * sizeof(V), hipMemcpyHostToDevice, st));
+    *p = d;
+    return MMISS_OK;
+}
+
+// are a call's outputs (cnt and opt may be null) all host or all device memory? *dev: which
+int outputs_all_host_or_all_device(const char* who, const void* lab, const void* dist, const void* cnt, const void* opt, bool* dev) {
+    *dev = mmiss_is_device_ptr(lab);
+    if (*dev != mmiss_is_device_ptr(dist) || (cnt && *dev != mmiss_is_device_ptr(cnt)) || (opt && *dev != mmiss_is_device_ptr(opt)))
+        MM_FAIL(MMISS_ERR_ARG, "%s: output pointers must be all host or all device", who);
+    return MMISS_OK;
+}
+
+// what an entry does under the lock before it touches the device: no query open, the handle's device current; *st: its stream
+int enter(mmiss_index* ix, const char* who, hipStream_t* st) {
+    MM_NO_PENDING(ix, who);
+    MM_TRY(mmiss_use_device(ix->device));
+    *st = ix->stream();
+    return MMISS_OK;
+}
+
+PlanOptions plan_options() {
+    PlanOptions o;
+    o.scan_rounds = mmiss_option("scan_rounds", o.scan_rounds); o.scan_max_slabs = mmiss_option("scan_max_slabs", o.scan_max_slabs);
+    o.merge_two_level_min = mmiss_option("merge_two_level_min", o.merge_two_level_min);
+    o.score_strip_fit = mmiss_option("score_strip_fit", o.score_strip_fit); o.score_strip = mmiss_option("score_strip", o.score_strip);
+    o.probe_scratch_kb = mmiss_option("probe_scratch_kb", o.probe_scratch_kb);
+    return o;
 }
 
 inline bool tag_admits_h(uint64_t tag, uint64_t req, uint64_t exc) { return (tag & req) == req && (tag & exc) == 0; }
@@ -217,67 +300,6 @@ int64_t find_row(const mmiss_index* ix, int64_t label) {
     auto it = std::lower_bound(ix->labels_h.begin(), ix->labels_h.end(), label);
     if (it == ix->labels_h.end() || *it != label) return -1;
     return it - ix->labels_h.begin();
-}
-
-// a streaming scan launch: 16 * nqt queries per block in list mode (cap entries per query and wave) or, thr, in threshold mode
-// (the widen pass: every row reaching its query's threshold is appended to a.glist)
-struct ScanPlan {
-    int nqt, cap, lds, slabs, qtiles, tiles_per_block;
-    bool thr;
-};
-
-constexpr int SCAN_LDS_LIMIT = 160 * 1024;
-// dynamic LDS of the streaming scan for a block of 16 * nqt queries: the staged query rows (+ 16 B of padding each) and,
-// in list mode, four waves' (score, row) lists of `cap` entries per query with their counts and thresholds
-int scan_lds_bytes(int D, int qelt, int nqt, int cap) {
-    const int NQ = 16 * nqt;
-    return (((NQ * (D * qelt + 16)) + 15) & ~15) + 2 * 4 * NQ * cap * 4 + 2 * 4 * NQ * 4;
-}
-// ... in threshold mode (the widen pass): the query rows only
-int sweep_scan_lds(int D, int qelt, int nqt) { return ((16 * nqt * (D * qelt + 16)) + 15) & ~15; }
-
-ScanPlan plan_scan(int D, int elt, int Q, int kp, int64_t N) {
-    ScanPlan p{};
-    const int limit = SCAN_LDS_LIMIT;
-    p.nqt = 1; p.cap = 64;
-    if (kp <= 16 && Q > 16) {
-        for (int nqt : {4, 2})
-            if (scan_lds_bytes(D, elt, nqt, 32) <= limit && (Q > 16 * nqt / 2)) { p.nqt = nqt; p.cap = 32; break; }
-    }
-    const int NQ = 16 * p.nqt;
-    p.lds = scan_lds_bytes(D, elt, p.nqt, p.cap);
-    p.qtiles = (Q + NQ - 1) / NQ;
-    const int64_t ntiles = (N + 15) / 16;
-    const int blocks_per_cu = std::max(1, std::min(8, limit / p.lds));
-    int64_t target = (int64_t)256 * blocks_per_cu * mmiss_option("scan_rounds", 1) / p.qtiles;
-    if (target < 1) target = 1;
-    if (target > mmiss_option("scan_max_slabs", 1024)) target = mmiss_option("scan_max_slabs", 1024);
-    int64_t tpb = (ntiles + target - 1) / target;
-    tpb = (tpb + 3) / 4 * 4;  // every wave of a block gets the same number of tiles
-    if (tpb < 4) tpb = 4;
-    p.tiles_per_block = (int)tpb;
-    p.slabs = (int)((ntiles + tpb - 1) / tpb);
-    return p;
-}
-
-// The widen pass's scan of Qf queries: the widest query tile the flagged queries fill AND whose staged query block fits the
-// CU's LDS (f32 rows at the reference's D = 768: 64 queries x 3088 B = 193 KB do not, 32 do). nqt = 1 always fits:
-// mmiss_index_create admits only dims whose 16-query block does.
-ScanPlan plan_sweep(int D, int qelt, int Qf, int64_t N) {
-    ScanPlan p{};
-    p.thr = true;
-    p.cap = 32;
-    p.nqt = Qf > 32 ? 4 : Qf > 16 ? 2 : 1;
-    while (p.nqt > 1 && sweep_scan_lds(D, qelt, p.nqt) > SCAN_LDS_LIMIT) p.nqt >>= 1;
-    p.lds = sweep_scan_lds(D, qelt, p.nqt);
-    p.qtiles = (Qf + 16 * p.nqt - 1) / (16 * p.nqt);
-    const int64_t ntiles = (N + 15) / 16;
-    const int per_cu = std::max(1, std::min(8, SCAN_LDS_LIMIT / p.lds));
-    int64_t target = std::max<int64_t>(1, (int64_t)256 * per_cu / p.qtiles);
-    int64_t tpb = std::max<int64_t>(4, (((ntiles + target - 1) / target) + 3) / 4 * 4);
-    p.tiles_per_block = (int)tpb;
-    p.slabs = (int)((ntiles + tpb - 1) / tpb);
-    return p;
 }
 
 // The one map from a scan plan to its kernel: list mode keeps 64 entries per query and wave in a 16-query tile and 32 in the
@@ -311,13 +333,8 @@ int launch_scan(mmiss_index* ix, hipStream_t st, const ScanArgs& a, const ScanPl
     return MMISS_OK;
 }
 
-// merge L per-slab lists of every query into its candidate page; above 64 lists in two levels so that a single
-// query (the API path) is not merged by one lone workgroup
-constexpr int MERGE_LISTS_PER_BLOCK = 32;   // lists per first-level merge block
-bool merge_two_level(int L) { return L > mmiss_option("merge_two_level_min", 64); }
-
 int launch_merge(mmiss_index* ix, hipStream_t st, MergeArgs m) {
-    if (merge_two_level(m.L)) {
+    if (merge_two_level(m.L, plan_options())) {
         const int per = MERGE_LISTS_PER_BLOCK;
         const int S = (m.L + per - 1) / per;
         MM_TRY(ix->lists2_s.ensure((size_t)S * m.Q * m.kp * 4));
@@ -443,11 +460,10 @@ extern "C" int mmiss_index_add(mmiss_index* ix, const float* vecs, const int64_t
     if (n < 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_add: n = %lld", (long long)n);
     if (n == 0) return MMISS_OK;
     std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_add");
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, "mmiss_index_add", &st));
     std::vector<int64_t> lab;
-    MM_TRY(fetch_i64(labels, n, lab));
+    MM_TRY(fetch_host(labels, n, lab));
     int64_t prev = ix->labels_h.empty() ? INT64_MIN : ix->labels_h.back();
     for (int64_t i = 0; i < n; ++i) {
         if (lab[i] < 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_add: negative label %lld", (long long)lab[i]);
@@ -484,11 +500,10 @@ extern "C" int mmiss_index_update(mmiss_index* ix, const int64_t* labels, const 
     if (!ix || (n > 0 && (!vecs || !labels))) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_update: null argument");
     if (n <= 0) return n == 0 ? MMISS_OK : MMISS_ERR_ARG;
     std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_update");
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, "mmiss_index_update", &st));
     std::vector<int64_t> lab;
-    MM_TRY(fetch_i64(labels, n, lab));
+    MM_TRY(fetch_host(labels, n, lab));
     std::vector<int64_t> rows((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         rows[i] = find_row(ix, lab[i]);
@@ -497,11 +512,7 @@ extern "C" int mmiss_index_update(mmiss_index* ix, const int64_t* labels, const 
     drop_partition(ix);   // (rows change)
     const int D = ix->dim;
     const float* src = vecs;
-    if (!mmiss_is_device_ptr(vecs)) {
-        MM_TRY(ix->stage.ensure((size_t)n * D * 4));
-        MM_HIP(hipMemcpyAsync(ix->stage.p, vecs, (size_t)n * D * 4, hipMemcpyHostToDevice, st));
-        src = ix->stage.as<float>();
-    }
+    MM_TRY(device_view(&src, (size_t)n * D, ix->stage, 0, (size_t)n * D * 4, st));
     for (int64_t i = 0; i < n; ++i)
         MM_TRY(launch_normalize(ix, src + i * D, ix->rows.as<char>() + (size_t)rows[i] * D * ix->elt, 1, st, rows[i]));
     MM_HIP(hipStreamSynchronize(st));
@@ -513,11 +524,10 @@ extern "C" int mmiss_index_remove(mmiss_index* ix, const int64_t* labels, int64_
     if (removed) *removed = 0;
     if (n <= 0) return n == 0 ? MMISS_OK : MMISS_ERR_ARG;
     std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_remove");
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, "mmiss_index_remove", &st));
     std::vector<int64_t> lab;
-    MM_TRY(fetch_i64(labels, n, lab));
+    MM_TRY(fetch_host(labels, n, lab));
     std::vector<char> drop((size_t)ix->count, 0);
     int64_t ndrop = 0;
     for (int64_t i = 0; i < n; ++i) {
@@ -561,11 +571,10 @@ extern "C" int mmiss_index_get(mmiss_index* ix, const int64_t* labels, int64_t n
     if (!ix || (n > 0 && (!labels || !out))) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_get: null argument");
     if (n <= 0) return n == 0 ? MMISS_OK : MMISS_ERR_ARG;
     std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_get");
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, "mmiss_index_get", &st));
     std::vector<int64_t> lab;
-    MM_TRY(fetch_i64(labels, n, lab));
+    MM_TRY(fetch_host(labels, n, lab));
     std::vector<int64_t> map((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         map[i] = find_row(ix, lab[i]);
@@ -606,13 +615,12 @@ extern "C" int mmiss_index_set_tags(mmiss_index* ix, const int64_t* labels, cons
     if (n < 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_set_tags: n = %lld", (long long)n);
     if (n == 0) return MMISS_OK;
     std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_set_tags");
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, "mmiss_index_set_tags", &st));
     std::vector<int64_t> lab;
     std::vector<uint64_t> val;
-    MM_TRY(fetch_i64(labels, n, lab));
-    MM_TRY(fetch_u64(tags, n, val, st));
+    MM_TRY(fetch_host(labels, n, lab));
+    MM_TRY(fetch_host(tags, n, val, &st));
     std::vector<int64_t> rows((size_t)n);
     for (int64_t i = 0; i < n; ++i) {   // every label first: a missing one changes nothing
         rows[i] = find_row(ix, lab[i]);
@@ -641,7 +649,7 @@ extern "C" int mmiss_index_get_tags(mmiss_index* ix, const int64_t* labels, int6
     std::lock_guard<std::mutex> lk(ix->mu);
     MM_NO_PENDING(ix, "mmiss_index_get_tags");
     std::vector<int64_t> lab;
-    MM_TRY(fetch_i64(labels, n, lab));
+    MM_TRY(fetch_host(labels, n, lab));
     std::vector<uint64_t> val((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const int64_t r = find_row(ix, lab[i]);
@@ -713,20 +721,25 @@ int launch_rerank(mmiss_index* ix, hipStream_t st, const RerankArgs& r, int bloc
     return MMISS_OK;
 }
 
-// The canonical distance of every row to query q of the call's normalised queries (ix->qn), left in the pinned block
-// ix->dist_pin (float [N]; dist_all / dist_pin sized by the caller). Returns with the stream drained.
-int canonical_distances(mmiss_index* ix, hipStream_t st, int32_t q) {
+// the canonical distance of every row to query q of the call's normalised queries (ix->qn) into ix->dist_all (float [N], sized
+// by the caller); queued
+int launch_canonical_scan(mmiss_index* ix, hipStream_t st, int32_t q) {
     const int64_t N = ix->count;
     const int D = ix->dim;
-    {
-        MM_PROF("canonical_scan", st, 2.0 * N * D, (double)N * D * ix->elt);
-        const int grid = (int)std::min<int64_t>(8192, (N + 15) / 16);
-        with_storage(ix->dtype, [&](auto s) {   // (inv: the inverse norms of fp8 rows, null for the others)
-            hipLaunchKernelGGL(canonical_scan_kernel<typename decltype(s)::T>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
-                               ix->qn.as<float>() + (size_t)q * D, ix->dist_all.as<float>(), (const float*)ix->inv.as<float>());
-        });
-        MM_HIP(hipGetLastError());
-    }
+    MM_PROF("canonical_scan", st, 2.0 * N * D, (double)N * D * ix->elt);
+    const int grid = (int)std::min<int64_t>(8192, (N + 15) / 16);
+    with_storage(ix->dtype, [&](auto s) {   // (inv: the inverse norms of fp8 rows, null for the others)
+        hipLaunchKernelGGL(canonical_scan_kernel<typename decltype(s)::T>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
+                           ix->qn.as<float>() + (size_t)q * D, ix->dist_all.as<float>(), (const float*)ix->inv.as<float>());
+    });
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+// ... and from there to the pinned block ix->dist_pin (sized by the caller). Returns with the stream drained.
+int canonical_distances(mmiss_index* ix, hipStream_t st, int32_t q) {
+    const int64_t N = ix->count;
+    MM_TRY(launch_canonical_scan(ix, st, q));
     MM_HIP(hipMemcpyAsync(ix->dist_pin.p, ix->dist_all.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
     MM_HIP(hipStreamSynchronize(st));
     return MMISS_OK;
@@ -774,35 +787,11 @@ int exhaustive_queries(mmiss_index* ix, hipStream_t st, const mmiss_index::Pendi
     r.rows = ix->rows.p; r.D = D; r.inv = ix->inv.as<float>(); r.qn = ix->qn.as<float>(); r.cand = ix->cand2.as<int32_t>();
     r.cand_stride = kkpad; r.ncand = kkpad; r.group_mode = 0; r.nrows = N;
     r.labels = ix->labels_d.as<int64_t>(); r.k = pd.k;
-    r.out_labels = pd.d_lab; r.out_dist = pd.d_dist; r.out_count = pd.d_cnt;
+    r.out_labels = pd.out.lab; r.out_dist = pd.out.dist; r.out_count = pd.out.cnt;
     r.qmap = ix->qmap.as<int32_t>();
     MM_TRY(launch_rerank(ix, st, r, nq));
     MM_HIP(hipStreamSynchronize(st));  // (`cand` and `which` leave scope with the caller)
     return MMISS_OK;
-}
-
-// consecutive index tiles per workgroup of the strip score GEMM (Mq queries padded to 256, ncol column tiles of 256 rows):
-// long enough to amortise the pipeline fill, short enough to leave >= 8 workgroups per CU for balance; among the strip
-// lengths down to half that, the one whose rounds x length (+ a quarter tile of pipeline fill per workgroup and round) is
-// smallest (10M rows x 1024 queries: strip 32 gave 4884 workgroups = 19.08 rounds of 256 -> 5 % of the launch spent with 18
-// workgroups on the chip).
-int strip_length(int Mq, int64_t nbn, int64_t ncol) {
-    const int64_t tiles = nbn * (Mq / 256);
-    int strip = (int)std::min<int64_t>(32, std::max<int64_t>(1, tiles / 2048));
-    if (strip >= 8 && mmiss_option("score_strip_fit", 1) != 0) {
-        double best = 1e300;
-        int best_s = strip;
-        for (int sl = strip; sl >= strip / 2; --sl) {
-            const int64_t wgs = (Mq / 256) * ((ncol + sl - 1) / sl);
-            const int64_t rounds = (wgs + 255) / 256;
-            const double cost = (double)rounds * (sl + 0.25);
-            if (cost < best - 1e-9) { best = cost; best_s = sl; }
-        }
-        strip = best_s;
-    }
-    const int forced = mmiss_option("score_strip", 0);
-    if (forced > 0) strip = forced;
-    return strip;
 }
 
 // the strip score GEMM on the staggered loop of the persistent encoder GEMM (gemm_strip_p256.h; round 3): D % 128 == 0
@@ -857,12 +846,12 @@ int threshold_pass(mmiss_index* ix, hipStream_t st, int Qf, const void* qs_sw, c
         flt.tau = thr_sw; flt.tau_stride = 1; flt.cnt = ix->swp_cnt.as<int32_t>();
         flt.buf_s = nullptr; flt.buf_g = ix->swp_list.as<int32_t>(); flt.cap = SWEEP_CAP;
         flt.bn_begin = (int)(std::min<int64_t>(std::max<int64_t>(row_begin, 0), N - 1) / 256);
-        const int strip = strip_length(Qfp, nbn, nbn - flt.bn_begin);
+        const int strip = strip_length(Qfp, nbn, nbn - flt.bn_begin, plan_options());
         MM_PROF(ix->dtype == MMISS_F8 ? "sweep_gemm_f8" : "sweep_gemm_f16", st, 2.0 * Qf * (double)N * D, (double)N * D * ix->elt);
         MM_TRY(launch_strip_gemm(ix, st, true, qs_sw, ep, Qfp, (int)Npad, strip, &flt));
         *pages = 1;
     } else {
-        const ScanPlan p = plan_sweep(D, ix->qelt(), Qf, N);
+        const ScanPlan p = plan_dense(D, ix->qelt(), Qf, N, false).as_scan();
         if (p.lds > SCAN_LDS_LIMIT)
             MM_FAIL(MMISS_ERR_UNSUPPORTED, "widen pass: a 16-query block of dim %d does not fit the LDS (%d bytes)", D, p.lds);
         ScanArgs a{};
@@ -975,7 +964,7 @@ int sweep_queries(mmiss_index* ix, hipStream_t st, const mmiss_index::Pending& p
     // Re-rank what was collected; past SWEEP_CAP, the exhaustive pass.
     RerankArgs r{};
     r.k = pd.k;
-    r.out_labels = pd.d_lab; r.out_dist = pd.d_dist; r.out_count = pd.d_cnt;
+    r.out_labels = pd.out.lab; r.out_dist = pd.out.dist; r.out_count = pd.out.cnt;
     r.qmap = qmap_sw;
     std::vector<int32_t> over, rest;   // blocks whose list overflowed / their original indices for the exhaustive pass
     MM_TRY(rerank_swept(ix, st, r, Qf, which.data(), false, over));
@@ -1043,7 +1032,7 @@ int plan_query(const mmiss_index* ix, int Q, int k, bool filt, QueryPlan& p) {
     const int filter_opt = mmiss_option("score_filter", 1);
     p.sample = p.big && p.nbn >= 128 && filter_opt != 0 && (filter_opt == 2 || (double)p.Mq * (double)p.Npad >= 1e9);
     p.Ndense = p.sample ? p.ns_tiles * 256 : p.Npad;   // rows whose group maxima are materialised
-    if (p.big) p.strip = strip_length(p.Mq, p.nbn, p.sample ? p.nbn - p.ns_tiles : p.nbn);
+    if (p.big) p.strip = strip_length(p.Mq, p.nbn, p.sample ? p.nbn - p.ns_tiles : p.nbn, plan_options());
     if (p.sample) p.filter_cap = mmiss_option("score_filter_cap", 2048);
     return MMISS_OK;
 }
@@ -1054,8 +1043,8 @@ int stage_filter(mmiss_index* ix, hipStream_t st, int Q, const uint64_t* req, co
     pd.filt = req || exc;
     pd.d_mask = nullptr;
     if (!pd.filt) return MMISS_OK;
-    if (req) MM_TRY(fetch_u64(req, Q, pd.req, st)); else pd.req.assign((size_t)Q, 0);
-    if (exc) MM_TRY(fetch_u64(exc, Q, pd.exc, st)); else pd.exc.assign((size_t)Q, 0);
+    if (req) MM_TRY(fetch_host(req, Q, pd.req, &st)); else pd.req.assign((size_t)Q, 0);
+    if (exc) MM_TRY(fetch_host(exc, Q, pd.exc, &st)); else pd.exc.assign((size_t)Q, 0);
     MM_TRY(ix->fmask.ensure((size_t)Q * 16));
     MM_HIP(hipMemcpyAsync(ix->fmask.p, pd.req.data(), (size_t)Q * 8, hipMemcpyHostToDevice, st));
     MM_HIP(hipMemcpyAsync(ix->fmask.as<uint64_t>() + Q, pd.exc.data(), (size_t)Q * 8, hipMemcpyHostToDevice, st));
@@ -1063,27 +1052,15 @@ int stage_filter(mmiss_index* ix, hipStream_t st, int Q, const uint64_t* req, co
     return MMISS_OK;
 }
 
-// outputs: the caller's device buffers, or the pinned host block (copied to the caller's host buffers at the end); the guard's
-// per-query flags always go to the pinned block
-int stage_outputs(mmiss_index* ix, hipStream_t st, int Q, int k, int64_t* out_labels, float* out_dist, int32_t* out_count) {
+// the query's result block into ix->pend: k slots per query and the guard's flags; device outputs without counts count into scratch
+int stage_outputs(mmiss_index* ix, hipStream_t st, int Q, int k, bool out_dev, int64_t* out_labels, float* out_dist, int32_t* out_count) {
     mmiss_index::Pending& pd = ix->pend;
     pd.Q = Q; pd.k = k;
-    const size_t pin_dist = (size_t)Q * k * 8, pin_cnt = pin_dist + (size_t)Q * k * 4, pin_flags = pin_cnt + (size_t)Q * 4;
-    const size_t need = pin_flags + (size_t)Q * 4;
-    size_t grow = 4096;
-    while (grow < need) grow *= 2;
-    MM_TRY(ix->pin.ensure(need, st, grow));
-    char* const pin = ix->pin.as<char>();
-    pd.d_lab = out_labels; pd.d_dist = out_dist; pd.d_cnt = out_count;
-    if (!pd.out_dev) {
-        pd.d_lab = reinterpret_cast<int64_t*>(pin); pd.d_dist = reinterpret_cast<float*>(pin + pin_dist);
-        pd.d_cnt = reinterpret_cast<int32_t*>(pin + pin_cnt);
-    } else if (!out_count) {
+    MM_TRY(pd.out.stage(ix->pin, st, Q, k, out_dev, false, true, out_labels, out_dist, out_count, nullptr));
+    if (!pd.out.cnt) {
         MM_TRY(ix->out_c.ensure((size_t)Q * 4));
-        pd.d_cnt = ix->out_c.as<int32_t>();
+        pd.out.cnt = ix->out_c.as<int32_t>();
     }
-    pd.h_flags = reinterpret_cast<int32_t*>(pin + pin_flags);
-    pd.out_labels = out_labels; pd.out_dist = out_dist; pd.out_count = out_count;
     return MMISS_OK;
 }
 
@@ -1093,11 +1070,7 @@ int upload_queries(mmiss_index* ix, hipStream_t st, const float* queries, int Q)
     const int D = ix->dim;
     const int Qpad = (int)round_up(Q, 256);
     const float* qsrc = queries;
-    if (!mmiss_is_device_ptr(queries)) {
-        MM_TRY(ix->qstage.ensure((size_t)Q * D * 4));
-        MM_HIP(hipMemcpyAsync(ix->qstage.p, queries, (size_t)Q * D * 4, hipMemcpyHostToDevice, st));
-        qsrc = ix->qstage.as<float>();
-    }
+    MM_TRY(device_view(&qsrc, (size_t)Q * D, ix->qstage, 0, (size_t)Q * D * 4, st));
     MM_TRY(ix->qn.ensure((size_t)Qpad * D * 4));
     MM_TRY(ix->qs.ensure((size_t)Qpad * D * ix->qelt()));
     MM_TRY(ix->eps_q.ensure((size_t)Qpad * 4));
@@ -1112,17 +1085,6 @@ int upload_queries(mmiss_index* ix, hipStream_t st, const float* queries, int Q)
     });
     MM_HIP(hipGetLastError());
     return MMISS_OK;
-}
-
-// blocks per query of select_topk over ng group maxima: about 1024 blocks per call, every block at least one unit of
-// SELECT_UNIT groups, 32 at the most
-int select_splits(int ng, int Q) {
-    const int units = (ng + SELECT_UNIT - 1) / SELECT_UNIT;
-    int splits = (1024 + Q - 1) / Q;
-    if (splits > units) splits = units;
-    if (splits > 32) splits = 32;
-    if (splits < 1) splits = 1;
-    return splits;
 }
 
 // The dense first pass: the score GEMM writes the maximum of every group of 16 rows per query, select_topk / merge_lists keep
@@ -1193,7 +1155,7 @@ int dense_pass(mmiss_index* ix, hipStream_t st, const QueryPlan& p, int Q) {
 int scan_pass(mmiss_index* ix, hipStream_t st, const QueryPlan& qp, int Q) {
     const mmiss_index::Pending& pd = ix->pend;
     const int kp = qp.kp;
-    const ScanPlan p = plan_scan(ix->dim, ix->qelt(), Q, kp, ix->count);
+    const ScanPlan p = plan_scan(ix->dim, ix->qelt(), Q, kp, ix->count, plan_options());
     MM_TRY(ix->lists_s.ensure((size_t)p.slabs * Q * kp * 4));
     MM_TRY(ix->lists_r.ensure((size_t)p.slabs * Q * kp * 4));
     const bool paging = qp.pages > 1;
@@ -1232,11 +1194,11 @@ int rerank_first(mmiss_index* ix, hipStream_t st, const QueryPlan& p) {
     r.rows = ix->rows.p; r.D = ix->dim; r.inv = ix->inv.as<float>(); r.qn = ix->qn.as<float>(); r.cand = ix->cand.as<int32_t>();
     r.cand_stride = p.ncand; r.ncand = p.dense ? p.ncand * 16 : p.ncand; r.group_mode = p.dense ? 1 : 0; r.nrows = ix->count;
     r.labels = ix->labels_d.as<int64_t>(); r.k = pd.k;
-    r.out_labels = pd.d_lab; r.out_dist = pd.d_dist; r.out_count = pd.d_cnt;
+    r.out_labels = pd.out.lab; r.out_dist = pd.out.dist; r.out_count = pd.out.cnt;
     if (pd.guard) {
         r.tau = ix->cur_s.as<float>(); r.eps_q = ix->eps_q.as<float>();
         r.thr_out = ix->thr.as<float>();
-        r.flags = pd.h_flags; r.nflag = nullptr;
+        r.flags = pd.out.flags; r.nflag = nullptr;
         r.force_flag = mmiss_option("guard_force", 0);
         // threshold-filtered selection: per-query append counts and their capacity
         if (p.sample) { r.ovf_cnt = ix->fcnt.as<int32_t>(); r.ovf_cap = p.filter_cap; }
@@ -1256,11 +1218,10 @@ int query_begin_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t
     hipStream_t st = ix->stream();
     const int64_t N = ix->count;
     mmiss_index::Pending& pd = ix->pend;
-    pd.out_dev = mmiss_is_device_ptr(out_labels);
-    if (pd.out_dev != mmiss_is_device_ptr(out_dist) || (out_count && pd.out_dev != mmiss_is_device_ptr(out_count)))
-        MM_FAIL(MMISS_ERR_ARG, "mmiss_index_query: output pointers must be all host or all device");
+    bool out_dev = false;
+    MM_TRY(outputs_all_host_or_all_device("mmiss_index_query", out_labels, out_dist, out_count, nullptr, &out_dev));
     MM_TRY(stage_filter(ix, st, Q, req, exc));
-    MM_TRY(stage_outputs(ix, st, Q, k, out_labels, out_dist, out_count));
+    MM_TRY(stage_outputs(ix, st, Q, k, out_dev, out_labels, out_dist, out_count));
     QueryPlan p;
     MM_TRY(plan_query(ix, Q, k, pd.filt, p));
     MM_TRY(upload_queries(ix, st, queries, Q));
@@ -1291,7 +1252,7 @@ int query_end_locked(mmiss_index* ix) {
     ix->pend.active = false;
     MM_TRY(mmiss_use_device(ix->device));
     hipStream_t st = ix->stream();
-    if (!pd.guard && pd.out_dev && ix->has_user_stream) {  // device outputs on the caller's stream, nothing to decide: stays queued
+    if (!pd.guard && pd.out.dev && ix->has_user_stream) {  // device outputs on the caller's stream, nothing to decide: stays queued
         ix->async_pending = true;
         return MMISS_OK;
     }
@@ -1299,7 +1260,7 @@ int query_end_locked(mmiss_index* ix) {
     if (pd.guard) {
         std::vector<int32_t> which;
         for (int q = 0; q < pd.Q; ++q)
-            if (pd.h_flags[q]) which.push_back(q);
+            if (pd.out.flags[q]) which.push_back(q);
         if (!which.empty()) {
             ix->stat_flagged += (int64_t)which.size();
             hipStream_t ws = side_stream_mode() != 0 ? ix->side_stream : st;
@@ -1311,11 +1272,7 @@ int query_end_locked(mmiss_index* ix) {
             }
         }
     }
-    if (!pd.out_dev) {
-        memcpy(pd.out_labels, pd.d_lab, (size_t)pd.Q * pd.k * 8);
-        memcpy(pd.out_dist, pd.d_dist, (size_t)pd.Q * pd.k * 4);
-        if (pd.out_count) memcpy(pd.out_count, pd.d_cnt, (size_t)pd.Q * 4);
-    }
+    pd.out.deliver();
     return MMISS_OK;
 }
 
@@ -1417,19 +1374,6 @@ struct RadiusCall {
     int64_t* out_labels = nullptr; float* out_dist = nullptr; int32_t* out_count = nullptr; int64_t* out_total = nullptr;
 };
 
-// host copy of a (host or device) float array; device memory is read on the index's stream
-int fetch_f32(const float* p, int64_t n, std::vector<float>& out, hipStream_t st) {
-    out.resize((size_t)n);
-    if (n == 0) return MMISS_OK;
-    if (mmiss_is_device_ptr(p)) {
-        MM_HIP(hipMemcpyAsync(out.data(), p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        MM_HIP(hipStreamSynchronize(st));
-    } else {
-        memcpy(out.data(), p, (size_t)n * 4);
-    }
-    return MMISS_OK;
-}
-
 // The exhaustive pass of a radius query: chunk query qc (radius R, masks of ix->pend, later_only: rows above row_min) against
 // every row — the admitted rows with d <= R, all counted, the `cap` best by (distance, row) kept. `lab` / `dist`: [cap] host.
 int radius_exhaustive(mmiss_index* ix, hipStream_t st, int32_t qc, float R, int64_t row_min, int cap, int64_t* lab, float* dist,
@@ -1468,22 +1412,10 @@ int radius_chunk(mmiss_index* ix, hipStream_t st, const RadiusCall& c, const flo
     const int Qpad = (int)round_up(Qc, 256);
     MM_TRY(stage_filter(ix, st, Qc, c.req ? c.req + q0 : nullptr, c.exc ? c.exc + q0 : nullptr));
     const mmiss_index::Pending& pd = ix->pend;   // (the chunk's masks; no query is open: MM_NO_PENDING at the entry)
-    // outputs: the caller's device buffers, or a pinned host block the re-rank writes straight into
-    int64_t* d_lab; float* d_dist; int32_t* d_cnt; int64_t* d_tot;
-    if (c.out_dev) {
-        d_lab = c.out_labels + q0 * cap; d_dist = c.out_dist + q0 * cap; d_cnt = c.out_count + q0;
-        d_tot = c.out_total ? c.out_total + q0 : nullptr;
-        if (!d_tot) { MM_TRY(ix->rtotal.ensure((size_t)RADIUS_CHUNK * 8)); d_tot = ix->rtotal.as<int64_t>(); }
-    } else {
-        const size_t o_tot = (size_t)Qc * cap * 8, o_dist = o_tot + (size_t)Qc * 8, o_cnt = o_dist + (size_t)Qc * cap * 4;
-        const size_t need = o_cnt + (size_t)Qc * 4;
-        size_t grow = 4096;
-        while (grow < need) grow *= 2;
-        MM_TRY(ix->pin.ensure(need, st, grow));
-        char* const pin = ix->pin.as<char>();
-        d_lab = reinterpret_cast<int64_t*>(pin); d_tot = reinterpret_cast<int64_t*>(pin + o_tot);
-        d_dist = reinterpret_cast<float*>(pin + o_dist); d_cnt = reinterpret_cast<int32_t*>(pin + o_cnt);
-    }
+    ResultBlock out;   // with totals: the caller's, or scratch when device outputs come without them
+    MM_TRY(out.stage(ix->pin, st, Qc, cap, c.out_dev, true, false, c.out_labels + q0 * cap, c.out_dist + q0 * cap, c.out_count + q0,
+                     c.out_total ? c.out_total + q0 : nullptr));
+    if (!out.tot) { MM_TRY(ix->rtotal.ensure((size_t)RADIUS_CHUNK * 8)); out.tot = ix->rtotal.as<int64_t>(); }
     MM_TRY(upload_queries(ix, st, queries, Qc));   // qn, qs (pad rows zero), eps_q
     MM_TRY(ix->rad.ensure((size_t)RADIUS_CHUNK * 4));
     MM_HIP(hipMemcpyAsync(ix->rad.p, c.rad + q0, (size_t)Qc * 4, hipMemcpyHostToDevice, st));
@@ -1501,7 +1433,7 @@ int radius_chunk(mmiss_index* ix, hipStream_t st, const RadiusCall& c, const flo
     MM_TRY(threshold_pass(ix, st, Qc, ix->qs.p, ix->thr.as<float>(), pd.filt ? pd.d_mask : nullptr, row_begin, &pages));
     RerankArgs r{};
     r.k = cap;
-    r.out_labels = d_lab; r.out_dist = d_dist; r.out_count = d_cnt; r.out_total = d_tot;
+    r.out_labels = out.lab; r.out_dist = out.dist; r.out_count = out.cnt; r.out_total = out.tot;
     r.max_dist = ix->rad.as<float>();
     r.row_min = c.row_min ? ix->row_min.as<int32_t>() : nullptr;
     std::vector<int32_t> over;
@@ -1517,25 +1449,20 @@ int radius_chunk(mmiss_index* ix, hipStream_t st, const RadiusCall& c, const flo
             int64_t tot = 0;
             MM_TRY(radius_exhaustive(ix, st, qc, c.rad[q0 + qc], c.row_min ? c.row_min[q0 + qc] : -1, cap, xl.data(), xd.data(), &cnt, &tot));
             if (c.out_dev) {
-                MM_HIP(hipMemcpyAsync(d_lab + (size_t)qc * cap, xl.data(), (size_t)cap * 8, hipMemcpyHostToDevice, st));
-                MM_HIP(hipMemcpyAsync(d_dist + (size_t)qc * cap, xd.data(), (size_t)cap * 4, hipMemcpyHostToDevice, st));
-                MM_HIP(hipMemcpyAsync(d_cnt + qc, &cnt, 4, hipMemcpyHostToDevice, st));
-                MM_HIP(hipMemcpyAsync(d_tot + qc, &tot, 8, hipMemcpyHostToDevice, st));
+                MM_HIP(hipMemcpyAsync(out.lab + (size_t)qc * cap, xl.data(), (size_t)cap * 8, hipMemcpyHostToDevice, st));
+                MM_HIP(hipMemcpyAsync(out.dist + (size_t)qc * cap, xd.data(), (size_t)cap * 4, hipMemcpyHostToDevice, st));
+                MM_HIP(hipMemcpyAsync(out.cnt + qc, &cnt, 4, hipMemcpyHostToDevice, st));
+                MM_HIP(hipMemcpyAsync(out.tot + qc, &tot, 8, hipMemcpyHostToDevice, st));
                 MM_HIP(hipStreamSynchronize(st));   // (pageable sources, reused by the next query)
             } else {
-                memcpy(d_lab + (size_t)qc * cap, xl.data(), (size_t)cap * 8);
-                memcpy(d_dist + (size_t)qc * cap, xd.data(), (size_t)cap * 4);
-                d_cnt[qc] = cnt;
-                d_tot[qc] = tot;
+                memcpy(out.lab + (size_t)qc * cap, xl.data(), (size_t)cap * 8);
+                memcpy(out.dist + (size_t)qc * cap, xd.data(), (size_t)cap * 4);
+                out.cnt[qc] = cnt;
+                out.tot[qc] = tot;
             }
         }
     }
-    if (!c.out_dev) {
-        memcpy(c.out_labels + q0 * cap, d_lab, (size_t)Qc * cap * 8);
-        memcpy(c.out_dist + q0 * cap, d_dist, (size_t)Qc * cap * 4);
-        memcpy(c.out_count + q0, d_cnt, (size_t)Qc * 4);
-        if (c.out_total) memcpy(c.out_total + q0, d_tot, (size_t)Qc * 8);
-    }
+    out.deliver();
     return MMISS_OK;
 }
 
@@ -1543,10 +1470,7 @@ int radius_chunk(mmiss_index* ix, hipStream_t st, const RadiusCall& c, const flo
 int radius_check(const char* who, int cap, int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_total, RadiusCall& c) {
     if (!out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
     if (cap < 1 || cap > RADIUS_MAX_CAP) MM_FAIL(MMISS_ERR_ARG, "%s: cap = %d (1 .. %d result slots per query)", who, cap, RADIUS_MAX_CAP);
-    c.out_dev = mmiss_is_device_ptr(out_labels);
-    if (c.out_dev != mmiss_is_device_ptr(out_dist) || c.out_dev != mmiss_is_device_ptr(out_count) ||
-        (out_total && c.out_dev != mmiss_is_device_ptr(out_total)))
-        MM_FAIL(MMISS_ERR_ARG, "%s: output pointers must be all host or all device", who);
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_total, &c.out_dev));
     c.cap = cap;
     c.out_labels = out_labels; c.out_dist = out_dist; c.out_count = out_count; c.out_total = out_total;
     return MMISS_OK;
@@ -1564,11 +1488,10 @@ extern "C" int mmiss_index_query_radius(mmiss_index* ix, const float* queries, i
     RadiusCall c;
     MM_TRY(radius_check(who, cap, out_labels, out_dist, out_count, out_total, c));
     std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, who);
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, who, &st));
     std::vector<float> rad;
-    MM_TRY(fetch_f32(max_dist, Q, rad, st));
+    MM_TRY(fetch_host(max_dist, Q, rad, &st));
     for (int q = 0; q < Q; ++q)
         if (rad[(size_t)q] != rad[(size_t)q]) MM_FAIL(MMISS_ERR_ARG, "%s: max_dist[%d] is NaN", who, q);
     c.rad = rad.data(); c.req = require; c.exc = exclude;
@@ -1640,28 +1563,41 @@ extern "C" int mmiss_index_query_radius_by_label(mmiss_index* ix, const int64_t*
 //             (radius_exhaustive's host selection has nothing to select here).
 namespace {
 
-struct MemberPlan { int nqt, lds, slabs, tiles_per_block, passes; };
-
-// The probe tile of a membership pass: the narrowest of 16 / 32 / 64 probes that holds all P (a wider one would only multiply the
-// MFMA work of a pass that is bound by reading the rows), halved while its staged operands do not fit the LDS budget: 64 probes
-// fit at dim 512 / 768 / 1024 in f16 or fp8 and at dim 512 in f32, 16 at dim 3968 (and f32 at 1920); more probes than the tile
-// holds make several passes.
-MemberPlan plan_membership(int D, int qelt, int P, int64_t N) {
-    MemberPlan p{};
-    p.nqt = P > 32 ? 4 : P > 16 ? 2 : 1;
-    while (p.nqt > 1 && sweep_scan_lds(D, qelt, p.nqt) > SCAN_LDS_LIMIT) p.nqt >>= 1;
-    p.lds = sweep_scan_lds(D, qelt, p.nqt);
-    p.passes = (P + 16 * p.nqt - 1) / (16 * p.nqt);
-    const int64_t ntiles = (N + 15) / 16;
-    const int per_cu = std::max(1, std::min(8, SCAN_LDS_LIMIT / p.lds));
-    const int64_t target = (int64_t)256 * per_cu;
-    const int64_t tpb = std::max<int64_t>(4, (((ntiles + target - 1) / target) + 3) / 4 * 4);
-    p.tiles_per_block = (int)tpb;
-    p.slabs = (int)((ntiles + tpb - 1) / tpb);
-    return p;
+// One dense scan of every row (plan_dense, by passes) by a kernel family K — K::kernel<T, NQT>() over K::Args —: the instantiation
+// for the index's rows and the plan's operand tile, its dynamic LDS, and one launch per pass of 16 * nqt operands. The arguments
+// every family shares are set here; fill(a, j, NQ) adds pass j's own. prof: the family's profile names for f32 / f16 / fp8 rows;
+// state_bytes: what a pass moves per row beside the row.
+template <typename K, typename Fill>
+int launch_dense_scan(mmiss_index* ix, hipStream_t st, const DensePlan& p, const char* const (&prof)[3], int state_bytes, Fill&& fill) {
+    typedef typename K::Args Args;
+    typedef void (*Kern)(Args);
+    const Kern kern = with_storage(ix->dtype, [&](auto s) -> Kern {
+        using T = typename decltype(s)::T;
+        if (p.nqt == 4) return K::template kernel<T, 4>();
+        if (p.nqt == 2) return K::template kernel<T, 2>();
+        return K::template kernel<T, 1>();
+    });
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), p.lds));
+    const int NQ = 16 * p.nqt, D = ix->dim;
+    const int64_t N = ix->count;
+    const char* const name = prof[ix->dtype == MMISS_F16 ? 1 : ix->dtype == MMISS_F8 ? 2 : 0];
+    for (int j = 0; j < p.passes; ++j) {
+        Args a{};
+        a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>();
+        a.qs = ix->qs.as<char>() + (size_t)j * NQ * D * ix->qelt();
+        a.tiles_per_block = p.tiles_per_block;
+        fill(a, j, NQ);
+        MM_PROF(name, st, 2.0 * NQ * (double)N * D, (double)N * (D * ix->elt + state_bytes));
+        hipLaunchKernelGGL(kern, dim3(p.slabs), dim3(256), p.lds, st, a);
+        MM_HIP(hipGetLastError());
+    }
+    return MMISS_OK;
 }
 
-typedef void (*MemberKernel)(MemberScanArgs);
+struct MemberScan {
+    typedef MemberScanArgs Args;
+    template <typename T, int NQT> static auto kernel() { return &member_scan_kernel<T, NQT>; }
+};
 
 // Bit p of d_words[r] (device, [count]) = row r is a member of probe p, bits >= P zero. rad: [P] HOST radii (no NaN), left on
 // the device in ix->mem_thr ([64] floats). count > 0. Waits once, for the lists' lengths (launching the resolve blind, with a
@@ -1683,32 +1619,16 @@ int membership_core(mmiss_index* ix, hipStream_t st, const float* queries, int P
     MM_TRY(ix->swp_list.ensure((size_t)64 * SWEEP_CAP * 4));
     MM_TRY(ix->swp_pin.ensure(cnt_bytes, st));
     MM_HIP(hipMemsetAsync(ix->swp_cnt.p, 0, cnt_bytes, st));
-    const MemberPlan mp = plan_membership(D, ix->qelt(), P, N);
+    const DensePlan mp = plan_dense(D, ix->qelt(), P, N, true);
     if (mp.lds > SCAN_LDS_LIMIT)
         MM_FAIL(MMISS_ERR_UNSUPPORTED, "membership: a 16-probe block of dim %d does not fit the LDS (%d bytes)", D, mp.lds);
-    const MemberKernel kern = with_storage(ix->dtype, [&](auto s) -> MemberKernel {
-        using T = typename decltype(s)::T;
-        if (mp.nqt == 4) return &member_scan_kernel<T, 4>;
-        if (mp.nqt == 2) return &member_scan_kernel<T, 2>;
-        return &member_scan_kernel<T, 1>;
-    });
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), mp.lds));
-    const int NQ = 16 * mp.nqt;
-    for (int j = 0; j < mp.passes; ++j) {
-        MemberScanArgs a{};
-        a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>();
-        a.qs = ix->qs.as<char>() + (size_t)j * NQ * D * ix->qelt();
+    MM_TRY(launch_dense_scan<MemberScan>(ix, st, mp, {"member_scan_f32", "member_scan_f16", "member_scan_f8"}, 8, [&](MemberScanArgs& a, int j, int NQ) {
         a.lo = d_lo + j * NQ; a.hi = d_hi + j * NQ;
-        a.tiles_per_block = mp.tiles_per_block;
         a.words = d_words; a.bit0 = j * NQ; a.first = j == 0;
         a.bcnt = ix->swp_cnt.as<int32_t>() + (size_t)j * NQ * MEMBER_CNT_STRIDE;
         a.blist = ix->swp_list.as<int32_t>() + (size_t)j * NQ * SWEEP_CAP;
         a.bcap = SWEEP_CAP;
-        const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
-        MM_PROF(f16 ? "member_scan_f16" : f8 ? "member_scan_f8" : "member_scan_f32", st, 2.0 * NQ * (double)N * D, (double)N * (D * ix->elt + 8));
-        hipLaunchKernelGGL(kern, dim3(mp.slabs), dim3(256), mp.lds, st, a);
-        MM_HIP(hipGetLastError());
-    }
+    }));
     // the lists' lengths decide the rest
     MM_HIP(hipMemcpyAsync(ix->swp_pin.p, ix->swp_cnt.p, cnt_bytes, hipMemcpyDeviceToHost, st));
     MM_HIP(hipStreamSynchronize(st));
@@ -1734,13 +1654,7 @@ int membership_core(mmiss_index* ix, hipStream_t st, const float* queries, int P
     }
     for (int p : over) {   // more than SWEEP_CAP rows within eps of the probe's threshold: every row's canonical distance decides
         MM_TRY(ix->dist_all.ensure((size_t)N * 4));
-        MM_PROF("canonical_scan", st, 2.0 * N * D, (double)N * D * ix->elt);
-        const int grid = (int)std::min<int64_t>(8192, (N + 15) / 16);
-        with_storage(ix->dtype, [&](auto s) {
-            hipLaunchKernelGGL(canonical_scan_kernel<typename decltype(s)::T>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
-                               ix->qn.as<float>() + (size_t)p * D, ix->dist_all.as<float>(), (const float*)ix->inv.as<float>());
-        });
-        MM_HIP(hipGetLastError());
+        MM_TRY(launch_canonical_scan(ix, st, p));
         hipLaunchKernelGGL(member_from_dist_kernel, dim3((int)std::min<int64_t>(4096, (N + 255) / 256)), dim3(256), 0, st,
                            (const float*)ix->dist_all.as<float>(), N, (const float*)d_rad, p, d_words);
         MM_HIP(hipGetLastError());
@@ -1765,22 +1679,14 @@ int membership_counts(mmiss_index* ix, hipStream_t st, const uint64_t* d_words) 
 // out_members (host or device, may be null) <- the first P counts of ix->mem_cnt, or zeros (an empty index)
 int deliver_members(mmiss_index* ix, hipStream_t st, int P, int64_t* out_members, bool zeros) {
     if (!out_members) return MMISS_OK;
-    const bool dev = mmiss_is_device_ptr(out_members);
-    if (zeros) {
-        if (dev) { MM_HIP(hipMemsetAsync(out_members, 0, (size_t)P * 8, st)); MM_HIP(hipStreamSynchronize(st)); }
-        else memset(out_members, 0, (size_t)P * 8);
-        return MMISS_OK;
-    }
-    MM_HIP(hipMemcpyAsync(out_members, ix->mem_cnt.p, (size_t)P * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    return MMISS_OK;
+    if (zeros) return zero_any(out_members, (size_t)P * 8, st, true);
+    return copy_any(out_members, ix->mem_cnt.p, (size_t)P * 8, st);
 }
 
 // what both entry points check before they touch anything; on success `rad` holds the P radii on the host
 int membership_check(mmiss_index* ix, const char* who, int32_t P, const float* max_dist, hipStream_t* st, std::vector<float>& rad) {
-    MM_NO_PENDING(ix, who);
-    MM_TRY(mmiss_use_device(ix->device));
-    *st = ix->stream();
-    MM_TRY(fetch_f32(max_dist, P, rad, *st));
+    MM_TRY(enter(ix, who, st));
+    MM_TRY(fetch_host(max_dist, P, rad, st));
     for (int p = 0; p < P; ++p)
         if (rad[(size_t)p] != rad[(size_t)p]) MM_FAIL(MMISS_ERR_ARG, "%s: max_dist[%d] is NaN", who, p);
     return MMISS_OK;
@@ -1810,7 +1716,7 @@ extern "C" int mmiss_index_membership(mmiss_index* ix, const float* queries, int
     if (!out_dev) { MM_TRY(ix->mem_words.ensure((size_t)N * 8)); d_words = ix->mem_words.as<uint64_t>(); }
     MM_TRY(membership_core(ix, st, queries, P, rad.data(), d_words));
     if (out_members) MM_TRY(membership_counts(ix, st, d_words));
-    if (!out_dev) MM_HIP(hipMemcpyAsync(out_words, d_words, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+    if (!out_dev) MM_TRY(copy_any(out_words, d_words, (size_t)N * 8, st));
     MM_TRY(deliver_members(ix, st, P, out_members, false));
     MM_HIP(hipStreamSynchronize(st));
     return MMISS_OK;
@@ -1863,25 +1769,19 @@ namespace {
 constexpr int ASSIGN_MAX_CENTRES = 1024;
 constexpr size_t ASSIGN_META_SIZES = 64;   // byte offset of the [1024] u64 sizes in asg_meta; in front: float E, int live, int borderline
 
-// n zeros to a (host or device, may be null) int64 array
-int deliver_zeros_i64(hipStream_t st, int64_t* out, int64_t n) {
-    if (!out || n <= 0) return MMISS_OK;
-    if (mmiss_is_device_ptr(out)) { MM_HIP(hipMemsetAsync(out, 0, (size_t)n * 8, st)); MM_HIP(hipStreamSynchronize(st)); }
-    else memset(out, 0, (size_t)n * 8);
-    return MMISS_OK;
-}
-
 // sizes of clusters [0, C) of d_assign (device, [count]) -> out_sizes (host or device); queued, not waited for
 int assign_sizes(mmiss_index* ix, hipStream_t st, const int32_t* d_assign, int C, int64_t* out_sizes) {
     unsigned long long* const d_sizes = reinterpret_cast<unsigned long long*>(ix->asg_meta.as<char>() + ASSIGN_META_SIZES);
     MM_HIP(hipMemsetAsync(d_sizes, 0, (size_t)C * 8, st));
     hipLaunchKernelGGL(assign_sizes_kernel, dim3((int)std::min<int64_t>(1024, (ix->count + 255) / 256)), dim3(256), 0, st, d_assign, ix->count, C, d_sizes);
     MM_HIP(hipGetLastError());
-    MM_HIP(hipMemcpyAsync(out_sizes, d_sizes, (size_t)C * 8, mmiss_is_device_ptr(out_sizes) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    return MMISS_OK;
+    return copy_any(out_sizes, d_sizes, (size_t)C * 8, st);
 }
 
-typedef void (*AssignKernel)(AssignScanArgs);
+struct AssignScan {
+    typedef AssignScanArgs Args;
+    template <typename T, int NQT> static auto kernel() { return &assign_scan_kernel<T, NQT>; }
+};
 
 }  // namespace
 
@@ -1894,16 +1794,15 @@ extern "C" int mmiss_index_assign(mmiss_index* ix, const float* centres, int32_t
     std::lock_guard<std::mutex> lk(ix->mu);
     if (cap_rows < ix->count) MM_FAIL(MMISS_ERR_ARG, "%s: cap_rows = %lld for %lld rows", who, (long long)cap_rows, (long long)ix->count);
     if (ix->count > 0 && !out_assign) MM_FAIL(MMISS_ERR_ARG, "%s: null out_assign", who);
-    MM_NO_PENDING(ix, who);
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, who, &st));
     const int64_t N = ix->count;
     const int D = ix->dim;
     if (N == 0) {   // nothing to write but the sizes
         ix->stat_radius_queries += C;
-        return deliver_zeros_i64(st, out_sizes, C);
+        return zero_any(out_sizes, (size_t)C * 8, st, true);
     }
-    const MemberPlan mp = plan_membership(D, ix->qelt(), C, N);   // the centre tile and the slabs: §4c's choice
+    const DensePlan mp = plan_dense(D, ix->qelt(), C, N, true);   // the centre tile and the slabs: §4c's choice
     if (mp.lds > SCAN_LDS_LIMIT)
         MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: a 16-centre block of dim %d does not fit the LDS (%d bytes)", who, D, mp.lds);
     const bool asg_dev = mmiss_is_device_ptr(out_assign), dist_dev = out_dist && mmiss_is_device_ptr(out_dist);
@@ -1925,27 +1824,11 @@ extern "C" int mmiss_index_assign(mmiss_index* ix, const float* centres, int32_t
     MM_HIP(hipMemsetAsync(d_bcnt, 0, 4, st));
     hipLaunchKernelGGL(assign_bound_kernel, dim3(1), dim3(64), 0, st, eps, (int)C, d_E, d_live);
     MM_HIP(hipGetLastError());
-    const AssignKernel kern = with_storage(ix->dtype, [&](auto s) -> AssignKernel {
-        using T = typename decltype(s)::T;
-        if (mp.nqt == 4) return &assign_scan_kernel<T, 4>;
-        if (mp.nqt == 2) return &assign_scan_kernel<T, 2>;
-        return &assign_scan_kernel<T, 1>;
-    });
-    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), mp.lds));
-    const int NQ = 16 * mp.nqt;
-    const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
-    for (int j = 0; j < mp.passes; ++j) {
-        AssignScanArgs a{};
-        a.rows = ix->rows.p; a.N = N; a.D = D; a.inv = ix->inv.as<float>();
-        a.qs = ix->qs.as<char>() + (size_t)j * NQ * D * ix->qelt();
+    MM_TRY(launch_dense_scan<AssignScan>(ix, st, mp, {"assign_scan_f32", "assign_scan_f16", "assign_scan_f8"}, 12, [&](AssignScanArgs& a, int j, int NQ) {
         a.eps_q = eps;
-        a.tiles_per_block = mp.tiles_per_block;
         a.c0 = j * NQ; a.C = C; a.first = j == 0;
         a.st_s1 = st_s1; a.st_i1 = st_i1; a.st_s2 = st_s2;
-        MM_PROF(f16 ? "assign_scan_f16" : f8 ? "assign_scan_f8" : "assign_scan_f32", st, 2.0 * NQ * (double)N * D, (double)N * (D * ix->elt + 12));
-        hipLaunchKernelGGL(kern, dim3(mp.slabs), dim3(256), mp.lds, st, a);
-        MM_HIP(hipGetLastError());
-    }
+    }));
     hipLaunchKernelGGL(assign_decide_kernel, dim3((int)std::min<int64_t>(2048, (N + 255) / 256)), dim3(256), 0, st, (const float*)st_s1,
                        (const int32_t*)st_i1, (const float*)st_s2, N, (const float*)d_E, d_assign, d_dist, ix->asg_list.as<int32_t>(), d_bcnt);
     MM_HIP(hipGetLastError());
@@ -1965,8 +1848,8 @@ extern "C" int mmiss_index_assign(mmiss_index* ix, const float* centres, int32_t
     });
     MM_HIP(hipGetLastError());
     if (out_sizes) MM_TRY(assign_sizes(ix, st, d_assign, C, out_sizes));
-    if (!asg_dev) MM_HIP(hipMemcpyAsync(out_assign, d_assign, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-    if (out_dist && !dist_dev) MM_HIP(hipMemcpyAsync(out_dist, d_dist, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    if (!asg_dev) MM_TRY(copy_any(out_assign, d_assign, (size_t)N * 4, st));
+    if (out_dist && !dist_dev) MM_TRY(copy_any(out_dist, d_dist, (size_t)N * 4, st));
     MM_HIP(hipMemcpyAsync(ix->swp_pin.p, ix->asg_meta.p, 12, hipMemcpyDeviceToHost, st));
     MM_HIP(hipStreamSynchronize(st));
     const int32_t* meta = ix->swp_pin.as<int32_t>();   // (E, live centres, borderline rows)
@@ -1983,55 +1866,41 @@ extern "C" int mmiss_index_cluster_sums(mmiss_index* ix, const int32_t* assign, 
     if (!out_sums || (n > 0 && !assign)) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
     std::lock_guard<std::mutex> lk(ix->mu);
     if (n != ix->count) MM_FAIL(MMISS_ERR_ARG, "%s: %lld assignments for %lld rows", who, (long long)n, (long long)ix->count);
-    MM_NO_PENDING(ix, who);
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, who, &st));
     const int64_t N = ix->count;
     const int D = ix->dim;
-    const bool sums_dev = mmiss_is_device_ptr(out_sums);
     const size_t sum_bytes = (size_t)C * D * 8;
     if (N == 0) {
-        if (sums_dev) MM_HIP(hipMemsetAsync(out_sums, 0, sum_bytes, st)); else memset(out_sums, 0, sum_bytes);
-        MM_TRY(deliver_zeros_i64(st, out_sizes, C));
+        MM_TRY(zero_any(out_sums, sum_bytes, st, false));
+        MM_TRY(zero_any(out_sizes, (size_t)C * 8, st, true));
         MM_HIP(hipStreamSynchronize(st));
         return MMISS_OK;
     }
     MM_TRY(ix->asg_meta.ensure(ASSIGN_META_SIZES + (size_t)ASSIGN_MAX_CENTRES * 8));
     const int32_t* d_assign = assign;
-    if (!mmiss_is_device_ptr(assign)) {
-        MM_TRY(ix->asg_out.ensure((size_t)N * 4));
-        MM_HIP(hipMemcpyAsync(ix->asg_out.p, assign, (size_t)N * 4, hipMemcpyHostToDevice, st));
-        d_assign = ix->asg_out.as<int32_t>();
-    }
+    MM_TRY(device_view(&d_assign, (size_t)N, ix->asg_out, 0, (size_t)N * 4, st));
+    const bool sums_dev = mmiss_is_device_ptr(out_sums);
     unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(out_sums);
     if (!sums_dev) { MM_TRY(ix->asg_sums.ensure(sum_bytes)); d_sums = ix->asg_sums.as<unsigned long long>(); }
     MM_HIP(hipMemsetAsync(d_sums, 0, sum_bytes, st));
-    // the widest column chunk (a divisor of dim, a multiple of 16) whose [C][cols] table of 64-bit sums fits 128 KiB of LDS:
-    // all of dim 512 up to 32 clusters, 16 columns at 1024 clusters
-    constexpr int TABLE_LDS = 128 * 1024;
+    const ClusterSumsPlan cp = plan_cluster_sums(D, C, N);
     ClusterSumsArgs a{};
-    a.cols = 16;
-    for (int k = 1; k <= D / 16; ++k)
-        if (D % k == 0 && (D / k) % 16 == 0 && (size_t)C * (D / k) * 8 <= (size_t)TABLE_LDS) { a.cols = D / k; break; }
-    const int chunks = D / a.cols;
-    const int64_t slab_target = std::max<int64_t>(1, 2048 / chunks);
-    a.rows_per_block = (int)std::max<int64_t>(64, (N + slab_target - 1) / slab_target);
-    const int slabs = (int)((N + a.rows_per_block - 1) / a.rows_per_block);
+    a.cols = cp.cols; a.rows_per_block = cp.rows_per_block;
     a.rows = ix->rows.p; a.inv = ix->inv.as<float>(); a.assign = d_assign; a.N = N; a.D = D; a.C = C; a.sums = d_sums;
-    const int lds = C * a.cols * 8;
     {
         MM_PROF("cluster_sums", st, (double)N * D, (double)N * (D * ix->elt + 4));
         int rc = MMISS_OK;
         with_storage(ix->dtype, [&](auto s) {
             using T = typename decltype(s)::T;
-            rc = mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&cluster_sums_kernel<T>), lds);
-            if (rc == MMISS_OK) hipLaunchKernelGGL(cluster_sums_kernel<T>, dim3(slabs, chunks), dim3(1024), lds, st, a);
+            rc = mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(&cluster_sums_kernel<T>), cp.lds);
+            if (rc == MMISS_OK) hipLaunchKernelGGL(cluster_sums_kernel<T>, dim3(cp.slabs, cp.chunks), dim3(1024), cp.lds, st, a);
         });
         MM_TRY(rc);
         MM_HIP(hipGetLastError());
     }
     if (out_sizes) MM_TRY(assign_sizes(ix, st, d_assign, C, out_sizes));
-    if (!sums_dev) MM_HIP(hipMemcpyAsync(out_sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, st));
+    if (!sums_dev) MM_TRY(copy_any(out_sums, d_sums, sum_bytes, st));
     MM_HIP(hipStreamSynchronize(st));
     return MMISS_OK;
 }
@@ -2046,54 +1915,15 @@ namespace {
 
 constexpr int PROBE_MAX_K = 2040;   // the flat query's own limit
 
-// How a probed call of Q queries runs on the partition as it stands. bound: the most keys one query can have (the tail and the
-// NP largest cells, from the host mirror): it sizes the candidate areas and fixes the selection's levels, so nothing has to come
-// back from the device inside a call.
-struct ProbePlan {
-    int NP = 0;                 // probe slots: min(nprobe, C)
-    int splits = 1, share = 64; // workgroups per list of the scan, rows of a list per workgroup
-    int levels = 1;             // segment_topk launches, the FINAL one included
-    int qchunk = 1;             // queries per chunk (the scratch budget)
-    int64_t bound = 0, stride0 = 1, stride1 = 0;   // keys per query of the two key areas
-};
-
+// how a probed call of Q queries runs on the partition as it stands and under the options as they stand (index_plans.h)
 ProbePlan plan_probed(const mmiss_index* ix, int Q, int k, int nprobe) {
     const mmiss_index::Partition& pt = ix->part;
-    ProbePlan p;
-    p.NP = std::min(nprobe, pt.C);
-    const int64_t tail = ix->count - pt.B;
-    p.bound = tail + pt.top_prefix[(size_t)p.NP];
-    p.stride0 = std::max<int64_t>(p.bound, 1);
-    for (int64_t n = p.bound; n > PROBE_SEG; n = (n + PROBE_SEG - 1) / PROBE_SEG * k) {
-        if (p.levels == 1) p.stride1 = (n + PROBE_SEG - 1) / PROBE_SEG * k;
-        ++p.levels;
-    }
-    // chunks: the key areas of a chunk's queries stay under the budget (one query always runs, whatever it needs)
-    const int64_t budget = (int64_t)mmiss_option("probe_scratch_kb", 512 * 1024) * 1024;
-    const int64_t per_query = (p.stride0 + p.stride1) * 8;
-    p.qchunk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(Q, 32768), budget / per_query));
-    // the scan: about eight workgroups per CU over (lists x queries of a chunk), 64 rows per workgroup at the least, so that a
-    // single query with few probes still fills the chip
-    const int64_t maxlist = std::max(tail, pt.largest);
-    const int64_t lists = (int64_t)p.qchunk * (p.NP + 1);
-    const int64_t want = std::max<int64_t>(1, (2048 + lists - 1) / lists);
-    p.share = (int)std::max<int64_t>(64, round_up((maxlist + want - 1) / want, 16));
-    p.splits = (int)std::max<int64_t>(1, (maxlist + p.share - 1) / p.share);
-    return p;
+    return plan_probed(ix->count, pt.B, pt.largest, pt.top_prefix.data(), pt.C, Q, k, nprobe, plan_options());
 }
 
 // what the partition calls check alike
 #define MM_NEED_PARTITION(ix, who) \
     do { if ((ix)->part.C == 0) MM_FAIL(MMISS_ERR_STATE, "%s: the index has no partition (mmiss_index_partition_set)", who); } while (0)
-
-// n bytes from src (host or device) to dst (host or device), queued on st
-int copy_any(void* dst, const void* src, size_t n, hipStream_t st) {
-    if (n == 0) return MMISS_OK;
-    const bool sd = mmiss_is_device_ptr(src), dd = mmiss_is_device_ptr(dst);
-    if (!sd && !dd) { memcpy(dst, src, n); return MMISS_OK; }
-    MM_HIP(hipMemcpyAsync(dst, src, n, sd ? (dd ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost) : hipMemcpyHostToDevice, st));
-    return MMISS_OK;
-}
 
 }  // namespace
 
@@ -2119,11 +1949,7 @@ extern "C" int mmiss_index_partition_set(mmiss_index* ix, const float* centres, 
     unsigned long long* const d_sizes = reinterpret_cast<unsigned long long*>(ix->prb_meta.as<char>() + (size_t)PROBE_MAX_CENTRES * 4);
     int32_t* const d_cursor = reinterpret_cast<int32_t*>(ix->prb_meta.as<char>() + (size_t)PROBE_MAX_CENTRES * 12);
     const float* src = centres;
-    if (!mmiss_is_device_ptr(centres)) {
-        MM_TRY(ix->stage.ensure((size_t)C * D * 4));
-        MM_HIP(hipMemcpyAsync(ix->stage.p, centres, (size_t)C * D * 4, hipMemcpyHostToDevice, st));
-        src = ix->stage.as<float>();
-    }
+    MM_TRY(device_view(&src, (size_t)C * D, ix->stage, 0, (size_t)C * D * 4, st));
     {   // the canonical normalisation of an f32 row: what oracle normalize_rows(centres, "f32") restates
         MM_PROF("normalize_rows", st, 4.0 * C * D, 8.0 * C * D);
         hipLaunchKernelGGL(normalize_rows_kernel<float>, dim3((C + 3) / 4), dim3(256), 0, st, src, fresh.cn.as<float>(), (int64_t)C, D);
@@ -2222,10 +2048,8 @@ extern "C" int mmiss_index_query_probed(mmiss_index* ix, const float* queries, i
     if (!ix || !queries || !out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
     if (Q < 1 || k < 1 || nprobe < 1) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d nprobe=%d", who, Q, k, nprobe);
     if (k > PROBE_MAX_K) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: k = %d too large (max %d)", who, k, PROBE_MAX_K);
-    const bool out_dev = mmiss_is_device_ptr(out_labels);
-    if (out_dev != mmiss_is_device_ptr(out_dist) || out_dev != mmiss_is_device_ptr(out_count) ||
-        (out_scanned && out_dev != mmiss_is_device_ptr(out_scanned)))
-        MM_FAIL(MMISS_ERR_ARG, "%s: output pointers must be all host or all device", who);
+    bool out_dev = false;
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_scanned, &out_dev));
     std::lock_guard<std::mutex> lk(ix->mu);
     MM_NO_PENDING(ix, who);
     MM_NEED_PARTITION(ix, who);
@@ -2235,33 +2059,15 @@ extern "C" int mmiss_index_query_probed(mmiss_index* ix, const float* queries, i
     const int D = ix->dim;
     const int tail = (int)(ix->count - pt.B);
     const ProbePlan p = plan_probed(ix, Q, k, nprobe);
-    // outputs: the caller's device buffers, or a pinned host block the last kernel writes straight into; the scanned rows always
-    // go to a pinned block (the partition's counter adds them up) and from there to the caller
-    int64_t* d_lab = out_labels; float* d_dist = out_dist; int32_t* d_cnt = out_count;
-    if (!out_dev) {
-        const size_t o_dist = (size_t)Q * k * 8, o_cnt = o_dist + (size_t)Q * k * 4;
-        const size_t need = o_cnt + (size_t)Q * 4;
-        size_t grow = 4096;
-        while (grow < need) grow *= 2;
-        MM_TRY(ix->pin.ensure(need, st, grow));
-        char* const pin = ix->pin.as<char>();
-        d_lab = reinterpret_cast<int64_t*>(pin); d_dist = reinterpret_cast<float*>(pin + o_dist); d_cnt = reinterpret_cast<int32_t*>(pin + o_cnt);
-    }
+    // the scanned rows always go to a pinned block of their own (the partition's counter adds them up) and from there to the caller
+    ResultBlock out;
+    MM_TRY(out.stage(ix->pin, st, Q, k, out_dev, false, false, out_labels, out_dist, out_count, nullptr));
     MM_TRY(ix->swp_pin.ensure((size_t)Q * 8, st, (size_t)std::max(Q, 512) * 8));
     int64_t* const h_scn = ix->swp_pin.as<int64_t>();
     MM_TRY(upload_queries(ix, st, queries, Q));   // qn of every query of the call
-    const uint64_t* d_req = require; const uint64_t* d_exc = exclude;
-    if ((require && !mmiss_is_device_ptr(require)) || (exclude && !mmiss_is_device_ptr(exclude))) {
-        MM_TRY(ix->prb_mask.ensure((size_t)Q * 16));
-        if (require && !mmiss_is_device_ptr(require)) {
-            MM_HIP(hipMemcpyAsync(ix->prb_mask.p, require, (size_t)Q * 8, hipMemcpyHostToDevice, st));
-            d_req = ix->prb_mask.as<uint64_t>();
-        }
-        if (exclude && !mmiss_is_device_ptr(exclude)) {
-            MM_HIP(hipMemcpyAsync(ix->prb_mask.as<uint64_t>() + Q, exclude, (size_t)Q * 8, hipMemcpyHostToDevice, st));
-            d_exc = ix->prb_mask.as<uint64_t>() + Q;
-        }
-    }
+    const uint64_t* d_req = require; const uint64_t* d_exc = exclude;   // host masks: [Q] required, then [Q] excluded in prb_mask
+    MM_TRY(device_view(&d_req, (size_t)Q, ix->prb_mask, 0, (size_t)Q * 16, st));
+    MM_TRY(device_view(&d_exc, (size_t)Q, ix->prb_mask, (size_t)Q * 8, (size_t)Q * 16, st));
     MM_TRY(ix->prb_cell.ensure((size_t)p.qchunk * std::max(p.NP, 1) * 4));
     MM_TRY(ix->prb_base.ensure((size_t)p.qchunk * (p.NP + 1) * 4));
     MM_TRY(ix->prb_total.ensure((size_t)p.qchunk * 4));
@@ -2305,7 +2111,7 @@ extern "C" int mmiss_index_query_probed(mmiss_index* ix, const float* queries, i
             a.in_stride = from_a ? p.stride0 : p.stride1; a.out_stride = from_a ? p.stride1 : p.stride0;
             a.total = ix->prb_total.as<int32_t>(); a.level = l; a.k = k;
             a.labels = ix->labels_d.as<int64_t>();
-            a.out_labels = d_lab + (size_t)q0 * k; a.out_dist = d_dist + (size_t)q0 * k; a.out_count = d_cnt + q0; a.out_scanned = h_scn + q0;
+            a.out_labels = out.lab + (size_t)q0 * k; a.out_dist = out.dist + (size_t)q0 * k; a.out_count = out.cnt + q0; a.out_scanned = h_scn + q0;
             MM_PROF("segment_topk", st, 0.0, (double)Qc * nb * 8);
             if (last) hipLaunchKernelGGL(segment_topk_kernel<true>, dim3(1, Qc), dim3(1024), 0, st, a);
             else hipLaunchKernelGGL(segment_topk_kernel<false>, dim3(nseg, Qc), dim3(1024), 0, st, a);
@@ -2315,12 +2121,8 @@ extern "C" int mmiss_index_query_probed(mmiss_index* ix, const float* queries, i
     }
     if (out_dev && out_scanned) MM_HIP(hipMemcpyAsync(out_scanned, h_scn, (size_t)Q * 8, hipMemcpyHostToDevice, st));
     MM_HIP(hipStreamSynchronize(st));
-    if (!out_dev) {
-        memcpy(out_labels, d_lab, (size_t)Q * k * 8);
-        memcpy(out_dist, d_dist, (size_t)Q * k * 4);
-        memcpy(out_count, d_cnt, (size_t)Q * 4);
-        if (out_scanned) memcpy(out_scanned, h_scn, (size_t)Q * 8);
-    }
+    out.deliver();
+    if (!out_dev && out_scanned) memcpy(out_scanned, h_scn, (size_t)Q * 8);
     pt.queries += Q;
     for (int q = 0; q < Q; ++q) pt.scanned += h_scn[q];
     return MMISS_OK;
@@ -2358,9 +2160,9 @@ extern "C" int mmiss_dbg_index_radius_plan(mmiss_index* ix, int32_t Q, int32_t f
         if (sweep_uses_gemm(ix, filtered != 0, Qc[i])) {
             const int64_t nbn = round_up(N, 256) / 256;
             o[1] = 1;
-            o[2] = strip_length((int)round_up(Qc[i], 256), nbn, nbn);
+            o[2] = strip_length((int)round_up(Qc[i], 256), nbn, nbn, plan_options());
         } else {
-            const ScanPlan sp = plan_sweep(ix->dim, ix->qelt(), Qc[i], N);
+            const DensePlan sp = plan_dense(ix->dim, ix->qelt(), Qc[i], N, false);
             o[3] = sp.nqt; o[4] = sp.slabs; o[5] = sp.tiles_per_block; o[6] = sp.qtiles;
         }
     }
@@ -2386,20 +2188,20 @@ extern "C" int mmiss_dbg_index_plan(mmiss_index* ix, int32_t Q, int32_t k, int32
         out[7] = p.Mq; out[8] = i32(p.Npad); out[9] = i32(p.ns_tiles); out[10] = p.strip;
         const int ng = (int)(p.Ndense / 16);
         out[16] = select_splits(ng, Q);
-        out[17] = merge_two_level(p.sample ? 1 : out[16]);   // (sample form: the last merge reads the one seed list)
+        out[17] = merge_two_level(p.sample ? 1 : out[16], plan_options());   // (sample form: the last merge reads the one seed list)
         out[23] = select_split_groups(ng, out[16]);
     } else {
-        const ScanPlan sp = plan_scan(ix->dim, ix->qelt(), Q, p.kp, N);
+        const ScanPlan sp = plan_scan(ix->dim, ix->qelt(), Q, p.kp, N, plan_options());
         out[11] = sp.nqt; out[12] = sp.cap; out[13] = sp.slabs; out[14] = sp.tiles_per_block; out[15] = sp.qtiles;
-        out[17] = merge_two_level(sp.slabs);
+        out[17] = merge_two_level(sp.slabs, plan_options());
     }
     if (flagged > 0) {
         if (sweep_uses_gemm(ix, filt, flagged)) {
             const int64_t nbn = round_up(N, 256) / 256;
             out[18] = 1;
-            out[22] = strip_length((int)round_up(flagged, 256), nbn, nbn);
+            out[22] = strip_length((int)round_up(flagged, 256), nbn, nbn, plan_options());
         } else {
-            const ScanPlan sp = plan_sweep(ix->dim, ix->qelt(), flagged, N);
+            const DensePlan sp = plan_dense(ix->dim, ix->qelt(), flagged, N, false);
             out[19] = sp.nqt; out[20] = sp.slabs; out[21] = sp.tiles_per_block;
         }
     }
@@ -2431,9 +2233,8 @@ extern "C" int mmiss_dbg_index_prep_queries(mmiss_index* ix, const float* querie
     if (!ix || !queries) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_prep_queries: null argument");
     if (Q <= 0) MM_FAIL(MMISS_ERR_ARG, "mmiss_dbg_index_prep_queries: Q=%d", Q);
     std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_dbg_index_prep_queries");
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, "mmiss_dbg_index_prep_queries", &st));
     MM_TRY(upload_queries(ix, st, queries, Q));
     MM_HIP(hipStreamSynchronize(st));
     const size_t D = (size_t)ix->dim, Qpad = (size_t)round_up(Q, 256);
@@ -2509,9 +2310,8 @@ extern "C" int mmiss_index_save(mmiss_index* ix, const char* path) {
 extern "C" int mmiss_index_load(mmiss_index* ix, const char* path) {
     if (!ix || !path) MM_FAIL(MMISS_ERR_ARG, "mmiss_index_load: null argument");
     std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, "mmiss_index_load");
-    MM_TRY(mmiss_use_device(ix->device));
-    hipStream_t st = ix->stream();
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, "mmiss_index_load", &st));
     // the rows are overwritten by blocking copies that do not run on `st`: a query with device outputs may still be queued on a
     // caller's stream (async_pending) and reads them
     MM_HIP(hipStreamSynchronize(st));

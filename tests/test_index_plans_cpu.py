@@ -1,0 +1,420 @@
+"""csrc/index_plans.h — the launch-shape arithmetic of the index's host layer — checked on the host: a small stand-alone C++
+program (g++, no HIP, nothing loaded into Python) includes the header api_index.hip plans with and compares every field it
+returns with a literal transcription of the rules as api_index.hip carried them before they moved there (namespace parent:
+plan_scan, plan_sweep, plan_membership, strip_length, select_splits, merge_two_level, plan_probed, the cluster_sums chunking
+and the three result-block layouts), over every dim class, operand count, k', index size and option the index meets."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multimodal-image-similarity-search_amd", "csrc")
+
+PROGRAM = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <cstdint>
+#include <vector>
+#include <algorithm>
+#include <functional>
+#include "index_plans.h"
+
+// ---------------------------------------------------------------------------------------------- the parent's rules, literally
+static PlanOptions g_opt;   // what the parent's mmiss_option() answers
+static int mmiss_option(const char* key, int dflt) {
+    (void)dflt;
+    if (!strcmp(key, "scan_rounds")) return g_opt.scan_rounds;
+    if (!strcmp(key, "scan_max_slabs")) return g_opt.scan_max_slabs;
+    if (!strcmp(key, "merge_two_level_min")) return g_opt.merge_two_level_min;
+    if (!strcmp(key, "score_strip_fit")) return g_opt.score_strip_fit;
+    if (!strcmp(key, "score_strip")) return g_opt.score_strip;
+    if (!strcmp(key, "probe_scratch_kb")) return g_opt.probe_scratch_kb;
+    std::printf("unknown option %s\n", key);
+    std::abort();
+}
+
+namespace parent {
+
+constexpr int SELECT_UNIT = 1024;   // retrieval_kernels.h
+constexpr int PROBE_SEG = 4096;     // partition_kernels.h
+static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+struct ScanPlan {
+    int nqt, cap, lds, slabs, qtiles, tiles_per_block;
+    bool thr;
+};
+
+constexpr int SCAN_LDS_LIMIT = 160 * 1024;
+int scan_lds_bytes(int D, int qelt, int nqt, int cap) {
+    const int NQ = 16 * nqt;
+    return (((NQ * (D * qelt + 16)) + 15) & ~15) + 2 * 4 * NQ * cap * 4 + 2 * 4 * NQ * 4;
+}
+int sweep_scan_lds(int D, int qelt, int nqt) { return ((16 * nqt * (D * qelt + 16)) + 15) & ~15; }
+
+ScanPlan plan_scan(int D, int elt, int Q, int kp, int64_t N) {
+    ScanPlan p{};
+    const int limit = SCAN_LDS_LIMIT;
+    p.nqt = 1; p.cap = 64;
+    if (kp <= 16 && Q > 16) {
+        for (int nqt : {4, 2})
+            if (scan_lds_bytes(D, elt, nqt, 32) <= limit && (Q > 16 * nqt / 2)) { p.nqt = nqt; p.cap = 32; break; }
+    }
+    const int NQ = 16 * p.nqt;
+    p.lds = scan_lds_bytes(D, elt, p.nqt, p.cap);
+    p.qtiles = (Q + NQ - 1) / NQ;
+    const int64_t ntiles = (N + 15) / 16;
+    const int blocks_per_cu = std::max(1, std::min(8, limit / p.lds));
+    int64_t target = (int64_t)256 * blocks_per_cu * mmiss_option("scan_rounds", 1) / p.qtiles;
+    if (target < 1) target = 1;
+    if (target > mmiss_option("scan_max_slabs", 1024)) target = mmiss_option("scan_max_slabs", 1024);
+    int64_t tpb = (ntiles + target - 1) / target;
+    tpb = (tpb + 3) / 4 * 4;  // every wave of a block gets the same number of tiles
+    if (tpb < 4) tpb = 4;
+    p.tiles_per_block = (int)tpb;
+    p.slabs = (int)((ntiles + tpb - 1) / tpb);
+    return p;
+}
+
+ScanPlan plan_sweep(int D, int qelt, int Qf, int64_t N) {
+    ScanPlan p{};
+    p.thr = true;
+    p.cap = 32;
+    p.nqt = Qf > 32 ? 4 : Qf > 16 ? 2 : 1;
+    while (p.nqt > 1 && sweep_scan_lds(D, qelt, p.nqt) > SCAN_LDS_LIMIT) p.nqt >>= 1;
+    p.lds = sweep_scan_lds(D, qelt, p.nqt);
+    p.qtiles = (Qf + 16 * p.nqt - 1) / (16 * p.nqt);
+    const int64_t ntiles = (N + 15) / 16;
+    const int per_cu = std::max(1, std::min(8, SCAN_LDS_LIMIT / p.lds));
+    int64_t target = std::max<int64_t>(1, (int64_t)256 * per_cu / p.qtiles);
+    int64_t tpb = std::max<int64_t>(4, (((ntiles + target - 1) / target) + 3) / 4 * 4);
+    p.tiles_per_block = (int)tpb;
+    p.slabs = (int)((ntiles + tpb - 1) / tpb);
+    return p;
+}
+
+struct MemberPlan { int nqt, lds, slabs, tiles_per_block, passes; };
+
+MemberPlan plan_membership(int D, int qelt, int P, int64_t N) {
+    MemberPlan p{};
+    p.nqt = P > 32 ? 4 : P > 16 ? 2 : 1;
+    while (p.nqt > 1 && sweep_scan_lds(D, qelt, p.nqt) > SCAN_LDS_LIMIT) p.nqt >>= 1;
+    p.lds = sweep_scan_lds(D, qelt, p.nqt);
+    p.passes = (P + 16 * p.nqt - 1) / (16 * p.nqt);
+    const int64_t ntiles = (N + 15) / 16;
+    const int per_cu = std::max(1, std::min(8, SCAN_LDS_LIMIT / p.lds));
+    const int64_t target = (int64_t)256 * per_cu;
+    const int64_t tpb = std::max<int64_t>(4, (((ntiles + target - 1) / target) + 3) / 4 * 4);
+    p.tiles_per_block = (int)tpb;
+    p.slabs = (int)((ntiles + tpb - 1) / tpb);
+    return p;
+}
+
+constexpr int MERGE_LISTS_PER_BLOCK = 32;   // lists per first-level merge block
+bool merge_two_level(int L) { return L > mmiss_option("merge_two_level_min", 64); }
+
+int strip_length(int Mq, int64_t nbn, int64_t ncol) {
+    const int64_t tiles = nbn * (Mq / 256);
+    int strip = (int)std::min<int64_t>(32, std::max<int64_t>(1, tiles / 2048));
+    if (strip >= 8 && mmiss_option("score_strip_fit", 1) != 0) {
+        double best = 1e300;
+        int best_s = strip;
+        for (int sl = strip; sl >= strip / 2; --sl) {
+            const int64_t wgs = (Mq / 256) * ((ncol + sl - 1) / sl);
+            const int64_t rounds = (wgs + 255) / 256;
+            const double cost = (double)rounds * (sl + 0.25);
+            if (cost < best - 1e-9) { best = cost; best_s = sl; }
+        }
+        strip = best_s;
+    }
+    const int forced = mmiss_option("score_strip", 0);
+    if (forced > 0) strip = forced;
+    return strip;
+}
+
+int select_splits(int ng, int Q) {
+    const int units = (ng + SELECT_UNIT - 1) / SELECT_UNIT;
+    int splits = (1024 + Q - 1) / Q;
+    if (splits > units) splits = units;
+    if (splits > 32) splits = 32;
+    if (splits < 1) splits = 1;
+    return splits;
+}
+
+// (the handle, as far as plan_probed reads it)
+struct mmiss_index {
+    int64_t count = 0;
+    struct Partition {
+        int C = 0;
+        int64_t B = 0, largest = 0;
+        std::vector<int64_t> top_prefix;
+    } part;
+};
+
+struct ProbePlan {
+    int NP = 0;                 // probe slots: min(nprobe, C)
+    int splits = 1, share = 64; // workgroups per list of the scan, rows of a list per workgroup
+    int levels = 1;             // segment_topk launches, the FINAL one included
+    int qchunk = 1;             // queries per chunk (the scratch budget)
+    int64_t bound = 0, stride0 = 1, stride1 = 0;   // keys per query of the two key areas
+};
+
+ProbePlan plan_probed(const mmiss_index* ix, int Q, int k, int nprobe) {
+    const mmiss_index::Partition& pt = ix->part;
+    ProbePlan p;
+    p.NP = std::min(nprobe, pt.C);
+    const int64_t tail = ix->count - pt.B;
+    p.bound = tail + pt.top_prefix[(size_t)p.NP];
+    p.stride0 = std::max<int64_t>(p.bound, 1);
+    for (int64_t n = p.bound; n > PROBE_SEG; n = (n + PROBE_SEG - 1) / PROBE_SEG * k) {
+        if (p.levels == 1) p.stride1 = (n + PROBE_SEG - 1) / PROBE_SEG * k;
+        ++p.levels;
+    }
+    // chunks: the key areas of a chunk's queries stay under the budget (one query always runs, whatever it needs)
+    const int64_t budget = (int64_t)mmiss_option("probe_scratch_kb", 512 * 1024) * 1024;
+    const int64_t per_query = (p.stride0 + p.stride1) * 8;
+    p.qchunk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(Q, 32768), budget / per_query));
+    // the scan: about eight workgroups per CU over (lists x queries of a chunk), 64 rows per workgroup at the least, so that a
+    // single query with few probes still fills the chip
+    const int64_t maxlist = std::max(tail, pt.largest);
+    const int64_t lists = (int64_t)p.qchunk * (p.NP + 1);
+    const int64_t want = std::max<int64_t>(1, (2048 + lists - 1) / lists);
+    p.share = (int)std::max<int64_t>(64, round_up((maxlist + want - 1) / want, 16));
+    p.splits = (int)std::max<int64_t>(1, (maxlist + p.share - 1) / p.share);
+    return p;
+}
+
+// mmiss_index_cluster_sums, between the memset of the sums and the launch
+struct ClusterSums { int cols, chunks, rows_per_block, slabs, lds; };
+ClusterSums cluster_sums(int D, int C, int64_t N) {
+    constexpr int TABLE_LDS = 128 * 1024;
+    struct { int cols, rows_per_block; } a{};
+    a.cols = 16;
+    for (int k = 1; k <= D / 16; ++k)
+        if (D % k == 0 && (D / k) % 16 == 0 && (size_t)C * (D / k) * 8 <= (size_t)TABLE_LDS) { a.cols = D / k; break; }
+    const int chunks = D / a.cols;
+    const int64_t slab_target = std::max<int64_t>(1, 2048 / chunks);
+    a.rows_per_block = (int)std::max<int64_t>(64, (N + slab_target - 1) / slab_target);
+    const int slabs = (int)((N + a.rows_per_block - 1) / a.rows_per_block);
+    const int lds = C * a.cols * 8;
+    return ClusterSums{a.cols, chunks, a.rows_per_block, slabs, lds};
+}
+
+// the three result blocks: byte offsets of labels (0), totals, distances, counts, flags (-1: none), and the pinned block's sizes
+struct Block { long long tot, dist, cnt, flags; size_t need, grow; };
+static size_t grown(size_t need) {
+    size_t grow = 4096;
+    while (grow < need) grow *= 2;
+    return grow;
+}
+Block stage_outputs(int Q, int k) {
+    const size_t pin_dist = (size_t)Q * k * 8, pin_cnt = pin_dist + (size_t)Q * k * 4, pin_flags = pin_cnt + (size_t)Q * 4;
+    const size_t need = pin_flags + (size_t)Q * 4;
+    return Block{-1, (long long)pin_dist, (long long)pin_cnt, (long long)pin_flags, need, grown(need)};
+}
+Block radius_chunk(int Qc, int cap) {
+    const size_t o_tot = (size_t)Qc * cap * 8, o_dist = o_tot + (size_t)Qc * 8, o_cnt = o_dist + (size_t)Qc * cap * 4;
+    const size_t need = o_cnt + (size_t)Qc * 4;
+    return Block{(long long)o_tot, (long long)o_dist, (long long)o_cnt, -1, need, grown(need)};
+}
+Block query_probed(int Q, int k) {
+    const size_t o_dist = (size_t)Q * k * 8, o_cnt = o_dist + (size_t)Q * k * 4;
+    const size_t need = o_cnt + (size_t)Q * 4;
+    return Block{-1, (long long)o_dist, (long long)o_cnt, -1, need, grown(need)};
+}
+
+}  // namespace parent
+
+// ---------------------------------------------------------------------------------------------- the grid
+static const char* g_where = "";
+static long long g_ctx[6];
+#define CHECK(c)                                                                                                          \
+    do {                                                                                                                  \
+        if (!(c)) {                                                                                                       \
+            std::printf("FAILED %s in %s: %lld %lld %lld %lld %lld %lld, option set %d\n", #c, g_where, g_ctx[0], g_ctx[1], \
+                        g_ctx[2], g_ctx[3], g_ctx[4], g_ctx[5], g_set);                                                   \
+            return 1;                                                                                                     \
+        }                                                                                                                 \
+    } while (0)
+#define AT(name, a, b, c, d, e, f) (g_where = (name), g_ctx[0] = (a), g_ctx[1] = (b), g_ctx[2] = (c), g_ctx[3] = (d), g_ctx[4] = (e), g_ctx[5] = (f))
+
+static int g_set = 0;
+static long g_checked = 0;
+
+static const int DIMS[] = {128, 256, 512, 768, 1024, 1920, 3968};
+static const int QELTS[] = {2, 4};
+static const int KPS[] = {8, 16, 17, 32, 64};
+static const int64_t NS[] = {1, 15, 16, 17, 63, 64, 65, 4095, 4096, 4097, 100003, 1000000, 10000000, 2147483647LL - 16};
+static std::vector<int> counts() {
+    std::vector<int> c;
+    for (int i = 1; i <= 64; ++i) c.push_back(i);
+    for (int i : {65, 128, 255, 256, 257, 1024}) c.push_back(i);
+    return c;
+}
+
+static int scans_and_dense(const PlanOptions& o) {
+    for (int D : DIMS) for (int qelt : QELTS) for (int n : counts()) for (int64_t N : NS) {
+        for (int kp : KPS) {
+            AT("plan_scan", D, qelt, n, kp, N, 0);
+            const parent::ScanPlan a = parent::plan_scan(D, qelt, n, kp, N);
+            const ScanPlan b = plan_scan(D, qelt, n, kp, N, o);
+            CHECK(a.nqt == b.nqt && a.cap == b.cap && a.lds == b.lds && a.slabs == b.slabs && a.qtiles == b.qtiles);
+            CHECK(a.tiles_per_block == b.tiles_per_block && a.thr == b.thr && !b.thr);
+            CHECK(b.lds == scan_lds_bytes(D, qelt, b.nqt, b.cap) && b.lds == parent::scan_lds_bytes(D, qelt, b.nqt, b.cap));
+            CHECK(b.slabs >= 1 && (int64_t)b.slabs * b.tiles_per_block * 16 >= N);   // every row has a block
+            ++g_checked;
+        }
+        {
+            AT("plan_sweep", D, qelt, n, N, 0, 0);
+            const parent::ScanPlan a = parent::plan_sweep(D, qelt, n, N);
+            const DensePlan d = plan_dense(D, qelt, n, N, false);
+            const ScanPlan b = d.as_scan();
+            CHECK(a.nqt == b.nqt && a.cap == b.cap && a.lds == b.lds && a.slabs == b.slabs && a.qtiles == b.qtiles);
+            CHECK(a.tiles_per_block == b.tiles_per_block && a.thr == b.thr && b.thr);
+            CHECK(d.nqt == a.nqt && d.lds == a.lds && d.slabs == a.slabs && d.tiles_per_block == a.tiles_per_block && d.qtiles == a.qtiles);
+            CHECK(d.passes == 1);
+            CHECK(d.lds == sweep_scan_lds(D, qelt, d.nqt) && d.lds == parent::sweep_scan_lds(D, qelt, d.nqt));
+            CHECK(16 * d.nqt * d.qtiles >= n && (int64_t)d.slabs * d.tiles_per_block * 16 >= N);
+        }
+        {
+            AT("plan_membership", D, qelt, n, N, 0, 0);
+            const parent::MemberPlan a = parent::plan_membership(D, qelt, n, N);
+            const DensePlan d = plan_dense(D, qelt, n, N, true);
+            CHECK(d.nqt == a.nqt && d.lds == a.lds && d.slabs == a.slabs && d.tiles_per_block == a.tiles_per_block && d.passes == a.passes);
+            CHECK(d.qtiles == 1);
+            CHECK(16 * d.nqt * d.passes >= n && (int64_t)d.slabs * d.tiles_per_block * 16 >= N);
+        }
+        g_checked += 2;
+    }
+    static_assert(SCAN_LDS_LIMIT == parent::SCAN_LDS_LIMIT && MERGE_LISTS_PER_BLOCK == parent::MERGE_LISTS_PER_BLOCK, "constants");
+    static_assert(PLAN_SELECT_UNIT == parent::SELECT_UNIT && PLAN_PROBE_SEG == parent::PROBE_SEG, "what the kernel headers fix");
+    return 0;
+}
+
+static int gemm_select_merge(const PlanOptions& o) {
+    for (int n : counts()) for (int64_t N : NS) {
+        const int Mq = (int)parent::round_up(n, 256);
+        const int64_t Npad = parent::round_up(N, 256), nbn = Npad / 256;
+        const int64_t ns_tiles = std::max<int64_t>(16, nbn / 32);   // plan_query's sample
+        for (int64_t ncol : {nbn, std::max<int64_t>(nbn - ns_tiles, 1), std::max<int64_t>(nbn / 2, 1)}) {
+            AT("strip_length", Mq, nbn, ncol, 0, 0, 0);
+            CHECK(parent::strip_length(Mq, nbn, ncol) == strip_length(Mq, nbn, ncol, o));
+            ++g_checked;
+        }
+        for (int64_t rows : {Npad, std::min(Npad, ns_tiles * 256), parent::round_up(N, 128)}) {
+            const int ng = (int)(rows / 16);
+            AT("select_splits", ng, n, 0, 0, 0, 0);
+            CHECK(parent::select_splits(ng, n) == select_splits(ng, n));
+            ++g_checked;
+        }
+    }
+    for (int L = 0; L <= 5000; ++L) {
+        AT("merge_two_level", L, 0, 0, 0, 0, 0);
+        CHECK(parent::merge_two_level(L) == merge_two_level(L, o));
+    }
+    return 0;
+}
+
+static int cluster_sums() {
+    for (int D : DIMS) for (int C : counts()) for (int64_t N : NS) {
+        AT("plan_cluster_sums", D, C, N, 0, 0, 0);
+        const parent::ClusterSums a = parent::cluster_sums(D, C, N);
+        const ClusterSumsPlan b = plan_cluster_sums(D, C, N);
+        CHECK(a.cols == b.cols && a.chunks == b.chunks && a.rows_per_block == b.rows_per_block && a.slabs == b.slabs && a.lds == b.lds);
+        CHECK(b.cols * b.chunks == D && b.cols % 16 == 0 && (int64_t)b.slabs * b.rows_per_block >= N);
+        CHECK(b.lds <= 128 * 1024 || b.cols == 16);
+        ++g_checked;
+    }
+    return 0;
+}
+
+// hand-built partitions: the cell sizes of the first B rows, then `tail` rows added since
+static int probed(const PlanOptions& o) {
+    const int64_t SEG = PLAN_PROBE_SEG;
+    for (int shape = 0; shape < 3; ++shape) for (int64_t per : {1, 100, 9766}) for (int64_t tail : {(int64_t)0, SEG - 1, SEG, SEG + 1}) {
+        const int C = shape == 0 ? 1 : 1024;
+        const int64_t B = per * 1024;
+        std::vector<int64_t> sizes((size_t)C, 0);
+        if (shape == 0) sizes[0] = B;                                        // one cell holding everything
+        else if (shape == 1) std::fill(sizes.begin(), sizes.end(), per);     // 1024 equal cells
+        else sizes[517] = B;                                                 // 1023 empty cells and one full one
+        parent::mmiss_index ix;
+        ix.count = B + tail;
+        ix.part.C = C; ix.part.B = B;
+        ix.part.largest = *std::max_element(sizes.begin(), sizes.end());
+        std::vector<int64_t> desc(sizes);
+        std::sort(desc.begin(), desc.end(), std::greater<int64_t>());
+        ix.part.top_prefix.assign((size_t)C + 1, 0);
+        for (int c = 0; c < C; ++c) ix.part.top_prefix[(size_t)c + 1] = ix.part.top_prefix[(size_t)c] + desc[(size_t)c];
+        for (int k : {1, 10, 1000, 2040}) for (int nprobe : {1, 32, C, C + 1}) for (int Q : {1, 7, 256, 32768, 40000}) {
+            AT("plan_probed", shape, B, tail, k, nprobe, Q);
+            const parent::ProbePlan a = parent::plan_probed(&ix, Q, k, nprobe);
+            const ProbePlan b = plan_probed(ix.count, ix.part.B, ix.part.largest, ix.part.top_prefix.data(), ix.part.C, Q, k, nprobe, o);
+            CHECK(a.NP == b.NP && a.splits == b.splits && a.share == b.share && a.levels == b.levels && a.qchunk == b.qchunk);
+            CHECK(a.bound == b.bound && a.stride0 == b.stride0 && a.stride1 == b.stride1);
+            CHECK(b.NP >= 1 && b.NP <= C && b.qchunk >= 1 && b.qchunk <= Q && b.share % 16 == 0);
+            CHECK((int64_t)b.splits * b.share >= std::max(tail, ix.part.largest));   // every row of the longest list has a workgroup
+            int64_t n = b.bound;                                                     // ... and the last level fits one segment
+            for (int l = 1; l < b.levels; ++l) n = (n + SEG - 1) / SEG * k;
+            CHECK(n <= SEG);
+            ++g_checked;
+        }
+    }
+    return 0;
+}
+
+static int one_block(const parent::Block& a, const ResultLayout& b, int64_t Q, int64_t slots) {
+    CHECK(a.tot < 0 || (size_t)a.tot == b.tot);
+    CHECK((size_t)a.dist == b.dist && (size_t)a.cnt == b.cnt);
+    CHECK(a.flags < 0 || (size_t)a.flags == b.flags);
+    CHECK(a.need == b.need && a.grow == b.grow);
+    CHECK(b.tot % 8 == 0 && b.dist % 4 == 0 && b.cnt % 4 == 0 && b.flags % 4 == 0);   // (labels: offset 0 of a page-aligned block)
+    CHECK(b.tot == (size_t)Q * slots * 8 && b.dist >= b.tot && b.cnt == b.dist + (size_t)Q * slots * 4 && b.flags == b.cnt + (size_t)Q * 4);
+    CHECK(b.need >= b.flags && b.need <= b.grow && b.grow >= 4096 && (b.grow & (b.grow - 1)) == 0);
+    ++g_checked;
+    return 0;
+}
+
+static int result_blocks() {
+    for (int Q : counts()) for (int slots : {1, 3, 8, 10, 16, 17, 32, 64, 1000, 2040, 4096}) {
+        AT("result block of a query", Q, slots, 0, 0, 0, 0);
+        if (one_block(parent::stage_outputs(Q, slots), result_layout(Q, slots, false, true), Q, slots)) return 1;
+        AT("result block of a radius chunk", Q, slots, 0, 0, 0, 0);
+        if (one_block(parent::radius_chunk(Q, slots), result_layout(Q, slots, true, false), Q, slots)) return 1;
+        AT("result block of a probed call", Q, slots, 0, 0, 0, 0);
+        if (one_block(parent::query_probed(Q, slots), result_layout(Q, slots, false, false), Q, slots)) return 1;
+    }
+    return 0;
+}
+
+int main() {
+    // the options at their defaults, then each at one other value
+    std::vector<PlanOptions> sets(7);
+    sets[1].scan_rounds = 3; sets[2].scan_max_slabs = 256; sets[3].merge_two_level_min = 4096;
+    sets[4].score_strip_fit = 0; sets[5].score_strip = 5; sets[6].probe_scratch_kb = 64;
+    {
+        const PlanOptions d;
+        g_where = "defaults";
+        CHECK(d.scan_rounds == 1 && d.scan_max_slabs == 1024 && d.merge_two_level_min == 64 && d.score_strip_fit == 1);
+        CHECK(d.score_strip == 0 && d.probe_scratch_kb == 512 * 1024);
+    }
+    for (g_set = 0; g_set < (int)sets.size(); ++g_set) {
+        g_opt = sets[(size_t)g_set];
+        if (scans_and_dense(g_opt) || gemm_select_merge(g_opt) || probed(g_opt)) return 1;
+    }
+    g_set = 0;
+    if (cluster_sums() || result_blocks()) return 1;
+    std::printf("ok: %ld plans\n", g_checked);
+    return 0;
+}
+"""
+
+
+def test_every_plan_and_layout_is_the_parents(tmp_path):
+    src = tmp_path / "plans_check.cpp"
+    src.write_text(PROGRAM)
+    exe = str(tmp_path / "plans_check")
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok:"), r.stdout
