@@ -533,6 +533,48 @@ int mmiss_index_partition_get(mmiss_index* idx, float* centres, int32_t* cells, 
 int mmiss_index_query_probed(mmiss_index* idx, const float* queries, int32_t Q, int32_t k, int32_t nprobe, const uint64_t* require,
                              const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_scanned);
 
+/* ---------------------------------------------------------------- distinct results ------------- */
+/*
+ * Top-k with near-duplicates of kept hits suppressed, on the device: ten DIFFERENT images instead of ten copies of one (a burst of
+ * shots, re-encodes of one picture). The reference has no counterpart: its duplicate check is an exact perceptual hash at upload
+ * (backend/app/main.py:628-640) and its searches return collection.query's list as it comes (main.py:761-782).
+ *
+ * For a query q:
+ *   L(q)      = the list mmiss_index_query_filtered(q, k = pool, require, exclude) returns — labels and distance bits in
+ *               (distance, label) order, length m = its out_count; with nprobe >= 1 the list of
+ *               mmiss_index_query_probed(q, pool, nprobe, ...) instead (no partition: MMISS_ERR_STATE, as there).
+ *   sep(s, i) = the float distance mmiss_index_query_radius_by_label defines with label L[s] as the query and the row of L[i]
+ *               as the row: the query is the REPRESENTED row of L[s] (fp8 rows: values x inverse norm, one float multiply),
+ *               normalised again as every query is. sep is NOT symmetric on f16 and fp8 rows; the direction is "the kept row
+ *               is the query". An exact copy sits at whatever distance the flat query reports for it (about 6e-5 on f16 rows),
+ *               not at 0.
+ *   the walk  = positions 0 .. m-1 in order. Position i is SUPPRESSED when an earlier KEPT position s has sep(s, i) <= min_sep
+ *               (compared as floats) and is then OWNED by the smallest such s; otherwise it is kept while fewer than k
+ *               positions are kept; positions that are neither, behind the k-th kept one, are left over and ignored. Every kept
+ *               position, the k-th included, suppresses over all of L.
+ * out_labels / out_dist [Q, k]: the kept entries with L's own distance bits, unused slots -1 / +inf; out_count[q]: the kept
+ * entries; out_dups [Q, k] (may be null): the entries of L each kept entry owns ("+12 similar"), unused slots 0; out_listed [Q]
+ * (may be null): m. The outputs are all host or all device memory; queries and masks host or device as in the other calls.
+ *
+ * Consequences:
+ *   the walk is prefix-stable: the kept labels for pool p are a prefix of those for any pool > p. So whenever out_count == k the
+ *   labels and distances are those of the walk over the ENTIRE ranking, independent of pool; only out_dups depends on pool;
+ *   out_count < k && out_listed == pool means the pool ran out and should be raised;
+ *   a min_sep below every sep (e.g. -1) gives the first k of L bit for bit with dups 0; min_sep >= 4 keeps only the first entry,
+ *   with dups[0] = m - 1.
+ *
+ * Arguments: 1 <= k <= pool (k > pool, k < 1: MMISS_ERR_ARG), pool <= 2040 (above: MMISS_ERR_UNSUPPORTED, the list calls' own
+ * limit); a NaN min_sep is MMISS_ERR_ARG, a negative one is legal; nprobe < 0 is MMISS_ERR_ARG, nprobe == 0 the flat / filtered
+ * list. A query without a direction gives count 0 and listed 0; an empty index gives zeros.
+ * The call locks the handle, runs on its current stream, returns with its work finished, fails with MMISS_ERR_STATE while a
+ * _begin query is open, and checks every argument before it writes anything. The list stage is the restated call's own code and
+ * counts in the guard (or partition) counters exactly as that call; the suppression stage — one kernel launch for all queries,
+ * every comparison a canonical distance, at worst k rounds of pool distances per query — counts nothing.
+ */
+int mmiss_index_query_distinct(mmiss_index* idx, const float* queries, int32_t Q, int32_t k, int32_t pool, float min_sep, int32_t nprobe,
+                               const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
+                               int32_t* out_count, int32_t* out_dups, int32_t* out_listed);
+
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*
  * out[q] = normalize(w * normalize(img[q]) + (1-w) * normalize(txt[q])), float32 [Q,dim].

@@ -238,6 +238,13 @@ int mmiss_dbg_index_prep_queries(struct mmiss_index* ix, const float* queries, i
  *   candidates (the tail and the min(nprobe, C) largest cells)   [5] share: rows of a list per scan workgroup   [6] probe slots
  *   min(nprobe, C)   [7] chunks */
 int mmiss_dbg_index_probe_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int32_t nprobe, int32_t* out);
+/* How the suppression stage of a distinct call (mmiss_index_query_distinct) of Q >= 1 queries is laid out on this index: the call's
+ * own planning function (plan_distinct, csrc/index_plans.h), evaluated on the host. Launches nothing, changes nothing. out is a
+ * HOST int32 [8]:
+ *   [0] rows per trip: consecutive list positions a workgroup takes at a time behind a kept entry (one per group of 16 lanes)
+ *   [1] threads per workgroup (one workgroup per query)   [2] dynamic LDS bytes   [3] queries per launch   [4] launches per call
+ *   [5] the largest pool   [6], [7] 0 */
+int mmiss_dbg_index_distinct_plan(struct mmiss_index* ix, int32_t Q, int32_t* out);
 
 
 /* The path one chunk of an encode call would take on the handle as it stands and under the options as they stand: B items

@@ -109,6 +109,7 @@ SIGNATURES = {
     "mmiss_index_partition_info": (_I, [_P, C.POINTER(_I64)]),
     "mmiss_index_partition_get": (_I, [_P, _P, _P, _I64, _P]),
     "mmiss_index_query_probed": (_I, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "mmiss_index_query_distinct": (_I, [_P, _P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "mmiss_blend": (_I, [_I, _P, _P, _P, C.c_double, _I32, _I32, _P]),
     "mmiss_merge_topk": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_prof_enable": (_I, [_I]),
@@ -158,6 +159,7 @@ SIGNATURES = {
     "mmiss_dbg_index_read_rows": (_I, [_P, _I64, _I64, _P, _P, _P, _P]),
     "mmiss_dbg_index_prep_queries": (_I, [_P, _P, _I32, _P, _P, _P]),
     "mmiss_dbg_index_probe_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
+    "mmiss_dbg_index_distinct_plan": (_I, [_P, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
@@ -295,6 +297,17 @@ def index_probe_plan(handle, Q: int, k: int, nprobe: int) -> dict:
     out = (_I32 * 8)()
     check(load().mmiss_dbg_index_probe_plan(handle, int(Q), int(k), int(nprobe), out))
     return dict(zip(PROBE_PLAN_FIELDS, (int(v) for v in out)))
+
+
+DISTINCT_PLAN_FIELDS = ("rows_per_trip", "threads", "lds_bytes", "queries_per_launch", "launches", "max_pool")
+
+
+def index_distinct_plan(handle, Q: int) -> dict:
+    """mmiss_dbg_index_distinct_plan as a dict: how the suppression stage of a distinct call of Q queries is laid out on the index
+    `handle`. Nothing is launched."""
+    out = (_I32 * 8)()
+    check(load().mmiss_dbg_index_distinct_plan(handle, int(Q), out))
+    return dict(zip(DISTINCT_PLAN_FIELDS, (int(v) for v in out)))
 
 
 _INDEX_ELT = {MMISS_F32: "float32", MMISS_F16: "float16", MMISS_F8: "uint8"}

@@ -12,6 +12,9 @@ The post-filter returns however many of the `limit` nearest images pass the filt
 three search routes therefore take one optional field the reference does not have, `prefilter` ("1" / "true"): with it
 the filters go into the search itself and `limit` filtered results come back (the exact nearest among the images that pass;
 mmiss_amd.search's `filters=`). Without it the routes keep the reference's post-filter, byte for byte.
+A second optional field, `distinct_similarity` (a number in [0, 1]), asks for `limit` DIFFERENT images: a result at least that
+similar to an earlier kept one is dropped and counted in that one's "duplicates" (mmiss_amd.search's `distinct_similarity=`).
+Absent, the call is today's call.
 This is SURVEY.md §8(f) N1: the caller of the hot path, kept thin; everything numeric goes through
 mmiss_amd.utils / mmiss_amd.search. The other ten routes (metadata editing, Moondream filters, reset, static
 files) are out of scope.
@@ -182,7 +185,8 @@ def create_app():
             fields, files = await _form(request)
             image = _open(files, convert_all=True)
             limit = int(_first(fields, "limit", 10))
-            sim = _similarity_kw(fields, "min_similarity", "min_similarity")
+            sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity")}
             model, processor = utils.load_clip_model()
             embedding_result = utils.generate_clip_embedding(image=image, model=model, processor=processor)
             if _prefilter(fields):
@@ -202,7 +206,8 @@ def create_app():
                 return JSONResponse(status_code=422, content={"detail": "field 'query' is required"})
             query = fields["query"][0]
             limit = int(_first(fields, "limit", 10))
-            sim = _similarity_kw(fields, "min_similarity", "min_similarity")
+            sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity")}
             filters = fields.get("filters")
             if not query.strip() and filters:
                 # filter-only browse (main.py:245-249,1225-1242): every stored image, no vector search
@@ -227,7 +232,8 @@ def create_app():
                 return JSONResponse(status_code=422, content={"detail": "field 'query' is required"})
             weight_image = float(_first(fields, "weight_image", 0.5))  # not clamped, as in the backend route
             limit = int(_first(fields, "limit", 10))
-            sim = _similarity_kw(fields, "min_similarity", "min_similarity")
+            sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity")}
             if _prefilter(fields):
                 return {"results": search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,
                                                             limit=limit, filters=fields.get("filters"), **sim)}

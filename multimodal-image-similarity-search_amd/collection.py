@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .index import FlatIndex
+from .index import MAX_POOL, FlatIndex, default_distinct_pool
 
 logger = logging.getLogger("image-match")
 MAX_N_RESULTS = 2040  # mmiss_index_query's per-call limit on k
@@ -378,9 +378,41 @@ class FlatCollection:
             cnt[qi] = len(keep)
         return labs, dist, cnt
 
+    def _distinct_query(self, q: np.ndarray, k: int, filters: List[str], distinct_distance: float, pool: Optional[int],
+                        max_distance=None, n_probe=None):
+        """The distinct top-k (FlatIndex.query_distinct) among the rows answering "yes" to every filter -> (labels [Q,k], distances
+        [Q,k], counts [Q], dups [Q,k]). A query whose pool ran out (count < k, listed == pool) below the largest pool repeats the
+        call once at the largest: sound, because the kept entries for a pool are a prefix of those for any larger one.
+        max_distance cuts the kept list at the radius: the ranking is sorted by distance, so the cut is a prefix."""
+        Q = q.shape[0]
+        masks = {}
+        if filters:
+            self._push_tags()
+            over = [f for f in filters if f in self._filter_overflow]
+            if over:
+                raise ValueError(f"distinct_distance cannot be combined with filter names past the {MAX_FILTER_BITS}th ({over[:3]}): "
+                                 "the host post-filter would change which images count as kept")
+            if any(f not in self._filter_bits for f in filters):   # a name no row has ever answered admits nothing
+                return (np.full((Q, k), -1, np.int64), np.full((Q, k), np.inf, np.float32), np.zeros((Q,), np.int32),
+                        np.zeros((Q, k), np.int32))
+            req = 0
+            for f in filters:
+                req |= 1 << self._filter_bits[f]
+            masks = {"require": np.uint64(req)}
+        nprobe = int(n_probe) if n_probe is not None and self._index.partition_info()["cells"] > 0 else 0
+        pool = default_distinct_pool(k) if pool is None else min(max(int(pool), k), MAX_POOL)
+        labs, dist, cnt, dups, listed = self._index.query_distinct(q, k, distinct_distance, pool, nprobe, **masks)
+        if pool < MAX_POOL and bool(((np.asarray(cnt) < k) & (np.asarray(listed) == pool)).any()):
+            labs, dist, cnt, dups, listed = self._index.query_distinct(q, k, distinct_distance, MAX_POOL, nprobe, **masks)
+        labs, dist, cnt, dups = np.asarray(labs), np.asarray(dist), np.array(cnt, np.int32), np.asarray(dups)
+        if max_distance is not None:
+            within = (dist <= np.float32(max_distance)) & (np.arange(k)[None, :] < cnt[:, None])
+            cnt = within.sum(1).astype(np.int32)
+        return labs, dist, cnt, dups
+
     def query(self, query_embeddings=None, n_results: int = 10, include: Sequence[str] = ("metadatas", "documents", "distances"),
               filters: Optional[Sequence[str]] = None, max_distance: Optional[float] = None, n_probe: Optional[int] = None,
-              **_unused) -> dict:
+              distinct_distance: Optional[float] = None, pool: Optional[int] = None, **_unused) -> dict:
         """collection.query. filters: names of yes/no filters; when given, the result is the exact n_results nearest among the
         rows whose filter_results_json answers "yes" to every one of them (pre-filtering; see the module docstring).
         max_distance: a radius query (FlatIndex.query_radius) — only the rows within that cosine distance are returned, exactly,
@@ -390,9 +422,21 @@ class FlatCollection:
         n_probe: with a partition present (build_partition), search only the n_probe cells nearest to each query and the rows
         added since (FlatIndex.query_probed): the exact n_results nearest among those rows, filters included (up to 64 filter
         names). Without a partition, with max_distance, or with more than 64 filter names it is ignored: the exact answer, never
-        an error. Nothing is written, neither metadata nor journal."""
+        an error.
+        distinct_distance: suppress near-duplicates of kept results (FlatIndex.query_distinct): walking the exact ranking, a row
+        within that cosine distance of an earlier KEPT result is dropped and counted under that result; n_results different
+        images come back, and the dict gains "duplicates" — per query, the rows each result stands for besides itself. pool:
+        how much of the ranking is walked (None: min(2040, max(8 n_results, 64)); a query that runs out is repeated once at
+        2040). Works with filters (up to 64 names; a name past the 64th raises ValueError), n_probe and max_distance (the kept
+        list cut at the radius). Without distinct_distance nothing changes.
+        Nothing is written, neither metadata nor journal."""
         if n_probe is not None and int(n_probe) < 1:
             raise ValueError(f"n_probe: at least 1, got {n_probe}")
+        if distinct_distance is not None:
+            distinct_distance = float(distinct_distance)
+            if distinct_distance != distinct_distance:
+                raise ValueError("distinct_distance is NaN")
+        dups = None
         filters = list(dict.fromkeys(_as_list(filters))) if filters else []
         if query_embeddings is None:
             raise ValueError("FlatCollection.query needs query_embeddings (text embedding functions are out of scope)")
@@ -412,7 +456,9 @@ class FlatCollection:
                 if k > MAX_N_RESULTS:  # one mmiss_index_query call ranks at most 2040 rows per query: clamp, do not fail
                     logger.warning(f"n_results={n_results} clamped to {MAX_N_RESULTS}")
                     k = MAX_N_RESULTS
-                if filters:
+                if distinct_distance is not None:
+                    labs, dist, cnt, dups = self._distinct_query(q, k, filters, distinct_distance, pool, max_distance, n_probe)
+                elif filters:
                     labs, dist, cnt = self._filtered_query(q, k, filters, max_distance, n_probe)
                 else:
                     labs, dist, cnt = self._index_query(q, k, max_distance, n_probe)
@@ -432,6 +478,8 @@ class FlatCollection:
                 out["documents"] = [[self._docs.get(l) for l in ls] for ls in rows]
             if "embeddings" in include:
                 out["embeddings"] = [self._index.get(np.asarray(ls, dtype=np.int64)) for ls in rows]
+            if distinct_distance is not None:
+                out["duplicates"] = [[] if dups is None else [int(x) for x in dups[qi, : int(cnt[qi])]] for qi in range(Q)]
             return out
 
     def add_similarity_filter(self, name: str, embedding, max_distance: float) -> int:

@@ -6,12 +6,15 @@
 #include "membership_kernels.h"
 #include "assign_kernels.h"
 #include "partition_kernels.h"
+#include "distinct_kernels.h"
 #include "gemm_bf16_256.h"
 #include "gemm_strip_p256.h"
 #include <algorithm>
 #include "index_plans.h"
 
 static_assert(PLAN_SELECT_UNIT == SELECT_UNIT && PLAN_PROBE_SEG == PROBE_SEG, "index_plans.h repeats what the kernel headers fix");
+static_assert(PLAN_DISTINCT_THREADS == DISTINCT_THREADS && PLAN_DISTINCT_SLOTS == DISTINCT_SLOTS && PLAN_DISTINCT_MAX_POOL < DISTINCT_SLOTS,
+              "index_plans.h repeats what distinct_kernels.h fixes");
 
 // The results of a query-like call of Q queries: `slots` labels and distances and a count per query, for some calls a total and
 // a flag per query. lab / tot / dist / cnt are where the kernels write them: the caller's device buffers, or a pinned host block
@@ -122,6 +125,9 @@ struct mmiss_index {
     // ... and a probed call's scratch: the probed cells, their key offsets and the totals per query of a chunk, the masks when
     // the caller's are host memory, the two key areas of the selection, and set's small block (live centres, sizes, cursors)
     DevBuf prb_cell, prb_base, prb_total, prb_mask, prb_keys_a, prb_keys_b, prb_meta;
+    // distinct results (mmiss_index_query_distinct): the list stage's labels, distances and counts ([Q, pool], [Q, pool], [Q]), and the
+    // suppression stage's outputs when the caller's are host memory
+    DevBuf dst_list, dst_out;
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -2042,17 +2048,12 @@ extern "C" int mmiss_index_partition_get(mmiss_index* ix, float* centres, int32_
     return MMISS_OK;
 }
 
-extern "C" int mmiss_index_query_probed(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int32_t nprobe, const uint64_t* require,
-                                        const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_scanned) {
-    const char* who = "mmiss_index_query_probed";
-    if (!ix || !queries || !out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
-    if (Q < 1 || k < 1 || nprobe < 1) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d nprobe=%d", who, Q, k, nprobe);
-    if (k > PROBE_MAX_K) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: k = %d too large (max %d)", who, k, PROBE_MAX_K);
-    bool out_dev = false;
-    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_scanned, &out_dev));
-    std::lock_guard<std::mutex> lk(ix->mu);
-    MM_NO_PENDING(ix, who);
-    MM_NEED_PARTITION(ix, who);
+namespace {
+
+// A probed call under the handle's lock, its arguments checked (a partition included): the probed cells, the scan of their lists,
+// the selection. Returns with the stream drained and host outputs delivered.
+int probed_locked(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int32_t nprobe, const uint64_t* require, const uint64_t* exclude,
+                  int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_scanned, bool out_dev) {
     MM_TRY(mmiss_use_device(ix->device));
     hipStream_t st = ix->stream();
     mmiss_index::Partition& pt = ix->part;
@@ -2125,6 +2126,109 @@ extern "C" int mmiss_index_query_probed(mmiss_index* ix, const float* queries, i
     if (!out_dev && out_scanned) memcpy(out_scanned, h_scn, (size_t)Q * 8);
     pt.queries += Q;
     for (int q = 0; q < Q; ++q) pt.scanned += h_scn[q];
+    return MMISS_OK;
+}
+
+}  // namespace
+
+extern "C" int mmiss_index_query_probed(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int32_t nprobe, const uint64_t* require,
+                                        const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_count, int64_t* out_scanned) {
+    const char* who = "mmiss_index_query_probed";
+    if (!ix || !queries || !out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || nprobe < 1) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d nprobe=%d", who, Q, k, nprobe);
+    if (k > PROBE_MAX_K) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: k = %d too large (max %d)", who, k, PROBE_MAX_K);
+    bool out_dev = false;
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_scanned, &out_dev));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    MM_NEED_PARTITION(ix, who);
+    return probed_locked(ix, queries, Q, k, nprobe, require, exclude, out_labels, out_dist, out_count, out_scanned, out_dev);
+}
+
+// ================================================================================================ distinct results
+// mmiss_index_query_distinct: the exact ranked list of each query — the flat / filtered query's (nprobe = 0) or the probed query's,
+// k = pool, the very code of those calls writing into device scratch, so the list and the counters are theirs — and then the
+// suppression stage (distinct_kernels.h): ONE launch for all queries, the greedy walk entirely on the device.
+namespace {
+
+int launch_distinct(mmiss_index* ix, hipStream_t st, const DistinctArgs& a, int Q) {
+    const DistinctPlan p = plan_distinct(ix->dim, Q);
+    const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
+    // (worst case: k rounds of pool dots per query)
+    MM_PROF(f16 ? "distinct_f16" : f8 ? "distinct_f8" : "distinct_f32", st, 2.0 * Q * (double)a.k * a.pool * a.D, (double)Q * a.k * a.pool * a.D * ix->elt);
+    typedef void (*Kernel)(DistinctArgs);
+    const Kernel kern = with_storage(ix->dtype, [&](auto s) -> Kernel { return &distinct_kernel<typename decltype(s)::T>; });
+    MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), p.lds));
+    hipLaunchKernelGGL(kern, dim3(p.queries_per_launch), dim3(p.threads), p.lds, st, a);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+}  // namespace
+
+extern "C" int mmiss_index_query_distinct(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int32_t pool, float min_sep, int32_t nprobe,
+                                          const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
+                                          int32_t* out_count, int32_t* out_dups, int32_t* out_listed) {
+    const char* who = "mmiss_index_query_distinct";
+    if (!ix || (Q > 0 && !queries) || !out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 0 || k < 1 || pool < 1 || nprobe < 0) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d pool=%d nprobe=%d", who, Q, k, pool, nprobe);
+    if (pool > PLAN_DISTINCT_MAX_POOL) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: pool = %d too large (max %d)", who, pool, PLAN_DISTINCT_MAX_POOL);
+    if (k > pool) MM_FAIL(MMISS_ERR_ARG, "%s: k = %d above pool = %d", who, k, pool);
+    if (min_sep != min_sep) MM_FAIL(MMISS_ERR_ARG, "%s: min_sep is NaN", who);
+    bool out_dev = false, opt_dev = false;
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_dups, &out_dev));
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_listed, &opt_dev));
+    if (Q == 0) return MMISS_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    if (nprobe >= 1) MM_NEED_PARTITION(ix, who);
+    MM_TRY(mmiss_use_device(ix->device));
+    hipStream_t st = ix->stream();
+    // the list stage: [Q, pool] labels, [Q, pool] distances, [Q] counts in device scratch
+    const size_t QP = (size_t)Q * pool, QK = (size_t)Q * k;
+    MM_TRY(ix->dst_list.ensure(QP * 12 + (size_t)Q * 4));
+    int64_t* const l_lab = ix->dst_list.as<int64_t>();
+    float* const l_dist = reinterpret_cast<float*>(ix->dst_list.as<char>() + QP * 8);
+    int32_t* const l_cnt = reinterpret_cast<int32_t*>(ix->dst_list.as<char>() + QP * 12);
+    if (nprobe >= 1) {
+        MM_TRY(probed_locked(ix, queries, Q, pool, nprobe, require, exclude, l_lab, l_dist, l_cnt, nullptr, true));
+    } else {
+        MM_TRY(query_begin_locked(ix, queries, Q, pool, require, exclude, l_lab, l_dist, l_cnt));
+        MM_TRY(query_end_locked(ix));
+    }
+    // the suppression stage, into the caller's device buffers or into scratch on its way to the caller's host buffers
+    DistinctArgs a{};
+    a.rows = ix->rows.p; a.D = ix->dim; a.inv = ix->inv.as<float>(); a.labels = ix->labels_d.as<int64_t>(); a.N = ix->count;
+    a.list_lab = l_lab; a.list_dist = l_dist; a.list_cnt = l_cnt; a.pool = pool; a.k = k; a.min_sep = min_sep;
+    a.out_labels = out_labels; a.out_dist = out_dist; a.out_count = out_count; a.out_dups = out_dups; a.out_listed = out_listed;
+    if (!out_dev) {
+        MM_TRY(ix->dst_out.ensure(QK * 16 + (size_t)Q * 8));
+        char* const b = ix->dst_out.as<char>();
+        a.out_labels = reinterpret_cast<int64_t*>(b); a.out_dist = reinterpret_cast<float*>(b + QK * 8);
+        a.out_dups = reinterpret_cast<int32_t*>(b + QK * 12); a.out_count = reinterpret_cast<int32_t*>(b + QK * 16);
+        a.out_listed = a.out_count + Q;
+    }
+    MM_TRY(launch_distinct(ix, st, a, Q));
+    if (!out_dev) {
+        MM_HIP(hipMemcpyAsync(out_labels, a.out_labels, QK * 8, hipMemcpyDeviceToHost, st));
+        MM_HIP(hipMemcpyAsync(out_dist, a.out_dist, QK * 4, hipMemcpyDeviceToHost, st));
+        MM_HIP(hipMemcpyAsync(out_count, a.out_count, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+        if (out_dups) MM_HIP(hipMemcpyAsync(out_dups, a.out_dups, QK * 4, hipMemcpyDeviceToHost, st));
+        if (out_listed) MM_HIP(hipMemcpyAsync(out_listed, a.out_listed, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+    }
+    MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: the layout of the suppression stage of a distinct call of Q queries on this index (plan_distinct, nothing launched).
+extern "C" int mmiss_dbg_index_distinct_plan(mmiss_index* ix, int32_t Q, int32_t* out) {
+    const char* who = "mmiss_dbg_index_distinct_plan";
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d", who, Q);
+    const DistinctPlan p = plan_distinct(ix->dim, Q);
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = p.rows_per_trip; out[1] = p.threads; out[2] = p.lds; out[3] = p.queries_per_launch; out[4] = p.launches;
+    out[5] = PLAN_DISTINCT_MAX_POOL;
     return MMISS_OK;
 }
 

@@ -1,6 +1,6 @@
 // index_plans.h — the launch-shape arithmetic of the index's host layer (api_index.hip): how many queries a scan block stages, how
-// the rows are cut into slabs, how a selection or a merge is split, how a probed call is chunked, where the arrays of a result
-// block lie. Plain C++, no HIP include, no option lookup: api_index.hip, its debug plan entries (mmiss_dbg_index_*plan) and a
+// the rows are cut into slabs, how a selection or a merge is split, how a probed call is chunked, how the suppression stage of a
+// distinct call is laid out, where the arrays of a result block lie. Plain C++, no HIP include, no option lookup: api_index.hip, its debug plan entries (mmiss_dbg_index_*plan) and a
 // host-only test program (tests/test_index_plans_cpu.py) all take the rules from here.
 #pragma once
 
@@ -168,6 +168,25 @@ inline ProbePlan plan_probed(int64_t count, int64_t B, int64_t largest, const in
     const int64_t want = std::max<int64_t>(1, (2048 + lists - 1) / lists);
     p.share = (int)std::max<int64_t>(64, ((maxlist + want - 1) / want + 15) / 16 * 16);
     p.splits = (int)std::max<int64_t>(1, (maxlist + p.share - 1) / p.share);
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------ distinct results
+// The suppression stage of mmiss_index_query_distinct (distinct_kernels.h): one workgroup of PLAN_DISTINCT_THREADS per query, all
+// queries of the call in ONE launch; a group of 16 lanes per list position, so a trip covers threads / 16 consecutive positions;
+// LDS: the kept row as an f32 query and four int32 arrays of PLAN_DISTINCT_SLOTS list positions (row, owner, kept, owned counts).
+constexpr int PLAN_DISTINCT_THREADS = 1024;
+constexpr int PLAN_DISTINCT_SLOTS = 2048;
+constexpr int PLAN_DISTINCT_MAX_POOL = 2040;   // the list calls' own limit on k
+struct DistinctPlan { int rows_per_trip, threads, lds, queries_per_launch, launches; };
+
+inline DistinctPlan plan_distinct(int D, int Q) {
+    DistinctPlan p{};
+    p.threads = PLAN_DISTINCT_THREADS;
+    p.rows_per_trip = p.threads / 16;
+    p.lds = D * 4 + 4 * PLAN_DISTINCT_SLOTS * 4;
+    p.queries_per_launch = Q;
+    p.launches = 1;
     return p;
 }
 

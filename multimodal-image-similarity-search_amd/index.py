@@ -18,8 +18,16 @@ F32, F16, F8 = _lib.MMISS_F32, _lib.MMISS_F16, _lib.MMISS_F8
 _DTYPES = {"f32": F32, "float32": F32, "f16": F16, "float16": F16, "f8": F8, "fp8": F8, "e4m3": F8, F32: F32, F16: F16, F8: F8}
 
 
+MAX_POOL = 2040   # mmiss_index_query_distinct's limit on pool (the list calls' own limit on k)
+
+
 def _is_torch(x) -> bool:
     return hasattr(x, "data_ptr")
+
+
+def default_distinct_pool(k: int) -> int:
+    """the list length FlatIndex.query_distinct walks when the caller names none"""
+    return min(MAX_POOL, max(8 * int(k), 64))
 
 
 class FlatIndex:
@@ -604,6 +612,47 @@ class FlatIndex:
             _lib.check(self._lib.mmiss_index_query_probed(self._h, _lib.ptr(q), Q, k, nprobe, _lib.ptr(masks[0]), _lib.ptr(masks[1]),
                                                           _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt), _lib.ptr(scanned)))
         return lab, dist, cnt, scanned
+
+    # ------------------------------------------------------------------ distinct results
+    MAX_POOL = MAX_POOL
+
+    def query_distinct(self, queries, k: int, min_sep: float, pool: Optional[int] = None, nprobe: int = 0, require=None, exclude=None):
+        """Top-k with near-duplicates of kept hits suppressed on the device (mmiss_index_query_distinct) -> (labels int64 [Q,k],
+        distances float32 [Q,k], counts int32 [Q], dups int32 [Q,k], listed int32 [Q]). The greedy walk over the exact ranked list
+        of `pool` entries — query()'s, or with nprobe >= 1 query_probed()'s: an entry is suppressed when an earlier KEPT entry lies
+        within cosine distance min_sep of it (the distance query_radius_by_label reports with the kept label as the query), else
+        kept while fewer than k are. dups[q, j] = the list entries kept entry j owns, listed[q] = the list's length. The kept
+        entries do not depend on pool once counts == k; counts < k with listed == pool means the pool ran out. pool None:
+        min(2040, max(8 k, 64)). 1 <= k <= pool <= 2040; min_sep must not be NaN (negative: nothing is suppressed). require /
+        exclude as in query(). numpy in -> numpy out, CUDA tensor in -> CUDA tensors out."""
+        k, nprobe = int(k), int(nprobe)
+        pool = default_distinct_pool(k) if pool is None else int(pool)
+        min_sep = float(min_sep)
+        if k < 1:
+            raise ValueError(f"k: at least 1, got {k}")
+        if not k <= pool <= self.MAX_POOL:
+            raise ValueError(f"pool: k .. {self.MAX_POOL}, got {pool} (k = {k})")
+        if min_sep != min_sep:
+            raise ValueError("min_sep is NaN")
+        if nprobe < 0:
+            raise ValueError(f"nprobe: 0 (the flat list) or at least 1, got {nprobe}")
+        q, (lab, dist, cnt) = self._prepare(queries, k)
+        Q = int(q.shape[0])
+        masks = self._masks(q, require, exclude) or (None, None)
+        if _is_torch(q) and q.is_cuda:
+            import torch
+
+            dups = torch.empty((Q, k), dtype=torch.int32, device=q.device)
+            listed = torch.empty((Q,), dtype=torch.int32, device=q.device)
+        else:
+            dups = np.empty((Q, k), dtype=np.int32)
+            listed = np.empty((Q,), dtype=np.int32)
+        with self._call_lock:
+            self._sync_stream(q)
+            _lib.check(self._lib.mmiss_index_query_distinct(self._h, _lib.ptr(q), Q, k, pool, min_sep, nprobe, _lib.ptr(masks[0]),
+                                                            _lib.ptr(masks[1]), _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt), _lib.ptr(dups),
+                                                            _lib.ptr(listed)))
+        return lab, dist, cnt, dups, listed
 
     def guard_stats(self) -> dict:
         """Exactness accounting (mmiss_index_guard_stats_ex): queries served, queries whose first pass could not be proven

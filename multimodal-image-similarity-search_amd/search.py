@@ -14,6 +14,7 @@ plus batched forms (the reference is batch-1 everywhere; BASELINE configs 2-4 ar
 Like the reference, the wrappers catch every exception, log it and return [].
 Every search takes a keyword-only `filters` (names of yes/no filters): the exact `limit` nearest among the images that answer
 "yes" to all of them (FlatCollection.query(filters=...)); the default None searches everything, as the reference does.
+Every search also takes `distinct_similarity`: near-duplicates of kept results are suppressed on the device and counted.
 """
 from __future__ import annotations
 
@@ -52,12 +53,15 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
     result_ids = results["ids"][qi]
     result_metadatas = results["metadatas"][qi]
     result_distances = results["distances"][qi]
+    result_duplicates = results["duplicates"][qi] if results.get("duplicates") is not None else None
     # cosine distance: 0 = identical, 2 = opposite; similarity 1 = identical, 0 = opposite (main.py:782)
     similarities = [1 - (distance / 2) for distance in result_distances]
     for i, img_id in enumerate(result_ids):
         metadata = result_metadatas[i]
         result_metadata = metadata.copy() if metadata is not None else {}
         result_metadata["similarity_score"] = similarities[i]
+        if result_duplicates is not None:
+            result_metadata["duplicates"] = result_duplicates[i]
         if "url" not in result_metadata:
             result_metadata["url"] = f"/static/processed/{img_id}.png"
         if "thumbnail_url" not in result_metadata:
@@ -66,28 +70,36 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
     return similar_images
 
 
-def _filter_kw(filters, min_similarity=None, n_probe=None) -> dict:
-    """the keyword arguments of FlatCollection.query for a search's filters, similarity threshold and probe count; min_similarity =
-    s becomes the radius utils.max_distance_for_similarity(s): on its results "similarity_score >= s" holds for exactly the members"""
+def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=None) -> dict:
+    """the keyword arguments of FlatCollection.query for a search's filters, similarity threshold, probe count and distinctness;
+    min_similarity = s becomes the radius utils.max_distance_for_similarity(s): on its results "similarity_score >= s" holds for
+    exactly the members; distinct_similarity = s becomes distinct_distance the same way: a result at least s similar to an earlier
+    kept result is dropped and counted under it"""
     kw = {"filters": list(filters)} if filters else {}
     if min_similarity is not None:
         kw["max_distance"] = float(utils.max_distance_for_similarity(min_similarity))
     if n_probe is not None:
         kw["n_probe"] = int(n_probe)
+    if distinct_similarity is not None:
+        kw["distinct_distance"] = float(utils.max_distance_for_similarity(distinct_similarity))
     return kw
 
 
 def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
-                   min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[Dict]:
+                   min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
+                   distinct_similarity: Optional[float] = None) -> List[Dict]:
     """Search for similar images using an embedding (main.py:748-805). min_similarity: only the images whose similarity_score
     reaches it, exactly (a radius query; `limit` caps how many) — the reference's roadmap item "Adjustable similarity
     thresholds" (CHANGELOG.md:475). n_probe: search only the n_probe k-means cells nearest to the embedding, and what was added
-    since (build_search_partition; FlatCollection.query(n_probe=)); without a partition the search is the exact one."""
+    since (build_search_partition; FlatCollection.query(n_probe=)); without a partition the search is the exact one.
+    distinct_similarity: `limit` DIFFERENT images — walking the ranking, an image at least that similar to an earlier kept result is
+    dropped and counted under it; every result then carries "duplicates", the images it stands for besides itself
+    (FlatCollection.query(distinct_distance=))."""
     try:
         actual_limit = 1000 if limit <= 0 else limit  # "All" option (limit of 0), main.py:757
         results = _collection().query(query_embeddings=[np.asarray(embedding, dtype=np.float32).tolist()],
                                       n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity, n_probe))
+                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity))
         out = _results_from_query(results, 0)
         logger.info(f"Found {len(out)} similar images")
         return out
@@ -97,13 +109,14 @@ def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[
 
 
 def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
-                         min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[List[Dict]]:
+                         min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
+                         distinct_similarity: Optional[float] = None) -> List[List[Dict]]:
     """[Q, D] embeddings -> one result list per query, one index pass for the whole batch."""
     try:
         actual_limit = 1000 if limit <= 0 else limit
         q = np.asarray(embeddings, dtype=np.float32)
         results = _collection().query(query_embeddings=q, n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity, n_probe))
+                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity))
         return [_results_from_query(results, qi) for qi in range(q.shape[0])]
     except Exception as e:
         logger.error(f"Error searching for similar images: {e}")
@@ -111,20 +124,23 @@ def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Op
 
 
 def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
-                   min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[Dict]:
+                   min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
+                   distinct_similarity: Optional[float] = None) -> List[Dict]:
     """Search for images using a text query (main.py:807-827)."""
     try:
         model, processor = utils.load_clip_model()
         embedding_result = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)
         text_embedding = embedding_result["text"][0]
-        return search_similar(embedding=text_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe)
+        return search_similar(embedding=text_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe,
+                              distinct_similarity=distinct_similarity)
     except Exception as e:
         logger.error(f"Error in text search: {e}")
         return []
 
 
 def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: int = 10, *,
-                      filters: Optional[Sequence[str]] = None, min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[Dict]:
+                      filters: Optional[Sequence[str]] = None, min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
+                      distinct_similarity: Optional[float] = None) -> List[Dict]:
     """Search using both image and text with a weighted combination (main.py:829-867); weight_image is not
     clamped, as in the backend route."""
     try:
@@ -133,7 +149,8 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
         text_embedding = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)["text"][0]
         # normalise both, weighted sum, normalise again (main.py:852-860) — one GPU kernel
         combined_embedding = blend(image_embedding[None], text_embedding[None], weight_image)[0]
-        return search_similar(embedding=combined_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe)
+        return search_similar(embedding=combined_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe,
+                              distinct_similarity=distinct_similarity)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
@@ -141,11 +158,12 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
 
 def search_multimodal_batch(image_embeddings: np.ndarray, text_embeddings: np.ndarray, weight_image: float = 0.5,
                             limit: int = 10, *, filters: Optional[Sequence[str]] = None,
-                            min_similarity: Optional[float] = None, n_probe: Optional[int] = None) -> List[List[Dict]]:
+                            min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
+                            distinct_similarity: Optional[float] = None) -> List[List[Dict]]:
     """BASELINE config 4: a batch of (image, text) embedding pairs, blended and searched in one pass."""
     try:
         return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit, filters=filters,
-                                    min_similarity=min_similarity, n_probe=n_probe)
+                                    min_similarity=min_similarity, n_probe=n_probe, distinct_similarity=distinct_similarity)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
