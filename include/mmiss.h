@@ -575,6 +575,38 @@ int mmiss_index_query_distinct(mmiss_index* idx, const float* queries, int32_t Q
                                const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
                                int32_t* out_count, int32_t* out_dups, int32_t* out_listed);
 
+/* ---------------------------------------------------------------- subset search ---------------- */
+/*
+ * The exact top-k within a caller's list of labels: "the nearest rows among THESE images" — an album, a folder, the hits of an
+ * earlier search, the rows a metadata predicate admits. The reference's store has it as collection.query(where=..., ids=...).
+ *
+ *   S = { r < count : labels[r] is in cand_labels }. A label that is not stored is ignored, a label listed several times counts
+ *       once, the order of the list means nothing.
+ * The result of query q is the exact top-k by (distance, label), with mmiss_index_query's distance bits, over the rows of S that
+ * the masks of q admit (require / exclude as mmiss_index_query_filtered, null = 0) and that have a distance; unused slots are
+ * -1 / +inf; out_count[q] = min(k, those rows); a query without a direction gives count 0. out_matched[q] = |S| for every q,
+ * independent of the masks and of the query; it may be null.
+ *
+ * Consequences: with every stored label listed, the labels, distance bits and counts are those of mmiss_index_query /
+ * mmiss_index_query_filtered; a row outside the list is never returned, however near it is.
+ *
+ * queries float32 [Q, dim], cand_labels int64 [n_cand], require / exclude uint64 [Q]: each host or device memory; the four outputs
+ * (out_labels int64 [Q, k], out_dist float32 [Q, k], out_count int32 [Q], out_matched int64 [Q]) all host or all device memory.
+ * n_cand = 0 is legal (cand_labels may then be null): every count is 0. Q >= 1; 1 <= k <= 2040 (above: MMISS_ERR_UNSUPPORTED);
+ * k < 1, Q < 1, n_cand < 0 or a null pointer where one is needed: MMISS_ERR_ARG; n_cand above 2^31 - 1: MMISS_ERR_UNSUPPORTED.
+ *
+ * The call locks the handle, runs on its current stream, returns with its work finished, fails with MMISS_ERR_STATE while a
+ * _begin query is open, checks every argument before it writes anything, leaves the eight guard counters and the partition's
+ * counters alone, and neither needs nor touches a partition. Every listed row gets its canonical distance directly (no
+ * approximate pass, no guard); each listed row is read once per block of up to 16 queries; the queries are taken in chunks that
+ * keep the scratch under 512 MB.
+ *
+ * Not offered: one list per query (a CSR of lists); a subset as the list stage of mmiss_index_query_distinct; ShardedIndex.
+ */
+int mmiss_index_query_subset(mmiss_index* idx, const float* queries, int32_t Q, int32_t k, const int64_t* cand_labels, int64_t n_cand,
+                             const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
+                             int32_t* out_count, int64_t* out_matched);
+
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*
  * out[q] = normalize(w * normalize(img[q]) + (1-w) * normalize(txt[q])), float32 [Q,dim].

@@ -245,6 +245,17 @@ int mmiss_dbg_index_probe_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int
  *   [1] threads per workgroup (one workgroup per query)   [2] dynamic LDS bytes   [3] queries per launch   [4] launches per call
  *   [5] the largest pool   [6], [7] 0 */
 int mmiss_dbg_index_distinct_plan(struct mmiss_index* ix, int32_t Q, int32_t* out);
+/* How a subset call (mmiss_index_query_subset) of Q >= 1 queries, this k (1 .. 2040) and a list of n_cand >= 0 labels would run on
+ * the index as it stands and under the options as they stand (probe_scratch_kb: the scratch budget in KB): the call's own planning
+ * function (plan_subset, csrc/index_plans.h), evaluated on the host. Launches nothing, changes nothing. out is a HOST int32 [16]:
+ *   [0] bound: min(n_cand, rows), the most rows the list can name   [1] segment size of the selection (keys)   [2] levels:
+ *   segment_topk launches per chunk, the last (the one that writes the results) included   [3], [4] keys per query of the two key
+ *   areas   [5] queries per chunk   [6] chunks   [7] query block: the queries a scan workgroup stages and scores each of its rows
+ *   against   [8] the scan's dynamic LDS bytes   [9] share: list positions per scan workgroup   [10] splits: scan workgroups per
+ *   query block   [11] list positions a scan workgroup takes per trip   [12] blocks of the bitmap's compaction   [13] rows per
+ *   such block   [14], [15] the query block the first / the last chunk runs with: [7] halved while half of it still holds the
+ *   chunk's queries */
+int mmiss_dbg_index_subset_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int64_t n_cand, int32_t* out);
 
 
 /* The path one chunk of an encode call would take on the handle as it stands and under the options as they stand: B items

@@ -110,6 +110,7 @@ SIGNATURES = {
     "mmiss_index_partition_get": (_I, [_P, _P, _P, _I64, _P]),
     "mmiss_index_query_probed": (_I, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "mmiss_index_query_distinct": (_I, [_P, _P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "mmiss_index_query_subset": (_I, [_P, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "mmiss_blend": (_I, [_I, _P, _P, _P, C.c_double, _I32, _I32, _P]),
     "mmiss_merge_topk": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_prof_enable": (_I, [_I]),
@@ -160,6 +161,7 @@ SIGNATURES = {
     "mmiss_dbg_index_prep_queries": (_I, [_P, _P, _I32, _P, _P, _P]),
     "mmiss_dbg_index_probe_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_distinct_plan": (_I, [_P, _I32, C.POINTER(_I32)]),
+    "mmiss_dbg_index_subset_plan": (_I, [_P, _I32, _I32, _I64, C.POINTER(_I32)]),
     "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
@@ -308,6 +310,19 @@ def index_distinct_plan(handle, Q: int) -> dict:
     out = (_I32 * 8)()
     check(load().mmiss_dbg_index_distinct_plan(handle, int(Q), out))
     return dict(zip(DISTINCT_PLAN_FIELDS, (int(v) for v in out)))
+
+
+SUBSET_PLAN_FIELDS = ("bound", "segment", "levels", "stride0", "stride1", "queries_per_chunk", "chunks", "query_block", "lds_bytes",
+                      "share", "splits", "rows_per_trip", "compact_blocks", "compact_block_rows", "first_chunk_block",
+                      "last_chunk_block")
+
+
+def index_subset_plan(handle, Q: int, k: int, n_cand: int) -> dict:
+    """mmiss_dbg_index_subset_plan as a dict: how a subset call of this shape would run on the index `handle` as it stands (and
+    under the option probe_scratch_kb as it stands). Nothing is launched."""
+    out = (_I32 * 16)()
+    check(load().mmiss_dbg_index_subset_plan(handle, int(Q), int(k), int(n_cand), out))
+    return dict(zip(SUBSET_PLAN_FIELDS, (int(v) for v in out)))
 
 
 _INDEX_ELT = {MMISS_F32: "float32", MMISS_F16: "float16", MMISS_F8: "uint8"}

@@ -15,6 +15,8 @@ mmiss_amd.search's `filters=`). Without it the routes keep the reference's post-
 A second optional field, `distinct_similarity` (a number in [0, 1]), asks for `limit` DIFFERENT images: a result at least that
 similar to an earlier kept one is dropped and counted in that one's "duplicates" (mmiss_amd.search's `distinct_similarity=`).
 Absent, the call is today's call.
+A third optional field, `ids` (image ids, comma-separated), searches among those images only (mmiss_amd.search's `within_ids=`):
+the exact `limit` nearest of them; unknown ids are ignored, a malformed value (an empty entry) is answered as a bad `limit` is.
 This is SURVEY.md §8(f) N1: the caller of the hot path, kept thin; everything numeric goes through
 mmiss_amd.utils / mmiss_amd.search. The other ten routes (metadata editing, Moondream filters, reset, static
 files) are out of scope.
@@ -87,6 +89,19 @@ def _similarity_kw(fields, field: str, kw: str) -> dict:
     if not 0.0 <= s <= 1.0:      # (NaN fails both comparisons)
         raise ValueError(f"{field} must be a number in [0, 1], got {raw!r}")
     return {kw: s}
+
+
+def _ids_kw(fields) -> dict:
+    """The optional form field `ids`, image ids separated by commas, as the keyword argument `within_ids` of the search call; absent:
+    no argument at all (today's call). An empty entry ("", "a,,b", a trailing comma) raises, and the route answers as it answers
+    a bad `limit`."""
+    raw = _first(fields, "ids")
+    if raw is None:
+        return {}
+    ids = [part.strip() for part in str(raw).split(",")]
+    if any(not part for part in ids):
+        raise ValueError(f"ids must be image ids separated by commas, got {raw!r}")
+    return {"within_ids": list(dict.fromkeys(ids))}
 
 
 def apply_filters(results: List[dict], filters: Optional[List[str]]) -> List[dict]:
@@ -186,7 +201,7 @@ def create_app():
             image = _open(files, convert_all=True)
             limit = int(_first(fields, "limit", 10))
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
-                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity")}
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
             model, processor = utils.load_clip_model()
             embedding_result = utils.generate_clip_embedding(image=image, model=model, processor=processor)
             if _prefilter(fields):
@@ -207,7 +222,7 @@ def create_app():
             query = fields["query"][0]
             limit = int(_first(fields, "limit", 10))
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
-                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity")}
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
             filters = fields.get("filters")
             if not query.strip() and filters:
                 # filter-only browse (main.py:245-249,1225-1242): every stored image, no vector search
@@ -233,7 +248,7 @@ def create_app():
             weight_image = float(_first(fields, "weight_image", 0.5))  # not clamped, as in the backend route
             limit = int(_first(fields, "limit", 10))
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
-                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity")}
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
             if _prefilter(fields):
                 return {"results": search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,
                                                             limit=limit, filters=fields.get("filters"), **sim)}

@@ -52,6 +52,64 @@ def answers_yes(value) -> bool:
     return str(value).lower().strip() == "yes"
 
 
+_WHERE_COMPARE = {
+    "$eq": lambda a, b: a == b, "$ne": lambda a, b: a != b,
+    "$gt": lambda a, b: a > b, "$gte": lambda a, b: a >= b, "$lt": lambda a, b: a < b, "$lte": lambda a, b: a <= b,
+    "$in": lambda a, b: a in b, "$nin": lambda a, b: a not in b,
+}
+
+
+def check_where(where) -> None:
+    """Raise ValueError unless `where` is a predicate where_matches evaluates: {"field": value}, {"field": {"$op": operand}} with
+    $eq $ne $gt $gte $lt $lte $in $nin, {"$and": [predicates]}, {"$or": [predicates]}; several keys of one dict all have to hold."""
+    if not isinstance(where, dict) or not where:
+        raise ValueError(f"where: a non-empty dict expected, got {where!r}")
+    for key, cond in where.items():
+        if key in ("$and", "$or"):
+            if not isinstance(cond, (list, tuple)) or not cond:
+                raise ValueError(f"where: {key} takes a non-empty list of predicates")
+            for sub in cond:
+                check_where(sub)
+        elif not isinstance(key, str) or key.startswith("$"):
+            raise ValueError(f"where: unknown operator {key!r}")
+        elif isinstance(cond, dict):
+            if not cond:
+                raise ValueError(f"where: no operator for field {key!r}")
+            for op, operand in cond.items():
+                if op not in _WHERE_COMPARE:
+                    raise ValueError(f"where: unknown operator {op!r}")
+                if op in ("$in", "$nin") and not isinstance(operand, (list, tuple, set, frozenset)):
+                    raise ValueError(f"where: {op} takes a list of values")
+        elif isinstance(cond, (list, tuple, set)):
+            raise ValueError(f"where: field {key!r} compared with {type(cond).__name__}; use $in")
+
+
+def where_matches(metadata, where) -> bool:
+    """Does one row's metadata satisfy `where` (checked by check_where)? A row without the field matches only $ne / $nin; values
+    that do not compare ($gt between a string and a number) do not match."""
+    metadata = metadata or {}
+    for key, cond in where.items():
+        if key == "$and":
+            ok = all(where_matches(metadata, sub) for sub in cond)
+        elif key == "$or":
+            ok = any(where_matches(metadata, sub) for sub in cond)
+        else:
+            ok = True
+            for op, operand in (cond.items() if isinstance(cond, dict) else (("$eq", cond),)):
+                if key not in metadata:
+                    ok = op in ("$ne", "$nin")
+                else:
+                    try:
+                        ok = bool(_WHERE_COMPARE[op](metadata[key], operand))
+                    except TypeError:
+                        ok = False
+                if not ok:
+                    break
+        if not ok:
+            return False
+    return True
+
+
 class DuplicateIDError(ValueError):
     """Same condition chromadb reports for add() of an id that already exists."""
 
@@ -410,9 +468,50 @@ class FlatCollection:
             cnt = within.sum(1).astype(np.int32)
         return labs, dist, cnt, dups
 
+    def _admitted_labels(self, ids, where) -> List[int]:
+        """The labels `ids` (chroma ids; unknown ones are ignored; None: every row) and `where` (a metadata predicate, None: every
+        row) admit, in label order."""
+        if ids is None:
+            labs = self._labels
+        else:
+            labs = sorted({self._by_id[i] for i in _as_list(ids) if i in self._by_id})
+        if where is not None:
+            labs = [lab for lab in labs if where_matches(self._meta.get(lab), where)]
+        return list(labs)
+
+    def _subset_query(self, q: np.ndarray, k: int, labs: List[int], filters: List[str], max_distance=None):
+        """Exact top-k among the rows `labs` that answer "yes" to every filter (FlatIndex.query_subset) -> (labels [Q,k], distances
+        [Q,k], counts [Q]). Up to 64 filter names travel as masks; a name past the 64th bit is folded into the list on the host,
+        which stays exact at any size. max_distance cuts the sorted result at the radius: a prefix."""
+        Q = q.shape[0]
+        empty = (np.full((Q, k), -1, np.int64), np.full((Q, k), np.inf, np.float32), np.zeros((Q,), np.int32))
+        masks = {}
+        if filters:
+            self._push_tags()
+            if any(f not in self._filter_bits and f not in self._filter_overflow for f in filters):
+                return empty                                             # a name no row has ever answered admits nothing
+            req = 0
+            for f in filters:
+                if f in self._filter_bits:
+                    req |= 1 << self._filter_bits[f]
+            if req:
+                masks = {"require": np.uint64(req)}
+            over = [f for f in filters if f in self._filter_overflow]
+            if over:
+                labs = [lab for lab in labs if all(answers_yes(filter_answers(self._meta.get(lab)).get(f, "")) for f in over)]
+        if not labs:
+            return empty
+        labs_o, dist, cnt, _ = self._index.query_subset(q, k, np.asarray(labs, dtype=np.int64), **masks)
+        labs_o, dist, cnt = np.asarray(labs_o), np.asarray(dist), np.array(cnt, np.int32)
+        if max_distance is not None:
+            within = (dist <= np.float32(max_distance)) & (np.arange(k)[None, :] < cnt[:, None])
+            cnt = within.sum(1).astype(np.int32)
+        return labs_o, dist, cnt
+
     def query(self, query_embeddings=None, n_results: int = 10, include: Sequence[str] = ("metadatas", "documents", "distances"),
               filters: Optional[Sequence[str]] = None, max_distance: Optional[float] = None, n_probe: Optional[int] = None,
-              distinct_distance: Optional[float] = None, pool: Optional[int] = None, **_unused) -> dict:
+              distinct_distance: Optional[float] = None, pool: Optional[int] = None, ids=None, where: Optional[dict] = None,
+              **_unused) -> dict:
         """collection.query. filters: names of yes/no filters; when given, the result is the exact n_results nearest among the
         rows whose filter_results_json answers "yes" to every one of them (pre-filtering; see the module docstring).
         max_distance: a radius query (FlatIndex.query_radius) — only the rows within that cosine distance are returned, exactly,
@@ -429,9 +528,21 @@ class FlatCollection:
         how much of the ranking is walked (None: min(2040, max(8 n_results, 64)); a query that runs out is repeated once at
         2040). Works with filters (up to 64 names; a name past the 64th raises ValueError), n_probe and max_distance (the kept
         list cut at the radius). Without distinct_distance nothing changes.
+        ids / where (chromadb's collection.query(ids=, where=)): search only among these rows — `ids` chroma ids (unknown ones are
+        ignored), `where` a metadata predicate ({"field": v}, $eq $ne $gt $gte $lt $lte $in $nin, $and, $or; anything else raises
+        ValueError; a row without the field matches only $ne / $nin); both given: their intersection. The result is the exact
+        n_results nearest among the admitted rows (FlatIndex.query_subset), at any size of the list. filters combine (up to 64
+        names as masks, names past the 64th folded into the list: exact, where the filtered query's host post-filter is not),
+        max_distance cuts the sorted result at the radius, n_probe is ignored (the subset is exact), distinct_distance raises
+        ValueError, an empty admitted set gives empty results. Without ids and where nothing changes.
         Nothing is written, neither metadata nor journal."""
         if n_probe is not None and int(n_probe) < 1:
             raise ValueError(f"n_probe: at least 1, got {n_probe}")
+        subset = ids is not None or where is not None
+        if where is not None:
+            check_where(where)
+        if subset and distinct_distance is not None:
+            raise ValueError("distinct_distance cannot be combined with ids / where")
         if distinct_distance is not None:
             distinct_distance = float(distinct_distance)
             if distinct_distance != distinct_distance:
@@ -456,7 +567,9 @@ class FlatCollection:
                 if k > MAX_N_RESULTS:  # one mmiss_index_query call ranks at most 2040 rows per query: clamp, do not fail
                     logger.warning(f"n_results={n_results} clamped to {MAX_N_RESULTS}")
                     k = MAX_N_RESULTS
-                if distinct_distance is not None:
+                if subset:
+                    labs, dist, cnt = self._subset_query(q, k, self._admitted_labels(ids, where), filters, max_distance)
+                elif distinct_distance is not None:
                     labs, dist, cnt, dups = self._distinct_query(q, k, filters, distinct_distance, pool, max_distance, n_probe)
                 elif filters:
                     labs, dist, cnt = self._filtered_query(q, k, filters, max_distance, n_probe)
@@ -579,13 +692,18 @@ class FlatCollection:
             return [(label_to_id[int(x)], label_to_id[int(y)], float(z)) for x, y, z in zip(a, b, d)]
 
     def get(self, ids=None, include: Sequence[str] = ("metadatas", "documents"), limit: Optional[int] = None,
-            offset: Optional[int] = None, **_unused) -> dict:
+            offset: Optional[int] = None, where: Optional[dict] = None, **_unused) -> dict:
+        """collection.get. where: the metadata predicate of query(where=), applied before offset and limit."""
         include = list(include)
+        if where is not None:
+            check_where(where)
         with self._lock:
             if ids is None:
                 sel = list(zip(self._ids, self._labels))
             else:
                 sel = [(i, self._by_id[i]) for i in _as_list(ids) if i in self._by_id]  # missing ids are skipped
+            if where is not None:
+                sel = [(i, l) for i, l in sel if where_matches(self._meta.get(l), where)]
             if offset:
                 sel = sel[int(offset):]
             if limit is not None:

@@ -7,6 +7,7 @@
 #include "assign_kernels.h"
 #include "partition_kernels.h"
 #include "distinct_kernels.h"
+#include "subset_kernels.h"
 #include "gemm_bf16_256.h"
 #include "gemm_strip_p256.h"
 #include <algorithm>
@@ -15,6 +16,7 @@
 static_assert(PLAN_SELECT_UNIT == SELECT_UNIT && PLAN_PROBE_SEG == PROBE_SEG, "index_plans.h repeats what the kernel headers fix");
 static_assert(PLAN_DISTINCT_THREADS == DISTINCT_THREADS && PLAN_DISTINCT_SLOTS == DISTINCT_SLOTS && PLAN_DISTINCT_MAX_POOL < DISTINCT_SLOTS,
               "index_plans.h repeats what distinct_kernels.h fixes");
+static_assert(PLAN_SUBSET_BLOCK_ROWS == SUBSET_BLOCK_ROWS, "index_plans.h repeats what subset_kernels.h fixes");
 
 // The results of a query-like call of Q queries: `slots` labels and distances and a count per query, for some calls a total and
 // a flag per query. lab / tot / dist / cnt are where the kernels write them: the caller's device buffers, or a pinned host block
@@ -128,6 +130,10 @@ struct mmiss_index {
     // distinct results (mmiss_index_query_distinct): the list stage's labels, distances and counts ([Q, pool], [Q, pool], [Q]), and the
     // suppression stage's outputs when the caller's are host memory
     DevBuf dst_list, dst_out;
+    // subset search (mmiss_index_query_subset): the caller's list when it is host memory, the bitmap of one bit per row, the
+    // block counts / offsets of its compaction, the listed rows in ascending order. The totals, masks and key areas are the
+    // probed call's (prb_total, prb_mask, prb_keys_a / _b): both calls hold the handle's lock from their first launch to their last
+    DevBuf sub_cand, sub_bitmap, sub_blk, sub_rows;
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -2217,6 +2223,150 @@ extern "C" int mmiss_index_query_distinct(mmiss_index* ix, const float* queries,
         if (out_listed) MM_HIP(hipMemcpyAsync(out_listed, a.out_listed, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
     }
     MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+// ================================================================================================ subset search
+// mmiss_index_query_subset: the exact top-k among the rows whose labels the caller lists (subset_kernels.h). The list becomes a
+// bitmap and then an ascending row list on the device, the scan scores every listed row against a block of queries at a time, and
+// the probed call's selection picks the k best. No first pass, no guard, no partition: every listed row gets its canonical
+// distance, and the guard's and the partition's counters stay as they are.
+namespace {
+
+SubsetPlan plan_subset(const mmiss_index* ix, int Q, int k, int64_t n_cand) {
+    return plan_subset(ix->count, n_cand, ix->dim, Q, k, plan_options());
+}
+
+typedef void (*SubsetScanKernel)(SubsetScanArgs);
+template <typename T> SubsetScanKernel subset_scan_kernel_for(int nqb) {
+    switch (nqb) {
+        case 16: return &subset_scan_kernel<T, 16>;
+        case 8: return &subset_scan_kernel<T, 8>;
+        case 4: return &subset_scan_kernel<T, 4>;
+        case 2: return &subset_scan_kernel<T, 2>;
+        default: return &subset_scan_kernel<T, 1>;
+    }
+}
+
+// stages 1 and 2: the caller's list -> sub_rows (ascending rows of S) and prb_total[0 .. nq) = |S|
+int subset_rows(mmiss_index* ix, hipStream_t st, const SubsetPlan& p, const int64_t* d_cand, int64_t n_cand, int nq) {
+    uint32_t* const bitmap = ix->sub_bitmap.as<uint32_t>();
+    int32_t* const blk = ix->sub_blk.as<int32_t>();
+    MM_HIP(hipMemsetAsync(bitmap, 0, (size_t)p.words * 4, st));
+    {
+        MM_PROF("subset_mark", st, 0.0, 8.0 * n_cand);
+        hipLaunchKernelGGL(subset_mark_kernel, dim3((unsigned)((n_cand + 255) / 256)), dim3(256), 0, st, d_cand, n_cand,
+                           (const int64_t*)ix->labels_d.as<int64_t>(), ix->count, bitmap);
+        MM_HIP(hipGetLastError());
+    }
+    MM_PROF("subset_compact", st, 0.0, 8.0 * p.words + 4.0 * p.bound);
+    hipLaunchKernelGGL(subset_count_kernel, dim3(p.blocks), dim3(SUBSET_BLOCK_THREADS), 0, st, (const uint32_t*)bitmap, p.words, blk);
+    MM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(subset_offsets_kernel, dim3(1), dim3(SUBSET_BLOCK_THREADS), 0, st, blk, p.blocks, ix->prb_total.as<int32_t>(), nq);
+    MM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(subset_scatter_kernel, dim3(p.blocks), dim3(SUBSET_BLOCK_THREADS), 0, st, (const uint32_t*)bitmap, p.words,
+                       (const int32_t*)blk, ix->sub_rows.as<int32_t>(), p.bound);
+    MM_HIP(hipGetLastError());
+    return MMISS_OK;
+}
+
+}  // namespace
+
+extern "C" int mmiss_index_query_subset(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const int64_t* cand_labels, int64_t n_cand,
+                                        const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
+                                        int32_t* out_count, int64_t* out_matched) {
+    const char* who = "mmiss_index_query_subset";
+    if (!ix || !queries || !out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || n_cand < 0) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d n_cand=%lld", who, Q, k, (long long)n_cand);
+    if (n_cand > 0 && !cand_labels) MM_FAIL(MMISS_ERR_ARG, "%s: null cand_labels for %lld labels", who, (long long)n_cand);
+    if (k > PROBE_MAX_K) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: k = %d too large (max %d)", who, k, PROBE_MAX_K);
+    if (n_cand > INT32_MAX) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: n_cand = %lld too large (max %d)", who, (long long)n_cand, INT32_MAX);
+    bool out_dev = false;
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_matched, &out_dev));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, who, &st));
+    const int D = ix->dim;
+    const SubsetPlan p = plan_subset(ix, Q, k, n_cand);
+    ResultBlock out;
+    MM_TRY(out.stage(ix->pin, st, Q, k, out_dev, true, false, out_labels, out_dist, out_count, out_matched));
+    MM_TRY(upload_queries(ix, st, queries, Q));   // qn of every query of the call
+    const uint64_t* d_req = require; const uint64_t* d_exc = exclude;   // host masks: [Q] required, then [Q] excluded in prb_mask
+    MM_TRY(device_view(&d_req, (size_t)Q, ix->prb_mask, 0, (size_t)Q * 16, st));
+    MM_TRY(device_view(&d_exc, (size_t)Q, ix->prb_mask, (size_t)Q * 8, (size_t)Q * 16, st));
+    MM_TRY(ix->prb_total.ensure((size_t)p.qchunk * 4));
+    MM_TRY(ix->prb_keys_a.ensure((size_t)p.qchunk * p.stride0 * 8));
+    if (p.stride1) MM_TRY(ix->prb_keys_b.ensure((size_t)p.qchunk * p.stride1 * 8));
+    if (p.bound > 0) {
+        const int64_t* d_cand = cand_labels;
+        MM_TRY(device_view(&d_cand, (size_t)n_cand, ix->sub_cand, 0, (size_t)n_cand * 8, st));
+        MM_TRY(ix->sub_bitmap.ensure((size_t)p.words * 4));
+        MM_TRY(ix->sub_blk.ensure((size_t)p.blocks * 4));
+        MM_TRY(ix->sub_rows.ensure((size_t)p.bound * 4));
+        MM_TRY(subset_rows(ix, st, p, d_cand, n_cand, p.qchunk));
+    } else {
+        MM_HIP(hipMemsetAsync(ix->prb_total.p, 0, (size_t)p.qchunk * 4, st));   // an empty list or an empty index: |S| = 0
+    }
+    const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
+    for (int q0 = 0; q0 < Q; q0 += p.qchunk) {
+        const int Qc = std::min(p.qchunk, Q - q0);
+        if (p.bound > 0) {
+            SubsetScanArgs a{};
+            a.rows = ix->rows.p; a.inv = ix->inv.as<float>(); a.tags = ix->tags.as<uint64_t>();
+            a.qn = ix->qn.as<float>() + (size_t)q0 * D;
+            a.req = d_req ? d_req + q0 : nullptr; a.exc = d_exc ? d_exc + q0 : nullptr;
+            a.list = ix->sub_rows.as<int32_t>(); a.total = ix->prb_total.as<int32_t>();
+            a.Q = Qc; a.D = D; a.share = p.share;
+            a.keys = ix->prb_keys_a.as<unsigned long long>(); a.stride = p.stride0;
+            const int nqb = subset_block_for(p.qblock, Qc);
+            const int qblocks = (Qc + nqb - 1) / nqb;
+            // (the rows are read once per query block)
+            MM_PROF(f16 ? "subset_scan_f16" : f8 ? "subset_scan_f8" : "subset_scan_f32", st, 2.0 * Qc * (double)p.bound * D,
+                    (double)qblocks * p.bound * (D * ix->elt + 12) + 8.0 * Qc * p.bound);
+            const SubsetScanKernel kern = with_storage(ix->dtype, [&](auto s) { return subset_scan_kernel_for<typename decltype(s)::T>(nqb); });
+            const int lds = subset_scan_lds_bytes(D, nqb);
+            MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds));
+            hipLaunchKernelGGL(kern, dim3(p.splits, qblocks), dim3(256), lds, st, a);
+            MM_HIP(hipGetLastError());
+        }
+        int64_t nb = p.bound;   // the most keys a query has at this level
+        for (int l = 0; l < p.levels; ++l) {
+            const bool last = l == p.levels - 1;
+            const bool from_a = (l & 1) == 0;
+            const int nseg = last ? 1 : (int)((nb + PROBE_SEG - 1) / PROBE_SEG);
+            SegmentTopkArgs a{};
+            a.in = from_a ? ix->prb_keys_a.as<unsigned long long>() : ix->prb_keys_b.as<unsigned long long>();
+            a.out = from_a ? ix->prb_keys_b.as<unsigned long long>() : ix->prb_keys_a.as<unsigned long long>();
+            a.in_stride = from_a ? p.stride0 : p.stride1; a.out_stride = from_a ? p.stride1 : p.stride0;
+            a.total = ix->prb_total.as<int32_t>(); a.level = l; a.k = k;
+            a.labels = ix->labels_d.as<int64_t>();
+            a.out_labels = out.lab + (size_t)q0 * k; a.out_dist = out.dist + (size_t)q0 * k; a.out_count = out.cnt + q0;
+            a.out_scanned = out.tot ? out.tot + q0 : nullptr;
+            MM_PROF("segment_topk", st, 0.0, (double)Qc * nb * 8);
+            if (last) hipLaunchKernelGGL(segment_topk_kernel<true>, dim3(1, Qc), dim3(1024), 0, st, a);
+            else hipLaunchKernelGGL(segment_topk_kernel<false>, dim3(nseg, Qc), dim3(1024), 0, st, a);
+            MM_HIP(hipGetLastError());
+            nb = (int64_t)nseg * k;
+        }
+    }
+    MM_HIP(hipStreamSynchronize(st));
+    out.deliver();
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: how a subset call of this shape would run on the index as it stands (plan_subset, nothing launched).
+extern "C" int mmiss_dbg_index_subset_plan(mmiss_index* ix, int32_t Q, int32_t k, int64_t n_cand, int32_t* out) {
+    const char* who = "mmiss_dbg_index_subset_plan";
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || k > PROBE_MAX_K || n_cand < 0) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d n_cand=%lld", who, Q, k, (long long)n_cand);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    const SubsetPlan p = plan_subset(ix, Q, k, n_cand);
+    auto i32 = [](int64_t v) { return (int32_t)std::min<int64_t>(v, INT32_MAX); };
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    out[0] = i32(p.bound); out[1] = PROBE_SEG; out[2] = p.levels; out[3] = i32(p.stride0); out[4] = i32(p.stride1);
+    out[5] = p.qchunk; out[6] = p.chunks; out[7] = p.qblock; out[8] = p.lds; out[9] = p.share; out[10] = p.splits;
+    out[11] = SUBSET_ROWS_PER_TRIP; out[12] = p.blocks; out[13] = SUBSET_BLOCK_ROWS;
+    out[14] = subset_block_for(p.qblock, std::min(Q, p.qchunk)); out[15] = subset_block_for(p.qblock, Q - (p.chunks - 1) * p.qchunk);
     return MMISS_OK;
 }
 

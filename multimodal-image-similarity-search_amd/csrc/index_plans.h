@@ -1,5 +1,5 @@
 // index_plans.h — the launch-shape arithmetic of the index's host layer (api_index.hip): how many queries a scan block stages, how
-// the rows are cut into slabs, how a selection or a merge is split, how a probed call is chunked, how the suppression stage of a
+// the rows are cut into slabs, how a selection or a merge is split, how a probed or a subset call is chunked, how the suppression stage of a
 // distinct call is laid out, where the arrays of a result block lie. Plain C++, no HIP include, no option lookup: api_index.hip, its debug plan entries (mmiss_dbg_index_*plan) and a
 // host-only test program (tests/test_index_plans_cpu.py) all take the rules from here.
 #pragma once
@@ -168,6 +168,57 @@ inline ProbePlan plan_probed(int64_t count, int64_t B, int64_t largest, const in
     const int64_t want = std::max<int64_t>(1, (2048 + lists - 1) / lists);
     p.share = (int)std::max<int64_t>(64, ((maxlist + want - 1) / want + 15) / 16 * 16);
     p.splits = (int)std::max<int64_t>(1, (maxlist + p.share - 1) / p.share);
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------ subset search
+// How a subset call of Q queries with a list of n_cand labels runs on `count` rows of dim D (subset_kernels.h). bound: the most
+// rows the list can name, min(n_cand, count): it sizes rows[] and the key areas and fixes the selection's levels, as plan_probed's
+// bound does, so nothing comes back from the device inside a call. qblock: the queries a scan workgroup stages and scores every
+// row of its share against — the largest of 16 / 8 / 4 / 2 / 1 whose f32 staging fits PLAN_SUBSET_LDS (the storage dtype does not
+// enter: the staged queries are f32 for every dtype). A chunk with fewer queries than that runs the narrowest instance that holds
+// them (subset_block_for): a single query is not scored as sixteen.
+constexpr int PLAN_SUBSET_LDS = 64 * 1024;
+constexpr int PLAN_SUBSET_BLOCK_ROWS = 32768;   // rows per block of the bitmap's compaction
+struct SubsetPlan {
+    int64_t bound = 0, stride0 = 1, stride1 = 0;   // keys per query of the two key areas
+    int levels = 1;                                // segment_topk launches, the FINAL one included
+    int qchunk = 1, chunks = 1;                    // queries per chunk (the scratch budget), chunks of the call
+    int qblock = 1, lds = 0;                       // queries per scan workgroup, its dynamic LDS
+    int share = 64, splits = 1;                    // list positions per scan workgroup, workgroups per query block
+    int64_t words = 0;                             // 32-bit words of the bitmap
+    int blocks = 0;                                // blocks of the compaction
+};
+
+// the query block a chunk of Qc queries runs with: qblock halved while half of it still holds them all
+inline int subset_block_for(int qblock, int Qc) {
+    while (qblock > 1 && qblock / 2 >= Qc) qblock /= 2;
+    return qblock;
+}
+
+inline SubsetPlan plan_subset(int64_t count, int64_t n_cand, int D, int Q, int k, const PlanOptions& o) {
+    SubsetPlan p;
+    p.bound = std::min(n_cand, count);
+    p.stride0 = std::max<int64_t>(p.bound, 1);
+    for (int64_t n = p.bound; n > PLAN_PROBE_SEG; n = (n + PLAN_PROBE_SEG - 1) / PLAN_PROBE_SEG * k) {
+        if (p.levels == 1) p.stride1 = (n + PLAN_PROBE_SEG - 1) / PLAN_PROBE_SEG * k;
+        ++p.levels;
+    }
+    const int64_t budget = (int64_t)o.probe_scratch_kb * 1024;
+    const int64_t per_query = (p.stride0 + p.stride1) * 8;
+    p.qchunk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(Q, 32768), budget / per_query));
+    p.chunks = (Q + p.qchunk - 1) / p.qchunk;
+    p.qblock = 1;
+    for (int nqb : {16, 8, 4, 2})
+        if ((int64_t)nqb * D * 4 <= PLAN_SUBSET_LDS) { p.qblock = nqb; break; }
+    p.lds = p.qblock * D * 4;
+    // the scan: about 2048 workgroups over (shares x query blocks of a chunk), 64 list positions per workgroup at the least
+    const int64_t qblocks = (p.qchunk + p.qblock - 1) / p.qblock;
+    const int64_t want = std::max<int64_t>(1, (2048 + qblocks - 1) / qblocks);
+    p.share = (int)std::max<int64_t>(64, ((p.bound + want - 1) / want + 15) / 16 * 16);
+    p.splits = (int)std::max<int64_t>(1, (p.bound + p.share - 1) / p.share);
+    p.words = (count + 31) / 32;
+    p.blocks = (int)((count + PLAN_SUBSET_BLOCK_ROWS - 1) / PLAN_SUBSET_BLOCK_ROWS);
     return p;
 }
 

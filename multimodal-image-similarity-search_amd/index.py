@@ -613,6 +613,55 @@ class FlatIndex:
                                                           _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt), _lib.ptr(scanned)))
         return lab, dist, cnt, scanned
 
+    # ------------------------------------------------------------------ subset search
+    def query_subset(self, queries, k: int, labels, require=None, exclude=None):
+        """The exact top-k among the rows whose labels are listed (mmiss_index_query_subset) -> (labels int64 [Q,k], distances
+        float32 [Q,k], counts int32 [Q], matched int64 [Q]): the distance bits and the order of query(); with every stored label
+        listed, query()'s result. A row outside the list is not returned however near it is. `labels`: int64 [n], numpy or a
+        CUDA tensor (a CUDA list goes with CUDA queries); a label that is not stored is ignored, a repeated one counts once, the
+        order means nothing, an empty list gives counts 0. matched[q] = the listed rows that exist, the same for every query.
+        require / exclude as in query(). 1 <= k <= 2040, at least one query. numpy in -> numpy out, CUDA tensor in -> CUDA
+        tensors out."""
+        k = int(k)
+        if not 1 <= k <= self.MAX_K:
+            raise ValueError(f"k: 1 .. {self.MAX_K}, got {k}")
+        if _is_torch(labels):
+            import torch
+
+            if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.dtype.is_complex:
+                raise TypeError(f"labels: integers expected, got {labels.dtype}")
+            cand = labels.to(torch.int64).reshape(-1).contiguous()
+            if not cand.is_cuda:
+                cand = cand.numpy()
+        else:
+            cand = np.asarray(labels)
+            if cand.size and cand.dtype.kind not in "ui":
+                raise TypeError(f"labels: integers expected, got {cand.dtype}")
+            cand = np.ascontiguousarray(cand, dtype=np.int64).reshape(-1)
+        n_cand = int(cand.shape[0])
+        if n_cand > 2 ** 31 - 1:
+            raise ValueError(f"labels: at most {2 ** 31 - 1}, got {n_cand}")
+        q, (lab, dist, cnt) = self._prepare(queries, k)
+        Q = int(q.shape[0])
+        if Q < 1:
+            raise ValueError("query_subset takes at least one query")
+        on_device = _is_torch(q) and q.is_cuda
+        if _is_torch(cand) and not on_device:
+            raise ValueError("labels: a CUDA list goes with CUDA queries")
+        masks = self._masks(q, require, exclude) or (None, None)
+        if on_device:
+            import torch
+
+            matched = torch.empty((Q,), dtype=torch.int64, device=q.device)
+        else:
+            matched = np.empty((Q,), dtype=np.int64)
+        with self._call_lock:
+            self._sync_stream(q)
+            _lib.check(self._lib.mmiss_index_query_subset(self._h, _lib.ptr(q), Q, k, _lib.ptr(cand) if n_cand else None, n_cand,
+                                                          _lib.ptr(masks[0]), _lib.ptr(masks[1]), _lib.ptr(lab), _lib.ptr(dist),
+                                                          _lib.ptr(cnt), _lib.ptr(matched)))
+        return lab, dist, cnt, matched
+
     # ------------------------------------------------------------------ distinct results
     MAX_POOL = MAX_POOL
 

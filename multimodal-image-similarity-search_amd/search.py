@@ -15,6 +15,8 @@ Like the reference, the wrappers catch every exception, log it and return [].
 Every search takes a keyword-only `filters` (names of yes/no filters): the exact `limit` nearest among the images that answer
 "yes" to all of them (FlatCollection.query(filters=...)); the default None searches everything, as the reference does.
 Every search also takes `distinct_similarity`: near-duplicates of kept results are suppressed on the device and counted.
+Every search also takes `within_ids` (image ids) and `where` (a metadata predicate): the exact `limit` nearest among those images
+only (FlatCollection.query(ids=, where=)) — an album, a folder, the hits of an earlier search.
 """
 from __future__ import annotations
 
@@ -70,7 +72,7 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
     return similar_images
 
 
-def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=None) -> dict:
+def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=None, within_ids=None, where=None) -> dict:
     """the keyword arguments of FlatCollection.query for a search's filters, similarity threshold, probe count and distinctness;
     min_similarity = s becomes the radius utils.max_distance_for_similarity(s): on its results "similarity_score >= s" holds for
     exactly the members; distinct_similarity = s becomes distinct_distance the same way: a result at least s similar to an earlier
@@ -82,24 +84,32 @@ def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=N
         kw["n_probe"] = int(n_probe)
     if distinct_similarity is not None:
         kw["distinct_distance"] = float(utils.max_distance_for_similarity(distinct_similarity))
+    # within_ids / where: search among these images only; absent, no argument at all (today's call)
+    if within_ids is not None:
+        kw["ids"] = [within_ids] if isinstance(within_ids, str) else list(within_ids)
+    if where is not None:
+        kw["where"] = where
     return kw
 
 
 def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                    min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
-                   distinct_similarity: Optional[float] = None) -> List[Dict]:
+                   distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
+                   where: Optional[dict] = None) -> List[Dict]:
     """Search for similar images using an embedding (main.py:748-805). min_similarity: only the images whose similarity_score
     reaches it, exactly (a radius query; `limit` caps how many) — the reference's roadmap item "Adjustable similarity
     thresholds" (CHANGELOG.md:475). n_probe: search only the n_probe k-means cells nearest to the embedding, and what was added
     since (build_search_partition; FlatCollection.query(n_probe=)); without a partition the search is the exact one.
     distinct_similarity: `limit` DIFFERENT images — walking the ranking, an image at least that similar to an earlier kept result is
     dropped and counted under it; every result then carries "duplicates", the images it stands for besides itself
-    (FlatCollection.query(distinct_distance=))."""
+    (FlatCollection.query(distinct_distance=)).
+    within_ids / where: only among these images — ids (unknown ones are ignored) and / or a metadata predicate; the exact `limit`
+    nearest of them (FlatCollection.query(ids=, where=)); n_probe is then ignored, and distinct_similarity is refused (logged, [])."""
     try:
         actual_limit = 1000 if limit <= 0 else limit  # "All" option (limit of 0), main.py:757
         results = _collection().query(query_embeddings=[np.asarray(embedding, dtype=np.float32).tolist()],
                                       n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity))
+                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where))
         out = _results_from_query(results, 0)
         logger.info(f"Found {len(out)} similar images")
         return out
@@ -110,13 +120,14 @@ def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[
 
 def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                          min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
-                         distinct_similarity: Optional[float] = None) -> List[List[Dict]]:
+                         distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
+                         where: Optional[dict] = None) -> List[List[Dict]]:
     """[Q, D] embeddings -> one result list per query, one index pass for the whole batch."""
     try:
         actual_limit = 1000 if limit <= 0 else limit
         q = np.asarray(embeddings, dtype=np.float32)
         results = _collection().query(query_embeddings=q, n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity))
+                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where))
         return [_results_from_query(results, qi) for qi in range(q.shape[0])]
     except Exception as e:
         logger.error(f"Error searching for similar images: {e}")
@@ -125,14 +136,15 @@ def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Op
 
 def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                    min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
-                   distinct_similarity: Optional[float] = None) -> List[Dict]:
+                   distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
+                   where: Optional[dict] = None) -> List[Dict]:
     """Search for images using a text query (main.py:807-827)."""
     try:
         model, processor = utils.load_clip_model()
         embedding_result = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)
         text_embedding = embedding_result["text"][0]
         return search_similar(embedding=text_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe,
-                              distinct_similarity=distinct_similarity)
+                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where)
     except Exception as e:
         logger.error(f"Error in text search: {e}")
         return []
@@ -140,7 +152,8 @@ def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequen
 
 def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: int = 10, *,
                       filters: Optional[Sequence[str]] = None, min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
-                      distinct_similarity: Optional[float] = None) -> List[Dict]:
+                      distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
+                      where: Optional[dict] = None) -> List[Dict]:
     """Search using both image and text with a weighted combination (main.py:829-867); weight_image is not
     clamped, as in the backend route."""
     try:
@@ -150,7 +163,7 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
         # normalise both, weighted sum, normalise again (main.py:852-860) — one GPU kernel
         combined_embedding = blend(image_embedding[None], text_embedding[None], weight_image)[0]
         return search_similar(embedding=combined_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe,
-                              distinct_similarity=distinct_similarity)
+                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
@@ -159,11 +172,13 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
 def search_multimodal_batch(image_embeddings: np.ndarray, text_embeddings: np.ndarray, weight_image: float = 0.5,
                             limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                             min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
-                            distinct_similarity: Optional[float] = None) -> List[List[Dict]]:
+                            distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
+                            where: Optional[dict] = None) -> List[List[Dict]]:
     """BASELINE config 4: a batch of (image, text) embedding pairs, blended and searched in one pass."""
     try:
         return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit, filters=filters,
-                                    min_similarity=min_similarity, n_probe=n_probe, distinct_similarity=distinct_similarity)
+                                    min_similarity=min_similarity, n_probe=n_probe, distinct_similarity=distinct_similarity,
+                                    within_ids=within_ids, where=where)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
