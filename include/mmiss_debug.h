@@ -256,6 +256,19 @@ int mmiss_dbg_index_distinct_plan(struct mmiss_index* ix, int32_t Q, int32_t* ou
  *   such block   [14], [15] the query block the first / the last chunk runs with: [7] halved while half of it still holds the
  *   chunk's queries */
 int mmiss_dbg_index_subset_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int64_t n_cand, int32_t* out);
+/* How the dense scans and the kernels behind them would walk the index as it stands with n_operands (1 .. 1024) probes, centres or
+ * clusters: the calls' own planning functions (plan_dense by passes, the capped grids, plan_cluster_sums, subset_compact_blocks;
+ * csrc/index_plans.h), evaluated on the host. Launches nothing, changes nothing. out is a HOST int32 [40]; an empty index leaves
+ * all but [37] 0:
+ *   the scan of membership / assignment: [0] nqt   [1] dynamic LDS bytes   [2] slabs   [3] tiles_per_block   [4] passes
+ *     [5] trips of every wave of a full block (tiles_per_block / 4)   [6] rows of a block (16 * tiles_per_block)
+ *   grid-stride kernels, three fields each — blocks, rows (or list positions) the grid covers per trip, trips over the rows:
+ *     [8] canonical_scan   [11] assign_resolve   [14] member_count   [17] assign_sizes   [20] assign_decide
+ *     [23] member_from_dist   [26] member_merge_tags
+ *   cluster sums into n_operands clusters: [30] columns per chunk   [31] chunks   [32] rows per block   [33] slabs   [34] LDS bytes
+ *   the subset call's compaction: [35] blocks   [36] rows per block
+ *   [37] rows of the index */
+int mmiss_dbg_index_dense_plan(struct mmiss_index* ix, int32_t n_operands, int32_t* out);
 
 
 /* The path one chunk of an encode call would take on the handle as it stands and under the options as they stand: B items

@@ -162,6 +162,7 @@ SIGNATURES = {
     "mmiss_dbg_index_probe_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_distinct_plan": (_I, [_P, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_subset_plan": (_I, [_P, _I32, _I32, _I64, C.POINTER(_I32)]),
+    "mmiss_dbg_index_dense_plan": (_I, [_P, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
 }
@@ -323,6 +324,26 @@ def index_subset_plan(handle, Q: int, k: int, n_cand: int) -> dict:
     out = (_I32 * 16)()
     check(load().mmiss_dbg_index_subset_plan(handle, int(Q), int(k), int(n_cand), out))
     return dict(zip(SUBSET_PLAN_FIELDS, (int(v) for v in out)))
+
+
+DENSE_PLAN_KERNELS = ("canonical_scan", "assign_resolve", "member_count", "assign_sizes", "assign_decide", "member_from_dist",
+                      "member_merge_tags")
+
+
+def index_dense_plan(handle, n_operands: int) -> dict:
+    """mmiss_dbg_index_dense_plan as a dict: how the dense scans over the index `handle` as it stands would run with n_operands
+    probes / centres / clusters — {"scan": {nqt, lds_bytes, slabs, tiles_per_block, passes, wave_trips, block_rows}, one
+    {"grid", "rows_per_trip", "trips"} per kernel of DENSE_PLAN_KERNELS, "cluster_sums": {cols, chunks, rows_per_block, slabs,
+    lds_bytes}, "compact_blocks", "compact_block_rows", "rows"}. Nothing is launched."""
+    out = (_I32 * 40)()
+    check(load().mmiss_dbg_index_dense_plan(handle, int(n_operands), out))
+    v = [int(x) for x in out]
+    d = {"scan": dict(zip(("nqt", "lds_bytes", "slabs", "tiles_per_block", "passes", "wave_trips", "block_rows"), v[0:7]))}
+    for i, name in enumerate(DENSE_PLAN_KERNELS):
+        d[name] = dict(zip(("grid", "rows_per_trip", "trips"), v[8 + 3 * i:11 + 3 * i]))
+    d["cluster_sums"] = dict(zip(("cols", "chunks", "rows_per_block", "slabs", "lds_bytes"), v[30:35]))
+    d["compact_blocks"], d["compact_block_rows"], d["rows"] = v[35], v[36], v[37]
+    return d
 
 
 _INDEX_ELT = {MMISS_F32: "float32", MMISS_F16: "float16", MMISS_F8: "uint8"}

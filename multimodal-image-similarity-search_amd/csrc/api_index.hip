@@ -739,7 +739,7 @@ int launch_canonical_scan(mmiss_index* ix, hipStream_t st, int32_t q) {
     const int64_t N = ix->count;
     const int D = ix->dim;
     MM_PROF("canonical_scan", st, 2.0 * N * D, (double)N * D * ix->elt);
-    const int grid = (int)std::min<int64_t>(8192, (N + 15) / 16);
+    const int grid = canonical_scan_grid(N);
     with_storage(ix->dtype, [&](auto s) {   // (inv: the inverse norms of fp8 rows, null for the others)
         hipLaunchKernelGGL(canonical_scan_kernel<typename decltype(s)::T>, dim3(grid), dim3(256), 0, st, ix->rows.p, N, D,
                            ix->qn.as<float>() + (size_t)q * D, ix->dist_all.as<float>(), (const float*)ix->inv.as<float>());
@@ -1667,7 +1667,7 @@ int membership_core(mmiss_index* ix, hipStream_t st, const float* queries, int P
     for (int p : over) {   // more than SWEEP_CAP rows within eps of the probe's threshold: every row's canonical distance decides
         MM_TRY(ix->dist_all.ensure((size_t)N * 4));
         MM_TRY(launch_canonical_scan(ix, st, p));
-        hipLaunchKernelGGL(member_from_dist_kernel, dim3((int)std::min<int64_t>(4096, (N + 255) / 256)), dim3(256), 0, st,
+        hipLaunchKernelGGL(member_from_dist_kernel, dim3(member_from_dist_grid(N)), dim3(256), 0, st,
                            (const float*)ix->dist_all.as<float>(), N, (const float*)d_rad, p, d_words);
         MM_HIP(hipGetLastError());
     }
@@ -1682,7 +1682,7 @@ int membership_core(mmiss_index* ix, hipStream_t st, const float* queries, int P
 int membership_counts(mmiss_index* ix, hipStream_t st, const uint64_t* d_words) {
     MM_TRY(ix->mem_cnt.ensure((size_t)64 * 8));
     MM_HIP(hipMemsetAsync(ix->mem_cnt.p, 0, (size_t)64 * 8, st));
-    hipLaunchKernelGGL(member_count_kernel, dim3((int)std::min<int64_t>(1024, (ix->count + 255) / 256)), dim3(256), 0, st, d_words, ix->count,
+    hipLaunchKernelGGL(member_count_kernel, dim3(member_count_grid(ix->count)), dim3(256), 0, st, d_words, ix->count,
                        ix->mem_cnt.as<unsigned long long>());
     MM_HIP(hipGetLastError());
     return MMISS_OK;
@@ -1762,7 +1762,7 @@ extern "C" int mmiss_index_tag_by_radius(mmiss_index* ix, const float* queries, 
     // the merge under the named bits, then the host mirror (get_tags, remove and the exhaustive passes read it)
     int32_t* const d_bits = reinterpret_cast<int32_t*>(ix->mem_thr.as<float>() + 192);
     MM_HIP(hipMemcpyAsync(d_bits, bits, (size_t)P * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(member_merge_tags_kernel, dim3((int)std::min<int64_t>(4096, (N + 255) / 256)), dim3(256), 0, st, ix->tags.as<uint64_t>(),
+    hipLaunchKernelGGL(member_merge_tags_kernel, dim3(member_merge_tags_grid(N)), dim3(256), 0, st, ix->tags.as<uint64_t>(),
                        (const uint64_t*)d_words, N, (const int32_t*)d_bits, P, mask);
     MM_HIP(hipGetLastError());
     MM_HIP(hipMemcpyAsync(ix->tags_h.data(), ix->tags.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
@@ -1785,7 +1785,7 @@ constexpr size_t ASSIGN_META_SIZES = 64;   // byte offset of the [1024] u64 size
 int assign_sizes(mmiss_index* ix, hipStream_t st, const int32_t* d_assign, int C, int64_t* out_sizes) {
     unsigned long long* const d_sizes = reinterpret_cast<unsigned long long*>(ix->asg_meta.as<char>() + ASSIGN_META_SIZES);
     MM_HIP(hipMemsetAsync(d_sizes, 0, (size_t)C * 8, st));
-    hipLaunchKernelGGL(assign_sizes_kernel, dim3((int)std::min<int64_t>(1024, (ix->count + 255) / 256)), dim3(256), 0, st, d_assign, ix->count, C, d_sizes);
+    hipLaunchKernelGGL(assign_sizes_kernel, dim3(assign_sizes_grid(ix->count)), dim3(256), 0, st, d_assign, ix->count, C, d_sizes);
     MM_HIP(hipGetLastError());
     return copy_any(out_sizes, d_sizes, (size_t)C * 8, st);
 }
@@ -1841,11 +1841,11 @@ extern "C" int mmiss_index_assign(mmiss_index* ix, const float* centres, int32_t
         a.c0 = j * NQ; a.C = C; a.first = j == 0;
         a.st_s1 = st_s1; a.st_i1 = st_i1; a.st_s2 = st_s2;
     }));
-    hipLaunchKernelGGL(assign_decide_kernel, dim3((int)std::min<int64_t>(2048, (N + 255) / 256)), dim3(256), 0, st, (const float*)st_s1,
+    hipLaunchKernelGGL(assign_decide_kernel, dim3(assign_decide_grid(N)), dim3(256), 0, st, (const float*)st_s1,
                        (const int32_t*)st_i1, (const float*)st_s2, N, (const float*)d_E, d_assign, d_dist, ix->asg_list.as<int32_t>(), d_bcnt);
     MM_HIP(hipGetLastError());
     // the resolve kernels are launched blind: the list's length stays on the device
-    const int rgrid = (int)std::min<int64_t>(4096, (N + 15) / 16);
+    const int rgrid = assign_resolve_grid(N);
     with_storage(ix->dtype, [&](auto s) {
         using T = typename decltype(s)::T;
         if (d_dist) {   // the sure rows' one distance
@@ -1972,7 +1972,7 @@ extern "C" int mmiss_index_partition_set(mmiss_index* ix, const float* centres, 
     MM_TRY(copy_any(fresh.cells.p, cells, (size_t)n * 4, st));
     MM_HIP(hipMemsetAsync(d_sizes, 0, (size_t)C * 8, st));
     if (n > 0) {
-        hipLaunchKernelGGL(assign_sizes_kernel, dim3((int)std::min<int64_t>(1024, (n + 255) / 256)), dim3(256), 0, st,
+        hipLaunchKernelGGL(assign_sizes_kernel, dim3(assign_sizes_grid(n)), dim3(256), 0, st,
                            (const int32_t*)fresh.cells.as<int32_t>(), n, (int)C, d_sizes);
         MM_HIP(hipGetLastError());
     }
@@ -2420,6 +2420,38 @@ extern "C" int mmiss_dbg_index_radius_plan(mmiss_index* ix, int32_t Q, int32_t f
             o[3] = sp.nqt; o[4] = sp.slabs; o[5] = sp.tiles_per_block; o[6] = sp.qtiles;
         }
     }
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: how the dense scans (membership / tagging, assignment, cluster sums) and the kernels behind them would run over
+// the index as it stands with n_operands probes / centres / clusters: the functions the calls themselves use, nothing launched, no
+// state changed.
+extern "C" int mmiss_dbg_index_dense_plan(mmiss_index* ix, int32_t n_operands, int32_t* out) {
+    const char* who = "mmiss_dbg_index_dense_plan";
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (n_operands < 1 || n_operands > ASSIGN_MAX_CENTRES) MM_FAIL(MMISS_ERR_ARG, "%s: n_operands=%d (1 .. %d)", who, n_operands, ASSIGN_MAX_CENTRES);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (int i = 0; i < 40; ++i) out[i] = 0;
+    const int64_t N = ix->count;
+    auto i32 = [](int64_t v) { return (int32_t)std::min<int64_t>(v, INT32_MAX); };
+    out[37] = i32(N);
+    if (N <= 0) return MMISS_OK;   // (an empty index: no launch at all)
+    const DensePlan dp = plan_dense(ix->dim, ix->qelt(), n_operands, N, true);
+    out[0] = dp.nqt; out[1] = dp.lds; out[2] = dp.slabs; out[3] = dp.tiles_per_block; out[4] = dp.passes;
+    out[5] = dp.tiles_per_block / 4;   // trips of every wave of a full block: tiles tile0 + wave, + 4, ...
+    out[6] = 16 * dp.tiles_per_block;  // rows of a block
+    const struct { int grid, per_block; } k[7] = {
+        {canonical_scan_grid(N), PLAN_CANON_ROWS_PER_BLOCK},  {assign_resolve_grid(N), PLAN_CANON_ROWS_PER_BLOCK},
+        {member_count_grid(N), PLAN_POINT_ROWS_PER_BLOCK},    {assign_sizes_grid(N), PLAN_POINT_ROWS_PER_BLOCK},
+        {assign_decide_grid(N), PLAN_POINT_ROWS_PER_BLOCK},   {member_from_dist_grid(N), PLAN_POINT_ROWS_PER_BLOCK},
+        {member_merge_tags_grid(N), PLAN_POINT_ROWS_PER_BLOCK}};
+    for (int i = 0; i < 7; ++i) {
+        const int64_t per_trip = (int64_t)k[i].grid * k[i].per_block;
+        out[8 + 3 * i] = k[i].grid; out[9 + 3 * i] = i32(per_trip); out[10 + 3 * i] = i32((N + per_trip - 1) / per_trip);
+    }
+    const ClusterSumsPlan cp = plan_cluster_sums(ix->dim, n_operands, N);
+    out[30] = cp.cols; out[31] = cp.chunks; out[32] = cp.rows_per_block; out[33] = cp.slabs; out[34] = cp.lds;
+    out[35] = subset_compact_blocks(N); out[36] = PLAN_SUBSET_BLOCK_ROWS;
     return MMISS_OK;
 }
 

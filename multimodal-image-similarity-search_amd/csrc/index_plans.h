@@ -94,6 +94,29 @@ inline DensePlan plan_dense(int D, int qelt, int n, int64_t N, bool by_passes) {
     return p;
 }
 
+// ------------------------------------------------------------------------------------------------ capped grids
+// The kernels behind the dense scans walk all N rows (or N list positions) with a grid-stride loop on a capped grid:
+// min(cap, ceil(N / per_block)) blocks of 256 threads, a block taking per_block consecutive items per trip — 16 where a group of
+// 16 lanes computes one canonical dot product (four rows per wave), 256 where a thread takes one row. The grid covers
+// grid * per_block items per trip, so a kernel's second trip starts at N > cap * per_block.
+inline int capped_grid(int64_t n, int per_block, int cap) { return (int)std::min<int64_t>(cap, (n + per_block - 1) / per_block); }
+
+constexpr int PLAN_CANON_ROWS_PER_BLOCK = 16;    // canonical_scan_kernel, assign_resolve_kernel
+constexpr int PLAN_POINT_ROWS_PER_BLOCK = 256;   // the pointwise kernels
+constexpr int PLAN_CANONICAL_SCAN_CAP = 8192;    // canonical_scan_kernel: second trip at N > 131 072
+constexpr int PLAN_ASSIGN_RESOLVE_CAP = 4096;    // assign_resolve_kernel: N (or list positions) > 65 536
+constexpr int PLAN_COUNT_CAP = 1024;             // member_count_kernel, assign_sizes_kernel: N > 262 144
+constexpr int PLAN_ASSIGN_DECIDE_CAP = 2048;     // assign_decide_kernel: N > 524 288
+constexpr int PLAN_MEMBER_WORDS_CAP = 4096;      // member_from_dist_kernel, member_merge_tags_kernel: N > 1 048 576
+
+inline int canonical_scan_grid(int64_t N) { return capped_grid(N, PLAN_CANON_ROWS_PER_BLOCK, PLAN_CANONICAL_SCAN_CAP); }
+inline int assign_resolve_grid(int64_t N) { return capped_grid(N, PLAN_CANON_ROWS_PER_BLOCK, PLAN_ASSIGN_RESOLVE_CAP); }
+inline int member_count_grid(int64_t N) { return capped_grid(N, PLAN_POINT_ROWS_PER_BLOCK, PLAN_COUNT_CAP); }
+inline int assign_sizes_grid(int64_t N) { return capped_grid(N, PLAN_POINT_ROWS_PER_BLOCK, PLAN_COUNT_CAP); }
+inline int assign_decide_grid(int64_t N) { return capped_grid(N, PLAN_POINT_ROWS_PER_BLOCK, PLAN_ASSIGN_DECIDE_CAP); }
+inline int member_from_dist_grid(int64_t N) { return capped_grid(N, PLAN_POINT_ROWS_PER_BLOCK, PLAN_MEMBER_WORDS_CAP); }
+inline int member_merge_tags_grid(int64_t N) { return capped_grid(N, PLAN_POINT_ROWS_PER_BLOCK, PLAN_MEMBER_WORDS_CAP); }
+
 // ------------------------------------------------------------------------------------------------ score GEMM, select, merge
 // consecutive index tiles per workgroup of the strip score GEMM (Mq queries padded to 256, ncol column tiles of 256 rows):
 // long enough to amortise the pipeline fill, short enough to leave >= 8 workgroups per CU for balance; among the strip
@@ -180,6 +203,8 @@ inline ProbePlan plan_probed(int64_t count, int64_t B, int64_t largest, const in
 // them (subset_block_for): a single query is not scored as sixteen.
 constexpr int PLAN_SUBSET_LDS = 64 * 1024;
 constexpr int PLAN_SUBSET_BLOCK_ROWS = 32768;   // rows per block of the bitmap's compaction
+// blocks of the compaction over `count` rows: block b > 0 writes behind the rows of blocks [0, b) (subset_offsets_kernel's sums)
+inline int subset_compact_blocks(int64_t count) { return (int)((count + PLAN_SUBSET_BLOCK_ROWS - 1) / PLAN_SUBSET_BLOCK_ROWS); }
 struct SubsetPlan {
     int64_t bound = 0, stride0 = 1, stride1 = 0;   // keys per query of the two key areas
     int levels = 1;                                // segment_topk launches, the FINAL one included
@@ -218,7 +243,7 @@ inline SubsetPlan plan_subset(int64_t count, int64_t n_cand, int D, int Q, int k
     p.share = (int)std::max<int64_t>(64, ((p.bound + want - 1) / want + 15) / 16 * 16);
     p.splits = (int)std::max<int64_t>(1, (p.bound + p.share - 1) / p.share);
     p.words = (count + 31) / 32;
-    p.blocks = (int)((count + PLAN_SUBSET_BLOCK_ROWS - 1) / PLAN_SUBSET_BLOCK_ROWS);
+    p.blocks = subset_compact_blocks(count);
     return p;
 }
 

@@ -55,9 +55,11 @@ def expected_sums(represented_rows, assign, C):
     return sums, np.bincount(a[ok], minlength=C).astype(np.int64)
 
 
-def expected_kmeans(stored, C, iters, init_pos=None):
+def expected_kmeans(stored, C, iters, init_pos=None, assign=None, sums=None):
     """FlatIndex.kmeans on row POSITIONS (init_pos None: floor(i n / C)) -> its dict plus `history`, the assignment of every
-    update step"""
+    update step. assign / sums: other evaluations of the same definitions than expected_assign / expected_sums (the large corpora
+    of dense_trip_cases.py)"""
+    expected_assign, expected_sums = assign or globals()["expected_assign"], sums or globals()["expected_sums"]
     x = represented(stored)
     n = x.shape[0]
     pos = (np.arange(C, dtype=np.int64) * n) // C if init_pos is None else np.asarray(init_pos, np.int64)

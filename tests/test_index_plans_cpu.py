@@ -1,8 +1,10 @@
 """csrc/index_plans.h — the launch-shape arithmetic of the index's host layer — checked on the host: a small stand-alone C++
 program (g++, no HIP, nothing loaded into Python) includes the header api_index.hip plans with and compares every field it
 returns with a literal transcription of the rules as api_index.hip carried them before they moved there (namespace parent:
-plan_scan, plan_sweep, plan_membership, strip_length, select_splits, merge_two_level, plan_probed, the cluster_sums chunking
-and the three result-block layouts), over every dim class, operand count, k', index size and option the index meets."""
+plan_scan, plan_sweep, plan_membership, strip_length, select_splits, merge_two_level, plan_probed, the cluster_sums chunking,
+the capped grids of the kernels behind the dense scans and the three result-block layouts), over every dim class, operand count,
+k', index size and option the index meets. The program's `figures` mode prints what mmiss_dbg_index_dense_plan reports for an
+index of a given shape: tests/dense_trip_cases.py reads the trip counts of its corpora from it where there is no GPU."""
 import os
 import subprocess
 
@@ -222,6 +224,16 @@ Block query_probed(int Q, int k) {
     return Block{-1, (long long)o_dist, (long long)o_cnt, -1, need, grown(need)};
 }
 
+// the capped grids, as the launches spelled them
+int canonical_scan_grid(int64_t N) { return (int)std::min<int64_t>(8192, (N + 15) / 16); }
+int assign_resolve_grid(int64_t N) { return (int)std::min<int64_t>(4096, (N + 15) / 16); }
+int member_count_grid(int64_t N) { return (int)std::min<int64_t>(1024, (N + 255) / 256); }
+int assign_sizes_grid(int64_t N) { return (int)std::min<int64_t>(1024, (N + 255) / 256); }
+int assign_decide_grid(int64_t N) { return (int)std::min<int64_t>(2048, (N + 255) / 256); }
+int member_from_dist_grid(int64_t N) { return (int)std::min<int64_t>(4096, (N + 255) / 256); }
+int member_merge_tags_grid(int64_t N) { return (int)std::min<int64_t>(4096, (N + 255) / 256); }
+int subset_blocks(int64_t count) { return (int)((count + 32768 - 1) / 32768); }
+
 }  // namespace parent
 
 // ---------------------------------------------------------------------------------------------- the grid
@@ -327,6 +339,64 @@ static int cluster_sums() {
     return 0;
 }
 
+// every capped grid is the parent's expression, and its second trip starts where the table of DESIGN 4c says: right behind
+// cap * per_block rows
+static int capped_grids() {
+    struct K { const char* name; int (*now)(int64_t); int (*then)(int64_t); int per_block; int64_t one_trip; };
+    const K ks[] = {
+        {"canonical_scan_grid", canonical_scan_grid, parent::canonical_scan_grid, 16, 131072},
+        {"assign_resolve_grid", assign_resolve_grid, parent::assign_resolve_grid, 16, 65536},
+        {"member_count_grid", member_count_grid, parent::member_count_grid, 256, 262144},
+        {"assign_sizes_grid", assign_sizes_grid, parent::assign_sizes_grid, 256, 262144},
+        {"assign_decide_grid", assign_decide_grid, parent::assign_decide_grid, 256, 524288},
+        {"member_from_dist_grid", member_from_dist_grid, parent::member_from_dist_grid, 256, 1048576},
+        {"member_merge_tags_grid", member_merge_tags_grid, parent::member_merge_tags_grid, 256, 1048576},
+    };
+    std::vector<int64_t> ns(NS, NS + sizeof(NS) / sizeof(NS[0]));
+    for (const K& k : ks) for (int64_t d : {-256, -16, -1, 0, 1, 16, 256}) ns.push_back(k.one_trip + d);
+    for (int64_t N : {(int64_t)140005, (int64_t)1048629, (int64_t)20005}) ns.push_back(N);
+    for (const K& k : ks) for (int64_t N : ns) {
+        AT(k.name, N, k.per_block, k.one_trip, 0, 0, 0);
+        const int g = k.now(N);
+        CHECK(g == k.then(N) && g >= 1);
+        CHECK(g == capped_grid(N, k.per_block, (int)(k.one_trip / k.per_block)));
+        const int64_t per_trip = (int64_t)g * k.per_block;
+        CHECK((per_trip >= N) == (N <= k.one_trip));          // one trip covers the rows up to cap * per_block, and no further
+        CHECK(per_trip - k.per_block < N);                    // no block without a row on the first trip
+        ++g_checked;
+    }
+    for (int64_t N : ns) {
+        AT("subset_compact_blocks", N, 0, 0, 0, 0, 0);
+        CHECK(subset_compact_blocks(N) == parent::subset_blocks(N));
+        CHECK((int64_t)subset_compact_blocks(N) * PLAN_SUBSET_BLOCK_ROWS >= N && (int64_t)(subset_compact_blocks(N) - 1) * PLAN_SUBSET_BLOCK_ROWS < N);
+        CHECK(plan_subset(N, 100, 128, 1, 10, PlanOptions()).blocks == subset_compact_blocks(N));
+        ++g_checked;
+    }
+    return 0;
+}
+
+// `figures D qelt n N`: what mmiss_dbg_index_dense_plan reports for an index of N rows of dim D (qelt: bytes of a staged operand
+// element) and n operands, one "name value" pair per line — the figures tests/dense_trip_cases.py reads on a machine without a GPU
+static int figures(int D, int qelt, int n, int64_t N) {
+    const DensePlan dp = plan_dense(D, qelt, n, N, true);
+    std::printf("nqt %d\nlds_bytes %d\nslabs %d\ntiles_per_block %d\npasses %d\nwave_trips %d\nblock_rows %d\n", dp.nqt, dp.lds, dp.slabs,
+                dp.tiles_per_block, dp.passes, dp.tiles_per_block / 4, 16 * dp.tiles_per_block);
+    const struct { const char* name; int grid, per_block; } ks[] = {
+        {"canonical_scan", canonical_scan_grid(N), PLAN_CANON_ROWS_PER_BLOCK}, {"assign_resolve", assign_resolve_grid(N), PLAN_CANON_ROWS_PER_BLOCK},
+        {"member_count", member_count_grid(N), PLAN_POINT_ROWS_PER_BLOCK}, {"assign_sizes", assign_sizes_grid(N), PLAN_POINT_ROWS_PER_BLOCK},
+        {"assign_decide", assign_decide_grid(N), PLAN_POINT_ROWS_PER_BLOCK}, {"member_from_dist", member_from_dist_grid(N), PLAN_POINT_ROWS_PER_BLOCK},
+        {"member_merge_tags", member_merge_tags_grid(N), PLAN_POINT_ROWS_PER_BLOCK}};
+    for (const auto& k : ks) {
+        const long long per_trip = (long long)k.grid * k.per_block;
+        std::printf("%s.grid %d\n%s.rows_per_trip %lld\n%s.trips %lld\n", k.name, k.grid, k.name, per_trip, k.name, (long long)((N + per_trip - 1) / per_trip));
+    }
+    const ClusterSumsPlan cp = plan_cluster_sums(D, n, N);
+    std::printf("cluster_sums.cols %d\ncluster_sums.chunks %d\ncluster_sums.rows_per_block %d\ncluster_sums.slabs %d\ncluster_sums.lds_bytes %d\n",
+                cp.cols, cp.chunks, cp.rows_per_block, cp.slabs, cp.lds);
+    std::printf("compact_blocks %d\ncompact_block_rows %d\nrows %lld\n", subset_compact_blocks(N), PLAN_SUBSET_BLOCK_ROWS, (long long)N);
+    return 0;
+}
+
 // hand-built partitions: the cell sizes of the first B rows, then `tail` rows added since
 static int probed(const PlanOptions& o) {
     const int64_t SEG = PLAN_PROBE_SEG;
@@ -386,7 +456,8 @@ static int result_blocks() {
     return 0;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc == 6 && !strcmp(argv[1], "figures")) return figures(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoll(argv[5]));
     // the options at their defaults, then each at one other value
     std::vector<PlanOptions> sets(7);
     sets[1].scan_rounds = 3; sets[2].scan_max_slabs = 256; sets[3].merge_two_level_min = 4096;
@@ -402,19 +473,43 @@ int main() {
         if (scans_and_dense(g_opt) || gemm_select_merge(g_opt) || probed(g_opt)) return 1;
     }
     g_set = 0;
-    if (cluster_sums() || result_blocks()) return 1;
+    if (cluster_sums() || result_blocks() || capped_grids()) return 1;
     std::printf("ok: %ld plans\n", g_checked);
     return 0;
 }
 """
 
 
-def test_every_plan_and_layout_is_the_parents(tmp_path):
-    src = tmp_path / "plans_check.cpp"
-    src.write_text(PROGRAM)
-    exe = str(tmp_path / "plans_check")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", exe], capture_output=True, text=True)
+def build_program(directory):
+    """the program above, compiled into `directory`; returns the executable's path"""
+    src = os.path.join(str(directory), "plans_check.cpp")
+    with open(src, "w") as f:
+        f.write(PROGRAM)
+    exe = os.path.join(str(directory), "plans_check")
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, src, "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+    return exe
+
+
+def dense_figures(exe, dim, qelt, n_operands, N):
+    """the program's `figures` mode as the dict _lib.index_dense_plan returns for such an index"""
+    r = subprocess.run([exe, "figures", str(dim), str(qelt), str(n_operands), str(N)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    flat = {k: int(v) for k, v in (line.split() for line in r.stdout.splitlines())}
+    out = {"scan": {}}
+    for k, v in flat.items():
+        if "." in k:
+            a, b = k.split(".")
+            out.setdefault(a, {})[b] = v
+        elif k in ("nqt", "lds_bytes", "slabs", "tiles_per_block", "passes", "wave_trips", "block_rows"):
+            out["scan"][k] = v
+        else:
+            out[k] = v
+    return out
+
+
+def test_every_plan_and_layout_is_the_parents(tmp_path):
+    exe = build_program(tmp_path)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.startswith("ok:"), r.stdout
