@@ -607,6 +607,56 @@ int mmiss_index_query_subset(mmiss_index* idx, const float* queries, int32_t Q, 
                              const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
                              int32_t* out_count, int64_t* out_matched);
 
+/* ---------------------------------------------------------------- search after ----------------- */
+/*
+ * The exact next k of a ranking behind a cursor (distance, label): "show more". The caller holds the last entry of the page it has
+ * and gets the k entries that follow it, at a cost that does not grow with the depth, and the number of rows still to come. The
+ * ranking is mmiss_index_query's: canonical distance bits, ties by label. Nothing is kept on the handle between pages.
+ *
+ * Admitted rows. A(q) is the set of rows r < count for which all of these hold:
+ *   - cand_labels is null, or labels[r] is in the list (mmiss_index_query_subset's list: an unknown label is ignored, a repeated
+ *     one counts once, the order means nothing);
+ *   - the masks of q admit tags[r] (require / exclude as mmiss_index_query_filtered, null = 0);
+ *   - the canonical distance d of r to q is not NaN (a query or a row without a direction has none);
+ *   - max_dist is null, or d <= max_dist[q] as floats; a NaN max_dist[q] admits nothing;
+ *   - r ranks strictly after the cursor: d > after_dist[q], or d == after_dist[q] and labels[r] > after_label[q]. Distances are
+ *     compared in the order the ranking itself uses (by their bits: -0.0 before +0.0); labels are compared as values, so the
+ *     cursor's label need not be stored — it may have been removed since the last page, and it may be any number. A NaN
+ *     after_dist[q] admits nothing; after_dist[q] = -inf is the start of the ranking, whatever the label.
+ * Result: the first k of A(q) by (distance, label), -1 / +inf behind the count; out_count[q] = min(k, |A(q)|);
+ * out_remaining[q] = |A(q)|, the rows delivered included; it may be null.
+ *
+ * Consequences:
+ *   1. First page. With the cursor -inf, no max_dist and no list, the labels, distance bits and counts are those of
+ *      mmiss_index_query / mmiss_index_query_filtered; with a list those of mmiss_index_query_subset; with max_dist those of
+ *      mmiss_index_query_radius at cap = k.
+ *   2. Pages tile the ranking. Start at -inf and feed each page's last (out_dist, out_labels) back as the next cursor: the chain is
+ *      the ranking of A entry for entry, without a repeat or a gap, through runs of equal distances that straddle a page boundary,
+ *      past position 2040, at whatever page size 1 <= k <= 2040 each step uses.
+ *   3. Remaining. On an unchanged index out_remaining falls by out_count from page to page; the last page has remaining == count;
+ *      the page after it has count 0 and remaining 0.
+ *   4. Stateless. Rows added, updated or removed between two pages are ranked as they stand at the second call.
+ *
+ * queries float32 [Q, dim], after_dist float32 [Q], after_label int64 [Q], max_dist float32 [Q], cand_labels int64 [n_cand],
+ * require / exclude uint64 [Q]: each host or device memory; the four outputs (out_labels int64 [Q, k], out_dist float32 [Q, k],
+ * out_count int32 [Q], out_remaining int64 [Q]) all host or all device memory. Q >= 1; 1 <= k <= 2040 (above:
+ * MMISS_ERR_UNSUPPORTED); k < 1, Q < 1, n_cand < 0, a null pointer where one is needed, or cand_labels null with n_cand > 0:
+ * MMISS_ERR_ARG; n_cand above 2^31 - 1: MMISS_ERR_UNSUPPORTED. A non-null list with n_cand = 0 is the empty set: counts 0. No
+ * cursor value is an error.
+ *
+ * The call locks the handle, runs on its current stream, returns with its work finished, fails with MMISS_ERR_STATE while a
+ * _begin query is open, checks every argument before it writes anything, and leaves the eight guard counters, the partition and
+ * its counters alone. Every row (every listed row) is read once per block of up to 16 queries and gets its canonical distance
+ * directly; the queries are taken in chunks that keep the scratch under 512 MB. The call is meant for the few queries a scrolling
+ * user has open: a large batch over the whole index is bound by the scan's fp64 arithmetic.
+ *
+ * Not offered: one cursor per shard (ShardedIndex); a cursor into a probed (nprobe) or a distinct ranking; one list per query.
+ */
+int mmiss_index_query_after(mmiss_index* idx, const float* queries, int32_t Q, int32_t k, const float* after_dist,
+                            const int64_t* after_label, const float* max_dist, const int64_t* cand_labels, int64_t n_cand,
+                            const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
+                            int32_t* out_count, int64_t* out_remaining);
+
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*
  * out[q] = normalize(w * normalize(img[q]) + (1-w) * normalize(txt[q])), float32 [Q,dim].

@@ -256,6 +256,13 @@ int mmiss_dbg_index_distinct_plan(struct mmiss_index* ix, int32_t Q, int32_t* ou
  *   such block   [14], [15] the query block the first / the last chunk runs with: [7] halved while half of it still holds the
  *   chunk's queries */
 int mmiss_dbg_index_subset_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int64_t n_cand, int32_t* out);
+/* How a continuation call (mmiss_index_query_after) of Q >= 1 queries, this k (1 .. 2040) and a list of n_cand labels (n_cand < 0:
+ * no list, the dense scan over every row) would run on the index as it stands and under the options as they stand: plan_after
+ * (csrc/index_plans.h), evaluated on the host. Launches nothing, changes nothing. out is a HOST int32 [16], laid out as
+ * mmiss_dbg_index_subset_plan's except:
+ *   [0] bound: rows without a list, min(n_cand, rows) with one   [12] blocks of the bitmap's compaction: 0 without a list
+ *   [13] 1: the dense scan (position i is row i), 0: the listed one */
+int mmiss_dbg_index_after_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int64_t n_cand, int32_t* out);
 /* How the dense scans and the kernels behind them would walk the index as it stands with n_operands (1 .. 1024) probes, centres or
  * clusters: the calls' own planning functions (plan_dense by passes, the capped grids, plan_cluster_sums, subset_compact_blocks;
  * csrc/index_plans.h), evaluated on the host. Launches nothing, changes nothing. out is a HOST int32 [40]; an empty index leaves

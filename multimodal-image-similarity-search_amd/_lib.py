@@ -111,6 +111,7 @@ SIGNATURES = {
     "mmiss_index_query_probed": (_I, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "mmiss_index_query_distinct": (_I, [_P, _P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "mmiss_index_query_subset": (_I, [_P, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "mmiss_index_query_after": (_I, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "mmiss_blend": (_I, [_I, _P, _P, _P, C.c_double, _I32, _I32, _P]),
     "mmiss_merge_topk": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_prof_enable": (_I, [_I]),
@@ -162,6 +163,7 @@ SIGNATURES = {
     "mmiss_dbg_index_probe_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_distinct_plan": (_I, [_P, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_subset_plan": (_I, [_P, _I32, _I32, _I64, C.POINTER(_I32)]),
+    "mmiss_dbg_index_after_plan": (_I, [_P, _I32, _I32, _I64, C.POINTER(_I32)]),
     "mmiss_dbg_index_dense_plan": (_I, [_P, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
@@ -344,6 +346,17 @@ def index_dense_plan(handle, n_operands: int) -> dict:
     d["cluster_sums"] = dict(zip(("cols", "chunks", "rows_per_block", "slabs", "lds_bytes"), v[30:35]))
     d["compact_blocks"], d["compact_block_rows"], d["rows"] = v[35], v[36], v[37]
     return d
+
+
+AFTER_PLAN_FIELDS = SUBSET_PLAN_FIELDS[:13] + ("dense",) + SUBSET_PLAN_FIELDS[14:]
+
+
+def index_after_plan(handle, Q: int, k: int, n_cand=None) -> dict:
+    """mmiss_dbg_index_after_plan as a dict: how a continuation call (FlatIndex.query_after) of this shape would run on the index
+    `handle` as it stands (and under the option probe_scratch_kb as it stands); n_cand None: no list. Nothing is launched."""
+    out = (_I32 * 16)()
+    check(load().mmiss_dbg_index_after_plan(handle, int(Q), int(k), -1 if n_cand is None else int(n_cand), out))
+    return dict(zip(AFTER_PLAN_FIELDS, (int(v) for v in out)))
 
 
 _INDEX_ELT = {MMISS_F32: "float32", MMISS_F16: "float16", MMISS_F8: "uint8"}

@@ -17,6 +17,10 @@ similar to an earlier kept one is dropped and counted in that one's "duplicates"
 Absent, the call is today's call.
 A third optional field, `ids` (image ids, comma-separated), searches among those images only (mmiss_amd.search's `within_ids=`):
 the exact `limit` nearest of them; unknown ids are ignored, a malformed value (an empty entry) is answered as a bad `limit` is.
+A fourth optional field, `after`, pages through a ranking ("show more"; mmiss_amd.search's `after=`): empty for the first page, the
+`next` of the previous response for the one behind it. The response then carries `next` (null on the last page) and `remaining`
+beside `results`; `filters` are then applied before the search, as with `prefilter`; `limit` <= 0 means pages of 1000; a malformed
+token is answered as a bad `limit` is. The other fields must be those of the page before.
 This is SURVEY.md §8(f) N1: the caller of the hot path, kept thin; everything numeric goes through
 mmiss_amd.utils / mmiss_amd.search. The other ten routes (metadata editing, Moondream filters, reset, static
 files) are out of scope.
@@ -37,6 +41,7 @@ from typing import Dict, List, Optional, Tuple
 from urllib.parse import parse_qs
 
 from . import search, utils
+from .collection import parse_token
 
 logger = logging.getLogger("image-match")
 
@@ -102,6 +107,24 @@ def _ids_kw(fields) -> dict:
     if any(not part for part in ids):
         raise ValueError(f"ids must be image ids separated by commas, got {raw!r}")
     return {"within_ids": list(dict.fromkeys(ids))}
+
+
+def _after_kw(fields) -> dict:
+    """The optional form field `after` as the keyword argument `after` of the search call: "" for the first page, else a
+    continuation token (checked here: a malformed one raises, and the route answers as it answers a bad `limit`); absent: no
+    argument at all (today's call)."""
+    raw = _first(fields, "after")
+    if raw is None:
+        return {}
+    token = str(raw).strip()
+    if token:
+        parse_token(token)
+    return {"after": token}
+
+
+def _page(got) -> dict:
+    """a paged search's answer as the route's response"""
+    return {"results": got["results"], "next": got["next"], "remaining": got["remaining"]}
 
 
 def apply_filters(results: List[dict], filters: Optional[List[str]]) -> List[dict]:
@@ -202,8 +225,12 @@ def create_app():
             limit = int(_first(fields, "limit", 10))
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
                    **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
+            page = _after_kw(fields)
             model, processor = utils.load_clip_model()
             embedding_result = utils.generate_clip_embedding(image=image, model=model, processor=processor)
+            if page:
+                return _page(search.search_similar(embedding=embedding_result["image"][0], limit=limit, filters=fields.get("filters"),
+                                                   **sim, **page))
             if _prefilter(fields):
                 return {"results": search.search_similar(embedding=embedding_result["image"][0], limit=limit,
                                                          filters=fields.get("filters"), **sim)}
@@ -224,11 +251,17 @@ def create_app():
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
                    **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
             filters = fields.get("filters")
+            page = _after_kw(fields)
             if not query.strip() and filters:
                 # filter-only browse (main.py:245-249,1225-1242): every stored image, no vector search
                 got = search._collection().get(include=["metadatas"])
                 n = 1000 if limit <= 0 else limit
                 results = [dict(m or {}) for m in got["metadatas"]][:n]
+                if page:   # (no ranking to continue: the browse is one page)
+                    results = apply_filters(results, filters)
+                    return {"results": results, "next": None, "remaining": len(results)}
+            elif page:
+                return _page(search.search_by_text(query_text=query, limit=limit, filters=filters, **sim, **page))
             elif _prefilter(fields):
                 return {"results": search.search_by_text(query_text=query, limit=limit, filters=filters, **sim)}
             else:
@@ -249,6 +282,10 @@ def create_app():
             limit = int(_first(fields, "limit", 10))
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
                    **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
+            page = _after_kw(fields)
+            if page:
+                return _page(search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,
+                                                      limit=limit, filters=fields.get("filters"), **sim, **page))
             if _prefilter(fields):
                 return {"results": search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,
                                                             limit=limit, filters=fields.get("filters"), **sim)}

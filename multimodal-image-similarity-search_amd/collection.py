@@ -24,6 +24,7 @@ from __future__ import annotations
 import json
 import logging
 import os
+import re
 import threading
 from typing import Dict, List, Optional, Sequence
 
@@ -108,6 +109,22 @@ def where_matches(metadata, where) -> bool:
         if not ok:
             return False
     return True
+
+
+_TOKEN = re.compile(r"^([0-9a-f]{8})\.(-?[0-9]{1,19})$")
+
+
+def make_token(distance, label: int) -> str:
+    """The continuation token of a result entry: the float32 distance's bits and the row's label, "%08x.%d". Opaque to callers."""
+    return "%08x.%d" % (int(np.asarray(distance, dtype=np.float32).view(np.uint32)), int(label))
+
+
+def parse_token(token) -> tuple:
+    """make_token's inverse -> (distance float32, label int); anything else raises ValueError."""
+    m = _TOKEN.match(token) if isinstance(token, str) else None
+    if m is None or not -2 ** 63 <= int(m.group(2)) < 2 ** 63:
+        raise ValueError(f"after: not a continuation token: {token!r}")
+    return np.array([int(m.group(1), 16)], dtype=np.uint32).view(np.float32)[0], int(m.group(2))
 
 
 class DuplicateIDError(ValueError):
@@ -508,10 +525,42 @@ class FlatCollection:
             cnt = within.sum(1).astype(np.int32)
         return labs_o, dist, cnt
 
+    def _after_query(self, q: np.ndarray, k: int, cursors, labs, filters: List[str], max_distance=None):
+        """The exact next k of every query's ranking behind its cursor (FlatIndex.query_after) -> (labels [Q,k], distances [Q,k],
+        counts [Q], remaining [Q]). cursors: (distance, label) per query; labs: the admitted labels, None for every row. Filters
+        travel as _subset_query's do: up to 64 names as masks, a name past the 64th bit folded into the list on the host."""
+        Q = q.shape[0]
+        empty = (np.full((Q, k), -1, np.int64), np.full((Q, k), np.inf, np.float32), np.zeros((Q,), np.int32), np.zeros((Q,), np.int64))
+        kw = {}
+        if filters:
+            self._push_tags()
+            if any(f not in self._filter_bits and f not in self._filter_overflow for f in filters):
+                return empty                                             # a name no row has ever answered admits nothing
+            req = 0
+            for f in filters:
+                if f in self._filter_bits:
+                    req |= 1 << self._filter_bits[f]
+            if req:
+                kw["require"] = np.uint64(req)
+            over = [f for f in filters if f in self._filter_overflow]
+            if over:
+                labs = [lab for lab in (self._labels if labs is None else labs)
+                        if all(answers_yes(filter_answers(self._meta.get(lab)).get(f, "")) for f in over)]
+        if labs is not None:
+            if not labs:
+                return empty
+            kw["labels"] = np.asarray(labs, dtype=np.int64)
+        if max_distance is not None:
+            kw["max_dist"] = np.full((Q,), max_distance, dtype=np.float32)
+        ad = np.array([c[0] for c in cursors], dtype=np.float32)
+        al = np.array([c[1] for c in cursors], dtype=np.int64)
+        labs_o, dist, cnt, rem = self._index.query_after(q, k, ad, al, **kw)
+        return np.asarray(labs_o), np.asarray(dist), np.array(cnt, np.int32), np.array(rem, np.int64)
+
     def query(self, query_embeddings=None, n_results: int = 10, include: Sequence[str] = ("metadatas", "documents", "distances"),
               filters: Optional[Sequence[str]] = None, max_distance: Optional[float] = None, n_probe: Optional[int] = None,
               distinct_distance: Optional[float] = None, pool: Optional[int] = None, ids=None, where: Optional[dict] = None,
-              **_unused) -> dict:
+              after: Optional[Sequence[Optional[str]]] = None, **_unused) -> dict:
         """collection.query. filters: names of yes/no filters; when given, the result is the exact n_results nearest among the
         rows whose filter_results_json answers "yes" to every one of them (pre-filtering; see the module docstring).
         max_distance: a radius query (FlatIndex.query_radius) — only the rows within that cosine distance are returned, exactly,
@@ -535,6 +584,14 @@ class FlatCollection:
         names as masks, names past the 64th folded into the list: exact, where the filtered query's host post-filter is not),
         max_distance cuts the sorted result at the radius, n_probe is ignored (the subset is exact), distinct_distance raises
         ValueError, an empty admitted set gives empty results. Without ids and where nothing changes.
+        after: continue a ranking ("show more"; FlatIndex.query_after) — one entry per query, the "next" token of the page the
+        caller holds, or None for the start of the ranking; a malformed token raises ValueError. The result is the exact
+        n_results entries that follow that one (up to 2040 per call; no warning), at a cost that does not grow with the depth,
+        and the dict gains "next" (per query: the token of the last entry, None when this page is the last) and "remaining" (per
+        query: the rows behind the cursor, this page's included). Tokens are opaque and hold no state: rows added or removed
+        between two pages are ranked as they stand. filters (masks; names past the 64th folded into the list), ids / where (the
+        list) and max_distance combine and must be the same on every page; n_probe is ignored (the continuation is exact);
+        distinct_distance raises ValueError. Without after nothing changes.
         Nothing is written, neither metadata nor journal."""
         if n_probe is not None and int(n_probe) < 1:
             raise ValueError(f"n_probe: at least 1, got {n_probe}")
@@ -543,6 +600,13 @@ class FlatCollection:
             check_where(where)
         if subset and distinct_distance is not None:
             raise ValueError("distinct_distance cannot be combined with ids / where")
+        cursors = None
+        if after is not None:
+            if distinct_distance is not None:
+                raise ValueError("distinct_distance cannot be combined with after")
+            if isinstance(after, str):
+                raise ValueError("after: a list with one entry per query expected")
+            cursors = [(np.float32(-np.inf), 0) if t is None else parse_token(t) for t in after]
         if distinct_distance is not None:
             distinct_distance = float(distinct_distance)
             if distinct_distance != distinct_distance:
@@ -553,13 +617,22 @@ class FlatCollection:
             raise ValueError("FlatCollection.query needs query_embeddings (text embedding functions are out of scope)")
         q = self._embeddings_array(query_embeddings)
         include = list(include)
+        if cursors is not None and len(cursors) != q.shape[0]:
+            raise ValueError(f"after: one entry per query ({q.shape[0]}) expected, got {len(cursors)}")
         with self._lock:
             Q = q.shape[0]
             n = len(self._ids)
+            rem = np.zeros((Q,), dtype=np.int64)
             if n == 0 or self._index is None:
                 labs = np.full((Q, 0), -1, dtype=np.int64)
                 dist = np.zeros((Q, 0), dtype=np.float32)
                 cnt = np.zeros((Q,), dtype=np.int32)
+            elif cursors is not None:
+                if q.shape[1] != self._dim:
+                    raise ValueError(f"query dimension {q.shape[1]} does not match the collection's {self._dim}")
+                k = max(1, min(int(n_results), n, MAX_N_RESULTS))
+                labs, dist, cnt, rem = self._after_query(q, k, cursors, self._admitted_labels(ids, where) if subset else None,
+                                                         filters, max_distance)
             else:
                 if q.shape[1] != self._dim:
                     raise ValueError(f"query dimension {q.shape[1]} does not match the collection's {self._dim}")
@@ -593,6 +666,10 @@ class FlatCollection:
                 out["embeddings"] = [self._index.get(np.asarray(ls, dtype=np.int64)) for ls in rows]
             if distinct_distance is not None:
                 out["duplicates"] = [[] if dups is None else [int(x) for x in dups[qi, : int(cnt[qi])]] for qi in range(Q)]
+            if cursors is not None:
+                out["remaining"] = [int(r) for r in rem]
+                out["next"] = [make_token(dist[qi, int(cnt[qi]) - 1], labs[qi, int(cnt[qi]) - 1]) if int(rem[qi]) > int(cnt[qi]) else None
+                               for qi in range(Q)]
             return out
 
     def add_similarity_filter(self, name: str, embedding, max_distance: float) -> int:

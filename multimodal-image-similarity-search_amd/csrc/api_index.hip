@@ -8,6 +8,7 @@
 #include "partition_kernels.h"
 #include "distinct_kernels.h"
 #include "subset_kernels.h"
+#include "after_kernels.h"
 #include "gemm_bf16_256.h"
 #include "gemm_strip_p256.h"
 #include <algorithm>
@@ -134,6 +135,9 @@ struct mmiss_index {
     // block counts / offsets of its compaction, the listed rows in ascending order. The totals, masks and key areas are the
     // probed call's (prb_total, prb_mask, prb_keys_a / _b): both calls hold the handle's lock from their first launch to their last
     DevBuf sub_cand, sub_bitmap, sub_blk, sub_rows;
+    // search after (mmiss_index_query_after): the caller's cursors and radii when they are host memory, the resolved cursors, the
+    // remaining counts — one block (after_layout). The list, its compaction, the totals, masks and key areas are the subset call's
+    DevBuf aft_cur;
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -2366,6 +2370,166 @@ extern "C" int mmiss_dbg_index_subset_plan(mmiss_index* ix, int32_t Q, int32_t k
     out[0] = i32(p.bound); out[1] = PROBE_SEG; out[2] = p.levels; out[3] = i32(p.stride0); out[4] = i32(p.stride1);
     out[5] = p.qchunk; out[6] = p.chunks; out[7] = p.qblock; out[8] = p.lds; out[9] = p.share; out[10] = p.splits;
     out[11] = SUBSET_ROWS_PER_TRIP; out[12] = p.blocks; out[13] = SUBSET_BLOCK_ROWS;
+    out[14] = subset_block_for(p.qblock, std::min(Q, p.qchunk)); out[15] = subset_block_for(p.qblock, Q - (p.chunks - 1) * p.qchunk);
+    return MMISS_OK;
+}
+
+// ================================================================================================ search after
+// mmiss_index_query_after: the exact next k of every query's ranking behind its cursor (after_kernels.h). The subset call's
+// stages with two differences: without a list nothing is marked or compacted (the dense scan's position is the row), and the
+// scan's admission adds the radius and the cursor and counts what it admits (out_remaining).
+namespace {
+
+AfterPlan plan_after(const mmiss_index* ix, int Q, int k, int64_t n_cand) {
+    return plan_after(ix->count, n_cand, ix->dim, Q, k, plan_options());
+}
+
+typedef void (*AfterScanKernel)(AfterScanArgs);
+template <typename T, bool DENSE> AfterScanKernel after_scan_kernel_for(int nqb) {
+    switch (nqb) {
+        case 16: return &after_scan_kernel<T, 16, DENSE>;
+        case 8: return &after_scan_kernel<T, 8, DENSE>;
+        case 4: return &after_scan_kernel<T, 4, DENSE>;
+        case 2: return &after_scan_kernel<T, 2, DENSE>;
+        default: return &after_scan_kernel<T, 1, DENSE>;
+    }
+}
+
+// aft_cur of a call of Q queries, in bytes from its start: the remaining counts and the caller's labels (8 bytes each), the
+// resolved cursors (16), the caller's distances and radii (4 each)
+struct AfterLayout {
+    size_t remaining, label, cur, dist, radius, need;
+};
+AfterLayout after_layout(int Q) {
+    AfterLayout l;
+    l.remaining = 0; l.label = (size_t)Q * 8; l.cur = (size_t)Q * 16; l.dist = (size_t)Q * 32; l.radius = (size_t)Q * 36;
+    l.need = (size_t)Q * 40;
+    return l;
+}
+
+}  // namespace
+
+extern "C" int mmiss_index_query_after(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, const float* after_dist,
+                                       const int64_t* after_label, const float* max_dist, const int64_t* cand_labels, int64_t n_cand,
+                                       const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
+                                       int32_t* out_count, int64_t* out_remaining) {
+    const char* who = "mmiss_index_query_after";
+    if (!ix || !queries || !after_dist || !after_label || !out_labels || !out_dist || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || n_cand < 0) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d n_cand=%lld", who, Q, k, (long long)n_cand);
+    if (n_cand > 0 && !cand_labels) MM_FAIL(MMISS_ERR_ARG, "%s: null cand_labels for %lld labels", who, (long long)n_cand);
+    if (k > PROBE_MAX_K) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: k = %d too large (max %d)", who, k, PROBE_MAX_K);
+    if (n_cand > INT32_MAX) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: n_cand = %lld too large (max %d)", who, (long long)n_cand, INT32_MAX);
+    bool out_dev = false;
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_remaining, &out_dev));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, who, &st));
+    if (ix->count > INT32_MAX) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: %lld rows (max %d)", who, (long long)ix->count, INT32_MAX);
+    const int D = ix->dim;
+    const bool listed = cand_labels != nullptr;
+    const AfterPlan p = plan_after(ix, Q, k, listed ? n_cand : -1);
+    ResultBlock out;
+    MM_TRY(out.stage(ix->pin, st, Q, k, out_dev, true, false, out_labels, out_dist, out_count, out_remaining));
+    MM_TRY(upload_queries(ix, st, queries, Q));   // qn of every query of the call
+    const uint64_t* d_req = require; const uint64_t* d_exc = exclude;   // host masks: [Q] required, then [Q] excluded in prb_mask
+    MM_TRY(device_view(&d_req, (size_t)Q, ix->prb_mask, 0, (size_t)Q * 16, st));
+    MM_TRY(device_view(&d_exc, (size_t)Q, ix->prb_mask, (size_t)Q * 8, (size_t)Q * 16, st));
+    const AfterLayout al = after_layout(Q);
+    MM_TRY(ix->aft_cur.ensure(al.need));
+    const float* d_ad = after_dist; const int64_t* d_al = after_label; const float* d_md = max_dist;
+    MM_TRY(device_view(&d_ad, (size_t)Q, ix->aft_cur, al.dist, al.need, st));
+    MM_TRY(device_view(&d_al, (size_t)Q, ix->aft_cur, al.label, al.need, st));
+    MM_TRY(device_view(&d_md, (size_t)Q, ix->aft_cur, al.radius, al.need, st));
+    AfterCursor* const d_cur = reinterpret_cast<AfterCursor*>(ix->aft_cur.as<char>() + al.cur);
+    unsigned long long* const d_rem = reinterpret_cast<unsigned long long*>(ix->aft_cur.as<char>() + al.remaining);
+    MM_TRY(ix->prb_total.ensure((size_t)p.qchunk * 4));
+    MM_TRY(ix->prb_keys_a.ensure((size_t)p.qchunk * p.stride0 * 8));
+    if (p.stride1) MM_TRY(ix->prb_keys_b.ensure((size_t)p.qchunk * p.stride1 * 8));
+    {
+        // (a dense call's totals are the row count, written here; a listed call's come from the compaction below)
+        MM_PROF("after_resolve", st, 0.0, 40.0 * Q);
+        hipLaunchKernelGGL(after_resolve_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, d_ad, d_al, d_md,
+                           (const int64_t*)ix->labels_d.as<int64_t>(), ix->count, Q, d_cur, d_rem,
+                           p.dense ? ix->prb_total.as<int32_t>() : (int32_t*)nullptr, p.qchunk);
+        MM_HIP(hipGetLastError());
+    }
+    if (!p.dense) {
+        if (p.bound > 0) {
+            const int64_t* d_cand = cand_labels;
+            MM_TRY(device_view(&d_cand, (size_t)n_cand, ix->sub_cand, 0, (size_t)n_cand * 8, st));
+            MM_TRY(ix->sub_bitmap.ensure((size_t)p.words * 4));
+            MM_TRY(ix->sub_blk.ensure((size_t)p.blocks * 4));
+            MM_TRY(ix->sub_rows.ensure((size_t)p.bound * 4));
+            MM_TRY(subset_rows(ix, st, p, d_cand, n_cand, p.qchunk));
+        } else {
+            MM_HIP(hipMemsetAsync(ix->prb_total.p, 0, (size_t)p.qchunk * 4, st));   // an empty list or an empty index: |S| = 0
+        }
+    }
+    const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
+    for (int q0 = 0; q0 < Q; q0 += p.qchunk) {
+        const int Qc = std::min(p.qchunk, Q - q0);
+        if (p.bound > 0) {
+            AfterScanArgs aa{};
+            SubsetScanArgs& a = aa.s;
+            a.rows = ix->rows.p; a.inv = ix->inv.as<float>(); a.tags = ix->tags.as<uint64_t>();
+            a.qn = ix->qn.as<float>() + (size_t)q0 * D;
+            a.req = d_req ? d_req + q0 : nullptr; a.exc = d_exc ? d_exc + q0 : nullptr;
+            a.list = p.dense ? nullptr : ix->sub_rows.as<int32_t>(); a.total = ix->prb_total.as<int32_t>();
+            a.Q = Qc; a.D = D; a.share = p.share;
+            a.keys = ix->prb_keys_a.as<unsigned long long>(); a.stride = p.stride0;
+            aa.cur = d_cur + q0; aa.remaining = d_rem + q0;
+            const int nqb = subset_block_for(p.qblock, Qc);
+            const int qblocks = (Qc + nqb - 1) / nqb;
+            MM_PROF(f16 ? "after_scan_f16" : f8 ? "after_scan_f8" : "after_scan_f32", st, 2.0 * Qc * (double)p.bound * D,
+                    (double)qblocks * p.bound * (D * ix->elt + 12) + 8.0 * Qc * p.bound);
+            const AfterScanKernel kern = with_storage(ix->dtype, [&](auto s) {
+                using T = typename decltype(s)::T;
+                return p.dense ? after_scan_kernel_for<T, true>(nqb) : after_scan_kernel_for<T, false>(nqb);
+            });
+            const int lds = subset_scan_lds_bytes(D, nqb);
+            MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds));
+            hipLaunchKernelGGL(kern, dim3(p.splits, qblocks), dim3(256), lds, st, aa);
+            MM_HIP(hipGetLastError());
+        }
+        int64_t nb = p.bound;   // the most keys a query has at this level
+        for (int l = 0; l < p.levels; ++l) {
+            const bool last = l == p.levels - 1;
+            const bool from_a = (l & 1) == 0;
+            const int nseg = last ? 1 : (int)((nb + PROBE_SEG - 1) / PROBE_SEG);
+            SegmentTopkArgs a{};
+            a.in = from_a ? ix->prb_keys_a.as<unsigned long long>() : ix->prb_keys_b.as<unsigned long long>();
+            a.out = from_a ? ix->prb_keys_b.as<unsigned long long>() : ix->prb_keys_a.as<unsigned long long>();
+            a.in_stride = from_a ? p.stride0 : p.stride1; a.out_stride = from_a ? p.stride1 : p.stride0;
+            a.total = ix->prb_total.as<int32_t>(); a.level = l; a.k = k;
+            a.labels = ix->labels_d.as<int64_t>();
+            a.out_labels = out.lab + (size_t)q0 * k; a.out_dist = out.dist + (size_t)q0 * k; a.out_count = out.cnt + q0;
+            a.out_scanned = nullptr;
+            MM_PROF("segment_topk", st, 0.0, (double)Qc * nb * 8);
+            if (last) hipLaunchKernelGGL(segment_topk_kernel<true>, dim3(1, Qc), dim3(1024), 0, st, a);
+            else hipLaunchKernelGGL(segment_topk_kernel<false>, dim3(nseg, Qc), dim3(1024), 0, st, a);
+            MM_HIP(hipGetLastError());
+            nb = (int64_t)nseg * k;
+        }
+    }
+    // the remaining counts leave by a copy of their own: into the caller's device array, or into the result block's pinned totals
+    if (out.tot) MM_HIP(hipMemcpyAsync(out.tot, d_rem, (size_t)Q * 8, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    MM_HIP(hipStreamSynchronize(st));
+    out.deliver();
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: how a continuation call of this shape would run on the index as it stands (plan_after, nothing launched).
+extern "C" int mmiss_dbg_index_after_plan(mmiss_index* ix, int32_t Q, int32_t k, int64_t n_cand, int32_t* out) {
+    const char* who = "mmiss_dbg_index_after_plan";
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || k > PROBE_MAX_K) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d", who, Q, k);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    const AfterPlan p = plan_after(ix, Q, k, n_cand < 0 ? -1 : n_cand);
+    auto i32 = [](int64_t v) { return (int32_t)std::min<int64_t>(v, INT32_MAX); };
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    out[0] = i32(p.bound); out[1] = PROBE_SEG; out[2] = p.levels; out[3] = i32(p.stride0); out[4] = i32(p.stride1);
+    out[5] = p.qchunk; out[6] = p.chunks; out[7] = p.qblock; out[8] = p.lds; out[9] = p.share; out[10] = p.splits;
+    out[11] = SUBSET_ROWS_PER_TRIP; out[12] = p.blocks; out[13] = p.dense ? 1 : 0;
     out[14] = subset_block_for(p.qblock, std::min(Q, p.qchunk)); out[15] = subset_block_for(p.qblock, Q - (p.chunks - 1) * p.qchunk);
     return MMISS_OK;
 }

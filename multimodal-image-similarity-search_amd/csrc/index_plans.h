@@ -1,5 +1,5 @@
 // index_plans.h — the launch-shape arithmetic of the index's host layer (api_index.hip): how many queries a scan block stages, how
-// the rows are cut into slabs, how a selection or a merge is split, how a probed or a subset call is chunked, how the suppression stage of a
+// the rows are cut into slabs, how a selection or a merge is split, how a probed, a subset or a continuation call is chunked, how the suppression stage of a
 // distinct call is laid out, where the arrays of a result block lie. Plain C++, no HIP include, no option lookup: api_index.hip, its debug plan entries (mmiss_dbg_index_*plan) and a
 // host-only test program (tests/test_index_plans_cpu.py) all take the rules from here.
 #pragma once
@@ -244,6 +244,25 @@ inline SubsetPlan plan_subset(int64_t count, int64_t n_cand, int D, int Q, int k
     p.splits = (int)std::max<int64_t>(1, (p.bound + p.share - 1) / p.share);
     p.words = (count + 31) / 32;
     p.blocks = subset_compact_blocks(count);
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------ search after
+// How a continuation call (mmiss_index_query_after, after_kernels.h) of Q queries runs on `count` rows of dim D. n_cand < 0: no
+// list — the dense scan, whose position i is row i: the bound is count, nothing is marked or compacted (words = blocks = 0).
+// n_cand >= 0: a list, and plan_subset's bound min(n_cand, count) with its compaction. Everything else — levels and strides,
+// chunks under probe_scratch_kb, the query block from PLAN_SUBSET_LDS narrowed to the chunk (subset_block_for), share and
+// splits — is plan_subset's rule applied to that bound: the cursor removes keys on the device, never positions, so the host
+// bound does not depend on it.
+struct AfterPlan : SubsetPlan {
+    bool dense = true;
+};
+
+inline AfterPlan plan_after(int64_t count, int64_t n_cand, int D, int Q, int k, const PlanOptions& o) {
+    AfterPlan p;
+    static_cast<SubsetPlan&>(p) = plan_subset(count, n_cand < 0 ? count : n_cand, D, Q, k, o);
+    p.dense = n_cand < 0;
+    if (p.dense) { p.words = 0; p.blocks = 0; }
     return p;
 }
 

@@ -662,6 +662,124 @@ class FlatIndex:
                                                           _lib.ptr(cnt), _lib.ptr(matched)))
         return lab, dist, cnt, matched
 
+    # ------------------------------------------------------------------ search after
+    @staticmethod
+    def _per_query(x, Q: int, dtype, name: str):
+        """x as a contiguous [Q] array of `dtype` (a numpy dtype): a CUDA tensor stays one, anything else becomes numpy; a scalar
+        is repeated for every query."""
+        if _is_torch(x) and x.is_cuda:
+            import torch
+
+            t = x.to(getattr(torch, np.dtype(dtype).name)).reshape(-1).contiguous()
+            if t.shape[0] == 1 and Q > 1:
+                t = t.expand(Q).contiguous()
+            v = t
+        else:
+            if _is_torch(x):
+                x = x.numpy()
+            a = np.asarray(x)
+            if np.dtype(dtype).kind == "i" and a.size and a.dtype.kind not in "ui":
+                raise TypeError(f"{name}: integers expected, got {a.dtype}")
+            a = a.astype(dtype).reshape(-1)
+            if a.shape[0] == 1 and Q > 1:
+                a = np.repeat(a, Q)
+            v = np.ascontiguousarray(a)
+        if int(v.shape[0]) != Q:
+            raise ValueError(f"{name}: one value per query ({Q}) expected, got {int(v.shape[0])}")
+        return v
+
+    def query_after(self, queries, k: int, after_dist, after_label, max_dist=None, labels=None, require=None, exclude=None):
+        """The exact next k of every query's ranking behind its cursor (mmiss_index_query_after) -> (labels int64 [Q,k], distances
+        float32 [Q,k], counts int32 [Q], remaining int64 [Q]). The ranking is query()'s: canonical distance bits, ties by label.
+        after_dist float32 [Q] / after_label int64 [Q]: the last entry the caller holds — a row is returned when its distance is
+        larger (by the ranking's order of the bits), or equal with a larger label; -inf starts the ranking, NaN admits nothing,
+        the label need not be stored. max_dist [Q] (None: none): only rows with distance <= it. labels (None: every row): only
+        rows whose labels are listed, as query_subset's list; an empty list gives counts 0. require / exclude as in query().
+        remaining[q]: the rows behind the cursor, those delivered included — 0 means the ranking has ended, remaining == count
+        that this page is the last. Nothing is kept between calls. Scalars are repeated for every query. 1 <= k <= 2040, at
+        least one query. numpy in -> numpy out, CUDA tensor in -> CUDA tensors out."""
+        k = int(k)
+        if not 1 <= k <= self.MAX_K:
+            raise ValueError(f"k: 1 .. {self.MAX_K}, got {k}")
+        cand, n_cand = None, 0
+        if labels is not None:
+            if _is_torch(labels):
+                import torch
+
+                if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.dtype.is_complex:
+                    raise TypeError(f"labels: integers expected, got {labels.dtype}")
+                cand = labels.to(torch.int64).reshape(-1).contiguous()
+                if not cand.is_cuda:
+                    cand = cand.numpy()
+            else:
+                cand = np.asarray(labels)
+                if cand.size and cand.dtype.kind not in "ui":
+                    raise TypeError(f"labels: integers expected, got {cand.dtype}")
+                cand = np.ascontiguousarray(cand, dtype=np.int64).reshape(-1)
+            n_cand = int(cand.shape[0])
+            if n_cand > 2 ** 31 - 1:
+                raise ValueError(f"labels: at most {2 ** 31 - 1}, got {n_cand}")
+            if n_cand == 0:
+                cand = np.zeros((1,), dtype=np.int64)   # the empty list is a non-null pointer with n_cand = 0
+        q, (lab, dist, cnt) = self._prepare(queries, k)
+        Q = int(q.shape[0])
+        if Q < 1:
+            raise ValueError("query_after takes at least one query")
+        on_device = _is_torch(q) and q.is_cuda
+        ad = self._per_query(after_dist, Q, np.float32, "after_dist")
+        al = self._per_query(after_label, Q, np.int64, "after_label")
+        md = None if max_dist is None else self._per_query(max_dist, Q, np.float32, "max_dist")
+        if not on_device and any(_is_torch(v) for v in (ad, al, md, cand)):
+            raise ValueError("CUDA cursors, radii and labels go with CUDA queries")
+        masks = self._masks(q, require, exclude) or (None, None)
+        if on_device:
+            import torch
+
+            remaining = torch.empty((Q,), dtype=torch.int64, device=q.device)
+        else:
+            remaining = np.empty((Q,), dtype=np.int64)
+        with self._call_lock:
+            self._sync_stream(q)
+            _lib.check(self._lib.mmiss_index_query_after(self._h, _lib.ptr(q), Q, k, _lib.ptr(ad), _lib.ptr(al),
+                                                         None if md is None else _lib.ptr(md), None if cand is None else _lib.ptr(cand),
+                                                         n_cand, _lib.ptr(masks[0]), _lib.ptr(masks[1]), _lib.ptr(lab), _lib.ptr(dist),
+                                                         _lib.ptr(cnt), _lib.ptr(remaining)))
+        return lab, dist, cnt, remaining
+
+    def ranking(self, query, n: int, page: int = 1000, **same):
+        """The first n entries of ONE query's ranking, for any n, by chaining pages of query_after -> (labels int64 [m], distances
+        float32 [m]), m <= n: it stops when a page comes back short. page: entries per call, 1 .. 2040. **same: the max_dist,
+        labels, require and exclude of query_after, the same on every page."""
+        n, page = int(n), int(page)
+        if n < 0:
+            raise ValueError(f"n: at least 0, got {n}")
+        if not 1 <= page <= self.MAX_K:
+            raise ValueError(f"page: 1 .. {self.MAX_K}, got {page}")
+        on_device = _is_torch(query) and query.is_cuda
+        q = query.reshape(1, -1) if _is_torch(query) else np.asarray(query, dtype=np.float32).reshape(1, -1)
+        labs, dists = [], []
+        ad, al = np.float32(-np.inf), np.int64(0)
+        got = 0
+        while got < n:
+            k = min(page, n - got)
+            lab, dist, cnt, _ = self.query_after(q, k, ad, al, **same)
+            c = int(cnt[0])
+            labs.append(lab[0, :c])
+            dists.append(dist[0, :c])
+            got += c
+            if c < k:
+                break
+            ad, al = dist[0, c - 1:c], lab[0, c - 1:c]   # (views: a CUDA page's cursor stays on the device)
+        if on_device:
+            import torch
+
+            if not labs:
+                return (torch.empty((0,), dtype=torch.int64, device=query.device), torch.empty((0,), dtype=torch.float32, device=query.device))
+            return torch.cat(labs), torch.cat(dists)
+        if not labs:
+            return np.empty((0,), np.int64), np.empty((0,), np.float32)
+        return np.concatenate(labs), np.concatenate(dists)
+
     # ------------------------------------------------------------------ distinct results
     MAX_POOL = MAX_POOL
 

@@ -17,6 +17,10 @@ Every search takes a keyword-only `filters` (names of yes/no filters): the exact
 Every search also takes `distinct_similarity`: near-duplicates of kept results are suppressed on the device and counted.
 Every search also takes `within_ids` (image ids) and `where` (a metadata predicate): the exact `limit` nearest among those images
 only (FlatCollection.query(ids=, where=)) — an album, a folder, the hits of an earlier search.
+Every search also takes `after`: "show more". "" asks for the first page, the "next" token of a page for the one behind it (one
+entry per query for the batch forms); the call then returns {"results": [...], "next": token or None, "remaining": n} instead of the
+bare list (the batch forms: one such dict per query) — the exact continuation of the ranking at any depth
+(FlatCollection.query(after=)). The other arguments must be those of the page before. None (the default): today's call and list.
 """
 from __future__ import annotations
 
@@ -72,7 +76,17 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
     return similar_images
 
 
-def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=None, within_ids=None, where=None) -> dict:
+def _paged(results: dict, qi: int) -> Dict:
+    """one query's page of a FlatCollection.query(after=) result"""
+    return {"results": _results_from_query(results, qi), "next": results["next"][qi], "remaining": results["remaining"][qi]}
+
+
+def _no_page() -> Dict:
+    """what a paged search answers when it fails (the list forms answer [])"""
+    return {"results": [], "next": None, "remaining": 0}
+
+
+def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=None, within_ids=None, where=None, after=None) -> dict:
     """the keyword arguments of FlatCollection.query for a search's filters, similarity threshold, probe count and distinctness;
     min_similarity = s becomes the radius utils.max_distance_for_similarity(s): on its results "similarity_score >= s" holds for
     exactly the members; distinct_similarity = s becomes distinct_distance the same way: a result at least s similar to an earlier
@@ -89,13 +103,16 @@ def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=N
         kw["ids"] = [within_ids] if isinstance(within_ids, str) else list(within_ids)
     if where is not None:
         kw["where"] = where
+    # after: one token per query, "" / None for the start of the ranking; absent, no argument at all (today's call)
+    if after is not None:
+        kw["after"] = [t or None for t in after]
     return kw
 
 
 def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                    min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                    distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                   where: Optional[dict] = None) -> List[Dict]:
+                   where: Optional[dict] = None, after: Optional[str] = None):
     """Search for similar images using an embedding (main.py:748-805). min_similarity: only the images whose similarity_score
     reaches it, exactly (a radius query; `limit` caps how many) — the reference's roadmap item "Adjustable similarity
     thresholds" (CHANGELOG.md:475). n_probe: search only the n_probe k-means cells nearest to the embedding, and what was added
@@ -104,30 +121,40 @@ def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[
     dropped and counted under it; every result then carries "duplicates", the images it stands for besides itself
     (FlatCollection.query(distinct_distance=)).
     within_ids / where: only among these images — ids (unknown ones are ignored) and / or a metadata predicate; the exact `limit`
-    nearest of them (FlatCollection.query(ids=, where=)); n_probe is then ignored, and distinct_similarity is refused (logged, [])."""
+    nearest of them (FlatCollection.query(ids=, where=)); n_probe is then ignored, and distinct_similarity is refused (logged, []).
+    after: "" for the first page, a page's "next" token for the one behind it -> {"results", "next", "remaining"} (module docstring);
+    n_probe is then ignored; distinct_similarity and a malformed token are refused (logged, an empty page)."""
     try:
         actual_limit = 1000 if limit <= 0 else limit  # "All" option (limit of 0), main.py:757
         results = _collection().query(query_embeddings=[np.asarray(embedding, dtype=np.float32).tolist()],
                                       n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where))
+                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where,
+                                                   None if after is None else [after]))
+        if after is not None:
+            return _paged(results, 0)
         out = _results_from_query(results, 0)
         logger.info(f"Found {len(out)} similar images")
         return out
     except Exception as e:
         logger.error(f"Error searching for similar images: {e}")
-        return []
+        return [] if after is None else _no_page()
 
 
 def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                          min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                          distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                         where: Optional[dict] = None) -> List[List[Dict]]:
-    """[Q, D] embeddings -> one result list per query, one index pass for the whole batch."""
+                         where: Optional[dict] = None, after: Optional[Sequence[Optional[str]]] = None):
+    """[Q, D] embeddings -> one result list per query, one index pass for the whole batch. after: one entry per query ("" / None:
+    the first page) -> one {"results", "next", "remaining"} per query."""
     try:
         actual_limit = 1000 if limit <= 0 else limit
         q = np.asarray(embeddings, dtype=np.float32)
+        if after is not None and (isinstance(after, str) or len(after) != q.shape[0]):
+            raise ValueError(f"after: one entry per query ({q.shape[0]}) expected")
         results = _collection().query(query_embeddings=q, n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where))
+                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where, after))
+        if after is not None:
+            return [_paged(results, qi) for qi in range(q.shape[0])]
         return [_results_from_query(results, qi) for qi in range(q.shape[0])]
     except Exception as e:
         logger.error(f"Error searching for similar images: {e}")
@@ -137,23 +164,23 @@ def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Op
 def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                    min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                    distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                   where: Optional[dict] = None) -> List[Dict]:
+                   where: Optional[dict] = None, after: Optional[str] = None):
     """Search for images using a text query (main.py:807-827)."""
     try:
         model, processor = utils.load_clip_model()
         embedding_result = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)
         text_embedding = embedding_result["text"][0]
         return search_similar(embedding=text_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe,
-                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where)
+                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where, after=after)
     except Exception as e:
         logger.error(f"Error in text search: {e}")
-        return []
+        return [] if after is None else _no_page()
 
 
 def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: int = 10, *,
                       filters: Optional[Sequence[str]] = None, min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                       distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                      where: Optional[dict] = None) -> List[Dict]:
+                      where: Optional[dict] = None, after: Optional[str] = None):
     """Search using both image and text with a weighted combination (main.py:829-867); weight_image is not
     clamped, as in the backend route."""
     try:
@@ -163,22 +190,22 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
         # normalise both, weighted sum, normalise again (main.py:852-860) — one GPU kernel
         combined_embedding = blend(image_embedding[None], text_embedding[None], weight_image)[0]
         return search_similar(embedding=combined_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe,
-                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where)
+                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where, after=after)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
-        return []
+        return [] if after is None else _no_page()
 
 
 def search_multimodal_batch(image_embeddings: np.ndarray, text_embeddings: np.ndarray, weight_image: float = 0.5,
                             limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                             min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                             distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                            where: Optional[dict] = None) -> List[List[Dict]]:
+                            where: Optional[dict] = None, after: Optional[Sequence[Optional[str]]] = None):
     """BASELINE config 4: a batch of (image, text) embedding pairs, blended and searched in one pass."""
     try:
         return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit, filters=filters,
                                     min_similarity=min_similarity, n_probe=n_probe, distinct_similarity=distinct_similarity,
-                                    within_ids=within_ids, where=where)
+                                    within_ids=within_ids, where=where, after=after)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []

@@ -6,7 +6,7 @@ compiler's resource figures (csrc/*.resources.txt) of an OLD and a NEW build.
     usage: python tools/codeobj_diff.py OLD/csrc NEW/csrc      (both built by `make -C .../csrc`; no GPU needed)
 
 Kernels are matched by demangled name through RENAMES (old -> new, for kernels whose template or argument lists changed);
-the match must be a bijection over all kernels of an object. Padding behind a kernel's last instruction (zeros, or s_nop behind
+the match must be a bijection over all kernels of an object. Padding behind a kernel's last instruction (zeros — a single zero dword included —, or s_nop behind
 an s_endpgm / s_branch) is not part of it. Kernels of the OLD build whose demangled name matches a pattern of
 REMOVED are reported as "removed, expected" and not counted (for a refactor that retires kernels). ONE normalisation: the 32-bit literal of the s_add_u32 behind
 an s_getpc_b64 is a PC-relative distance to read-only data and moves when anything earlier in the code object changes size;
@@ -20,6 +20,7 @@ import sys
 import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
+ZERO_DWORD = "v_cndmask_b32_e32 v0, s0, v0, vcc"   # what the disassembler prints for 0x00000000
 
 # (pattern on the OLD demangled name, replacement): for a refactor that changes kernels' template or argument lists. Empty
 # between such refactors: a stale rule maps kernels that kept their names onto names that do not exist.
@@ -58,9 +59,11 @@ def disassembly(csrc, obj):
             cur = kernels.setdefault(m.group(1), [])
         elif cur is not None and line.startswith("\t") and line.strip() != "...":   # ("...": zero padding behind a kernel's end)
             cur.append(line.split("//")[0].strip())
-    for ins in kernels.values():   # alignment padding behind a kernel's end comes as s_nop as well: it moves with the kernel's place in the object
+    # alignment padding behind a kernel's end comes as s_nop as well, or as ONE zero dword (which decodes as ZERO_DWORD; only a longer
+    # run of zeros prints as "..."): it moves with the kernel's place in the object
+    for ins in kernels.values():
         n = len(ins)
-        while n and ins[n - 1].startswith("s_nop"):
+        while n and (ins[n - 1].startswith("s_nop") or ins[n - 1] == ZERO_DWORD):
             n -= 1
         if n and ins[n - 1].split()[0] in ("s_endpgm", "s_branch"):
             del ins[n:]
