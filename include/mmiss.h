@@ -173,6 +173,12 @@ int mmiss_encoder_calibration_set(mmiss_encoder* enc, const float* mu, int64_t n
  * (passed as void*; NULL = the legacy default stream) and return without synchronising unless an
  * input or output lives in host memory. Changing the stream waits for the work the handle's LAST call left on the
  * stream being left (its workspaces are reused), not for anything else the caller has queued there since.
+ * The same rule holds for every call that writes state a queued encode may still read: mmiss_encoder_set_weight,
+ * mmiss_encoder_finalize, mmiss_encoder_calibrate, mmiss_encoder_calibration_set / _clear (and the debug tap switch where
+ * it forces the workspaces to be reallocated) first wait, on the host, for the handle's last call that returned with work
+ * queued on a caller's stream — for that call's work and for nothing else on the caller's stream. A call queued before
+ * such a change computes with the state it was queued under. (mmiss_encoder_set_precision / _set_tower_precision drain
+ * the handle's current stream.)
  * Threads: every call locks its handle, but the stream is handle state — a thread that sets the stream and then calls
  * must keep other threads off that handle in between (the Python wrappers hold a per-handle lock around the pair);
  * different handles never interact (several batches in flight: one encoder handle per host thread / stream,

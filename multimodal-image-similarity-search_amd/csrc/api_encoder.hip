@@ -730,6 +730,15 @@ int finish_call(mmiss_encoder* e, hipStream_t st, bool must_sync) {
     return MMISS_OK;
 }
 
+// (caller holds e->mu, the device is current) The rule of every handle call that writes state a queued encode may read — weights,
+// the calibration table, workspaces that are about to be reallocated, or another stream's turn at the workspaces: wait first for
+// the handle's last call that returned with work queued on a caller's stream. That call's work only (done_ev), never the rest
+// of the caller's stream.
+int wait_last_call(mmiss_encoder* e) {
+    if (e->async_pending) MM_HIP(hipEventSynchronize(e->done_ev));
+    e->async_pending = false;
+    return MMISS_OK;
+}
 
 // Resize + centre-crop images b0 .. b0+nb-1 of a raw RGB8 blob into dst_dev (uint8 [nb,S,S,3], device), on st.
 // `staged` != null: the chunk's byte range [its lo, its hi) of the host blob already sits at `staged` in HBM.
@@ -921,8 +930,7 @@ extern "C" int mmiss_encoder_set_stream(mmiss_encoder* enc, void* hip_stream, in
         // the handle's workspaces are shared by consecutive calls: wait for what the last call left on the stream being
         // left — that work only, not whatever else the caller has queued there since (calls on the own stream return drained)
         MM_TRY(mmiss_use_device(enc->device));
-        if (enc->async_pending) MM_HIP(hipEventSynchronize(enc->done_ev));
-        enc->async_pending = false;
+        MM_TRY(wait_last_call(enc));
     }
     enc->user_stream = next;
     enc->has_user_stream = next_user;
@@ -943,6 +951,7 @@ extern "C" int mmiss_encoder_set_weight(mmiss_encoder* enc, const char* hf_key, 
     if (numel != s.rows * s.cols)
         MM_FAIL(MMISS_ERR_ARG, "weight %s: got %lld elements, expected %lld (%lld x %lld)", hf_key, (long long)numel,
                 (long long)(s.rows * s.cols), (long long)s.rows, (long long)s.cols);
+    MM_TRY(wait_last_call(enc));   // a queued encode still reads the buffer this tensor lands in
     hipStream_t st = enc->own_stream;
     const float* src = data;
     if (!mmiss_is_device_ptr(data)) {
@@ -983,6 +992,7 @@ extern "C" int mmiss_encoder_finalize(mmiss_encoder* enc) {
                 n_missing > 4 ? ", ..." : "");
     // fold LayerNorm1 / LayerNorm2 into the QKV / FC1 weights (ln_mode 2)
     MM_TRY(mmiss_use_device(enc->device));
+    MM_TRY(wait_last_call(enc));   // the folded weights are rebuilt on the own stream
     for (Tower* tw : {&enc->vis, &enc->txt}) {
         const int d = tw->hidden;
         for (LayerW& L : tw->L) {
@@ -1190,6 +1200,7 @@ extern "C" int mmiss_encoder_calibrate(mmiss_encoder* enc, const float* pixels, 
     if (B < 1 || B > maxb) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibrate: B = %d outside 1 .. max_batch_image = %d", B, maxb);
     if (!pixels) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibrate: pixels is null");
     MM_TRY(mmiss_use_device(enc->device));
+    MM_TRY(wait_last_call(enc));
     hipStream_t st = enc->stream();
     Tower& tw = enc->vis;
     MM_TRY(ensure_tower_ws(enc, tw, maxb, P));
@@ -1220,6 +1231,8 @@ extern "C" int mmiss_encoder_calibrate(mmiss_encoder* enc, const float* pixels, 
 extern "C" int mmiss_encoder_calibration_clear(mmiss_encoder* enc) {
     if (!enc) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_clear: enc is null");
     std::lock_guard<std::mutex> lk(enc->mu);
+    MM_TRY(mmiss_use_device(enc->device));
+    MM_TRY(wait_last_call(enc));
     enc->vis.calibrated = false;
     return MMISS_OK;
 }
@@ -1261,6 +1274,7 @@ extern "C" int mmiss_encoder_calibration_set(mmiss_encoder* enc, const float* mu
     const int64_t want = (int64_t)2 * tw.layers * d;
     if (n != want) MM_FAIL(MMISS_ERR_ARG, "mmiss_encoder_calibration_set: n = %lld, the table holds 2 * v_layers * v_hidden = %lld floats", (long long)n, (long long)want);
     MM_TRY(mmiss_use_device(enc->device));
+    MM_TRY(wait_last_call(enc));
     hipStream_t st = enc->stream();
     MM_TRY(ensure_calibration_bufs(enc));
     tw.calibrated = false;
@@ -1409,7 +1423,11 @@ extern "C" int mmiss_dbg_encoder_record_taps(mmiss_encoder* enc, int on) {
     std::lock_guard<std::mutex> lk(enc->mu);
     enc->record_taps = on != 0;
     // force workspace re-allocation with the tap buffer
-    if (on) { enc->vis.ws_batch = 0; enc->txt.ws_batch = 0; }
+    if (on) {
+        MM_TRY(mmiss_use_device(enc->device));
+        MM_TRY(wait_last_call(enc));
+        enc->vis.ws_batch = 0; enc->txt.ws_batch = 0;
+    }
     return MMISS_OK;
 }
 

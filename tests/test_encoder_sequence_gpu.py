@@ -11,7 +11,6 @@ tests/golden/encoder_sequence_parent.json holds, per case, what the commit BEFOR
 gave for the first poison call and the victim call after it: the profile (kernel, launches) and the sha256 of the victim's output
 bytes. The entry and the refactoring that came with it must change neither (cases added later have no record there).
 """
-import contextlib
 import hashlib
 import json
 import os
@@ -20,6 +19,7 @@ import numpy as np
 import pytest
 
 import encoder_sequence_cases as sc
+from encoder_handles import bits as _bits, cos as _cos, new_handle as _new_handle, options as _options, plan as _plan
 
 pytestmark = pytest.mark.gpu
 
@@ -36,45 +36,11 @@ def _close_handles():
     _HANDLES.clear()
 
 
-def _new_handle(shape, tower, precision, max_batch, calibrated=False):
-    import mmiss_amd  # noqa: F401
-    from mmiss_amd.encoder import ClipEncoder, ClipShape
-
-    s = sc.SHAPES[shape]
-    mi, mt = (max_batch, 8) if tower == "vision" else (8, max_batch)
-    enc = ClipEncoder(ClipShape.from_any(s), max_batch_image=mi, max_batch_text=mt)
-    if precision == "fp8":
-        if tower == "vision":
-            enc.set_precision("fp8")
-        else:
-            enc.set_tower_precision("text", "fp8")
-    W = sc.weights(shape)
-    used, ignored = enc.load_state_dict(W)
-    assert ignored == 0 and used == len(W)
-    if calibrated:   # a table as mmiss_encoder_calibrate would leave it: a constant per channel of every LayerNorm output
-        g = np.random.Generator(np.random.Philox(key=[20251019, 6]))
-        enc.set_calibration((0.2 * g.standard_normal((2 * s.v_layers, s.v_hidden))).astype(np.float32))
-    return enc
-
-
 def _shared_handle(case):
     key = (case.shape, case.tower, case.precision, case.max_batch, case.calibrated)
     if key not in _HANDLES:
         _HANDLES[key] = _new_handle(*key)
     return _HANDLES[key]
-
-
-@contextlib.contextmanager
-def _options(opts):
-    from mmiss_amd import _lib
-
-    try:
-        for k, v in opts:
-            _lib.set_option(k, v)
-        yield
-    finally:
-        for k, _ in opts:
-            _lib.set_option(k, sc.OPTION_DEFAULTS[k])
 
 
 def _expected_kernels(plan, s, tower, rows):
@@ -140,18 +106,6 @@ def _check_names(what, prof, expected):
     assert must <= names and not (never & names), f"{what}: missing {sorted(must - names)}, unexpected {sorted(never & names)} in {sorted(names)}"
 
 
-def _plan(enc, case, call, T=0):
-    """The plan of one chunk, with the call's pinned fields asserted (the caller holds the call's options)."""
-    from mmiss_amd import _lib
-
-    tower = _lib.MMISS_TOWER_VISION if case.tower == "vision" else _lib.MMISS_TOWER_TEXT
-    plan = _lib.encoder_plan(enc._h, tower, call.B, T)
-    for k, v in call.expect:
-        assert plan[k] == v, f"{case.name} {call.kind} B={call.B}: plan {k} = {plan[k]!r}, the case wants {v!r} ({plan})"
-    assert plan["prune"] == 1, (case.name, plan)
-    return plan
-
-
 def _run(enc, case, call, x):
     """One call of the case on `enc`: the plan asserted before, the kernel names after. Returns the embeddings, the plan and the
     profile. Text: encode_text trims the matrix itself (trim_padding = call.trim); the plan is asked for the trimmed length."""
@@ -168,14 +122,6 @@ def _run(enc, case, call, x):
         out, prof = _profiled(lambda: enc.encode_image(x) if case.tower == "vision" else enc.encode_text(x, trim_padding=call.trim))
     _check_names(f"{case.name} {call.kind}", prof, [_expected_kernels(plan, s, case.tower, rows)])
     return out, plan, prof
-
-
-def _cos(a, b):
-    return (a * b).sum(-1) / (np.linalg.norm(a, axis=-1) * np.linalg.norm(b, axis=-1))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _launches(prof):
