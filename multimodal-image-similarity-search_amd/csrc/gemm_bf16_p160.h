@@ -23,12 +23,22 @@
 //     4-byte-per-lane filler into a dump area) and two per W slot — 7 per K-tile on every wave, so one counted wait serves all.
 //   * one tile per workgroup: the bf16 rows it adds to (its own output rows, 80 KB) are fetched UNDER the K loop, by the two
 //     stagings that have no K-tile left to fetch (issued during K-tiles nt - 2 and nt - 1; they used to wrap round and re-read
-//     K-tiles 0 and 1 for nobody) — same instructions, other descriptor and offsets — into the LDS slots those fill, behind the
-//     final vmcnt(0) and barrier that were always there; the epilogue reads them from LDS in the accumulator layout. Nothing
+//     K-tiles 0 and 1 for nobody) — same instructions, other descriptor and offsets — into the LDS slots those fill; a wave
+//     reads back only pieces it issued itself, so its own waits cover them (the first staging: the K loop's last vmcnt(7);
+//     the second: one vmcnt(0) in front of the wave's first output store), and the barrier behind the loop, which was always
+//     there, only frees the last fragment buffer. The epilogue reads them from LDS in the accumulator layout. Nothing
 //     of them is older than K-tile 0's pieces: they used to be 24 register loads in front of the prologue, which the
 //     prologue's first counted wait had to sit out (vector-memory operations retire in order) and which held 40 VGPRs
 //     through the loop. Only the bias (1 KB) is still requested ahead. The epilogue's transpose patches lie over the one
 //     staging buffer those two stagings do not fill, (nt - 1) % 3 (the patch-embedding GEMM: buffer 0).
+//   * the residual epilogue is fully exposed (one tile per workgroup, all 240 enter it together), so it is written for its
+//     instruction count (profiles/gemm_p160_epilogue.txt: 1102 -> 759 instructions behind the last MFMA, 52 -> 16 waits). The
+//     row statistics were 60 % of it: their eight-lane sums are DPP adds (no ds_bpermute, no LDS wait), two rows' four chains
+//     interleaved; statistics and rows leave through buffer stores whose per-lane offsets are fixed per tile (block steps
+//     are scalar), the statistics predicated by the descriptor's range check in place of ten exec-mask branches. Two
+//     patches per wave alternate, so block j + 1 is packed and written while block j's read-back is on its way, and blocks
+//     0..2 start on the first late staging while the second is still in flight (what each block reads: at the epilogue).
+//     The output rows are stored sc1 (written through): nothing is left dirty in the L2s for the kernel's end.
 //   * the patch-embedding GEMM straight from the f32 pixels (MMISS_EPI_PATCH_PIX_F32): its A operand is the [B,3,S,S] image,
 //     not an im2col copy. Tile row r is patch (img, py, px), K index k is (c, ky, kx), so a 64-wide K-tile of a row is 64 / P
 //     pixel-row segments of P floats. The A slot's 8-row pieces keep their owners and their swizzle; a lane fetches 16 bytes of the K-tile's
@@ -50,6 +60,42 @@
 #define G160_BUF (G160_A_BYTES + 2 * G160_W_BYTES)   // one K-tile: A | W n0 | W n1
 #define G160_DUMP (3 * G160_BUF)            // 8 waves x 256 B: where the 4-byte filler pieces land
 #define G160_LDS (G160_DUMP + 2048)         // 161 792 B of the CU's 163 840
+
+// Four values per lane, each added up over the eight lanes that share lane >> 3, by DPP adds instead of LDS permutes: xor 1 and
+// xor 2 within the quad (partner's + own: what v += __shfl_xor(v, 1 / 2) gives, x + y and y + x being the same bits), after
+// which a quad's four lanes hold one value, so the xor 4 step may take any lane of the other quad: the half-row mirror, lane l
+// of the eight <- lane 7 - l. Written as instructions because the compiler, which pairs the sums into packed adds, keeps a
+// v_mov_b32_dpp and two copies in front of every one of them. A DPP source must have been written at least two instructions
+// earlier: the leading s_nop covers whatever wrote the inputs, the four independent chains cover one another. The compiler
+// sees none of this inside the asm. What it ASSUMES of the caller: no VALU instruction writes EXEC (v_cmpx, v_readlane-style
+// masks) within five instructions in front of the call — a DPP instruction needs five wait states behind such a write. The
+// epilogue calls it from straight-line code under the full exec mask; anyone who puts it behind an exec-masked branch
+// makes the leading wait s_nop 4.
+__device__ __forceinline__ void g160_row_sum8(float& a, float& b, float& c, float& d) {
+#define G160_DPP4(ctrl)                                              \
+    "v_add_f32_dpp %0, %0, %0 " ctrl " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_add_f32_dpp %1, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_add_f32_dpp %2, %2, %2 " ctrl " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_add_f32_dpp %3, %3, %3 " ctrl " row_mask:0xf bank_mask:0xf\n\t"
+    asm("s_nop 1\n\t" G160_DPP4("quad_perm:[1,0,3,2]") G160_DPP4("quad_perm:[2,3,0,1]") G160_DPP4("row_half_mirror")
+        : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+#undef G160_DPP4
+}
+
+// (sum, sum of squares) of a lane's eight stored bf16 values, in gemm_epilogue's order. Every product and every sum is
+// rounded on its own, as the compiler has always built this loop: a contraction into FMAs, which it is otherwise free to
+// choose with the code around the loop, would change the statistics' bits.
+__device__ __forceinline__ void g160_row_part(const u32x4& pk, float& rs, float& rq) {
+#pragma clang fp contract(off)
+    rs = 0.f;
+    rq = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float a = __uint_as_float(pk[e] << 16), b = __uint_as_float(pk[e] & 0xFFFF0000u);
+        rs += a + b;
+        rq += a * a + b * b;
+    }
+}
 
 // EPI: MMISS_EPI_BIAS_RESID_BF16 (the residual GEMMs) or MMISS_EPI_PATCH_F32 (the patch-embedding GEMM: f32 rows scattered to
 // item * tokens + 1 + patch with the position row added, gemm_bf16.h gemm_epilogue's contract; no bias, no residual).
@@ -124,7 +170,7 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
 
     // ---- the old rows of the residual GEMMs (the bf16 rows this workgroup adds to: its own output rows, nobody else touches
     // them) ride in the two stagings that have no K-tile left to fetch — the ones issued during K-tiles nt - 2 and nt - 1, into
-    // buffers nt % 3 and (nt + 1) % 3 — and land behind the final vmcnt(0) and barrier that those stagings always had. Every
+    // buffers nt % 3 and (nt + 1) % 3 — and land behind the fetching wave's own waits (the epilogue: vmcnt(7), then vmcnt(0)). Every
     // wave fetches the rows of ITS OWN 80 x 64 block, as pieces of 16 rows x 64 bytes (32 columns): lane l reads 16 bytes of row
     // l >> 2, chunk (l & 3) ^ (l >> 4) — the four rows that share a 64-byte quarter of the 256-byte bank row hold a column chunk
     // at four different places, so the epilogue's 8-byte reads in the accumulator layout (16 rows x 2 half chunks per 32 lanes)
@@ -352,20 +398,17 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
     }
     }
     if (wm == 0) p256s_barrier();   // (the upper half's last barrier: the lower half is still one behind)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last two stagings (old rows / wrap-around) have landed ...
-    p256s_barrier();                // ... on every wave, and every wave has read its last fragments: the buffers are free
-    // the epilogue's transpose patches: the residual GEMMs' old rows sit in buffers nt % 3 and (nt + 1) % 3 now, so their
-    // patches lie over the third one, (nt - 1) % 3, the last one read; the patch-embedding GEMM keeps buffer 0
-    const int free_buf = RESID ? ((nt + 2) % 3) * G160_BUF : 0;
 
     if constexpr (PATCH) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last two stagings (wrap-around) have landed ...
+        p256s_barrier();                // ... on every wave, and every wave has read its last fragments: the buffers are free
         // f32 rows: 16 rows x 32 columns at a time through the wave's 2 KB patch (16-byte chunks XOR-swizzled by the row), read back
         // as whole 128-byte row segments; patch row m of the GEMM is token 1 + m % p0 of item m / p0, the position row is added
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));
         const int efr = lane_e & 15, efg = lane_e >> 4;
         const int rrow = lane_e >> 3, rchunk = lane_e & 7;
-        char* patch = smem + free_buf + wave * 2048;
+        char* patch = smem + wave * 2048;   // (buffer 0)
         float* outp = reinterpret_cast<float*>(ep.out);
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
@@ -394,78 +437,118 @@ __global__ __launch_bounds__(512, 2) void gemm160p_kernel(const __bf16* __restri
         }
     }
     // ---- epilogue of MMISS_EPI_BIAS_RESID_BF16 (gemm_bf16.h gemm_epilogue: same arithmetic, same statistics, bit for bit),
-    // per wave: 5 row blocks x 64 columns through the wave's 2 KB transpose patch, whole 128-byte row segments per store
+    // per wave: 5 row blocks x 64 columns through the wave's two 2 KB transpose patches, whole 128-byte row segments per store.
+    //
+    // What a block reads of the old rows, and who fetched it (G160_NEXT_KTILE, G160_STAGE_A / _W): block 0 = pieces (0,0), (0,1)
+    // = the first two A operations of the FIRST late staging, at a_dst and a_dst + 8 KB of buffer nt % 3; blocks 1 and 2 =
+    // that staging's W n0 / W n1 operations, at w_dst and w_dst + 1 KB of the two W slots; blocks 3 and 4 = the W n0 / W n1
+    // operations of the SECOND staging, same places in buffer (nt + 1) % 3. a_dst and w_dst are the wave's own: a wave reads
+    // only pieces it issued itself, so its own counted wait is all it needs. The K loop's last wait (vmcnt(7), phase 1 of
+    // K-tile nt - 1) has already retired the first staging; blocks 0..2 start behind it and the barrier that frees the last
+    // fragment buffer, while the second staging's seven operations are still in flight. The wait for those, vmcnt(0), stands
+    // in front of the wave's FIRST output store: stores count in vmcnt too and are not ordered against loads, so no counted
+    // wait could be had behind one.
     if constexpr (RESID) {
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));
         const int efr = lane_e & 15, efg = lane_e >> 4;
         const int rrow = lane_e >> 3, rchunk = lane_e & 7;
-        const __amdgpu_buffer_rsrc_t srdO = __builtin_amdgcn_make_buffer_rsrc(ep.out, 0, 0x7fffffff, 0x00020000);
-        char* patch = smem + free_buf + wave * 2048;
-        const int wr_off = efr * 128, wr_sw = 2 * (efr & 7);
-        const int col = bn * 256 + wn * 64 + rchunk * 8;
-        const int dump_row = M - 1;
         // the old rows, out of the slots the last two stagings filled, in the accumulator layout: 8 bytes per lane and 16 x 16 block
         u32x2 resid[5][4];
-        {
-            const char* const st0 = smem + (nt % 3) * G160_BUF;         // the staging issued during K-tile nt - 2
-            const char* const st1 = smem + ((nt + 1) % 3) * G160_BUF;   // ... during K-tile nt - 1
-            const int rd = efr * 64 + ((((efg >> 1) ^ (efr >> 2)) << 4) | ((efg & 1) << 3));
-#pragma unroll
-            for (int j = 0; j < 5; ++j)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int h = i >> 1;
-                    const char* piece = j == 0 ? st0 + a_dst + h * 8 * 1024
-                                               : (j < 3 ? st0 : st1) + G160_A_BYTES + ((j - 1) & 1) * G160_W_BYTES + w_dst + h * 1024;
-                    resid[j][i] = *reinterpret_cast<const u32x2*>(piece + (rd ^ ((i & 1) << 5)));
-                }
-        }
+        const char* const st0 = smem + (nt % 3) * G160_BUF;         // the staging issued during K-tile nt - 2
+        const char* const st1 = smem + ((nt + 1) % 3) * G160_BUF;   // ... during K-tile nt - 1
+        const int rd = efr * 64 + ((((efg >> 1) ^ (efr >> 2)) << 4) | ((efg & 1) << 3));
+#define G160_OLD_ROWS(j)                                                                                     \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                         \
+        const int h = i >> 1;                                                                               \
+        const char* piece = (j) == 0 ? st0 + a_dst + h * 8 * 1024                                           \
+                                     : ((j) < 3 ? st0 : st1) + G160_A_BYTES + (((j) - 1) & 1) * G160_W_BYTES + w_dst + h * 1024; \
+        resid[j][i] = *reinterpret_cast<const u32x2*>(piece + (rd ^ ((i & 1) << 5)));                       \
+    }
+        asm volatile("s_waitcnt vmcnt(7)" ::: "memory");   // the first late staging has landed (younger: the second one's seven)
+        G160_OLD_ROWS(0);
+        G160_OLD_ROWS(1);
+        G160_OLD_ROWS(2);
+        p256s_barrier();   // every wave has read its last fragments: buffer (nt - 1) % 3, which no late staging fills, is free
+        // two patches per wave, blocks alternate: block j + 1 is written while block j's read-back is on its way
+        char* const patch = smem + ((nt + 2) % 3) * G160_BUF + wave * 4096;
+        // a lane's four packed writes of a block (row efr, 8-byte unit (4 i + efg) ^ 2 (efr & 7)) and its two 16-byte reads
+        // (rows rrow and 8 + rrow, chunk rchunk ^ rrow): per-lane offsets fixed for the tile, block and half are immediates
+        const int wr0 = efr * 128 + ((efg ^ (2 * (efr & 7))) << 3);
+        const int wr[4] = {wr0, wr0 ^ 32, wr0 ^ 64, wr0 ^ 96};
+        const int rdp = rrow * 128 + ((rchunk ^ rrow) << 4);
+        // output rows: the lane's 16 bytes of rows row0 + rrow + 8 k, k = 0..9; row k is valid while 8 k < lim, every other
+        // one goes to the dump row M - 1
+        const int row0 = bm * 160 + wm * 80, col0 = bn * 256 + wn * 64;
+        const __amdgpu_buffer_rsrc_t srdO = __builtin_amdgcn_make_buffer_rsrc(ep.out, 0, 0x7fffffff, 0x00020000);
+        const int vo0 = ((row0 + rrow) * ep.ldo + col0 + rchunk * 8) * 2;
+        const int vo_dump = ((M - 1) * ep.ldo + col0 + rchunk * 8) * 2;
+        const int ostep = 8 * ep.ldo * 2;
+        const int lim = ep.m_valid - row0 - rrow;
+        // statistics [row][ldo / 64][2]: a descriptor that ends with the last valid row (no records without stats_out) drops
+        // the pad rows' stores, and the seven lanes of a row that do not store start beyond any record. Deliberately without
+        // a branch on stats_out: without statistics the sums are still computed and their ten stores dropped by the empty
+        // descriptor (not timed: the headline step's 22 launches all ask for statistics), which keeps the epilogue one straight line
+        const int mv = ep.m_valid < M ? ep.m_valid : M;
+        const __amdgpu_buffer_rsrc_t srdS =
+            __builtin_amdgcn_make_buffer_rsrc(ep.stats_out, 0, ep.stats_out ? mv * (ep.ldo >> 6) * 8 : 0, 0x00020000);
+        const int so0 = rchunk == 0 ? ((row0 + rrow) * (ep.ldo >> 6) + (col0 >> 6)) * 8 : (int)0x80000000u;
+        const int sstep = 8 * (ep.ldo >> 6) * 8;
+// block j: old rows + product + bias, rounded, packed, into patch j & 1
+#define G160_BLOCK(j)                                                                                        \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                         \
+        const f32x4 v = acc[i][j] + bias[i];                                                                \
+        float y[4];                                                                                         \
+        y[0] = __uint_as_float(resid[j][i][0] << 16) + v[0];                                                \
+        y[1] = __uint_as_float(resid[j][i][0] & 0xFFFF0000u) + v[1];                                        \
+        y[2] = __uint_as_float(resid[j][i][1] << 16) + v[2];                                                \
+        y[3] = __uint_as_float(resid[j][i][1] & 0xFFFF0000u) + v[3];                                        \
+        u32x2 pk;                                                                                           \
+        pk[0] = pack_bf16x2(y[0], y[1]);                                                                    \
+        pk[1] = pack_bf16x2(y[2], y[3]);                                                                    \
+        *reinterpret_cast<u32x2*>(patch + ((j) & 1) * 2048 + wr[i]) = pk;                                   \
+    }
+        G160_BLOCK(0);
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x4 v = acc[i][j] + bias[i];
-                float y[4];
-                y[0] = __uint_as_float(resid[j][i][0] << 16) + v[0];
-                y[1] = __uint_as_float(resid[j][i][0] & 0xFFFF0000u) + v[1];
-                y[2] = __uint_as_float(resid[j][i][1] << 16) + v[2];
-                y[3] = __uint_as_float(resid[j][i][1] & 0xFFFF0000u) + v[3];
-                u32x2 pk;
-                pk[0] = pack_bf16x2(y[0], y[1]);
-                pk[1] = pack_bf16x2(y[2], y[3]);
-                *reinterpret_cast<u32x2*>(patch + wr_off + (((i * 4 + efg) ^ wr_sw) << 3)) = pk;
-            }
+            // block j's writes before its reads; block j - 1's reads before block j + 1's writes (the same patch)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            u32x4 pk[2];
+#pragma unroll
+            for (int rh = 0; rh < 2; ++rh) pk[rh] = *reinterpret_cast<const u32x4*>(patch + (j & 1) * 2048 + rh * 1024 + rdp);
+            if (j == 0) { G160_BLOCK(1); }
+            if (j == 1) { G160_BLOCK(2); }
+            if (j == 2) { G160_BLOCK(3); }
+            if (j == 3) { G160_BLOCK(4); }
+            if (j == 0) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the second late staging has landed (no store issued yet)
+                G160_OLD_ROWS(3);
+                G160_OLD_ROWS(4);
+            }
+            // rows 2 j and 2 j + 1 of the lane's ten, and the statistics of what was STORED (the rounded rows are the residual
+            // stream from here on)
+            float rs[2], rq[2];
 #pragma unroll
             for (int rh = 0; rh < 2; ++rh) {
-                const int row = rh * 8 + rrow;
-                const u32x4 pk = *reinterpret_cast<const u32x4*>(patch + row * 128 + (((2 * rchunk) ^ (2 * (row & 7))) << 3));
-                const int m = bm * 160 + wm * 80 + j * 16 + row;
-                const int vo = ((m < ep.m_valid ? m : dump_row) * ep.ldo + col) * 2;
-                __builtin_amdgcn_raw_buffer_store_b128(pk, srdO, vo, 0, 0);
-                if (ep.stats_out) {  // of what was STORED (the rounded rows are the residual stream from here on)
-                    float rs = 0.f, rq = 0.f;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float a = __uint_as_float(pk[e] << 16), b = __uint_as_float(pk[e] & 0xFFFF0000u);
-                        rs += a + b;
-                        rq += a * a + b * b;
-                    }
-                    rs += __shfl_xor(rs, 1); rq += __shfl_xor(rq, 1);
-                    rs += __shfl_xor(rs, 2); rq += __shfl_xor(rq, 2);
-                    rs += __shfl_xor(rs, 4); rq += __shfl_xor(rq, 4);
-                    if (rchunk == 0 && m < ep.m_valid) {
-                        float* so = ep.stats_out + ((size_t)m * (ep.ldo >> 6) + ((bn * 256 + wn * 64) >> 6)) * 2;
-                        so[0] = rs;
-                        so[1] = rq;
-                    }
-                }
+                const int k = 2 * j + rh;
+                // sc1: written through. All 240 workgroups store their 80 KB at the same time and end right after; plain
+                // stores leave all of it dirty in the L2s for the write-back at the kernel's end, these go out while the
+                // other waves still compute (profiles/gemm_p160_epilogue.txt, section 3: isolated, out-projection 19.5 ->
+                // 18.1 us, FC2 51.8 -> 51.0, nt stores no gain; the step 2.621 -> 2.592 ms). The persistent 256 x 256 kernel,
+                // whose stores are spread over its run, found the three policies equal (profiles/gemm_p256_r03.txt)
+                __builtin_amdgcn_raw_buffer_store_b128(pk[rh], srdO, 8 * k < lim ? vo0 + k * ostep : vo_dump, 0, 16);
+                g160_row_part(pk[rh], rs[rh], rq[rh]);
             }
-            __builtin_amdgcn_wave_barrier();  // the patch is rewritten by the next j
+            g160_row_sum8(rs[0], rq[0], rs[1], rq[1]);
+#pragma unroll
+            for (int rh = 0; rh < 2; ++rh)
+                __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(rs[rh]), __float_as_uint(rq[rh])}, srdS,
+                                                      so0 + (2 * j + rh) * sstep, 0, 0);
         }
+#undef G160_OLD_ROWS
+#undef G160_BLOCK
     }
 }
 #undef G160_BLDS
