@@ -663,6 +663,68 @@ int mmiss_index_query_after(mmiss_index* idx, const float* queries, int32_t Q, i
                             const uint64_t* require, const uint64_t* exclude, int64_t* out_labels, float* out_dist,
                             int32_t* out_count, int64_t* out_remaining);
 
+/* ---------------------------------------------------------------- grouped search --------------- */
+/*
+ * The exact k nearest GROUPS of a query, one hit each: one best picture per folder, per upload batch, per k-means cluster. What
+ * Qdrant calls group_by, Milvus grouping search and Elasticsearch collapse. The reference ingests whole folders
+ * (POST /api/upload-folder, backend/app/main.py:1110) and returns collection.query's list as it comes (main.py:761-782), so a
+ * folder of 300 holiday shots fills every slot of a search.
+ *
+ * Every row carries an int32 GROUP with the lifecycle of the tag word: -1 ("no group: the row is a group of its own") when the
+ * row is added; update keeps it; stable removal keeps the survivors'; clear and load reset it. The file format does not hold it.
+ * A group id obeys -1 <= group < MMISS_MAX_GROUPS. The table of the exhaustive route (below) has one slot per id below the largest
+ * id set since the last clear or load, so ids should be dense.
+ */
+#define MMISS_MAX_GROUPS (1 << 24)
+/* labels: int64 [n], groups: int32 [n] (host or device). A label not in the index, or a group outside -1 .. MMISS_MAX_GROUPS - 1
+ * -> MMISS_ERR_ARG and nothing is changed. A label given twice keeps its last value. */
+int mmiss_index_set_groups(mmiss_index* idx, const int64_t* labels, const int32_t* groups, int64_t n);
+/* out: int32 [n] (host or device), the groups of `labels`; a label not in the index -> MMISS_ERR_ARG */
+int mmiss_index_get_groups(mmiss_index* idx, const int64_t* labels, int64_t n, int32_t* out);
+/*
+ * Contract.
+ *   - R(q) is the complete ranking of the rows that q admits (require / exclude as mmiss_index_query_filtered, null = 0) and that
+ *     have a direction, in (distance, label) order with mmiss_index_query's distance bits.
+ *   - The group of a row is its GROUP value. A row with -1 is a group of its own.
+ *   - A group's head is its first row in R(q).
+ *   - The result is the first k heads in R(q)'s order. The call never depends on `pool`: it is exact at any group size.
+ *   - out_labels / out_dist [Q, k] hold the heads. Slots behind the count hold -1 / +inf.
+ *   - out_group [Q, k] holds the head's GROUP. It is -1 for an ungrouped row and behind the count.
+ *   - out_count[q] = min(k, number of groups with at least one admitted row that has a direction). It is 0 for a query without a
+ *     direction.
+ *   - out_route[q] (may be null) is 0 when the list walk answered q, and 1 when q took the exhaustive route.
+ * Consequences:
+ *   - With every row ungrouped, or every row in a group of its own, the labels, distance bits and counts equal
+ *     mmiss_index_query_filtered's.
+ *   - With all rows in one group, the result is one entry: the top-1.
+ *   - The outputs do not depend on `pool`.
+ *
+ * How: the flat / filtered query at k = pool gives each query's exact ranked list (pool = 0: min(2040, max(8 k, 64))); one kernel
+ * walks all lists and keeps the first entry of every group. A walk that found k heads, or whose list ended before the pool did,
+ * has the answer (route 0). Any other query — one group owns the pool: a folder of 5000 near rows in front of a pool of 2040 —
+ * takes the exhaustive route in the same call (route 1): every admitted row gets its canonical distance directly, the minimum
+ * (distance, row) key per group is kept in a table of one slot per group id and one per ungrouped row, and the k smallest slots
+ * are selected. `pool` only moves queries between the routes.
+ *
+ * 1 <= k <= 2040 (above: MMISS_ERR_UNSUPPORTED). pool = 0, or k <= pool <= 2040: pool < k is MMISS_ERR_ARG, pool > 2040 is
+ * MMISS_ERR_UNSUPPORTED. Q >= 1. A missing pointer (out_route excepted) is MMISS_ERR_ARG. queries float32 [Q, dim] and require /
+ * exclude uint64 [Q] are each host or device memory; the outputs (out_labels int64 [Q, k], out_dist float32 [Q, k], out_group int32
+ * [Q, k], out_count int32 [Q], out_route int32 [Q]) are all host or all device memory.
+ *
+ * The call locks the handle, runs on its current stream, returns with its work finished, fails with MMISS_ERR_STATE while a
+ * _begin query is open, checks every argument before it writes anything, and neither needs nor touches a partition. The list stage
+ * counts in the guard counters exactly as mmiss_index_query / _filtered at k = pool do; the walk and the exhaustive route count
+ * nothing. The exhaustive route reads each row once per block of up to 16 of its queries and takes its queries in chunks that keep
+ * the tables under 512 MB; a large batch on that route is bound by the scan's fp64 arithmetic.
+ *
+ * Not offered: more than one row per group (expand a group with mmiss_index_query_subset over its labels); nprobe; a list or a
+ * cursor combined with grouping; ShardedIndex; an approximate matrix-core first pass for the exhaustive route.
+ */
+int mmiss_index_query_grouped(mmiss_index* idx, const float* queries, int32_t Q, int32_t k, int32_t pool,
+                              const uint64_t* require, const uint64_t* exclude,
+                              int64_t* out_labels, float* out_dist, int32_t* out_group, int32_t* out_count,
+                              int32_t* out_route /* may be null */);
+
 /* ---------------------------------------------------------------- glue kernels ----------------- */
 /*
  * out[q] = normalize(w * normalize(img[q]) + (1-w) * normalize(txt[q])), float32 [Q,dim].

@@ -256,6 +256,16 @@ int mmiss_dbg_index_distinct_plan(struct mmiss_index* ix, int32_t Q, int32_t* ou
  *   such block   [14], [15] the query block the first / the last chunk runs with: [7] halved while half of it still holds the
  *   chunk's queries */
 int mmiss_dbg_index_subset_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int64_t n_cand, int32_t* out);
+/* How a grouped call (mmiss_index_query_grouped) would run on the index as it stands and under the options as they stand
+ * (probe_scratch_kb), if Q >= 1 of its queries took the exhaustive route, at this k (1 .. 2040) and pool (0, or k .. 2040):
+ * plan_grouped (csrc/index_plans.h), evaluated on the host. Launches nothing, changes nothing. out is a HOST int32 [16]:
+ *   [0] the pool of the list stage (pool 0 resolved)   [1] threads of the walk's workgroup (one per query, one launch)   [2] its
+ *   LDS bytes   [3] table: slots per query of the exhaustive route, G + rows (G: the largest group id set since the last clear or
+ *   load, + 1)   [4] segment size of the selection (keys)   [5] levels: segment_topk launches per chunk, the last included
+ *   [6], [7] keys per query of the two key areas   [8] queries per chunk   [9] chunks   [10] query block of the scan   [11] its
+ *   dynamic LDS bytes   [12] share: rows per scan workgroup   [13] splits: scan workgroups per query block   [14], [15] the query
+ *   block the first / the last chunk runs with */
+int mmiss_dbg_index_grouped_plan(struct mmiss_index* ix, int32_t Q, int32_t k, int32_t pool, int32_t* out);
 /* How a continuation call (mmiss_index_query_after) of Q >= 1 queries, this k (1 .. 2040) and a list of n_cand labels (n_cand < 0:
  * no list, the dense scan over every row) would run on the index as it stands and under the options as they stand: plan_after
  * (csrc/index_plans.h), evaluated on the host. Launches nothing, changes nothing. out is a HOST int32 [16], laid out as

@@ -112,6 +112,9 @@ SIGNATURES = {
     "mmiss_index_query_distinct": (_I, [_P, _P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "mmiss_index_query_subset": (_I, [_P, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "mmiss_index_query_after": (_I, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "mmiss_index_set_groups": (_I, [_P, _P, _P, _I64]),
+    "mmiss_index_get_groups": (_I, [_P, _P, _I64, _P]),
+    "mmiss_index_query_grouped": (_I, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "mmiss_blend": (_I, [_I, _P, _P, _P, C.c_double, _I32, _I32, _P]),
     "mmiss_merge_topk": (_I, [_I, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mmiss_prof_enable": (_I, [_I]),
@@ -164,6 +167,7 @@ SIGNATURES = {
     "mmiss_dbg_index_distinct_plan": (_I, [_P, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_subset_plan": (_I, [_P, _I32, _I32, _I64, C.POINTER(_I32)]),
     "mmiss_dbg_index_after_plan": (_I, [_P, _I32, _I32, _I64, C.POINTER(_I32)]),
+    "mmiss_dbg_index_grouped_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_index_dense_plan": (_I, [_P, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_encoder_plan": (_I, [_P, _I32, _I32, _I32, C.POINTER(_I32)]),
     "mmiss_dbg_gemm_split_time": (_I, [_I, _I, _I, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.POINTER(C.c_float)]),
@@ -326,6 +330,19 @@ def index_subset_plan(handle, Q: int, k: int, n_cand: int) -> dict:
     out = (_I32 * 16)()
     check(load().mmiss_dbg_index_subset_plan(handle, int(Q), int(k), int(n_cand), out))
     return dict(zip(SUBSET_PLAN_FIELDS, (int(v) for v in out)))
+
+
+GROUPED_PLAN_FIELDS = ("pool", "walk_threads", "walk_lds_bytes", "table", "segment", "levels", "stride0", "stride1",
+                       "queries_per_chunk", "chunks", "query_block", "lds_bytes", "share", "splits", "first_chunk_block",
+                       "last_chunk_block")
+
+
+def index_grouped_plan(handle, Q: int, k: int, pool: int = 0) -> dict:
+    """mmiss_dbg_index_grouped_plan as a dict: how a grouped call of this k and pool would run on the index `handle` as it stands
+    (and under the option probe_scratch_kb as it stands) if Q of its queries took the exhaustive route. Nothing is launched."""
+    out = (_I32 * 16)()
+    check(load().mmiss_dbg_index_grouped_plan(handle, int(Q), int(k), int(pool), out))
+    return dict(zip(GROUPED_PLAN_FIELDS, (int(v) for v in out)))
 
 
 DENSE_PLAN_KERNELS = ("canonical_scan", "assign_resolve", "member_count", "assign_sizes", "assign_decide", "member_from_dist",

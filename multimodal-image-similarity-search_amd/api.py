@@ -109,6 +109,19 @@ def _ids_kw(fields) -> dict:
     return {"within_ids": list(dict.fromkeys(ids))}
 
 
+def _group_kw(fields) -> dict:
+    """The optional form field `group_by`, the name of a metadata field, as the keyword argument `group_by` of the search call
+    (one result per value of that field); absent: no argument at all (today's call). An empty name raises, and the route answers
+    as it answers a bad `limit`."""
+    raw = _first(fields, "group_by")
+    if raw is None:
+        return {}
+    name = str(raw).strip()
+    if not name:
+        raise ValueError("group_by must name a metadata field")
+    return {"group_by": name}
+
+
 def _after_kw(fields) -> dict:
     """The optional form field `after` as the keyword argument `after` of the search call: "" for the first page, else a
     continuation token (checked here: a malformed one raises, and the route answers as it answers a bad `limit`); absent: no
@@ -224,7 +237,8 @@ def create_app():
             image = _open(files, convert_all=True)
             limit = int(_first(fields, "limit", 10))
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
-                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields),
+                   **_group_kw(fields)}
             page = _after_kw(fields)
             model, processor = utils.load_clip_model()
             embedding_result = utils.generate_clip_embedding(image=image, model=model, processor=processor)
@@ -249,7 +263,8 @@ def create_app():
             query = fields["query"][0]
             limit = int(_first(fields, "limit", 10))
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
-                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields),
+                   **_group_kw(fields)}
             filters = fields.get("filters")
             page = _after_kw(fields)
             if not query.strip() and filters:
@@ -281,7 +296,8 @@ def create_app():
             weight_image = float(_first(fields, "weight_image", 0.5))  # not clamped, as in the backend route
             limit = int(_first(fields, "limit", 10))
             sim = {**_similarity_kw(fields, "min_similarity", "min_similarity"),
-                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields)}
+                   **_similarity_kw(fields, "distinct_similarity", "distinct_similarity"), **_ids_kw(fields),
+                   **_group_kw(fields)}
             page = _after_kw(fields)
             if page:
                 return _page(search.search_multimodal(image=image, query_text=fields["query"][0], weight_image=weight_image,

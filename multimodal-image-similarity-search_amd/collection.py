@@ -30,7 +30,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .index import MAX_POOL, FlatIndex, default_distinct_pool
+from .index import MAX_GROUPS, MAX_POOL, FlatIndex, default_distinct_pool
 
 logger = logging.getLogger("image-match")
 MAX_N_RESULTS = 2040  # mmiss_index_query's per-call limit on k
@@ -161,6 +161,12 @@ class FlatCollection:
         self._filter_bits: Dict[str, int] = {}
         self._filter_overflow: set = set()
         self._tag_dirty: set = set()
+        # grouped search: the metadata field the index's groups stand for, its values' dense ids (order of first appearance, by
+        # label), labels whose group the index does not have yet, rows per value (None: to be counted again)
+        self._group_field: Optional[str] = None
+        self._group_ids: Dict[tuple, int] = {}
+        self._group_dirty: set = set()
+        self._group_sizes: Optional[Dict[tuple, int]] = None
         self._lock = threading.RLock()         # 1 writer + readers (the reference has a background updater, main.py:410)
         self._persist_dir = persist_dir
         self._autosave = autosave
@@ -320,6 +326,8 @@ class FlatCollection:
         self._index_gen = int(blob.get("index_gen", 0))
         # the index file holds no tags (they load as 0): every row's tag is pushed again at the first filtered query
         self._filter_bits, self._filter_overflow, self._tag_dirty = {}, set(), set(self._labels)
+        # ... and no groups (they load as -1): the field is mapped and pushed again at the first grouped query
+        self._group_field, self._group_ids, self._group_dirty, self._group_sizes = None, {}, set(), None
         if self._dim is not None and self._labels:
             self._ensure_index(self._dim)
             self._index.load(self._index_path(self._index_gen))
@@ -388,6 +396,8 @@ class FlatCollection:
                 self._meta[lab] = dict(m) if m is not None else None
                 self._docs[lab] = d
             self._tag_dirty.update(labels.tolist())
+            self._group_dirty.update(labels.tolist())
+            self._group_sizes = None
             self._saved({"op": "add", "ids": ids, "metadatas": metadatas, "documents": documents}, emb)
 
     # ------------------------------------------------------------------ filtered search
@@ -485,6 +495,77 @@ class FlatCollection:
             cnt = within.sum(1).astype(np.int32)
         return labs, dist, cnt, dups
 
+    # ------------------------------------------------------------------ grouped search
+    @staticmethod
+    def _group_key(metadata, field: str):
+        """the value of `field` in a row's metadata as a dictionary key (1, 1.0, True and "1" are different groups), None when the
+        row has no such field"""
+        v = (metadata or {}).get(field)
+        return None if v is None else (type(v).__name__, v)
+
+    def _push_groups(self, field: str) -> None:
+        """Give the index the group of every dirty label (under the lock, at a grouped query); another field than the last one's
+        maps its values afresh and pushes every label. Labels are visited in label order, so a value's id is the order of its
+        first appearance. A row without the field is ungrouped (-1)."""
+        if field != self._group_field:
+            self._group_field, self._group_ids, self._group_sizes = field, {}, None
+            self._group_dirty = set(self._labels)
+        if not self._group_dirty:
+            return
+        labs = sorted(self._group_dirty)
+        groups = []
+        for lab in labs:
+            key = self._group_key(self._meta.get(lab), field)
+            if key is None:
+                groups.append(-1)
+                continue
+            gid = self._group_ids.get(key)
+            if gid is None:
+                if len(self._group_ids) >= MAX_GROUPS:
+                    raise ValueError(f"group_by: more than {MAX_GROUPS} different values of {field!r}")
+                gid = self._group_ids[key] = len(self._group_ids)
+            groups.append(gid)
+        self._index.set_groups(np.asarray(labs, dtype=np.int64), np.asarray(groups, dtype=np.int32))
+        self._group_dirty.clear()
+
+    def _group_counts(self, field: str) -> Dict[tuple, int]:
+        """stored rows per value of the field, from the host metadata; counted once per state of the collection"""
+        if self._group_sizes is None:
+            sizes: Dict[tuple, int] = {}
+            for lab in self._labels:
+                key = self._group_key(self._meta.get(lab), field)
+                if key is not None:
+                    sizes[key] = sizes.get(key, 0) + 1
+            self._group_sizes = sizes
+        return self._group_sizes
+
+    def _grouped_query(self, q: np.ndarray, k: int, field: str, filters: List[str], pool: Optional[int], max_distance=None):
+        """The k nearest groups of `field`, each by its best row (FlatIndex.query_grouped), among the rows answering "yes" to every
+        filter -> (labels [Q,k], distances [Q,k], counts [Q]). max_distance cuts the heads at the radius: they are sorted by
+        distance, and a group has a row within the radius exactly if its head is, so the cut is a prefix."""
+        Q = q.shape[0]
+        self._push_groups(field)
+        masks = {}
+        if filters:
+            self._push_tags()
+            over = [f for f in filters if f in self._filter_overflow]
+            if over:
+                raise ValueError(f"group_by cannot be combined with filter names past the {MAX_FILTER_BITS}th ({over[:3]}): "
+                                 "the host post-filter would change which image stands for a group")
+            if any(f not in self._filter_bits for f in filters):   # a name no row has ever answered admits nothing
+                return np.full((Q, k), -1, np.int64), np.full((Q, k), np.inf, np.float32), np.zeros((Q,), np.int32)
+            req = 0
+            for f in filters:
+                req |= 1 << self._filter_bits[f]
+            masks = {"require": np.uint64(req)}
+        pool = None if pool is None else min(max(int(pool), k), MAX_POOL)
+        labs, dist, _grp, cnt, _route = self._index.query_grouped(q, k, pool, **masks)
+        labs, dist, cnt = np.asarray(labs), np.asarray(dist), np.array(cnt, np.int32)
+        if max_distance is not None:
+            within = (dist <= np.float32(max_distance)) & (np.arange(k)[None, :] < cnt[:, None])
+            cnt = within.sum(1).astype(np.int32)
+        return labs, dist, cnt
+
     def _admitted_labels(self, ids, where) -> List[int]:
         """The labels `ids` (chroma ids; unknown ones are ignored; None: every row) and `where` (a metadata predicate, None: every
         row) admit, in label order."""
@@ -560,7 +641,7 @@ class FlatCollection:
     def query(self, query_embeddings=None, n_results: int = 10, include: Sequence[str] = ("metadatas", "documents", "distances"),
               filters: Optional[Sequence[str]] = None, max_distance: Optional[float] = None, n_probe: Optional[int] = None,
               distinct_distance: Optional[float] = None, pool: Optional[int] = None, ids=None, where: Optional[dict] = None,
-              after: Optional[Sequence[Optional[str]]] = None, **_unused) -> dict:
+              after: Optional[Sequence[Optional[str]]] = None, group_by: Optional[str] = None, **_unused) -> dict:
         """collection.query. filters: names of yes/no filters; when given, the result is the exact n_results nearest among the
         rows whose filter_results_json answers "yes" to every one of them (pre-filtering; see the module docstring).
         max_distance: a radius query (FlatIndex.query_radius) — only the rows within that cosine distance are returned, exactly,
@@ -592,9 +673,23 @@ class FlatCollection:
         between two pages are ranked as they stand. filters (masks; names past the 64th folded into the list), ids / where (the
         list) and max_distance combine and must be the same on every page; n_probe is ignored (the continuation is exact);
         distinct_distance raises ValueError. Without after nothing changes.
+        group_by: the n_results nearest GROUPS, one hit each (FlatIndex.query_grouped) — a group is the rows whose metadata field
+        `group_by` has the same value (a folder, an album, an upload batch, a cluster), a row without the field is a group of its
+        own; each group is represented by its nearest row, at any group size (one group holding the nearest 5000 rows costs a scan
+        of the index, not the result). The dict gains "groups" (per query and result: the field's value, None for a row without
+        the field) and "group_sizes" (the stored rows with that value, from the metadata; 1 for a row without the field). filters
+        combine (up to 64 names as masks; a name past the 64th raises ValueError), max_distance cuts the heads at the radius,
+        pool is how much of the ranking is walked before the scan takes over (it never changes the result); ids / where / after /
+        distinct_distance / n_probe raise ValueError. Without group_by nothing changes.
         Nothing is written, neither metadata nor journal."""
         if n_probe is not None and int(n_probe) < 1:
             raise ValueError(f"n_probe: at least 1, got {n_probe}")
+        if group_by is not None:
+            if not isinstance(group_by, str) or not group_by:
+                raise ValueError(f"group_by: the name of a metadata field expected, got {group_by!r}")
+            for name, given in (("ids", ids), ("where", where), ("after", after), ("distinct_distance", distinct_distance), ("n_probe", n_probe)):
+                if given is not None:
+                    raise ValueError(f"group_by cannot be combined with {name}")
         subset = ids is not None or where is not None
         if where is not None:
             check_where(where)
@@ -640,7 +735,9 @@ class FlatCollection:
                 if k > MAX_N_RESULTS:  # one mmiss_index_query call ranks at most 2040 rows per query: clamp, do not fail
                     logger.warning(f"n_results={n_results} clamped to {MAX_N_RESULTS}")
                     k = MAX_N_RESULTS
-                if subset:
+                if group_by is not None:
+                    labs, dist, cnt = self._grouped_query(q, k, group_by, filters, pool, max_distance)
+                elif subset:
                     labs, dist, cnt = self._subset_query(q, k, self._admitted_labels(ids, where), filters, max_distance)
                 elif distinct_distance is not None:
                     labs, dist, cnt, dups = self._distinct_query(q, k, filters, distinct_distance, pool, max_distance, n_probe)
@@ -666,6 +763,11 @@ class FlatCollection:
                 out["embeddings"] = [self._index.get(np.asarray(ls, dtype=np.int64)) for ls in rows]
             if distinct_distance is not None:
                 out["duplicates"] = [[] if dups is None else [int(x) for x in dups[qi, : int(cnt[qi])]] for qi in range(Q)]
+            if group_by is not None:
+                sizes = self._group_counts(group_by) if rows and any(rows) else {}
+                keys = [[self._group_key(self._meta.get(l), group_by) for l in ls] for ls in rows]
+                out["groups"] = [[None if key is None else key[1] for key in ks] for ks in keys]
+                out["group_sizes"] = [[1 if key is None else sizes.get(key, 0) for key in ks] for ks in keys]
             if cursors is not None:
                 out["remaining"] = [int(r) for r in rem]
                 out["next"] = [make_token(dist[qi, int(cnt[qi]) - 1], labs[qi, int(cnt[qi]) - 1]) if int(rem[qi]) > int(cnt[qi]) else None
@@ -810,6 +912,8 @@ class FlatCollection:
                         merged.update(m)  # chroma merges keys on update
                         self._meta[lab] = merged
                         self._tag_dirty.add(lab)
+                        self._group_dirty.add(lab)
+                        self._group_sizes = None
             if documents is not None:
                 for lab, d in zip(labs, _as_list(documents)):
                     self._docs[lab] = d
@@ -840,6 +944,8 @@ class FlatCollection:
                 self._meta.pop(l, None)
                 self._docs.pop(l, None)
                 self._tag_dirty.discard(l)
+                self._group_dirty.discard(l)
+            self._group_sizes = None
             self._saved({"op": "delete", "ids": ids})
 
     def peek(self, limit: int = 10) -> dict:

@@ -9,6 +9,7 @@
 #include "distinct_kernels.h"
 #include "subset_kernels.h"
 #include "after_kernels.h"
+#include "grouped_kernels.h"
 #include "gemm_bf16_256.h"
 #include "gemm_strip_p256.h"
 #include <algorithm>
@@ -18,6 +19,9 @@ static_assert(PLAN_SELECT_UNIT == SELECT_UNIT && PLAN_PROBE_SEG == PROBE_SEG, "i
 static_assert(PLAN_DISTINCT_THREADS == DISTINCT_THREADS && PLAN_DISTINCT_SLOTS == DISTINCT_SLOTS && PLAN_DISTINCT_MAX_POOL < DISTINCT_SLOTS,
               "index_plans.h repeats what distinct_kernels.h fixes");
 static_assert(PLAN_SUBSET_BLOCK_ROWS == SUBSET_BLOCK_ROWS, "index_plans.h repeats what subset_kernels.h fixes");
+static_assert(PLAN_GROUPED_THREADS == GROUPED_THREADS && PLAN_GROUPED_SLOTS == GROUPED_SLOTS && PLAN_GROUPED_MAX_POOL < GROUPED_SLOTS &&
+                  PLAN_GROUPED_WALK_LDS == GROUPED_WALK_LDS && PLAN_GROUPED_MAX_GROUPS == MMISS_MAX_GROUPS,
+              "index_plans.h repeats what grouped_kernels.h and mmiss.h fix");
 
 // The results of a query-like call of Q queries: `slots` labels and distances and a count per query, for some calls a total and
 // a flag per query. lab / tot / dist / cnt are where the kernels write them: the caller's device buffers, or a pinned host block
@@ -138,6 +142,17 @@ struct mmiss_index {
     // search after (mmiss_index_query_after): the caller's cursors and radii when they are host memory, the resolved cursors, the
     // remaining counts — one block (after_layout). The list, its compaction, the totals, masks and key areas are the subset call's
     DevBuf aft_cur;
+    // grouped search (mmiss_index_set_groups, mmiss_index_query_grouped): the GROUP of every row, -1 = a group of its own, as a
+    // host mirror beside tags_h; group_hwm = G, the largest group id set since the last clear or load, + 1. No kernel of any
+    // other call reads groups: the device copy ([count] int32) belongs to the grouped call, which uploads it when groups_dirty
+    // says the mirror changed (a set, an add, a removal, a clear, a load). Then the call's scratch: the list stage's lists, the
+    // outputs on their way to host buffers and the exhaustive route's [chunk, k] results, the flagged queries; the walk's flags
+    // arrive in a pinned block of its own. Totals, masks and key areas are the probed call's, as for the subset call.
+    std::vector<int32_t> groups_h;
+    int64_t group_hwm = 0;
+    bool groups_dirty = true;
+    DevBuf grp_col, grp_list, grp_out, grp_sel, grp_map;
+    PinBuf grp_pin;
     hipStream_t stream() const { return has_user_stream ? user_stream : own_stream; }
 };
 
@@ -193,6 +208,7 @@ int reset_rows(mmiss_index* ix, hipStream_t st) {
     ix->count = 0;
     ix->labels_h.clear();
     ix->tags_h.clear();
+    ix->groups_h.clear(); ix->group_hwm = 0; ix->groups_dirty = true;
     if (ix->capacity == 0) return MMISS_OK;
     if (ix->dtype == MMISS_F8) MM_HIP(hipMemsetAsync(ix->inv.p, 0, (size_t)ix->capacity * 4, st));
     MM_HIP(hipMemsetAsync(ix->tags.p, 0, (size_t)ix->capacity * 8, st));
@@ -508,6 +524,7 @@ extern "C" int mmiss_index_add(mmiss_index* ix, const float* vecs, const int64_t
     MM_HIP(hipStreamSynchronize(st));
     ix->labels_h.insert(ix->labels_h.end(), lab.begin(), lab.end());
     ix->tags_h.resize((size_t)(ix->count + n), 0);   // new rows: tag 0 (the device tags behind count are zero)
+    ix->groups_h.resize((size_t)(ix->count + n), -1); ix->groups_dirty = true;   // ... and no group
     ix->count += n;
     return MMISS_OK;
 }
@@ -557,8 +574,9 @@ extern "C" int mmiss_index_remove(mmiss_index* ix, const int64_t* labels, int64_
     if (keep == 0) return reset_rows(ix, st);   // every row removed
     std::vector<int64_t> map((size_t)keep), nl((size_t)keep);
     std::vector<uint64_t> ntag((size_t)keep);
+    std::vector<int32_t> ngrp((size_t)keep);
     for (int64_t r = 0, o = 0; r < ix->count; ++r)
-        if (!drop[r]) { map[o] = r; nl[o] = ix->labels_h[r]; ntag[o] = ix->tags_h[r]; ++o; }
+        if (!drop[r]) { map[o] = r; nl[o] = ix->labels_h[r]; ntag[o] = ix->tags_h[r]; ngrp[o] = ix->groups_h[r]; ++o; }
     // stable compaction into fresh buffers (row order == label order is the tie-break contract)
     RowStore fresh;
     MM_TRY(fresh.alloc(ix, ix->capacity, st));
@@ -579,6 +597,7 @@ extern "C" int mmiss_index_remove(mmiss_index* ix, const int64_t* labels, int64_
     swap_rows(ix, fresh);
     ix->labels_h.swap(nl);
     ix->tags_h.swap(ntag);
+    ix->groups_h.swap(ngrp); ix->groups_dirty = true;
     ix->count = keep;
     return MMISS_OK;
 }
@@ -678,6 +697,58 @@ extern "C" int mmiss_index_get_tags(mmiss_index* ix, const int64_t* labels, int6
         MM_HIP(hipStreamSynchronize(ix->stream()));
     } else {
         memcpy(out, val.data(), (size_t)n * 8);
+    }
+    return MMISS_OK;
+}
+
+// ================================================================================================ groups (grouped search)
+extern "C" int mmiss_index_set_groups(mmiss_index* ix, const int64_t* labels, const int32_t* groups, int64_t n) {
+    const char* who = "mmiss_index_set_groups";
+    if (!ix || (n > 0 && (!labels || !groups))) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (n < 0) MM_FAIL(MMISS_ERR_ARG, "%s: n = %lld", who, (long long)n);
+    if (n == 0) return MMISS_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, who, &st));
+    std::vector<int64_t> lab;
+    std::vector<int32_t> val;
+    MM_TRY(fetch_host(labels, n, lab));
+    MM_TRY(fetch_host(groups, n, val, &st));
+    std::vector<int64_t> rows((size_t)n);
+    int32_t top = -1;
+    for (int64_t i = 0; i < n; ++i) {   // every label and value first: a bad one changes nothing
+        rows[i] = find_row(ix, lab[i]);
+        if (rows[i] < 0) MM_FAIL(MMISS_ERR_ARG, "%s: label %lld not in the index", who, (long long)lab[i]);
+        if (val[i] < -1 || val[i] >= MMISS_MAX_GROUPS)
+            MM_FAIL(MMISS_ERR_ARG, "%s: group %d of label %lld outside -1 .. %d", who, val[i], (long long)lab[i], MMISS_MAX_GROUPS - 1);
+        top = std::max(top, val[i]);
+    }
+    for (int64_t i = 0; i < n; ++i) ix->groups_h[(size_t)rows[i]] = val[i];   // call order: a label given twice keeps its last group
+    ix->group_hwm = std::max<int64_t>(ix->group_hwm, (int64_t)top + 1);
+    ix->groups_dirty = true;   // (the device column is the grouped call's: uploaded there)
+    return MMISS_OK;
+}
+
+extern "C" int mmiss_index_get_groups(mmiss_index* ix, const int64_t* labels, int64_t n, int32_t* out) {
+    const char* who = "mmiss_index_get_groups";
+    if (!ix || (n > 0 && (!labels || !out))) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (n <= 0) return n == 0 ? MMISS_OK : MMISS_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    MM_NO_PENDING(ix, who);
+    std::vector<int64_t> lab;
+    MM_TRY(fetch_host(labels, n, lab));
+    std::vector<int32_t> val((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t r = find_row(ix, lab[i]);
+        if (r < 0) MM_FAIL(MMISS_ERR_ARG, "%s: label %lld not in the index", who, (long long)lab[i]);
+        val[i] = ix->groups_h[(size_t)r];
+    }
+    if (mmiss_is_device_ptr(out)) {
+        MM_TRY(mmiss_use_device(ix->device));
+        MM_HIP(hipMemcpyAsync(out, val.data(), (size_t)n * 4, hipMemcpyHostToDevice, ix->stream()));
+        MM_HIP(hipStreamSynchronize(ix->stream()));
+    } else {
+        memcpy(out, val.data(), (size_t)n * 4);
     }
     return MMISS_OK;
 }
@@ -2374,6 +2445,200 @@ extern "C" int mmiss_dbg_index_subset_plan(mmiss_index* ix, int32_t Q, int32_t k
     return MMISS_OK;
 }
 
+// ================================================================================================ grouped search
+// mmiss_index_query_grouped: the exact k nearest groups of each query, each by its best row (grouped_kernels.h). Stage 1 is the
+// flat / filtered query at k = pool, the very code of those calls writing into device scratch (as the distinct call runs it), so the
+// list and the guard counters are theirs. Stage 2 walks every list in ONE launch and flags the queries whose list did not settle
+// the answer; the host looks at the flags once. Stage 3, for those queries only and compacted: a scan of every row into a table of
+// one slot per group (an atomic minimum of the (distance, row) keys), the probed call's selection over the table, and the resolve
+// kernel that puts the heads into the queries' own output rows. Stages 2 and 3 count nothing.
+namespace {
+
+GroupedPlan plan_grouped(const mmiss_index* ix, int Qx, int k, int pool) {
+    return plan_grouped(ix->count, ix->group_hwm, ix->dim, Qx, k, pool, plan_options());
+}
+
+typedef void (*GroupedScanKernel)(GroupedScanArgs);
+template <typename T> GroupedScanKernel grouped_scan_kernel_for(int nqb) {
+    switch (nqb) {
+        case 16: return &grouped_scan_kernel<T, 16>;
+        case 8: return &grouped_scan_kernel<T, 8>;
+        case 4: return &grouped_scan_kernel<T, 4>;
+        case 2: return &grouped_scan_kernel<T, 2>;
+        default: return &grouped_scan_kernel<T, 1>;
+    }
+}
+
+// *col: the group column on the device, uploaded from the host mirror if that changed since the last upload; null while no row has
+// had a group since the last clear or load (the kernels read null as "every row ungrouped")
+int group_column(mmiss_index* ix, hipStream_t st, const int32_t** col) {
+    *col = nullptr;
+    if (ix->group_hwm == 0 || ix->count == 0) return MMISS_OK;
+    if (ix->groups_dirty) {
+        MM_TRY(ix->grp_col.ensure((size_t)ix->count * 4));   // (every grouped call returns finished: nothing queued reads the old one)
+        MM_HIP(hipMemcpyAsync(ix->grp_col.p, ix->groups_h.data(), (size_t)ix->count * 4, hipMemcpyHostToDevice, st));
+        MM_HIP(hipStreamSynchronize(st));
+        ix->groups_dirty = false;
+    }
+    *col = ix->grp_col.as<int32_t>();
+    return MMISS_OK;
+}
+
+// Stage 3 for the flagged queries `which` (indices into the call): returns with everything queued on st
+int grouped_exhaustive(mmiss_index* ix, hipStream_t st, const std::vector<int32_t>& which, int Q, int k, int pool, const int32_t* col,
+                       const uint64_t* require, const uint64_t* exclude, int64_t* o_lab, float* o_dist, int32_t* o_grp, int32_t* o_cnt,
+                       int32_t* o_route) {
+    const int Qf = (int)which.size(), D = ix->dim;
+    const GroupedPlan p = plan_grouped(ix, Qf, k, pool);
+    MM_TRY(ix->grp_map.ensure((size_t)Qf * 4));
+    MM_HIP(hipMemcpyAsync(ix->grp_map.p, which.data(), (size_t)Qf * 4, hipMemcpyHostToDevice, st));   // (`which` outlives the call's last wait)
+    const uint64_t* d_req = require; const uint64_t* d_exc = exclude;   // host masks: [Q] required, then [Q] excluded in prb_mask
+    MM_TRY(device_view(&d_req, (size_t)Q, ix->prb_mask, 0, (size_t)Q * 16, st));
+    MM_TRY(device_view(&d_exc, (size_t)Q, ix->prb_mask, (size_t)Q * 8, (size_t)Q * 16, st));
+    MM_TRY(ix->prb_total.ensure((size_t)p.qchunk * 4));
+    MM_TRY(ix->prb_keys_a.ensure((size_t)p.qchunk * p.stride0 * 8));
+    if (p.stride1) MM_TRY(ix->prb_keys_b.ensure((size_t)p.qchunk * p.stride1 * 8));
+    const size_t CK = (size_t)p.qchunk * k;
+    MM_TRY(ix->grp_sel.ensure(CK * 12 + (size_t)p.qchunk * 4));
+    int64_t* const s_lab = ix->grp_sel.as<int64_t>();
+    float* const s_dist = reinterpret_cast<float*>(ix->grp_sel.as<char>() + CK * 8);
+    int32_t* const s_cnt = reinterpret_cast<int32_t*>(ix->grp_sel.as<char>() + CK * 12);
+    MM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ix->prb_total.p), (int)p.table, (size_t)p.qchunk, st));   // every query: G + count slots
+    const bool f16 = ix->dtype == MMISS_F16, f8 = ix->dtype == MMISS_F8;
+    for (int c0 = 0; c0 < Qf; c0 += p.qchunk) {
+        const int Qc = std::min(p.qchunk, Qf - c0);
+        const int32_t* qmap = ix->grp_map.as<int32_t>() + c0;
+        MM_HIP(hipMemsetAsync(ix->prb_keys_a.p, 0xff, (size_t)Qc * p.stride0 * 8, st));   // PROBE_KEY_NONE in every slot
+        {
+            GroupedScanArgs a{};
+            a.rows = ix->rows.p; a.inv = ix->inv.as<float>(); a.tags = ix->tags.as<uint64_t>(); a.groups = col;
+            a.qn = ix->qn.as<float>(); a.req = d_req; a.exc = d_exc; a.qmap = qmap;
+            a.Qc = Qc; a.D = D; a.N = (int)ix->count; a.G = (int)ix->group_hwm; a.share = p.share;
+            a.table = ix->prb_keys_a.as<unsigned long long>(); a.stride = p.stride0;
+            const int nqb = subset_block_for(p.qblock, Qc);
+            const int qblocks = (Qc + nqb - 1) / nqb;
+            MM_PROF(f16 ? "grouped_scan_f16" : f8 ? "grouped_scan_f8" : "grouped_scan_f32", st, 2.0 * Qc * (double)ix->count * D,
+                    (double)qblocks * ix->count * (D * ix->elt + 12) + 8.0 * Qc * ix->count);
+            const GroupedScanKernel kern = with_storage(ix->dtype, [&](auto s) { return grouped_scan_kernel_for<typename decltype(s)::T>(nqb); });
+            const int lds = grouped_scan_lds_bytes(D, nqb);
+            MM_TRY(mmiss_ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds));
+            hipLaunchKernelGGL(kern, dim3(p.splits, qblocks), dim3(256), lds, st, a);
+            MM_HIP(hipGetLastError());
+        }
+        int64_t nb = p.table;   // the keys a query has at this level
+        for (int l = 0; l < p.levels; ++l) {
+            const bool last = l == p.levels - 1;
+            const bool from_a = (l & 1) == 0;
+            const int nseg = last ? 1 : (int)((nb + PROBE_SEG - 1) / PROBE_SEG);
+            SegmentTopkArgs a{};
+            a.in = from_a ? ix->prb_keys_a.as<unsigned long long>() : ix->prb_keys_b.as<unsigned long long>();
+            a.out = from_a ? ix->prb_keys_b.as<unsigned long long>() : ix->prb_keys_a.as<unsigned long long>();
+            a.in_stride = from_a ? p.stride0 : p.stride1; a.out_stride = from_a ? p.stride1 : p.stride0;
+            a.total = ix->prb_total.as<int32_t>(); a.level = l; a.k = k;
+            a.labels = ix->labels_d.as<int64_t>();
+            a.out_labels = s_lab; a.out_dist = s_dist; a.out_count = s_cnt; a.out_scanned = nullptr;
+            MM_PROF("segment_topk", st, 0.0, (double)Qc * nb * 8);
+            if (last) hipLaunchKernelGGL(segment_topk_kernel<true>, dim3(1, Qc), dim3(1024), 0, st, a);
+            else hipLaunchKernelGGL(segment_topk_kernel<false>, dim3(nseg, Qc), dim3(1024), 0, st, a);
+            MM_HIP(hipGetLastError());
+            nb = (int64_t)nseg * k;
+        }
+        {
+            GroupedResolveArgs a{};
+            a.labels = ix->labels_d.as<int64_t>(); a.N = ix->count; a.groups = col; a.qmap = qmap;
+            a.sel_labels = s_lab; a.sel_dist = s_dist; a.sel_count = s_cnt; a.k = k;
+            a.out_labels = o_lab; a.out_dist = o_dist; a.out_group = o_grp; a.out_count = o_cnt; a.out_route = o_route;
+            MM_PROF("grouped_resolve", st, 0.0, (double)Qc * k * 32);
+            hipLaunchKernelGGL(grouped_resolve_kernel, dim3(Qc), dim3(256), 0, st, a);
+            MM_HIP(hipGetLastError());
+        }
+    }
+    return MMISS_OK;
+}
+
+}  // namespace
+
+extern "C" int mmiss_index_query_grouped(mmiss_index* ix, const float* queries, int32_t Q, int32_t k, int32_t pool, const uint64_t* require,
+                                         const uint64_t* exclude, int64_t* out_labels, float* out_dist, int32_t* out_group,
+                                         int32_t* out_count, int32_t* out_route) {
+    const char* who = "mmiss_index_query_grouped";
+    if (!ix || !queries || !out_labels || !out_dist || !out_group || !out_count) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || pool < 0) MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d pool=%d", who, Q, k, pool);
+    if (k > PROBE_MAX_K) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: k = %d too large (max %d)", who, k, PROBE_MAX_K);
+    if (pool > PLAN_GROUPED_MAX_POOL) MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: pool = %d too large (max %d)", who, pool, PLAN_GROUPED_MAX_POOL);
+    if (pool != 0 && pool < k) MM_FAIL(MMISS_ERR_ARG, "%s: pool = %d below k = %d", who, pool, k);
+    bool out_dev = false, opt_dev = false;
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_group, &out_dev));
+    MM_TRY(outputs_all_host_or_all_device(who, out_labels, out_dist, out_count, out_route, &opt_dev));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    hipStream_t st = nullptr;
+    MM_TRY(enter(ix, who, &st));
+    if (ix->group_hwm + ix->count > (int64_t)INT32_MAX)
+        MM_FAIL(MMISS_ERR_UNSUPPORTED, "%s: %lld groups and %lld rows exceed 2^31 - 1 table slots", who, (long long)ix->group_hwm, (long long)ix->count);
+    const int P = pool > 0 ? pool : grouped_default_pool(k);
+    const int32_t* col = nullptr;
+    MM_TRY(group_column(ix, st, &col));
+    // stage 1, the list: [Q, P] labels, [Q, P] distances, [Q] counts in device scratch
+    const size_t QP = (size_t)Q * P, QK = (size_t)Q * k;
+    MM_TRY(ix->grp_list.ensure(QP * 12 + (size_t)Q * 4));
+    int64_t* const l_lab = ix->grp_list.as<int64_t>();
+    float* const l_dist = reinterpret_cast<float*>(ix->grp_list.as<char>() + QP * 8);
+    int32_t* const l_cnt = reinterpret_cast<int32_t*>(ix->grp_list.as<char>() + QP * 12);
+    MM_TRY(query_begin_locked(ix, queries, Q, P, require, exclude, l_lab, l_dist, l_cnt));
+    MM_TRY(query_end_locked(ix));
+    // stage 2, the walk: into the caller's device buffers, or into scratch on its way to the caller's host buffers
+    int64_t* o_lab = out_labels; float* o_dist = out_dist; int32_t* o_grp = out_group; int32_t* o_cnt = out_count; int32_t* o_route = out_route;
+    if (!out_dev) {
+        MM_TRY(ix->grp_out.ensure(QK * 16 + (size_t)Q * 8));
+        char* const b = ix->grp_out.as<char>();
+        o_lab = reinterpret_cast<int64_t*>(b); o_dist = reinterpret_cast<float*>(b + QK * 8); o_grp = reinterpret_cast<int32_t*>(b + QK * 12);
+        o_cnt = reinterpret_cast<int32_t*>(b + QK * 16); o_route = o_cnt + Q;
+    }
+    MM_TRY(ix->grp_pin.ensure((size_t)Q * 4, st, (size_t)std::max(Q, 1024) * 4));
+    int32_t* const complete = ix->grp_pin.as<int32_t>();
+    {
+        GroupedWalkArgs a{};
+        a.labels = ix->labels_d.as<int64_t>(); a.N = ix->count; a.groups = col;
+        a.list_lab = l_lab; a.list_dist = l_dist; a.list_cnt = l_cnt; a.pool = P; a.k = k;
+        a.out_labels = o_lab; a.out_dist = o_dist; a.out_group = o_grp; a.out_count = o_cnt; a.out_route = o_route; a.complete = complete;
+        MM_PROF("grouped_walk", st, 0.0, (double)Q * P * 12);
+        hipLaunchKernelGGL(grouped_walk_kernel, dim3(Q), dim3(GROUPED_THREADS), 0, st, a);
+        MM_HIP(hipGetLastError());
+    }
+    MM_HIP(hipStreamSynchronize(st));   // the one host look: which walks did not settle their query
+    std::vector<int32_t> which;
+    for (int q = 0; q < Q; ++q)
+        if (!complete[q]) which.push_back(q);
+    // stage 3, the exhaustive route
+    if (!which.empty()) MM_TRY(grouped_exhaustive(ix, st, which, Q, k, pool, col, require, exclude, o_lab, o_dist, o_grp, o_cnt, o_route));
+    if (!out_dev) {
+        MM_HIP(hipMemcpyAsync(out_labels, o_lab, QK * 8, hipMemcpyDeviceToHost, st));
+        MM_HIP(hipMemcpyAsync(out_dist, o_dist, QK * 4, hipMemcpyDeviceToHost, st));
+        MM_HIP(hipMemcpyAsync(out_group, o_grp, QK * 4, hipMemcpyDeviceToHost, st));
+        MM_HIP(hipMemcpyAsync(out_count, o_cnt, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+        if (out_route) MM_HIP(hipMemcpyAsync(out_route, o_route, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+    }
+    MM_HIP(hipStreamSynchronize(st));
+    return MMISS_OK;
+}
+
+// mmiss_debug.h: how a grouped call of this shape would run on the index as it stands (plan_grouped, nothing launched).
+extern "C" int mmiss_dbg_index_grouped_plan(mmiss_index* ix, int32_t Q, int32_t k, int32_t pool, int32_t* out) {
+    const char* who = "mmiss_dbg_index_grouped_plan";
+    if (!ix || !out) MM_FAIL(MMISS_ERR_ARG, "%s: null argument", who);
+    if (Q < 1 || k < 1 || k > PROBE_MAX_K || pool < 0 || pool > PLAN_GROUPED_MAX_POOL || (pool != 0 && pool < k))
+        MM_FAIL(MMISS_ERR_ARG, "%s: Q=%d k=%d pool=%d", who, Q, k, pool);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    const GroupedPlan p = plan_grouped(ix, Q, k, pool);
+    auto i32 = [](int64_t v) { return (int32_t)std::min<int64_t>(v, INT32_MAX); };
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    out[0] = p.pool; out[1] = p.walk_threads; out[2] = p.walk_lds; out[3] = i32(p.table); out[4] = PROBE_SEG; out[5] = p.levels;
+    out[6] = i32(p.stride0); out[7] = i32(p.stride1); out[8] = p.qchunk; out[9] = p.chunks; out[10] = p.qblock; out[11] = p.lds;
+    out[12] = p.share; out[13] = p.splits;
+    out[14] = subset_block_for(p.qblock, std::min(Q, p.qchunk)); out[15] = subset_block_for(p.qblock, Q - (p.chunks - 1) * p.qchunk);
+    return MMISS_OK;
+}
+
 // ================================================================================================ search after
 // mmiss_index_query_after: the exact next k of every query's ranking behind its cursor (after_kernels.h). The subset call's
 // stages with two differences: without a list nothing is marked or compacted (the dense scan's position is the row), and the
@@ -2806,6 +3071,7 @@ extern "C" int mmiss_index_load(mmiss_index* ix, const char* path) {
         MM_FAIL(rc, "%s; the index was cleared", why.c_str());
     }
     ix->tags_h.assign((size_t)h.count, 0);
+    ix->groups_h.assign((size_t)h.count, -1); ix->group_hwm = 0; ix->groups_dirty = true;   // (the file holds no groups either)
     ix->labels_h.swap(lab);
     ix->count = h.count;
     return MMISS_OK;

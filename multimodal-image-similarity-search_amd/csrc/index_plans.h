@@ -285,6 +285,45 @@ inline DistinctPlan plan_distinct(int D, int Q) {
     return p;
 }
 
+// ------------------------------------------------------------------------------------------------ grouped search
+// How a grouped call (mmiss_index_query_grouped, grouped_kernels.h) of Q queries runs on `count` rows of dim D whose group
+// high-water mark is G. The list stage is the flat query at k = pool (pool 0: min(2040, max(8 k, 64))); the walk is one workgroup
+// of PLAN_GROUPED_THREADS per query, all queries in one launch, with a fixed block of LDS. The exhaustive route — queries whose
+// walk is not complete, Qx of them at the most — selects over a table of G + count slots per query: the grouped rows' slots, then
+// one per row for the ungrouped. plan_subset's rules applied to that bound give levels and strides, the chunks under
+// probe_scratch_kb, the query block from PLAN_SUBSET_LDS (narrowed per chunk by subset_block_for) and the share of ROWS per scan
+// workgroup: the scan walks `count` rows, not `table` positions.
+constexpr int PLAN_GROUPED_THREADS = 1024;
+constexpr int PLAN_GROUPED_SLOTS = 2048;
+constexpr int PLAN_GROUPED_MAX_POOL = 2040;            // the list calls' own limit on k
+constexpr int PLAN_GROUPED_WALK_LDS = PLAN_GROUPED_SLOTS * 16 + 64;
+constexpr int PLAN_GROUPED_MAX_GROUPS = 1 << 24;       // MMISS_MAX_GROUPS
+inline int grouped_default_pool(int k) { return std::min(PLAN_GROUPED_MAX_POOL, std::max(8 * k, 64)); }
+struct GroupedPlan {
+    int pool = 0;
+    int walk_threads = PLAN_GROUPED_THREADS, walk_lds = PLAN_GROUPED_WALK_LDS;
+    int64_t table = 0, stride0 = 1, stride1 = 0;   // slots per query = keys at level 0; keys per query of the two key areas
+    int levels = 1;                                // segment_topk launches, the FINAL one included
+    int qchunk = 1, chunks = 1;                    // flagged queries per chunk, chunks when all Qx queries are flagged
+    int qblock = 1, lds = 0;                       // queries per scan workgroup, its dynamic LDS (queries and their masks)
+    int share = 64, splits = 1;                    // rows per scan workgroup, workgroups per query block
+};
+
+inline GroupedPlan plan_grouped(int64_t count, int64_t G, int D, int Qx, int k, int pool, const PlanOptions& o) {
+    GroupedPlan p;
+    p.pool = pool > 0 ? pool : grouped_default_pool(k);
+    p.table = G + count;
+    const SubsetPlan s = plan_subset(p.table, p.table, D, Qx, k, o);
+    p.stride0 = s.stride0; p.stride1 = s.stride1; p.levels = s.levels;
+    p.qchunk = s.qchunk; p.chunks = s.chunks; p.qblock = s.qblock;
+    p.lds = p.qblock * D * 4 + p.qblock * 16;
+    const int64_t qblocks = (p.qchunk + p.qblock - 1) / p.qblock;
+    const int64_t want = std::max<int64_t>(1, (2048 + qblocks - 1) / qblocks);
+    p.share = (int)std::max<int64_t>(64, ((count + want - 1) / want + 15) / 16 * 16);
+    p.splits = (int)std::max<int64_t>(1, (count + p.share - 1) / p.share);
+    return p;
+}
+
 // ------------------------------------------------------------------------------------------------ cluster sums
 // cluster_sums_kernel over N rows of dim D into C clusters: the widest column chunk (a divisor of dim, a multiple of 16) whose
 // [C][cols] table of 64-bit sums fits 128 KiB of LDS — all of dim 512 up to 32 clusters, 16 columns at 1024 clusters —, and the

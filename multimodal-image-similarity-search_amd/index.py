@@ -19,6 +19,7 @@ _DTYPES = {"f32": F32, "float32": F32, "f16": F16, "float16": F16, "f8": F8, "fp
 
 
 MAX_POOL = 2040   # mmiss_index_query_distinct's limit on pool (the list calls' own limit on k)
+MAX_GROUPS = 1 << 24   # MMISS_MAX_GROUPS: group ids are -1 (none) .. MAX_GROUPS - 1
 
 
 def _is_torch(x) -> bool:
@@ -820,6 +821,68 @@ class FlatIndex:
                                                             _lib.ptr(masks[1]), _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(cnt), _lib.ptr(dups),
                                                             _lib.ptr(listed)))
         return lab, dist, cnt, dups, listed
+
+    # ------------------------------------------------------------------ grouped search
+    MAX_GROUPS = MAX_GROUPS
+
+    def set_groups(self, labels, groups) -> None:
+        """Per-row int32 GROUP (mmiss_index_set_groups): labels [n], groups [n], -1 <= group < MAX_GROUPS; -1 = no group (the row
+        is a group of its own). A label not in the index or a value outside the range raises and changes nothing. Rows are added
+        with -1; update keeps a row's group; removal keeps the survivors'; clear and load reset every group to -1."""
+        lab = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        g = np.asarray(groups)
+        if g.dtype.kind not in "ui" and not (g.dtype == object and g.size == 0):
+            raise TypeError(f"groups must be integers, got {g.dtype}")
+        g = g.reshape(-1)
+        if g.shape[0] != lab.shape[0]:
+            raise ValueError(f"{lab.shape[0]} labels but {g.shape[0]} groups")
+        if g.size and (int(g.min()) < -1 or int(g.max()) >= self.MAX_GROUPS):
+            raise ValueError(f"groups: -1 .. {self.MAX_GROUPS - 1}, got {int(g.min())} .. {int(g.max())}")
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        with self._call_lock:
+            _lib.check(self._lib.mmiss_index_set_groups(self._h, lab.ctypes.data, g.ctypes.data, int(lab.shape[0])))
+
+    def get_groups(self, labels) -> np.ndarray:
+        """-> int32 [n], the groups of `labels` (a label not in the index raises)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        out = np.full(lab.shape[0], -1, dtype=np.int32)
+        if lab.shape[0]:
+            with self._call_lock:
+                _lib.check(self._lib.mmiss_index_get_groups(self._h, lab.ctypes.data, int(lab.shape[0]), out.ctypes.data))
+        return out
+
+    def query_grouped(self, queries, k: int, pool: Optional[int] = None, require=None, exclude=None):
+        """The exact k nearest GROUPS, each by its best row (mmiss_index_query_grouped) -> (labels int64 [Q,k], distances float32
+        [Q,k], groups int32 [Q,k], counts int32 [Q], route int32 [Q]): the first k group heads of the complete ranking query()
+        would give over all admitted rows, a row without a group counting as a group of its own; groups[q, j] = the head's group
+        (-1: none, and behind the count). Exact at any group size and independent of `pool`: route[q] = 0 when the walk over the
+        top-`pool` list answered, 1 when one group owned the pool and the query was answered by the scan of every row. pool None:
+        min(2040, max(8 k, 64)); else k <= pool <= 2040. 1 <= k <= 2040, at least one query. require / exclude as in query().
+        numpy in -> numpy out, CUDA tensor in -> CUDA tensors out."""
+        k = int(k)
+        if not 1 <= k <= self.MAX_K:
+            raise ValueError(f"k: 1 .. {self.MAX_K}, got {k}")
+        pool = 0 if pool is None else int(pool)
+        if pool != 0 and not k <= pool <= self.MAX_POOL:
+            raise ValueError(f"pool: k .. {self.MAX_POOL}, got {pool} (k = {k})")
+        q, (lab, dist, cnt) = self._prepare(queries, k)
+        Q = int(q.shape[0])
+        if Q < 1:
+            raise ValueError("query_grouped takes at least one query")
+        masks = self._masks(q, require, exclude) or (None, None)
+        if _is_torch(q) and q.is_cuda:
+            import torch
+
+            grp = torch.empty((Q, k), dtype=torch.int32, device=q.device)
+            route = torch.empty((Q,), dtype=torch.int32, device=q.device)
+        else:
+            grp = np.empty((Q, k), dtype=np.int32)
+            route = np.empty((Q,), dtype=np.int32)
+        with self._call_lock:
+            self._sync_stream(q)
+            _lib.check(self._lib.mmiss_index_query_grouped(self._h, _lib.ptr(q), Q, k, pool, _lib.ptr(masks[0]), _lib.ptr(masks[1]),
+                                                           _lib.ptr(lab), _lib.ptr(dist), _lib.ptr(grp), _lib.ptr(cnt), _lib.ptr(route)))
+        return lab, dist, grp, cnt, route
 
     def guard_stats(self) -> dict:
         """Exactness accounting (mmiss_index_guard_stats_ex): queries served, queries whose first pass could not be proven

@@ -60,6 +60,7 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
     result_metadatas = results["metadatas"][qi]
     result_distances = results["distances"][qi]
     result_duplicates = results["duplicates"][qi] if results.get("duplicates") is not None else None
+    result_groups = results["groups"][qi] if results.get("groups") is not None else None
     # cosine distance: 0 = identical, 2 = opposite; similarity 1 = identical, 0 = opposite (main.py:782)
     similarities = [1 - (distance / 2) for distance in result_distances]
     for i, img_id in enumerate(result_ids):
@@ -68,6 +69,9 @@ def _results_from_query(results: dict, qi: int) -> List[Dict]:
         result_metadata["similarity_score"] = similarities[i]
         if result_duplicates is not None:
             result_metadata["duplicates"] = result_duplicates[i]
+        if result_groups is not None:
+            result_metadata["group"] = result_groups[i]
+            result_metadata["group_size"] = results["group_sizes"][qi][i]
         if "url" not in result_metadata:
             result_metadata["url"] = f"/static/processed/{img_id}.png"
         if "thumbnail_url" not in result_metadata:
@@ -86,7 +90,8 @@ def _no_page() -> Dict:
     return {"results": [], "next": None, "remaining": 0}
 
 
-def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=None, within_ids=None, where=None, after=None) -> dict:
+def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=None, within_ids=None, where=None, after=None,
+               group_by=None) -> dict:
     """the keyword arguments of FlatCollection.query for a search's filters, similarity threshold, probe count and distinctness;
     min_similarity = s becomes the radius utils.max_distance_for_similarity(s): on its results "similarity_score >= s" holds for
     exactly the members; distinct_similarity = s becomes distinct_distance the same way: a result at least s similar to an earlier
@@ -106,13 +111,16 @@ def _filter_kw(filters, min_similarity=None, n_probe=None, distinct_similarity=N
     # after: one token per query, "" / None for the start of the ranking; absent, no argument at all (today's call)
     if after is not None:
         kw["after"] = [t or None for t in after]
+    # group_by: one result per value of this metadata field; absent, no argument at all (today's call)
+    if group_by is not None:
+        kw["group_by"] = group_by
     return kw
 
 
 def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                    min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                    distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                   where: Optional[dict] = None, after: Optional[str] = None):
+                   where: Optional[dict] = None, after: Optional[str] = None, group_by: Optional[str] = None):
     """Search for similar images using an embedding (main.py:748-805). min_similarity: only the images whose similarity_score
     reaches it, exactly (a radius query; `limit` caps how many) — the reference's roadmap item "Adjustable similarity
     thresholds" (CHANGELOG.md:475). n_probe: search only the n_probe k-means cells nearest to the embedding, and what was added
@@ -123,13 +131,17 @@ def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[
     within_ids / where: only among these images — ids (unknown ones are ignored) and / or a metadata predicate; the exact `limit`
     nearest of them (FlatCollection.query(ids=, where=)); n_probe is then ignored, and distinct_similarity is refused (logged, []).
     after: "" for the first page, a page's "next" token for the one behind it -> {"results", "next", "remaining"} (module docstring);
-    n_probe is then ignored; distinct_similarity and a malformed token are refused (logged, an empty page)."""
+    n_probe is then ignored; distinct_similarity and a malformed token are refused (logged, an empty page).
+    group_by: the `limit` nearest GROUPS, one image each — a group is the images whose metadata field `group_by` has the same value
+    (a folder, an upload batch), an image without the field is a group of its own; every result then carries "group" (the value,
+    None without the field) and "group_size" (the stored images with that value) (FlatCollection.query(group_by=)). Combined with
+    n_probe, distinct_similarity, within_ids, where or after it is refused (logged, [] or an empty page)."""
     try:
         actual_limit = 1000 if limit <= 0 else limit  # "All" option (limit of 0), main.py:757
         results = _collection().query(query_embeddings=[np.asarray(embedding, dtype=np.float32).tolist()],
                                       n_results=actual_limit, include=["metadatas", "distances"],
                                       **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where,
-                                                   None if after is None else [after]))
+                                                   None if after is None else [after], group_by))
         if after is not None:
             return _paged(results, 0)
         out = _results_from_query(results, 0)
@@ -143,7 +155,8 @@ def search_similar(embedding: np.ndarray, limit: int = 10, *, filters: Optional[
 def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                          min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                          distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                         where: Optional[dict] = None, after: Optional[Sequence[Optional[str]]] = None):
+                         where: Optional[dict] = None, after: Optional[Sequence[Optional[str]]] = None,
+                         group_by: Optional[str] = None):
     """[Q, D] embeddings -> one result list per query, one index pass for the whole batch. after: one entry per query ("" / None:
     the first page) -> one {"results", "next", "remaining"} per query."""
     try:
@@ -152,7 +165,8 @@ def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Op
         if after is not None and (isinstance(after, str) or len(after) != q.shape[0]):
             raise ValueError(f"after: one entry per query ({q.shape[0]}) expected")
         results = _collection().query(query_embeddings=q, n_results=actual_limit, include=["metadatas", "distances"],
-                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where, after))
+                                      **_filter_kw(filters, min_similarity, n_probe, distinct_similarity, within_ids, where, after,
+                                                   group_by))
         if after is not None:
             return [_paged(results, qi) for qi in range(q.shape[0])]
         return [_results_from_query(results, qi) for qi in range(q.shape[0])]
@@ -164,14 +178,14 @@ def search_similar_batch(embeddings: np.ndarray, limit: int = 10, *, filters: Op
 def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                    min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                    distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                   where: Optional[dict] = None, after: Optional[str] = None):
+                   where: Optional[dict] = None, after: Optional[str] = None, group_by: Optional[str] = None):
     """Search for images using a text query (main.py:807-827)."""
     try:
         model, processor = utils.load_clip_model()
         embedding_result = utils.generate_clip_embedding(text=query_text, model=model, processor=processor)
         text_embedding = embedding_result["text"][0]
         return search_similar(embedding=text_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe,
-                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where, after=after)
+                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where, after=after, group_by=group_by)
     except Exception as e:
         logger.error(f"Error in text search: {e}")
         return [] if after is None else _no_page()
@@ -180,7 +194,7 @@ def search_by_text(query_text: str, limit: int = 10, *, filters: Optional[Sequen
 def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: int = 10, *,
                       filters: Optional[Sequence[str]] = None, min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                       distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                      where: Optional[dict] = None, after: Optional[str] = None):
+                      where: Optional[dict] = None, after: Optional[str] = None, group_by: Optional[str] = None):
     """Search using both image and text with a weighted combination (main.py:829-867); weight_image is not
     clamped, as in the backend route."""
     try:
@@ -190,7 +204,7 @@ def search_multimodal(image, query_text: str, weight_image: float = 0.5, limit: 
         # normalise both, weighted sum, normalise again (main.py:852-860) — one GPU kernel
         combined_embedding = blend(image_embedding[None], text_embedding[None], weight_image)[0]
         return search_similar(embedding=combined_embedding, limit=limit, filters=filters, min_similarity=min_similarity, n_probe=n_probe,
-                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where, after=after)
+                              distinct_similarity=distinct_similarity, within_ids=within_ids, where=where, after=after, group_by=group_by)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return [] if after is None else _no_page()
@@ -200,12 +214,13 @@ def search_multimodal_batch(image_embeddings: np.ndarray, text_embeddings: np.nd
                             limit: int = 10, *, filters: Optional[Sequence[str]] = None,
                             min_similarity: Optional[float] = None, n_probe: Optional[int] = None,
                             distinct_similarity: Optional[float] = None, within_ids: Optional[Sequence[str]] = None,
-                            where: Optional[dict] = None, after: Optional[Sequence[Optional[str]]] = None):
+                            where: Optional[dict] = None, after: Optional[Sequence[Optional[str]]] = None,
+                         group_by: Optional[str] = None):
     """BASELINE config 4: a batch of (image, text) embedding pairs, blended and searched in one pass."""
     try:
         return search_similar_batch(blend(image_embeddings, text_embeddings, weight_image), limit, filters=filters,
                                     min_similarity=min_similarity, n_probe=n_probe, distinct_similarity=distinct_similarity,
-                                    within_ids=within_ids, where=where, after=after)
+                                    within_ids=within_ids, where=where, after=after, group_by=group_by)
     except Exception as e:
         logger.error(f"Error in multimodal search: {e}")
         return []
